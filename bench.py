@@ -5,9 +5,15 @@ One "step" = one `Hierarchy::apply` (V-cycle: Chebyshev(3) pre-smooth, residual,
 solve = one V-cycle of the smoothed-aggregation hierarchy below the first coarse level -- V(0,1), i.e. post-smoothing
 only, on its levels by default (`--amg-pre-levels`; the symmetric V(1,1) cycle is measured beside it) --, prolongation,
 Chebyshev(3) post-smooth) on the matrix-free Q1 Laplace of a synthetic 3-D hyper-cube, FP64, inputs
-resident in HBM.  The `cpu_baseline` leg runs the same cycle in the oracle's C++ port and compares its iterates with the
-GPU's (`parity_vs_gpu`).  Metric (BASELINE.json): fine-DoFs/sec per V-cycle.  One process per GPU; rank 0
+resident in HBM: a seeded random start vector and a seeded load (b = h^3 f, f in [0, 1)), so that the cycles converge to the
+discrete solution rather than to zero.  Metric (BASELINE.json): fine-DoFs/sec per V-cycle.  One process per GPU; rank 0
 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` cycles and prints the headline (`value`, `ms_per_step`: wall clock of one
+timed cycle).  `--full` adds everything else: the residual contraction, the roofline and per-kernel figures below, the
+`cpu_baseline` leg (the same cycle in the oracle's C++ port, its iterates compared with the GPU's: `parity_vs_gpu`) and the
+extra legs (other sizes, precisions and layouts, the 512^3 smoother).  `--dump-outputs DIR` writes the iterate of the last
+timed cycle to DIR/x.npy; the inputs are seeded, so two builds can be compared output for output.
 
 Byte accounting of the roofline block: `achieved` = ALGORITHMIC bytes of the smoother terms one launch of the
 dominant kernel performs -- per term what the data layout requires of a launch of that term (x, out, one id, the
@@ -18,6 +24,7 @@ for exactly this workload and tile (null otherwise); SURVEY.md 8(d)'s own figure
 per fused smoother term, 432 per Chebyshev(3) apply) are printed under `survey_8d_*`.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -33,6 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: float64 entries written at most (32 MiB)
 
 
 def parse_args():
@@ -81,7 +89,36 @@ def parse_args():
                          "Chebyshev(3) smoother of a rank is ONE sweep, x exchanged once and three planes deep) or 2 (rounds 2-3: "
                          "two terms per sweep + a launch for the third, two exchanges)")
     ap.add_argument("--tile", type=str, default="", help="ty,tz[,waves] override of the operator tile (default: timed choice)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: residual contraction, roofline and per-kernel figures, the CPU baseline "
+                         "and its parity check, the extra legs (other sizes, precisions, layouts, the 512^3 smoother; trimmed by "
+                         "the --no-* options).  Without it a run sets up, warms up, times --steps V-cycles and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the iterate x the last timed V-cycle handed back to DIR/x.npy (float64; "
+                         f"a fixed seeded sample of {DUMP_SAMPLE} entries when the vector is longer)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(directory, arrays, rank=0, world=1):
+    """--dump-outputs: the vectors the timed path hands its caller, one DIR/<name>.npy each, float64.  A vector longer than its
+    share of DUMP_SAMPLE entries is written as a sample at fixed positions (drawn from a seeded generator, sorted: the same on
+    every run with the same arguments), so that two builds can be compared output for output within DUMP_SAMPLE * 8 bytes.  In a
+    distributed run every rank writes its local vector, <name>_rank<r>.npy from rank 1 on."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    cap = max(DUMP_SAMPLE // (world * len(arrays)), 1)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(20240601).choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        fname = name if rank == 0 else f"{name}_rank{rank}"
+        np.save(os.path.join(directory, fname + ".npy"), t.cpu().numpy().astype(np.float64))
 
 
 def smoother_coefficients(degree, lmin, lmax):
@@ -530,6 +567,7 @@ def cpu_baseline(args, M, h, prob, lmin, lmax, torch):
 
 def main():
     args = parse_args()
+    full = args.full
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and os.environ.get("OMP_NUM_THREADS") in (None, "", "1"):
         # torch.distributed.run gives every worker ONE OpenMP thread; the host parts of the setup (sorting, class detection, CSR
@@ -615,7 +653,7 @@ def main():
     evaluator = "HipMatrixFreeMeshEvaluator" if args.evaluator == "matrix_free" else "HipMeshEvaluator"
     # (the FP32 instance of the fine operator rides along for the extra line `vcycle_fp32_fine_level_config5`;
     # the headline cycle below is the FP64 `apply`)
-    with_f32 = world == 1 and args.evaluator == "matrix_free" and not args.no_extras
+    with_f32 = full and world == 1 and args.evaluator == "matrix_free" and not args.no_extras
     torch.cuda.synchronize()
     t_problem = time.perf_counter() - t_setup          # mesh arrays of the synthetic problem (torch), partition, transport
     t_setup = time.perf_counter()
@@ -635,32 +673,45 @@ def main():
     else:
         x = part.local_from_global(torch.rand(part.n_global_dofs, dtype=torch.float64, device="cuda", generator=g))
         torch.cuda.empty_cache()
-    x *= (prob.constrained != 1).to(torch.float64)
-    b = torch.zeros(n_local, dtype=torch.float64, device="cuda")
+    free = (prob.constrained != 1).to(torch.float64)
+    x *= free
+    # right-hand side: a seeded load f in [0, 1) on the free DoFs, lumped (b = h^3 f), cut from one global vector like x.  The
+    # cycle converges to the discrete solution A^-1 b instead of decaying to zero (and, after enough steps, into the subnormal
+    # range), so the iterate a caller receives stays the same order of magnitude however many steps run
+    gb = torch.Generator(device="cuda").manual_seed(4)
+    if part is None:
+        b = torch.rand(n_local, dtype=torch.float64, device="cuda", generator=gb)
+    else:
+        b = part.local_from_global(torch.rand(part.n_global_dofs, dtype=torch.float64, device="cuda", generator=gb))
+        torch.cuda.empty_cache()
+    b *= math.prod(prob.h) * free
+    del free
 
     def barrier():
         if world > 1:
             dist.barrier()
 
-    # residual norms around the run: a bench of a cycle that does not contract would be meaningless
+    # residual norms around the run (--full): a bench of a cycle that does not contract would be meaningless
     assembled = args.evaluator == "assembled"
-    op_monitor = None if assembled else M.MatrixFreeLaplace(ctx, prob)
-    compact = (not assembled) and op_monitor.cell_constant_layout()   # same detection as inside the hierarchy
-    ids_computed = (not assembled) and op_monitor.ids_computed()
-    r = torch.empty_like(x)
+    op_monitor = None if assembled or not full else M.MatrixFreeLaplace(ctx, prob)
+    compact = op_monitor is not None and op_monitor.cell_constant_layout()   # same detection as inside the hierarchy
+    ids_computed = op_monitor is not None and op_monitor.ids_computed()
+    r = torch.empty_like(x) if full else None
 
     def residual_norm():
         if assembled and transport is None:
-            h.operator_apply(0, x, r)      # b = 0
+            h.operator_apply(0, x, r)
+            ctx.sadd(r, -1.0, 1.0, b)
             return ctx.l2_norm(r)
         if transport is None:
             op_monitor.vmult(r, x)
             ctx.sadd(r, -1.0, 1.0, b)
             return ctx.l2_norm(r)
-        h.operator_apply(0, x, r)          # with halo exchange; b = 0
+        h.operator_apply(0, x, r)          # with halo exchange
+        ctx.sadd(r, -1.0, 1.0, b)
         return transport.owned_norm(r)
 
-    res_start = residual_norm()
+    res_start = residual_norm() if full else None
     if args.tile and not assembled:
         _t = [int(v) for v in args.tile.split(',')]
         h.set_operator_tile(_t[2] if len(_t) > 2 else 0, _t[0], _t[1])
@@ -669,10 +720,11 @@ def main():
     sweep_tile = h.sweep_tile(sweep_terms[1]) if sweep_terms[1] else None
     for _ in range(args.warmup):
         h.apply(b, x)
-    # HIP events around the launches of the dominant kernel only: an event pair costs ~5 us on the stream, and the
+    # HIP events around the launches of the dominant kernel only (--full): an event pair costs ~5 us on the stream, and the
     # cycle has ~45 launches; the other kernel family is timed in a separate pass after the timed region
     dominant = "csr_spmv_kernel" if assembled else "mf_laplace_kernel,mf_cheb_fused_kernel"
-    ctx.profile_enable(True, only=dominant)
+    if full:
+        ctx.profile_enable(True, only=dominant)
     n_ex0 = transport.n_exchanges() if transport is not None else 0
     n_vol0 = transport.exchange_volume() if transport is not None else 0
     n_ov0 = transport.n_overlapped() if transport is not None else 0
@@ -684,6 +736,45 @@ def main():
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    ms_per_step = dt / args.steps * 1e3
+    value = n_global / (dt / args.steps)
+    if args.dump_outputs:
+        # (before the passes of --full below, which go on iterating on x)
+        dump_outputs(args.dump_outputs, {"x": x}, rank, world)
+
+    coarse_desc = (f"{args.coarse_iters} Jacobi-PCG steps" if args.coarse == "pcg" else
+                   "one V-cycle of a smoothed-aggregation hierarchy (Chebyshev(1) = damped-Jacobi smoothers, dense LU at the bottom; "
+                   + ("V(1,1) on every level" if args.amg_pre_levels < 0 else
+                      f"V(0,1) -- post-smoothing only -- from level {args.amg_pre_levels} of that hierarchy on") + ")")
+    workload = (f"3D Laplace on the unit cube, Q1 {'assembled CSR (BASELINE.json configs[2])' if assembled else 'matrix-free'}, "
+                f"{args.cells}^3 cells = {n}^3 DoFs per GPU (the mesh deal.II's refine_global gives; BASELINE.json configs[3] "
+                f"'512^3 on 8 GPUs' is this workload at N=8), spectral AMGe (2x2x2 agglomerates, 2 eigenvectors), "
+                f"Chebyshev({degree}) smoother, coarse level {n_coarse} DoFs: " + coarse_desc + ", FP64; right-hand side "
+                f"b = h^3 f with a seeded f in [0, 1), seeded random start vector")
+
+    def headline(config):
+        return {"metric": "fine-DoFs/sec per V-cycle (3D Laplace)", "value": value, "unit": "DoF/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": config}
+
+    if not full:
+        if rank == 0:
+            print(json.dumps(headline({
+                "workload": workload, "material": args.material, "fine_dofs_per_gpu": n_fine, "coarse_dofs_per_gpu": n_coarse,
+                "global_dofs": n_global,
+                "parallelism": "1 GPU" if world == 1 else
+                               f"{world} GPUs, {'x'.join(map(str, part.grid))} ranks (x, y, z) on a {gx}x{gy}x{gz}-cell box, "
+                               f"transport: {transport.name()}",
+                "setup_seconds": t_setup, "problem_seconds": t_problem,
+                "measured": "the headline only: residual contraction, roofline, CPU baseline and the extra legs with --full"})))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     n_exchanges_per_cycle = ((transport.n_exchanges() - n_ex0) / max(args.steps, 1)) if transport is not None else 0.0
     mb_sent_per_cycle = ((transport.exchange_volume() - n_vol0) * 8e-6 / max(args.steps, 1)) if transport is not None else 0.0
     n_overlapped_per_cycle = ((transport.n_overlapped() - n_ov0) / max(args.steps, 1)) if transport is not None else 0.0
@@ -734,39 +825,14 @@ def main():
         torch.cuda.synchronize()
         rr_launches, rr_ms, rr_bytes = ctx.profile_query("residual_restriction")
         ctx.profile_enable(False)
-    if world > 1:
-        t = torch.tensor([dt], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-    ms_per_step = dt / args.steps * 1e3
-    value = n_global / (dt / args.steps)
 
-    coarse_desc = (f"{args.coarse_iters} Jacobi-PCG steps" if args.coarse == "pcg" else
-                   "one V-cycle of a smoothed-aggregation hierarchy (Chebyshev(1) = damped-Jacobi smoothers, dense LU at the bottom; "
-                   + ("V(1,1) on every level" if args.amg_pre_levels < 0 else
-                      f"V(0,1) -- post-smoothing only -- from level {args.amg_pre_levels} of that hierarchy on") + ")")
     if rank == 0:
         # bytes the layout requires per launch (library accounting: x, out, one id, coefficients + epilogue operands)
         achieved = (k_bytes / launches) / (k_ms / launches * 1e-3) / 1e9 if launches else 0.0
         word = 8
         out = {
-            "metric": "fine-DoFs/sec per V-cycle (3D Laplace)",
-            "value": value,
-            "unit": "DoF/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"3D Laplace on the unit cube, Q1 {'assembled CSR (BASELINE.json configs[2])' if assembled else 'matrix-free'}, {args.cells}^3 cells = {n}^3 DoFs per GPU "
-                            f"(the mesh deal.II's refine_global gives; BASELINE.json configs[3] '512^3 on 8 GPUs' "
-                            f"is this workload at N=8), spectral AMGe (2x2x2 agglomerates, 2 eigenvectors), "
-                            f"Chebyshev({degree}) smoother, coarse level {n_coarse} DoFs: " + coarse_desc + ", FP64",
+            **headline({
+                "workload": workload,
                 "material": args.material,
                 "coefficient_layout": (None if assembled else
                                        ("one value per cell (the eight quadrature coefficients of every cell are equal)"
@@ -798,7 +864,7 @@ def main():
                                  "symmetric preconditioner; the symmetric V(1,1) cycle is measured beside it: "
                                  "vcycle_256cubed_coarse_cycle_v11, with ms_per_residual_decade for both)"),
                 "rccl_ranks": (transport.comm_ranks() if transport is not None else None),
-            },
+            }),
             "roofline": {
                 "kernel": (f"mf_cheb_fused_kernel (the {degree} terms of the Chebyshev smoother over the matrix-free operator in ONE sweep)"
                            if fused_dominant else "mf_laplace_kernel (fused matrix-free operator + smoother/residual epilogue)"),

@@ -14,7 +14,8 @@ import math
 g=[$C]*3
 for i in range(int(round(math.log2($N)))): g[2 - i % 3]*=2
 print(','.join(map(str,g)))")}
-python bench.py --gpus 1 --cells $C --box $G --steps 5 --warmup 2 --no-extras > gpurun_out/reh_one.log 2>&1 && show gpurun_out/reh_one.log one
+B=${BENCH_OUT:-bench_out}; mkdir -p $B
+python bench.py --gpus 1 --cells $C --box $G --steps 5 --warmup 2 --full --no-extras > $B/reh_one.log 2>&1 && show $B/reh_one.log one
 for P in slab box; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus $N --cells $C --steps 5 --warmup 2 --no-extras --partition $P ${BOX:+--box $BOX} $( [ $P = box ] && [ -n "$GRID" ] && echo --grid $GRID ) > gpurun_out/reh_$P.log 2>&1 && show gpurun_out/reh_$P.log $P
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus $N --cells $C --steps 5 --warmup 2 --full --no-extras --partition $P ${BOX:+--box $BOX} $( [ $P = box ] && [ -n "$GRID" ] && echo --grid $GRID ) > $B/reh_$P.log 2>&1 && show $B/reh_$P.log $P
 done

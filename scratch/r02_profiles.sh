@@ -2,8 +2,9 @@
 # round-2 profiles: kernel stats of the default bench + PMC passes of the operator kernel (separate passes, kernel trace only)
 R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT}
 cd /tmp && export TMPDIR=/tmp
-mkdir -p $R/gpurun_out/prof_r02
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_r02 -o p -- python3 $R/bench.py --no-cpu-baseline --no-extras > $R/gpurun_out/prof_r02/bench.log 2>&1 || echo "stats run failed"
+B=${BENCH_OUT:-$R/bench_out}
+mkdir -p $B/prof_r02
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $B/prof_r02 -o p -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $B/prof_r02/bench.log 2>&1 || echo "stats run failed"
 for cfg in "257 constant" "257 linear" "512 constant" "512 linear"; do
   set -- $cfg
   echo "pmc $1 $2"

@@ -13,7 +13,7 @@ O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 if [[ $STEPS == *a* ]]; then
   mkdir -p $O/prof_r04
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r04 -o p -- python3 $R/bench.py --no-cpu-baseline --no-extras > $O/prof_r04/bench.log 2>&1 || echo "stats run failed"
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r04 -o p -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $O/prof_r04/bench.log 2>&1 || echo "stats run failed"
   cp $O/prof_r04/p_kernel_stats.csv $O/r04_j_bench_kernel_stats.csv
   grep '"metric"' $O/prof_r04/bench.log > $O/r04_j_bench_line.json
   python3 -c "

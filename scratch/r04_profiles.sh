@@ -1,21 +1,22 @@
 #!/bin/bash
 # round-4 profiles (run on the GPU box through gpurun; every rocprofv3 pass is kernel-trace only, --pmc passes separate):
-#   a  kernel stats of the default bench                                   -> gpurun_out/r04_c_bench_kernel_stats.csv
+#   a  kernel stats of the full bench                                      -> $BENCH_OUT/r04_c_bench_kernel_stats.csv
 #   b  HBM bytes per launch of the multi-term sweep (257^3, 512^3)           -> gpurun_out/r04_d_sweep_traffic.txt (+ json entries)
 #   c  kernel sequence of one V-cycle (constant, linear)                     -> gpurun_out/r04_e_cycle_kernel_sequence*.txt
 #   d  HBM bytes per launch of every kernel of the cycle                     -> gpurun_out/r04_f_cycle_hbm_bytes_per_launch.txt
 R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT}
 STEPS=${1:-abcd}
+B=${BENCH_OUT:-$R/bench_out}
 cd /tmp && export TMPDIR=/tmp
 if [[ $STEPS == *a* ]]; then
-  mkdir -p $R/gpurun_out/prof_r04
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_r04 -o p -- python3 $R/bench.py --no-cpu-baseline --no-extras > $R/gpurun_out/prof_r04/bench.log 2>&1 || echo "stats run failed"
-  cp $R/gpurun_out/prof_r04/p_kernel_stats.csv $R/gpurun_out/r04_c_bench_kernel_stats.csv
-  grep '"metric"' $R/gpurun_out/prof_r04/bench.log > $R/gpurun_out/r04_c_bench_line.json
+  mkdir -p $B/prof_r04
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $B/prof_r04 -o p -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $B/prof_r04/bench.log 2>&1 || echo "stats run failed"
+  cp $B/prof_r04/p_kernel_stats.csv $B/r04_c_bench_kernel_stats.csv
+  grep '"metric"' $B/prof_r04/bench.log > $B/r04_c_bench_line.json
   python3 -c "
 import json
-d = json.loads(open('$R/gpurun_out/r04_c_bench_line.json').read()); print('bench under the profiler:', d['ms_per_step'], 'ms per cycle;', d['roofline']['kernel'], d['roofline']['avg_launch_ms'], 'ms over', d['roofline']['launches_in_timed_region'], 'launches, setup', d['config']['setup_seconds'], 's; 512^3 legs', d['north_star_512cubed_smoother']['ms_by_layout'])"
-  rm -rf $R/gpurun_out/prof_r04
+d = json.loads(open('$B/r04_c_bench_line.json').read()); print('bench under the profiler:', d['ms_per_step'], 'ms per cycle;', d['roofline']['kernel'], d['roofline']['avg_launch_ms'], 'ms over', d['roofline']['launches_in_timed_region'], 'launches, setup', d['config']['setup_seconds'], 's; 512^3 legs', d['north_star_512cubed_smoother']['ms_by_layout'])"
+  rm -rf $B/prof_r04
 fi
 if [[ $STEPS == *b* ]]; then
   : > $R/gpurun_out/r04_d_sweep_traffic.txt

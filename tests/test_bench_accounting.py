@@ -66,3 +66,37 @@ def test_committed_traffic_is_keyed_on_the_tiles_the_bench_ran_with():
     assert min(leg["frac_by_layout"].values()) >= 0.5               # north_star: >= 0.50 of 8 TB/s on every layout
     gen = line["smoother_apply_512cubed_general_coefficient"]
     assert bench.committed_traffic(512, 3, False, tuple(gen["tile_waves_ty_tz"]), prefix="dofs") is not None
+
+
+def test_dump_outputs_whole_vector(tmp_path):
+    import numpy as np
+    import torch
+    x = torch.arange(1000, dtype=torch.float64) * 0.5
+    bench.dump_outputs(str(tmp_path), {"x": x})
+    got = np.load(tmp_path / "x.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x.numpy())
+
+
+def test_dump_outputs_fixed_sample(tmp_path, monkeypatch):
+    """A vector longer than DUMP_SAMPLE is written as the same sorted sample on every run; every rank writes its own file."""
+    import numpy as np
+    import torch
+    assert 8 * bench.DUMP_SAMPLE + 4096 <= 64e6         # all files together stay within 64 MB
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    x = torch.arange(10000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": x})
+    bench.dump_outputs(str(tmp_path / "b"), {"x": x})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float64 and a.shape == (64,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 10000      # distinct positions, in order
+    bench.dump_outputs(str(tmp_path / "c"), {"x": x}, rank=1, world=2)
+    assert np.load(tmp_path / "c" / "x_rank1.npy").shape == (32,)
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert not args.full and args.dump_outputs == "" and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == "d"
