@@ -19,7 +19,7 @@
 // (the neighbour column comes by DPP from the next lane), so the planes x_{s-1} of the two node layers a stage reads sit
 // in an LDS ring of two slots per stage that only the lane itself writes and reads -- no barrier protects them.
 // b, D^-1, the cell coefficient and the momentum term of a DoF ride in registers from the super-pass that loads /
-// forms them to the later stages (shifted once per super-pass).  The only exchange between wavefronts is the one the
+// forms them to the later stages (a renaming: the march runs in trips of K super-passes).  The only exchange between wavefronts is the one the
 // one-term kernel has: the sums of a wavefront's first and last cell row go to the neighbours below and above (one
 // barrier per stage pass), and BOTH complete the node row they share, with the same operands in the same order, so
 // that each keeps the rows of its own cells to itself.
@@ -307,17 +307,10 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     const Off o = rec_off(r, n, (unsigned int)Rec<T, true>::kDinvOff);
     return BufIO<T>::ld(rs_rec, o.v, o.s);
   };
-  // slot of a node layer in a ring of depth 2 / 3 (layers are >= -1 here)
-  auto slot2 = [](int n) { return n & 1; };
-  auto slot3 = [](int n) { return (int)((unsigned int)(n + 3) % 3u); };
-  auto ring_at = [&](int s, int n, int r) -> T * {
-    const int sl = ring_depth(s, K) == 3 ? slot3(n) : slot2(n);
-    return ring + ((ring_base(s, K) + sl) * R + r) * 64;
-  };
-  auto ring_next_at = [&](int s, int n, int r) -> T const * {
-    const int sl = ring_depth(s, K) == 3 ? slot3(n) : slot2(n);
-    return ring_next + ((ring_base(s, K) + sl) * R + r) * 64;
-  };
+  // ring slot sl of ring s, node row r: the slot of node layer n is (n - cb) mod the depth of the ring; the march hands a stage
+  // pass its slots as constants of the position in its trip (march below)
+  auto ring_at = [&](int s, int sl, int r) -> T * { return ring + ((ring_base(s, K) + sl) * R + r) * 64; };
+  auto ring_next_at = [&](int s, int sl, int r) -> T const * { return ring_next + ((ring_base(s, K) + sl) * R + r) * 64; };
 
   // ---- per-lane state carried from super-pass to super-pass (stage s + 1 uses entry s)
   T bq[K][R];  // b of the DoF (row r, layer of the stage)
@@ -353,8 +346,8 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     {
       if constexpr (!ZERO0)
       {
-        *ring_at(0, cb, r) = ld_vec(rs_x, r, cb);
-        *ring_at(0, cb + 1, r) = ld_vec(rs_x, r, cb + 1);
+        *ring_at(0, 0, r) = ld_vec(rs_x, r, cb);
+        *ring_at(0, 1, r) = ld_vec(rs_x, r, cb + 1);
       }
       bq[0][r] = ld_vec(rs_b, r, cb);
       if constexpr (DREC)
@@ -377,8 +370,8 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
 
   unsigned int ex = 0; // stage passes so far (parity of the export buffers)
 
-  // ---- one stage pass: stage S (1-based) on the cell layer c
-  auto stage_pass = [&](auto tag, int c) {
+  // ---- one stage pass: stage S (1-based) on the cell layer c; sl(s, d) = the slot of node layer c + d in ring s
+  auto stage_pass = [&](auto tag, int c, auto sl) {
     constexpr int S = decltype(tag)::value;
     const bool lo_free = layer_free(c), hi_free = layer_free(c + 1);
     const bool l_own = layer_own(c);
@@ -391,7 +384,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         xown[r] = xl[r] = xu[r] = T(0);
         continue;
       }
-      const T l = *ring_at(S - 1, c, r), u = *ring_at(S - 1, c + 1, r);
+      const T l = *ring_at(S - 1, sl(S - 1, 0), r), u = *ring_at(S - 1, sl(S - 1, 1), r);
       xown[r] = l;
       if constexpr (S == 1)
       {
@@ -420,8 +413,8 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       {
         // x_{S-1} sits in its ring as the cells read it: the neighbour column straight from there (an LDS read instead of two
         // DPP moves and their presets per value; the same numbers)
-        xln[r] = *ring_next_at(S - 1, c, r);
-        xun[r] = *ring_next_at(S - 1, c + 1, r);
+        xln[r] = *ring_next_at(S - 1, sl(S - 1, 0), r);
+        xun[r] = *ring_next_at(S - 1, sl(S - 1, 1), r);
       }
     }
     // per cell row: what it contributes to the node row below (low) and above (up), two values each -- the corner sums of the
@@ -541,7 +534,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         }
         else
         {
-          *ring_at(1, c, r) = fr ? x1 : T(0);
+          *ring_at(1, sl(1, 0), r) = fr ? x1 : T(0);
           if constexpr (K == 2)
             if (st && fr && want_prev)
               st_vec(x1, rs_vec(offsetof(MfFusedArgs<T>, out_prev)), r, c);
@@ -567,12 +560,12 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       {
         // x_{S-1} and x_{S-2} of the DoF (zero where it is not free: the result is dropped there)
         const T xo = xown[r];
-        const T xoo = (S == 2 && ZERO0) ? T(0) : *ring_at(S - 2, c, r);
+        const T xoo = (S == 2 && ZERO0) ? T(0) : *ring_at(S - 2, sl(S - 2, 0), r);
         const T xoo_m = (S == 2) ? ((lane_free && ((rows_free >> r) & 1u) && lo_free) ? xoo : T(0)) : xoo; // (x_0 sits in its ring unmasked)
         const T xs = fmadd<T>(-(k_beta(S - 1) * dq[S - 1][r]), yv - bq[S - 1][r], fmadd<T>(k_alpha(S - 1), xo - xoo_m, xo));
         if constexpr (S < K)
         {
-          *ring_at(S, c, r) = fr ? xs : T(0);
+          *ring_at(S, sl(S, 0), r) = fr ? xs : T(0);
           if constexpr (S == K - 1)
             if (st && fr && want_prev)
               st_vec(xs, rs_vec(offsetof(MfFusedArgs<T>, out_prev)), r, c);
@@ -640,10 +633,9 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       ++ex;
   };
 
-  // ---- the march
-  const int c_last = stage_end(K) + (K - 1);
-  for (int c1 = cb; c1 <= c_last; ++c1)
-  {
+  // ---- the march.  Super-pass c1: stage s on the cell layer c1 - (s - 1), active from first(s) = stage_start(s) + s - 1 to
+  // last(s) = stage_end(s) + s - 1 (both grow with s).  sl(s, k) = the slot of node layer c1 + k in ring s.
+  auto super_pass = [&](int c1, auto sl) {
     // requests for the next super-pass: x_0 two node layers ahead, b (D^-1) and the coefficients one
     T pfx[R], pfb[R], pfd[R], pfc[TY], pflo = T(0), pfhi = T(0);
     const __amdgpu_buffer_rsrc_t rs_x = rs_vec(offsetof(MfFusedArgs<T>, x)), rs_b = rs_vec(offsetof(MfFusedArgs<T>, b)), rs_rec = rs_rec_f();
@@ -668,15 +660,15 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     }
 
     if (c1 <= stage_end(1))
-      stage_pass(IntTag<1>{}, c1);
+      stage_pass(IntTag<1>{}, c1, [&](int s, int d) { return sl(s, d); });
     if constexpr (K >= 2)
       if (c1 - 1 >= stage_start(2) && c1 - 1 <= stage_end(2))
-        stage_pass(IntTag<2>{}, c1 - 1);
+        stage_pass(IntTag<2>{}, c1 - 1, [&](int s, int d) { return sl(s, d - 1); });
     if constexpr (K >= 3)
       if (c1 - 2 >= stage_start(3) && c1 - 2 <= stage_end(3))
-        stage_pass(IntTag<3>{}, c1 - 2);
+        stage_pass(IntTag<3>{}, c1 - 2, [&](int s, int d) { return sl(s, d - 2); });
 
-    // shift the carried state by one stage, land the requests
+    // shift the carried state by one stage (a renaming: the trip of the march is K super-passes), land the requests
 #pragma unroll
     for (int s = K - 1; s >= 1; --s)
     {
@@ -697,7 +689,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       if constexpr (DREC)
         dq[0][r] = pfd[r];
       if constexpr (!ZERO0)
-        *ring_at(0, c1 + 2, r) = pfx[r];
+        *ring_at(0, sl(0, 2), r) = pfx[r];
     }
 #pragma unroll
     for (int q = 0; q < TY; ++q)
@@ -707,6 +699,42 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       clo = (Yw - 1 >= 0) ? pflo : T(0);
       chi = (Yw + TY >= 0) ? pfhi : T(0);
     }
+  };
+
+  // The loop's trip is K super-passes (the last trip may end early): the shift of the carried state is a renaming, and
+  // with the slot of node layer n taken as (n - cb) mod depth the slot of a layer in a ring of depth K is a constant of the
+  // position in the trip; a ring of the other depth takes one uniform base per trip.  (Tried: the march split into fill,
+  // steady state without range tests and drain -- five copies of the super-pass; compiled, its wide body took 222 VGPRs and
+  // 155 SGPR spills against 190 / 76 here and 198 / 50 before, so it was not run.)
+  const int c_last = stage_end(K) + (K - 1);
+  int c1 = cb, base2 = 0, base3 = 0;
+  auto sl_at = [&](auto jt) {
+    constexpr int j = decltype(jt)::value;
+    return [&](int s, int k) {
+      if (ring_depth(s, K) == 3)
+        return K % 3 == 0 ? ((j + k) % 3 + 3) % 3 : (base3 + j + k + 3) % 3;
+      return K % 2 == 0 ? ((j + k) & 1) : ((base2 + j + k) & 1);
+    };
+  };
+  for (;;)
+  {
+    super_pass(c1, sl_at(IntTag<0>{}));
+    if (++c1 > c_last)
+      break;
+    if constexpr (K >= 2)
+    {
+      super_pass(c1, sl_at(IntTag<1>{}));
+      if (++c1 > c_last)
+        break;
+    }
+    if constexpr (K >= 3)
+    {
+      super_pass(c1, sl_at(IntTag<2>{}));
+      if (++c1 > c_last)
+        break;
+    }
+    base2 = (base2 + K) & 1;
+    base3 = (base3 + K) % 3;
   }
 }
 
@@ -715,8 +743,9 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
 template <typename T, int K, int TY, bool DREC, bool MODES, int DBG = 0, bool NARROW_TOO = false, bool ZERO0 = false>
 __global__ __launch_bounds__(512, 2) void mf_cheb_fused_kernel(MfFusedArgs<T> a)
 {
-  // XCD-aware tile order (as mf_laplace_body): every XCD takes a contiguous run of the tile list
-  const unsigned int n_tiles = a.wide_tiles + a.ntiles_y2 * a.ntiles_z;
+  // XCD-aware tile order (as mf_laplace_body): every XCD takes a contiguous run of the tile list (without the narrow body:
+  // the tiles of the wide columns, which are all the tiles where there is no narrow column)
+  const unsigned int n_tiles = NARROW_TOO ? a.wide_tiles + a.ntiles_y2 * a.ntiles_z : a.wide_tiles;
   unsigned int w = blockIdx.x;
   if (n_tiles >= 64)
   {
@@ -734,6 +763,24 @@ __global__ __launch_bounds__(512, 2) void mf_cheb_fused_kernel(MfFusedArgs<T> a)
     }
   }
   mf_cheb_fused_body<T, K, TY, DREC, MODES, DBG, false, ZERO0>(a, w);
+}
+
+// The tiles of a narrow last chunk column alone, launched behind the wide-only kernel on the same stream (MFMG_MF_FUSED_NARROW=split;
+// each kernel gets the register budget of its own body).  The default carries both bodies in one launch: at 257^3 all tiles of
+// the sweep fit one round of the chip, and a second launch queues its tiles behind the first.
+template <typename T, int K, int TY, bool DREC, bool MODES, bool ZERO0 = false>
+__global__ __launch_bounds__(512, 2) void mf_cheb_fused_narrow_kernel(MfFusedArgs<T> a)
+{
+  const unsigned int n_tiles = a.ntiles_y2 * a.ntiles_z;
+  unsigned int w = blockIdx.x;
+  if (n_tiles >= 64)
+  {
+    const unsigned int per_xcd = (n_tiles + 7) / 8;
+    w = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    if (w >= n_tiles)
+      return;
+  }
+  mf_cheb_fused_body<T, K, TY, DREC, MODES, 0, true, ZERO0>(a, a.wide_tiles + w);
 }
 } // namespace
 
@@ -899,7 +946,8 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
   for (int k = 0; k < n_terms; ++k)
     bytes += required_bytes_apply() + epilogue_bytes(k == 0 ? 2 : 3);
   hipEvent_t stop = _handle.profiler.begin("mf_cheb_fused_kernel", bytes, st);
-  auto go = [&](auto kernel) {
+  static const bool narrow_split = std::getenv("MFMG_MF_FUSED_NARROW") && std::string(std::getenv("MFMG_MF_FUSED_NARROW")) == "split";
+  auto go = [&](auto kernel, unsigned int blocks) {
     static std::mutex attr_mutex;
     static std::set<std::pair<const void *, int>> attr_set;
     int dev = 0;
@@ -909,7 +957,18 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
       if (attr_set.insert({reinterpret_cast<const void *>(kernel), dev}).second)
         MFMG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
-    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(64 * nw), lds, st, a);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * nw), lds, st, a);
+  };
+  auto grid = [](uint64_t n) { return (unsigned int)(n >= 64 ? ((n + 7) / 8) * 8 : n); };
+  // a kernel that carries both bodies (joint) or the wide-only kernel followed by the narrow-only one (split)
+  auto go_narrow = [&](auto joint, auto wide, auto narrow_only) {
+    if (!narrow_split)
+      go(joint, n_blocks);
+    else
+    {
+      go(wide, grid(a.wide_tiles));
+      go(narrow_only, grid((uint64_t)a.ntiles_y2 * a.ntiles_z));
+    }
   };
   // the arithmetic of the cell kernel: mode space (default) or the bit-for-bit twin of the one-term kernel (set_fused_reference)
   const bool modes = !_fused_reference_arithmetic;
@@ -921,21 +980,21 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
     if constexpr (KK == 3)
       if (narrow && ty == 3)
       {
-        go(mf_cheb_fused_kernel<T, 3, 3, DR, MO, 0, true>);
+        go_narrow(mf_cheb_fused_kernel<T, 3, 3, DR, MO, 0, true>, mf_cheb_fused_kernel<T, 3, 3, DR, MO>, mf_cheb_fused_narrow_kernel<T, 3, 3, DR, MO>);
         return;
       }
     if constexpr (KK == 2)
       if (narrow && ty == 4)
       {
-        go(mf_cheb_fused_kernel<T, 2, 4, DR, MO, 0, true>);
+        go_narrow(mf_cheb_fused_kernel<T, 2, 4, DR, MO, 0, true>, mf_cheb_fused_kernel<T, 2, 4, DR, MO>, mf_cheb_fused_narrow_kernel<T, 2, 4, DR, MO>);
         return;
       }
     if (ty == 2)
-      go(mf_cheb_fused_kernel<T, KK, 2, DR, MO>);
+      go(mf_cheb_fused_kernel<T, KK, 2, DR, MO>, n_blocks);
     else if (ty == 3)
-      go(mf_cheb_fused_kernel<T, KK, 3, DR, MO>);
+      go(mf_cheb_fused_kernel<T, KK, 3, DR, MO>, n_blocks);
     else
-      go(mf_cheb_fused_kernel<T, KK, 4, DR, MO>);
+      go(mf_cheb_fused_kernel<T, KK, 4, DR, MO>, n_blocks);
   };
   auto pick_k = [&](auto kt) {
     if (_dinv_in_record)
@@ -960,24 +1019,26 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
     if (_dinv_in_record)
     {
       if (narrow)
-        go(mf_cheb_fused_kernel<T, 3, 3, true, true, 0, true, true>);
+        go_narrow(mf_cheb_fused_kernel<T, 3, 3, true, true, 0, true, true>, mf_cheb_fused_kernel<T, 3, 3, true, true, 0, false, true>,
+                  mf_cheb_fused_narrow_kernel<T, 3, 3, true, true, true>);
       else
-        go(mf_cheb_fused_kernel<T, 3, 3, true, true, 0, false, true>);
+        go(mf_cheb_fused_kernel<T, 3, 3, true, true, 0, false, true>, n_blocks);
     }
     else
     {
       if (narrow)
-        go(mf_cheb_fused_kernel<T, 3, 3, false, true, 0, true, true>);
+        go_narrow(mf_cheb_fused_kernel<T, 3, 3, false, true, 0, true, true>, mf_cheb_fused_kernel<T, 3, 3, false, true, 0, false, true>,
+                  mf_cheb_fused_narrow_kernel<T, 3, 3, false, true, true>);
       else
-        go(mf_cheb_fused_kernel<T, 3, 3, false, true, 0, false, true>);
+        go(mf_cheb_fused_kernel<T, 3, 3, false, true, 0, false, true>, n_blocks);
     }
   }
   else if (dbg > 0 && n_terms == 3 && ty == 3 && !_dinv_in_record && std::is_same<T, double>::value)
   {
     if (dbg == 1)
-      go(mf_cheb_fused_kernel<T, 3, 3, false, true, 1>);
+      go(mf_cheb_fused_kernel<T, 3, 3, false, true, 1>, n_blocks);
     else
-      go(mf_cheb_fused_kernel<T, 3, 3, false, true, 2>);
+      go(mf_cheb_fused_kernel<T, 3, 3, false, true, 2>, n_blocks);
   }
   else if (n_terms == 1)
     pick_k(IntTag<1>{});
