@@ -422,6 +422,7 @@ bool HipMatrixOperator::restrict_residual(Operator<DVector> const &a, DVector co
   ASSERT_THROW(x.size() == _matrix->n() && b.size() == _matrix->n() && b_coarse.size() == _matrix->m(),
                "vector sizes do not match the operator");
   HipHandle &hd = _matrix->handle();
+  ASSERT_THROW(!hd.comm.enabled() || _domain_space == 1, "internal: the one-pass residual restriction reads b in the fine DoF space");
   // distributed runs: two exchanges as in the two-step form (there: x for the residual, the residual for R) -- here x two
   // layers deep and b one layer deep
   hd.exchange(_rr_space, const_cast<double *>(x.get_values()));
@@ -445,6 +446,7 @@ void HipMatrixOperator::prefetch_rhs(DVector const &b) const
   if (!hd.comm.enabled() || !hd.overlap_exchange || _domain_space <= 0 || b.size() != _matrix->n() ||
       !(restriction_reads_it || hd.rhs_ghosts_wanted))
     return;
+  ASSERT_THROW(_domain_space == 1, "internal: the right-hand side is prefetched in the fine DoF space only");
   hd.exchange_async(hd.fine_space(hd.rhs_ghosts_wanted ? hd.rhs_ghost_width : 1), const_cast<double *>(b.get_values()));
   hd.rhs_fresh_width = hd.rhs_ghosts_wanted ? hd.rhs_ghost_width : 1;
   hd.rhs_in_flight = b.get_values();
@@ -813,6 +815,11 @@ bool HipMatrixFreeOperator::sweep_available(int n_terms) const
   return _mesh_evaluator->get_device_operator()->fused_sweep_available(n_terms);
 }
 
+bool HipMatrixFreeOperator::sweep_from_zero_available(int n_terms) const
+{
+  return _mesh_evaluator->get_device_operator()->fused_zero_guess_available(n_terms);
+}
+
 bool HipMatrixFreeOperator::smoother_sweep(int n_terms, double const *alpha, double const *beta, DVector const &b, DVector const &x,
                                            DVector &out, DVector *out_prev) const
 {
@@ -949,6 +956,25 @@ HipSmoother::HipSmoother(std::shared_ptr<Operator<DVector> const> op, std::share
     // Gauss-Seidel / SSOR / ILU are sequential Ifpack algorithms outside the HIP path
     ASSERT_THROW(false, "Unknown smoother name: \"" + _type + "\" (the HIP back-end implements Jacobi and Chebyshev)");
   }
+  if (matrix_free)
+  {
+    // The multi-term sweep changes the exchanges of a distributed smoother (x once per sweep, K planes deep, b widened; none of x
+    // from a zero guess), so all ranks run it or none does.  What a rank's operator offers follows from its local mesh alone --
+    // one coefficient per cell, the ghost planes it holds -- and differs between ranks whose materials differ: the ranks agree on
+    // the smallest offer, in ONE collective that every rank reaches here.  Encoded as 2 K + z (z: the sweep from x_0 = 0, which
+    // needs K = 3): the minimum over the ranks is the smallest K, with z set only where every rank has K = 3 and z.
+    int k = 0;
+    for (int K = 2; K <= _fused_terms; ++K)
+      if (_hip_operator->sweep_available(K))
+        k = K; // (available for K terms: also for fewer)
+    const bool z = k == 3 && _hip_operator->sweep_from_zero_available(3);
+    const double mine = 2. * k + (z ? 1. : 0.);
+    HipHandle &h = _hip_operator->get_hip_handle();
+    const int agreed = (int)(h.comm.enabled() ? -h.allreduce_max(-mine) : mine);
+    _sweep_max = agreed / 2;
+    _sweep_from_zero = (agreed & 1) != 0;
+    ASSERT_THROW(_sweep_max <= k, "internal: the ranks agreed on a sweep this rank cannot run");
+  }
 }
 
 void HipSmoother::estimate_eigenvalues(int n_iterations, double residual, double &min_est, double &max_est) const
@@ -1071,7 +1097,7 @@ void HipSmoother::run_terms(int k0, DVector const &b, DVector const *cur, DVecto
 // the first K terms in one sweep where the operator offers it: x_K -> out, x_{K-1} -> out_prev
 bool HipSmoother::run_sweep(int K, DVector const &b, DVector const &x_in, DVector &out, DVector *out_prev) const
 {
-  if (K < 2 || K > _fused_terms || !_hip_operator->sweep_available(K))
+  if (K < 2 || K > _fused_terms || K > _sweep_max)
     return false;
   double alpha[3], beta[3];
   for (int k = 0; k < K; ++k)
@@ -1081,7 +1107,9 @@ bool HipSmoother::run_sweep(int K, DVector const &b, DVector const &x_in, DVecto
   }
   if (alpha[0] != 0.)
     return false;
-  return _hip_operator->smoother_sweep(K, alpha, beta, b, x_in, out, out_prev);
+  // (K <= _sweep_max: every rank takes this path, a refusal here would leave the ranks with different exchanges)
+  ASSERT_THROW(_hip_operator->smoother_sweep(K, alpha, beta, b, x_in, out, out_prev), "internal: the agreed smoother sweep was refused");
+  return true;
 }
 
 void HipSmoother::apply(DVector const &b, DVector &x) const
@@ -1146,18 +1174,19 @@ void HipSmoother::sweep_terms(int &in_place, int &out_of_place) const
   if (d >= 3)
   {
     const int K = std::min(d - 1, _fused_terms);
-    if (K >= 2 && _hip_operator->sweep_available(K))
+    if (K >= 2 && K <= _sweep_max)
       in_place = K;
   }
   const int K = std::min(d, _fused_terms);
-  if (K >= 2 && _hip_operator->sweep_available(K))
+  if (K >= 2 && K <= _sweep_max)
     out_of_place = K;
 }
 
 bool HipSmoother::prefers_out_of_place() const
 {
   const int d = (int)_coefficients.size();
-  return d >= 2 && _fused_terms >= 2 && _hip_operator->sweep_available(std::min(d, _fused_terms));
+  const int K = std::min(d, _fused_terms);
+  return K >= 2 && K <= _sweep_max;
 }
 
 void HipSmoother::apply_to(DVector const &b, DVector const &x_in, DVector &x_out) const
@@ -1191,7 +1220,7 @@ bool HipSmoother::apply_from_zero(DVector const &b, DVector &x_out) const
 {
   // the whole polynomial as one sweep that does not read x_0 = 0 (three terms: the kernels that carry the variant)
   const int d = (int)_coefficients.size();
-  if (d != 3 || _fused_terms < 3 || _coefficients[0].first != 0.)
+  if (d != 3 || _fused_terms < 3 || _sweep_max < 3 || !_sweep_from_zero || _coefficients[0].first != 0.)
     return false;
   double alpha[3], beta[3];
   for (int k = 0; k < 3; ++k)
@@ -1199,6 +1228,7 @@ bool HipSmoother::apply_from_zero(DVector const &b, DVector &x_out) const
     alpha[k] = _coefficients[k].first;
     beta[k] = _coefficients[k].second;
   }
+  // (the ranks agreed on the sweep from zero at setup; a sweep tile set on this operator since then may still refuse it here)
   return _hip_operator->smoother_sweep_from_zero(3, alpha, beta, b, x_out);
 }
 
@@ -1615,6 +1645,9 @@ HipHierarchyHelpers<VectorType>::build_restrictor(Communicator, std::shared_ptr<
                  "this distributed context already carries a hierarchy: its halo spaces are in use -- destroy that "
                  "hierarchy first (one hierarchy per communicator context at a time)");
     comm.spaces_owner = this;
+    // the b-prefetch state of the context follows the smoother of THIS hierarchy (set by its first sweep): none of an earlier one
+    _handle.rhs_ghosts_wanted = false;
+    _handle.rhs_ghost_width = 1;
     // first coarse level: the agglomerates of the local mesh, `n_components` unknowns each
     HaloSpace &cs = comm.spaces[2];
     cs = HaloSpace();

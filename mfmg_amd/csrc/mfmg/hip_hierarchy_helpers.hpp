@@ -94,6 +94,7 @@ public:
   }
   virtual bool sweep_available(int /*n_terms*/) const { return false; }
   // the same sweep from x_0 = 0, which is not read (hierarchy.hpp:253-259: a preconditioner application starts from zero)
+  virtual bool sweep_from_zero_available(int /*n_terms*/) const { return false; }
   virtual bool smoother_sweep_from_zero(int /*n_terms*/, double const * /*alpha*/, double const * /*beta*/, DVector const & /*b*/,
                                         DVector & /*out*/) const
   {
@@ -207,6 +208,7 @@ public:
   bool smoother_sweep(int n_terms, double const *alpha, double const *beta, DVector const &b, DVector const &x, DVector &out,
                       DVector *out_prev) const override;
   bool sweep_available(int n_terms) const override;
+  bool sweep_from_zero_available(int n_terms) const override;
   bool smoother_sweep_from_zero(int n_terms, double const *alpha, double const *beta, DVector const &b, DVector &out) const override;
   double const *get_diagonal_inverse() const override;
   HipHandle &get_hip_handle() const override { return _mesh_evaluator->get_hip_handle(); }
@@ -308,6 +310,10 @@ private:
   double _lambda_min = 1., _lambda_max = 1.;
   std::vector<std::pair<double, double>> _coefficients; // (alpha_k, beta_k)
   int _fused_terms = 3; // polynomial terms per sweep (1: one launch per term)
+  // the most terms one sweep may run (0: none) and whether the sweep from a zero guess may run: what this rank's operator
+  // offers, and on a distributed context the smallest over the ranks, agreed once at setup (the sweep changes the exchanges)
+  int _sweep_max = 0;
+  bool _sweep_from_zero = false;
   mutable std::shared_ptr<DVector> _scratch_a, _scratch_b;
 };
 
@@ -419,6 +425,9 @@ public:
       _handle.comm.spaces_owner = nullptr;
       _handle.comm.spaces.resize(3);
       _handle.comm.spaces[2] = HaloSpace();
+      // ... and so does the b-prefetch state its smoother set (a later hierarchy on this context may not sweep)
+      _handle.rhs_ghosts_wanted = false;
+      _handle.rhs_ghost_width = 1;
     }
   }
 

@@ -22,6 +22,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
 import mfmg_amd as M  # noqa: E402
 from mfmg_amd import lib as L  # noqa: E402
 import mfmg_oracle as O  # noqa: E402
+import mixed_material  # noqa: E402
 
 PRM = {"eigensolver": {"number of eigenvectors": 2}, "agglomeration": {"nx": 2, "ny": 2, "nz": 2}}
 
@@ -459,6 +460,9 @@ MESHES = {
     # node columns wide: one full chunk column + a NARROW last one of 25 resp. 27 columns (the widest the sweep takes is 32 - halo:
     # the 259 / 261 columns of a rank of the 2 x 2 x 2 bench run are 4 full ones + 27 / 29)
     "boxnarrow": (16, (80, 32), "constant", {"coarsest_size": 300}),
+    # mixed: the "corner" material of tests/mixed_material.py (--grid 1x1x2, 2x1x2) -- every rank but the last holds a cell-wise
+    # constant coefficient, and could sweep several smoother terms at once on its own; the ranks agree on one smoother
+    "mixed": (24, (24, 24), "corner", {"coarsest_size": 40, "replicate_rows": 40}),
 }
 
 
@@ -476,11 +480,14 @@ def mode_gpu(args):
     params = dict(PRM)
     params.update({"smoother": {"type": "Chebyshev", "degree": 3, "smoothing_range": 20.0},
                    "solver": {"type": "amg", "amg": dict(amg)}, "is preconditioner": False})
+    mixed = material in mixed_material.PATTERNS
+    table = mixed_material.global_table(cells, material, part.h) if mixed else None
+    local_problem = lambda: mixed_material.local_problem(part, table, "cuda") if mixed else part.local_problem(material, "cuda")
     ctx = M.Context()
     tr = M.HaloTransport(ctx, part, 2)
     assert tr.name() == ("rccl" if native else "host")
     assert tr.selftest(4096) == 0.0          # loop-back, all-gather, sum / max all-reduce through the transport
-    h = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", part.local_problem(material, "cuda"), params)
+    h = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", local_problem(), params)
     deg, lmin, lmax = h.smoother_info()       # estimated with dot products summed over the ranks
     assert 1.4 < lmax < 2.2, lmax
     # one coefficient per cell: the first two Chebyshev terms run as ONE sweep (x exchanged two ghost planes deep once, the
@@ -488,17 +495,22 @@ def mode_gpu(args):
     # (with two agglomerates of every lower neighbour in the local mesh, --low-ghost 4, the whole Chebyshev(3) smoother of the
     # cycle is one sweep: x three planes deep, b two; an in-place call keeps the last term as a launch of its own)
     assert h.smoother_sweep_terms() == ((2, 3 if args.low_ghost == 4 else 0) if material == "constant" else (0, 0)), h.smoother_sweep_terms()
+    # ... the same on every rank: the sweep changes the exchanges (a mixed material: ranks that could sweep on their own do not)
+    terms = torch.zeros(world, 2, dtype=torch.float64)
+    terms[rank] = torch.tensor(h.smoother_sweep_terms(), dtype=torch.float64)
+    _all_reduce_cpu(terms)              # (the rows of all ranks)
+    assert (terms == terms[rank]).all(), terms
     # the halo spaces of the levels belong to this hierarchy: a second one on the same communicator context is refused
     # while it lives (every rank raises before any collective of the second setup)
     try:
-        M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", part.local_problem(material, "cuda"), params)
+        M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", local_problem(), params)
         raise AssertionError("a second hierarchy on a distributed context must be refused")
     except L.MfmgError as e:
         assert "already carries a hierarchy" in str(e)
     # global single-process reference on the same GPU (context without communicator): the SAME parameters -- the
     # distributed hierarchy must be the same preconditioner, eigenvalue estimates included
     gctx = M.Context()
-    gprob = M.LaplaceProblem(cells, material, device="cuda", cell_size=part.h)
+    gprob = mixed_material.global_problem(cells, table, part.h, "cuda") if mixed else M.LaplaceProblem(cells, material, device="cuda", cell_size=part.h)
     hg = M.Hierarchy(gctx, "HipMatrixFreeMeshEvaluator", gprob, params)
     _, glmin, glmax = hg.smoother_info()
     assert abs(glmax - lmax) < 1e-9 * lmax and abs(glmin - lmin) < 1e-9 * lmax, (lmin, lmax, glmin, glmax)
@@ -633,18 +645,37 @@ def mode_gpu(args):
     res_o = np.array(res_o)
     np.testing.assert_allclose(hist / hist[0], res_o[:n_cycles + 1] / res_o[0], rtol=1e-9, atol=1e-12)
     assert rate < 0.6
-    if material == "constant":
+    if material == "constant" or mixed:
         # a preconditioner application (Hierarchy::vmult with "is preconditioner" true, include/mfmg/common/hierarchy.hpp:253-259): with
         # the one-sweep smoother the first pre-smoothing step starts from zero inside the sweep -- x is not exchanged (zero on every
         # rank), b travels as deep as the sweep reads it; garbage in x must not matter.  Against the single-process hierarchy.
+        # (A mixed material: no rank sweeps, each one zeroes x and runs its first step term by term -- whatever its own operator
+        # could do; one that swept from zero would skip the exchange of x the others make.)
         del h
         pp = dict(params); pp["is preconditioner"] = True
-        hp = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", part.local_problem(material, "cuda"), pp)
+        hp = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", local_problem(), pp)
         hgp = M.Hierarchy(gctx, "HipMatrixFreeMeshEvaluator", gprob, pp)
         zl = dev(1e6 * rng.random(nl)); zg = dev(1e6 * rng.random(ng))
         hp.vmult(zl, dev(local(bg, False))); hgp.vmult(zg, dev(bg))
         check(zl, zg, "preconditioner application", 1e-10)
         del hp, hgp
+    if material == "constant" and not native:
+        # the ghost entries of b the sweep read (prefetched with the cycle, as deep as the sweep reads them) are context state: a
+        # hierarchy that does not sweep, built on the context after one that did, exchanges per cycle what it does on a fresh one
+        p1 = dict(params); p1["smoother"] = dict(params["smoother"], fused_terms=1)
+        def cycle_volume(c, t):
+            h1 = M.Hierarchy(c, "HipMatrixFreeMeshEvaluator", part.local_problem(material, "cuda"), p1)
+            assert h1.smoother_sweep_terms() == (0, 0)
+            x1 = dev(local(x0g, False))
+            h1.apply(dev(local(bg, False)), x1)
+            v = t.exchange_volume()
+            h1.apply(dev(local(bg, False)), x1)
+            c.synchronize()
+            return t.exchange_volume() - v
+        used = cycle_volume(ctx, tr)
+        ctx2 = M.Context()
+        tr2 = M.HaloTransport(ctx2, part, 2)
+        assert used == cycle_volume(ctx2, tr2), "a hierarchy inherited the b-prefetch of the one before it on its context"
     if rank == 0:
         print("gpu distributed checks passed; grid", "x".join(map(str, grid)), "transport", tr.name(), "exchanges", tr.n_exchanges(),
               "spaces", tr.space(1)["n_spaces"], "residuals", ["%.3e" % v for v in hist[:6]], flush=True)

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import mfmg_amd as M
+import mixed_material
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -50,16 +51,22 @@ class Mailboxes:
         return exchange, allreduce, allgather
 
 
+_REPLICATE = {"coarsest_size": 40, "replicate_rows": 40, "pre_smoothing_levels": 0}
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("material,amg,low_ghost", [("linear", {"coarsest_size": 40, "replicate_rows": 40, "pre_smoothing_levels": 0}, 2),
-                                                    ("constant", {"coarsest_size": 300}, 2),
-                                                    ("constant", {"coarsest_size": 40, "replicate_rows": 40, "pre_smoothing_levels": 0}, 4)])
+@pytest.mark.parametrize("material,amg,low_ghost", [("linear", _REPLICATE, 2), ("constant", {"coarsest_size": 300}, 2), ("constant", _REPLICATE, 4),
+                                                    ("corner", _REPLICATE, 2), ("rest", {"coarsest_size": 300}, 2),
+                                                    ("corner", {"coarsest_size": 300}, 4), ("rest", _REPLICATE, 4)])
 def test_box_2x2x2_eight_ranks_in_one_process(mfmg_lib, material, amg, low_ghost):
     """low_ghost = 4: two agglomerates of every lower neighbour in the local mesh -- the Chebyshev(3) smoother of every rank is
-    one sweep with one exchange of x, three ghost planes deep (asserted below)."""
+    one sweep with one exchange of x, three ghost planes deep (asserted below).
+    "corner" / "rest": mixed materials (tests/mixed_material.py) -- ranks with a cell-wise constant coefficient, which could sweep
+    several smoother terms at once, beside ranks without; the ranks agree on no sweep, and every one runs the same exchanges."""
     grid, per = (2, 2, 2), 24 if "replicate_rows" in amg else 16
     cells = tuple(per * g for g in grid)
     length = tuple(c / float(cells[0]) for c in cells)
+    mixed = material in mixed_material.PATTERNS
     params = {"eigensolver": {"number of eigenvectors": 2}, "agglomeration": {"nx": 2, "ny": 2, "nz": 2},
               "smoother": {"type": "Chebyshev", "degree": 3, "smoothing_range": 20.0},
               "solver": {"type": "amg", "amg": dict(amg)}, "is preconditioner": False}
@@ -67,7 +74,11 @@ def test_box_2x2x2_eight_ranks_in_one_process(mfmg_lib, material, amg, low_ghost
     # ---- the single-process hierarchy on the global mesh
     gctx = M.Context()
     h_cell = tuple(length[d] / cells[d] for d in range(3))
-    gprob = M.LaplaceProblem(cells, material, device="cuda", cell_size=h_cell)
+    if mixed:
+        table = mixed_material.global_table(cells, material, h_cell)
+        gprob = mixed_material.global_problem(cells, table, h_cell, "cuda")
+    else:
+        gprob = M.LaplaceProblem(cells, material, device="cuda", cell_size=h_cell)
     hg = M.Hierarchy(gctx, "HipMatrixFreeMeshEvaluator", gprob, params)
     deg, glmin, glmax = hg.smoother_info()
     ng = gprob.n_dofs
@@ -84,7 +95,7 @@ def test_box_2x2x2_eight_ranks_in_one_process(mfmg_lib, material, amg, low_ghost
     # ---- eight ranks, one thread each
     n_ranks = 8
     mb = Mailboxes(n_ranks)
-    hists, errors, info, overlapped = [None] * n_ranks, [None] * n_ranks, [None] * n_ranks, [0] * n_ranks
+    hists, errors, info, overlapped, sweeps = [None] * n_ranks, [None] * n_ranks, [None] * n_ranks, [0] * n_ranks, [None] * n_ranks
     x_final = np.zeros(ng)
 
     def worker(rank):
@@ -94,9 +105,11 @@ def test_box_2x2x2_eight_ranks_in_one_process(mfmg_lib, material, amg, low_ghost
             ctx = M.Context()
             tr = M.HaloTransport(ctx, part, callbacks=mb.callbacks(rank))
             assert tr.name() == "host" and tr.selftest(1024) == 0.0
-            h = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", part.local_problem(material, "cuda"), params)
+            lprob = mixed_material.local_problem(part, table, "cuda") if mixed else part.local_problem(material, "cuda")
+            h = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", lprob, params)
             _, lmin, lmax = h.smoother_info()
             assert abs(lmax - glmax) < 1e-9 * glmax and abs(lmin - glmin) < 1e-9 * glmax
+            sweeps[rank] = h.smoother_sweep_terms()
             if material == "constant":
                 assert h.smoother_sweep_terms() == (2, 3 if low_ghost == 4 else 0), h.smoother_sweep_terms()
             own_l, own_g, loc_g = (t.numpy() for t in tr.space_index(1))
@@ -153,6 +166,10 @@ def test_box_2x2x2_eight_ranks_in_one_process(mfmg_lib, material, amg, low_ghost
     if first is not None:
         raise first
     assert all(h is not None for h in hists)
+    # one smoother for all ranks: the sweep changes the exchanges (mixed materials: the ranks that could sweep do not)
+    assert all(s == sweeps[0] for s in sweeps), sweeps
+    if mixed:
+        assert sweeps[0] == (0, 0), sweeps
     if material == "constant":
         assert sum(overlapped) > 0      # (the ghost entries of b did travel on the second stream: the smoother sweep / the one-pass restriction read them)
     for hst in hists[1:]:
@@ -177,3 +194,22 @@ def test_box_2x2x2_eight_ranks_in_one_process(mfmg_lib, material, amg, low_ghost
     res_o = np.array(res_o)
     np.testing.assert_allclose(hists[0] / hists[0][0], res_o[:n_cycles + 1] / res_o[0], rtol=1e-9, atol=1e-12)
     assert rate < 0.6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("low_ghost", [2, 4])
+def test_mixed_corner_ranks_differ_on_their_own(mfmg_lib, low_ghost):
+    """What the ranks of the "corner" material would do without agreeing (no communicator, no exchange): the operator of each
+    local problem on a plain context keeps one coefficient per cell on ranks 0-6 and offers their smoother the sweep; rank 7
+    keeps eight coefficients per cell and does not.  The test above runs these ranks together."""
+    grid, cells = (2, 2, 2), (32, 32, 32)
+    h_cell = tuple(1.0 / c for c in cells)
+    table = mixed_material.global_table(cells, "corner", h_cell)
+    ctx = M.Context()
+    for rank in range(8):
+        part = M.BoxPartition(cells, rank, grid, low_ghost_cells=low_ghost)
+        op = M.MatrixFreeLaplace(ctx, mixed_material.local_problem(part, table, "cuda"))
+        assert op.cell_constant_layout() == (rank != 7), rank
+        assert op.sweep_available(2) == (rank != 7), rank
+        # three terms need three ghost planes on every side with a neighbour: two agglomerates of every lower one, or none
+        assert op.sweep_available(3) == (rank != 7 and (low_ghost == 4 or rank == 0)), rank

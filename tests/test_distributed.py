@@ -1,5 +1,6 @@
 """N > 1 path: world_size-2/3 gloo runs of tests/dist_worker.py (CPU: partition + host setup + exchange
 protocol; GPU: the library path with all ranks sharing one card)."""
+import math
 import os
 import socket
 import subprocess
@@ -10,6 +11,7 @@ import pytest
 import torch
 
 import mfmg_amd as M
+import mixed_material
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -96,6 +98,35 @@ def test_box_partition_geometry(mfmg_lib):
     assert slab.exchange_doubles() / box.exchange_doubles() > 2.6
 
 
+@pytest.mark.parametrize("low_ghost", [2, 4])
+@pytest.mark.parametrize("grid,cells,pattern", [((2, 2, 2), (32, 32, 32), "corner"), ((2, 2, 2), (32, 32, 32), "rest"),
+                                                ((2, 2, 2), (48, 48, 48), "corner"), ((2, 2, 2), (48, 48, 48), "rest"),
+                                                ((1, 1, 2), (24, 24, 48), "corner"), ((2, 1, 2), (48, 24, 48), "corner")])
+def test_mixed_material_fixture(mfmg_lib, grid, cells, pattern, low_ghost):
+    """The mixed materials of the GPU tests (tests/mixed_material.py) on the box grids and meshes they run (the 2 x 2 x 2 thread
+    test, the "mixed" mesh of tests/dist_worker.py): exactly the intended ranks hold a cell-wise constant local table ("corner":
+    all but the last rank, "rest": rank 0 only) -- so that those tests keep putting ranks with and ranks without the
+    one-coefficient-per-cell operator into one run if the partition geometry changes."""
+    n_ranks = grid[0] * grid[1] * grid[2]
+    length = tuple(c / float(cells[0]) for c in cells)
+    h = tuple(length[d] / cells[d] for d in range(3))
+    table = mixed_material.global_table(cells, pattern, h)
+    lin = M.LaplaceProblem(cells, "linear", cell_size=h).coefficient
+    inside = table != 1.0
+    # the linear material pulled towards 1 inside the region, exactly 1 outside it
+    assert inside.any() and (~inside).any() and (table >= 1.0).all() and (table <= lin).all()
+    constant = set()
+    for r in range(n_ranks):
+        part = M.BoxPartition(cells, r, grid, length=length, low_ghost_cells=low_ghost)
+        prob = mixed_material.local_problem(part, table)
+        assert prob.coefficient.shape == (math.prod(part.local_cells), 8) and prob.coefficient.dtype == torch.float64
+        # (the cell mapping: the same rows of the global "linear" table are the rank's own "linear" table)
+        assert torch.equal(mixed_material.local_rows(part, lin), part.local_problem("linear").coefficient)
+        if mixed_material.cell_constant(prob.coefficient):
+            constant.add(r)
+    assert constant == mixed_material.expected_constant_ranks(pattern, n_ranks)
+
+
 @pytest.mark.parametrize("world,grid,low_ghost", [(2, "2x1x1", 2), (4, "2x2x1", 2), (4, "1x2x2", 2), (8, "2x2x2", 2), (2, "1x1x2", 4), (8, "2x2x2", 4)])
 def test_box_construction_cpu_gloo(mfmg_lib, world, grid, low_ghost):
     """Box partition (SURVEY.md 8e): host setup on the local boxes + the all-neighbours exchange restated in numpy over gloo;
@@ -140,6 +171,17 @@ def test_box_decomposition_library_path_shared_gpu(mfmg_lib, world, grid, mesh):
     each operator against the single-process hierarchy, 20-cycle history == single process == oracle to 1e-10, and the
     doubles a fine exchange moves."""
     assert "gpu distributed checks passed; grid " + grid in _run("gpu", world, mesh=mesh, grid=grid, timeout=900)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("low_ghost", [2, 4])
+@pytest.mark.parametrize("world,grid", [(2, "1x1x2"), (4, "2x1x2")])
+def test_mixed_material_ranks_agree_on_the_smoother_shared_gpu(mfmg_lib, world, grid, low_ghost):
+    """The "mixed" mesh of the worker: every rank but the last holds a cell-wise constant coefficient (the operator layout that
+    lets a smoother sweep several terms behind one exchange of x), the last one does not.  The ranks agree on the smoother --
+    the same sweep terms on every rank (all-gathered in the worker), none here -- and so exchange alike: every operator of the
+    cycle, the 20-cycle history and a preconditioner application (the smoother from a zero guess) as in the tests above."""
+    assert "gpu distributed checks passed; grid " + grid in _run("gpu", world, mesh="mixed", grid=grid, timeout=900, low_ghost=low_ghost)
 
 
 @pytest.mark.gpu
