@@ -54,6 +54,8 @@ extern "C" {
 /* OperatorMode (include/mfmg/common/operator.hpp:19-23) */
 #define MFMG_HIP_NO_TRANS 0
 #define MFMG_HIP_TRANS 1
+/* restrictor_apply only: out -= R^T in (Operator::apply_subtract, the form the cycle uses) */
+#define MFMG_HIP_TRANS_SUBTRACT 2
 
 typedef struct mfmg_hip_context_s *mfmg_hip_context_t;       /* CudaHandle, include/mfmg/cuda/cuda_handle.cuh:25-48 */
 typedef struct mfmg_hip_csr_s *mfmg_hip_csr_t;               /* SparseMatrixDevice<double>, include/mfmg/cuda/sparse_matrix_device.cuh:28-104 */
@@ -404,6 +406,16 @@ int mfmg_hip_hierarchy_operator_apply(mfmg_hip_hierarchy_t h, int32_t level, con
 int mfmg_hip_hierarchy_smoother_apply(mfmg_hip_hierarchy_t h, int32_t level, const double *b, double *x);
 /* levels[level].get_restrictor()->apply(in, out, mode): level >= 1 (level.hpp:35-38) */
 int mfmg_hip_hierarchy_restrictor_apply(mfmg_hip_hierarchy_t h, int32_t level, const double *in, double *out, int mode);
+/* How the restrictor of `level` is evaluated (tests: which kernel paths a case reaches).  fields[0..10]:
+ *   0 1 = agglomerate-wise form (structured_restrictor.hpp), 0 = CSR (all other fields 0)
+ *   1 eigenvectors per agglomerate, 2-4 cells per agglomerate along x, y, z
+ *   5 1 = planes stored in float
+ *   6 agglomerates evaluated from the reference block table, 7 further block classes, 8 agglomerate positions listed
+ *     for the thread-per-node part of the 2 x 2 x 2 prolongation kernel
+ *   9 restriction kernel: 1 rows, 2 pairs of 2 x 2 x 2 agglomerates, 3 pairs of any agglomerate
+ *  10 prolongation kernel: 1 one thread per node, 2 the 2 x 2 x 2 block kernel */
+#define MFMG_HIP_RESTRICTOR_FORM_FIELDS 11
+int mfmg_hip_hierarchy_restrictor_form(mfmg_hip_hierarchy_t h, int32_t level, int32_t *fields, int32_t n);
 /* out = (A R^T) in for the A R^T the coarse operator of `level` was formed from -- `fast_multiply_transpose()` when the
  * parameter `fast_ap` is true (include/mfmg/common/hierarchy.hpp:214-221), `a->multiply_transpose(restrictor)` otherwise.
  * Kept only by a hierarchy built with `keep_ap = true` (tests: the comparison of tests/test_hierarchy.cc:507-642). */

@@ -560,9 +560,23 @@ class Hierarchy:
         check(self._lib.mfmg_hip_hierarchy_smoother_apply(self.handle, level, _dev_ptr(b, n), _dev_ptr(x, n)))
 
     def restrictor_apply(self, level: int, vin, vout, mode: int = _lib.NO_TRANS):
+        """vout = R vin (NO_TRANS), vout = R^T vin (TRANS) or vout -= R^T vin (TRANS_SUBTRACT)."""
         nf, nc = self.level_size(level - 1), self.level_size(level)
         ni, no = (nf, nc) if mode == _lib.NO_TRANS else (nc, nf)
         check(self._lib.mfmg_hip_hierarchy_restrictor_apply(self.handle, level, _dev_ptr(vin, ni), _dev_ptr(vout, no), mode))
+
+    _RESTRICT_KERNELS = {1: "rows", 2: "pair222", 3: "pair"}
+    _PROLONG_KERNELS = {1: "nodes", 2: "block222"}
+
+    def restrictor_form(self, level: int = 1) -> dict:
+        """How the restrictor of `level` is evaluated: the agglomerate-wise form or CSR, and which kernels it launches."""
+        f = (C.c_int32 * _lib.RESTRICTOR_FORM_FIELDS)()
+        check(self._lib.mfmg_hip_hierarchy_restrictor_form(self.handle, level, f, _lib.RESTRICTOR_FORM_FIELDS))
+        if not f[0]:
+            return {"structured": False}
+        return {"structured": True, "n_eig": f[1], "a": (f[2], f[3], f[4]), "float_planes": bool(f[5]),
+                "table_agglomerates": f[6], "n_classes": f[7], "listed_blocks": f[8],
+                "restrict": self._RESTRICT_KERNELS[f[9]], "prolong": self._PROLONG_KERNELS[f[10]]}
 
     def ap_apply(self, level: int, vin, vout):
         """vout = (A R^T) vin for the A R^T of `level` (hierarchies built with keep_ap = true)."""

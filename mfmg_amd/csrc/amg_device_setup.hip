@@ -11,7 +11,8 @@
 //                                                  (1 + r_l)^3 n_comp applications of A_l;
 //   A_{l+1} = P_l^T A_l P_l                        columns 2 r_{l+1} + 1 apart never meet in a row:
 //                                                  (2 r_{l+1} + 1)^3 n_comp applications of P_l, A_l, P_l^T
-// with r_l the reach of A_l in nodes (r_0 = 1 for the AMGe coarse operator, r_{l+1} = floor((1 + 3 r_l) / 2); aggregates of
+// with r_l the reach of A_l in nodes (r_0 = AmgGridHint::reach: 1 for the AMGe coarse operator, 2 where an agglomerate is one cell
+// wide; r_{l+1} = floor((1 + 3 r_l) / 2); aggregates of
 // b nodes per direction: r_{l+1} = floor((b - 1 + 3 r_l) / b), so b = 3 keeps a reach of 1).
 // Nothing but vectors crosses between ranks: the probing vectors are defined on global coordinates, A_l reads its
 // ghost layers after a forward halo exchange and P_l^T returns the partial sums of ghost aggregates to their owners
@@ -73,7 +74,8 @@ void HipSolver::setup_amg_on_device(std::shared_ptr<SparseMatrixDevice<double>> 
   ASSERT_THROW(blk >= 2 && grid.block[1] == blk && grid.block[2] == blk, "the device setup needs cubic aggregates");
 
   LevelGeom g;
-  g.reach = 1;
+  g.reach = grid.reach;
+  ASSERT_THROW(g.reach >= 1, "the device setup needs the reach of the operator");
   if (distributed)
   {
     g.s = comm.spaces[op_space];

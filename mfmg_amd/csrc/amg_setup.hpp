@@ -37,6 +37,8 @@ struct AmgGridHint
   int dims[3] = {0, 0, 0};
   int block[3] = {2, 2, 2};
   int n_components = 1;
+  // stencil reach of the operator in nodes (the AMGe coarse operator: 1, or 2 where an agglomerate is one cell wide)
+  int reach = 1;
   std::vector<int32_t> node_of_row;
   std::vector<int32_t> component_of_row; // empty: all rows are component 0
   bool valid(int64_t n_rows) const { return dims[0] > 0 && (int64_t)node_of_row.size() == n_rows; }

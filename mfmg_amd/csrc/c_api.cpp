@@ -1379,7 +1379,7 @@ int mfmg_hip_hierarchy_restrictor_apply(mfmg_hip_hierarchy_t h, int32_t level, c
 {
   return guarded([&] {
     require(h && in && out, "null argument");
-    require(mode == MFMG_HIP_NO_TRANS || mode == MFMG_HIP_TRANS, "unknown operator mode");
+    require(mode == MFMG_HIP_NO_TRANS || mode == MFMG_HIP_TRANS || mode == MFMG_HIP_TRANS_SUBTRACT, "unknown operator mode");
     require(level >= 1 && level < (int)h->hierarchy->levels().size(), "restrictors live on levels >= 1");
     const int64_t n_fine = level_size(h, level - 1), n_coarse = level_size(h, level);
     auto r = h->hierarchy->levels()[level].get_restrictor();
@@ -1391,8 +1391,35 @@ int mfmg_hip_hierarchy_restrictor_apply(mfmg_hip_hierarchy_t h, int32_t level, c
     else
     {
       DVector iv(*h->handle, n_coarse, const_cast<double *>(in)), ov(*h->handle, n_fine, out);
-      r->apply(iv, ov, OperatorMode::TRANS);
+      if (mode == MFMG_HIP_TRANS)
+        r->apply(iv, ov, OperatorMode::TRANS);
+      else
+        r->apply_subtract(iv, ov, OperatorMode::TRANS);
     }
+  });
+}
+
+int mfmg_hip_hierarchy_restrictor_form(mfmg_hip_hierarchy_t h, int32_t level, int32_t *fields, int32_t n)
+{
+  return guarded([&] {
+    require(h && fields, "null argument");
+    require(n >= MFMG_HIP_RESTRICTOR_FORM_FIELDS, "restrictor_form needs MFMG_HIP_RESTRICTOR_FORM_FIELDS fields");
+    require(level >= 1 && level < (int)h->hierarchy->levels().size(), "restrictors live on levels >= 1");
+    auto r = std::dynamic_pointer_cast<HipMatrixOperator const>(h->hierarchy->levels()[level].get_restrictor());
+    StructuredRestrictorDevice const *s = r ? r->structured() : nullptr;
+    std::fill(fields, fields + n, 0);
+    if (s == nullptr)
+      return;
+    fields[0] = 1;
+    fields[1] = s->n_eigenvectors();
+    for (int d = 0; d < 3; ++d)
+      fields[2 + d] = s->agglomerate_cells(d);
+    fields[5] = s->float_planes() ? 1 : 0;
+    fields[6] = (int32_t)s->regular_agglomerates();
+    fields[7] = s->block_classes();
+    fields[8] = (int32_t)s->listed_blocks();
+    fields[9] = s->restrict_kernel();
+    fields[10] = s->prolong_kernel();
   });
 }
 

@@ -499,12 +499,17 @@ std::shared_ptr<Operator<DVector>> HipMatrixOperator::multiply(std::shared_ptr<O
     if (_structured && !ghosts && hd.galerkin_on_device)
     {
       // On device, by probing (the reference's fast_ap idea,
-      // source/dealii/dealii_matrix_free_hierarchy_helpers.cc:77-288): R A R^T couples an agglomerate only to its 26
-      // neighbours, so the columns of all agglomerates with the same index mod 3 in every direction (and the same
-      // eigenvector) can be applied at once -- u = their indicator, y = R (A (R^T u)) with the kernels of the apply
-      // path -- and row (a, e) of y is the entry towards the one agglomerate of that class next to a:
-      // 27 n_eig operator applications instead of one per coarse column.
+      // source/dealii/dealii_matrix_free_hierarchy_helpers.cc:77-288): R A R^T couples an agglomerate only to the ones
+      // within a reach r_d per direction, so the columns of all agglomerates with the same index mod 2 r_d + 1 in every
+      // direction (and the same eigenvector) can be applied at once -- u = their indicator, y = R (A (R^T u)) with the
+      // kernels of the apply path -- and row (a, e) of y is the entry towards the one agglomerate of that class near a:
+      // 27 n_eig operator applications (45 n_eig with one axis of r_d = 2) instead of one per coarse column.  An agglomerate
+      // of a_d cells along d spans the nodes [i a_d, (i + 1) a_d], and A couples nodes one apart, so r_d = 1 + floor(1 / a_d):
+      // 1, and 2 for agglomerates one cell wide.
       const int ne = _structured->n_eigenvectors();
+      int reach[3];
+      for (int d = 0; d < 3; ++d)
+        reach[d] = _structured->agglomerate_cells(d) == 1 ? 2 : 1;
       const int na[3] = {_structured->agglomerates(0), _structured->agglomerates(1), _structured->agglomerates(2)};
       // period and phase on the GLOBAL agglomerate index (local + offset), rows of the owned agglomerates only
       int off[3] = {0, 0, 0};
@@ -522,7 +527,8 @@ std::shared_ptr<Operator<DVector>> HipMatrixOperator::multiply(std::shared_ptr<O
           glob[d] = cs.gn(d);
         }
       }
-      const int k[3] = {(int)std::min<int64_t>(3, glob[0]), (int)std::min<int64_t>(3, glob[1]), (int)std::min<int64_t>(3, glob[2])};
+      const int k[3] = {(int)std::min<int64_t>(2 * reach[0] + 1, glob[0]), (int)std::min<int64_t>(2 * reach[1] + 1, glob[1]),
+                        (int)std::min<int64_t>(2 * reach[2] + 1, glob[2])};
       const int64_t n_agg = (int64_t)na[0] * na[1] * na[2], nc = n_agg * ne;
       ASSERT_THROW(nc == _matrix->m(), "agglomerate grid does not match the restrictor");
       const int n_colors = k[0] * k[1] * k[2] * ne;
@@ -541,7 +547,7 @@ std::shared_ptr<Operator<DVector>> HipMatrixOperator::multiply(std::shared_ptr<O
           this->apply(*w, y);
         }
       }
-      auto coarse = std::make_shared<HipMatrixOperator>(galerkin_from_probes(hd, na, ne, k, off, own0, own1, Y.data()));
+      auto coarse = std::make_shared<HipMatrixOperator>(galerkin_from_probes(hd, na, ne, k, reach, off, own0, own1, Y.data()));
       coarse->set_spaces(_range_space, _range_space);
       return coarse;
     }
@@ -1627,6 +1633,11 @@ HipHierarchyHelpers<VectorType>::build_restrictor(Communicator, std::shared_ptr<
     }
   }
   const double t_r1 = now();
+  // R A R^T couples agglomerates up to two apart along an axis where they are one cell wide (HipMatrixOperator::multiply)
+  _grid_hint.reach = 1;
+  for (int d = 0; d < hip_mesh_evaluator->get_mesh().dim; ++d)
+    if (opts.agglomerate[d] == 1)
+      _grid_hint.reach = 2;
   // component of a coarse row = its position among the eigenvectors of its agglomerate
   _grid_hint.component_of_row.resize(_grid_hint.node_of_row.size());
   _grid_hint.n_components = 1;

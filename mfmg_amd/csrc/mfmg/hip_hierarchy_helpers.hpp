@@ -152,6 +152,7 @@ public:
   // stays for the setup algebra and for get_restrictor
   void set_structured(std::shared_ptr<StructuredRestrictorDevice> s) { _structured = std::move(s); }
   bool has_structured() const { return _structured != nullptr; }
+  StructuredRestrictorDevice const *structured() const { return _structured.get(); }
   // y = R x on this rank's arrays, no exchange: through the agglomerate-wise form where there is one (the CSR arrays of such a
   // restrictor stay on the host until somebody asks for them)
   void apply_local(double const *x, double *y) const

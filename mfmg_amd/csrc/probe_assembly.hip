@@ -67,6 +67,7 @@ int64_t scan_counts(HipHandle &h, DeviceBuffer<int32_t> &row_ptr, int64_t n_rows
 struct GalerkinGeom
 {
   int na[3], ne, k[3];
+  int reach[3]; // agglomerates coupled per axis: 1, or 2 for agglomerates one cell wide
   int off[3], own0[3], own1[3]; // global index of local agglomerate 0; owned agglomerates [own0, own1) per axis
   int all_owned;
   int64_t nc;
@@ -85,9 +86,9 @@ __global__ void galerkin_rows_kernel(GalerkinGeom g, double const *Y, int32_t *r
     const bool owned = ax >= g.own0[0] && ax < g.own1[0] && ay >= g.own0[1] && ay < g.own1[1] && az >= g.own0[2] && az < g.own1[2];
     int p = FILL ? row_ptr[r] : 0;
     if (owned)
-      for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-          for (int dx = -1; dx <= 1; ++dx)
+      for (int dz = -g.reach[2]; dz <= g.reach[2]; ++dz)
+        for (int dy = -g.reach[1]; dy <= g.reach[1]; ++dy)
+          for (int dx = -g.reach[0]; dx <= g.reach[0]; ++dx)
           {
             const int bx = ax + dx, by = ay + dy, bz = az + dz;
             if (bx < 0 || bx >= g.na[0] || by < 0 || by >= g.na[1] || bz < 0 || bz >= g.na[2])
@@ -370,8 +371,9 @@ std::shared_ptr<SparseMatrixDevice<double>> assemble(HipHandle &h, int64_t n_row
 }
 } // namespace
 
-std::shared_ptr<SparseMatrixDevice<double>> galerkin_from_probes(HipHandle &h, int const na[3], int ne, int const k[3], int const off[3],
-                                                                 int64_t const own0[3], int64_t const own1[3], double const *Y)
+std::shared_ptr<SparseMatrixDevice<double>> galerkin_from_probes(HipHandle &h, int const na[3], int ne, int const k[3], int const reach[3],
+                                                                 int const off[3], int64_t const own0[3], int64_t const own1[3],
+                                                                 double const *Y)
 {
   GalerkinGeom g;
   g.round_to_float = h.setup_values_float ? 1 : 0;
@@ -380,6 +382,8 @@ std::shared_ptr<SparseMatrixDevice<double>> galerkin_from_probes(HipHandle &h, i
   {
     g.na[d] = na[d];
     g.k[d] = k[d];
+    g.reach[d] = reach[d];
+    ASSERT_THROW(reach[d] >= 1 && (k[d] >= 2 * reach[d] + 1 || k[d] >= na[d]), "internal: probing period shorter than the reach");
     g.off[d] = off[d];
     g.own0[d] = (int)own0[d];
     g.own1[d] = (int)own1[d];

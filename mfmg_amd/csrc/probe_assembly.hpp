@@ -9,10 +9,11 @@
 namespace mfmg
 {
 // A_c = R A R^T on the local agglomerate grid `na` with `ne` rows per agglomerate: colours of period k on GLOBAL agglomerate
-// coordinates (local + off), rows of the owned agglomerates [own0, own1) only; every neighbour inside the grid is stored.
-// Y[colour][local row].
-std::shared_ptr<SparseMatrixDevice<double>> galerkin_from_probes(HipHandle &h, int const na[3], int ne, int const k[3], int const off[3],
-                                                                 int64_t const own0[3], int64_t const own1[3], double const *Y);
+// coordinates (local + off), rows of the owned agglomerates [own0, own1) only; every agglomerate within `reach` per axis
+// inside the grid is stored (k[d] >= min(2 reach[d] + 1, global agglomerates along d)).  Y[colour][local row].
+std::shared_ptr<SparseMatrixDevice<double>> galerkin_from_probes(HipHandle &h, int const na[3], int ne, int const k[3], int const reach[3],
+                                                                 int const off[3], int64_t const own0[3], int64_t const own1[3],
+                                                                 double const *Y);
 
 // P = (I - w D^-1 A) P_tent: Z[colour][local fine row] = (A y_colour)(row), t the tentative prolongator (ghosts exchanged),
 // dinv the inverse diagonal; rows of the owned nodes of `fine` only, zeros are dropped.  `fine` / `coarse`: the two levels as

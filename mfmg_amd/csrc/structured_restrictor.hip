@@ -13,8 +13,10 @@
 #include <omp.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <string>
 #include <unordered_map>
 
 namespace mfmg
@@ -446,6 +448,14 @@ StructuredRestrictorDevice::create(HipHandle &handle, StructuredMesh const &mesh
   s->_n_fine = mesh.n_dofs;
   s->_nnz = R.row_ptr[R.n_rows];
   s->_identity_numbering = identity;
+  // MFMG_SR_RESTRICT=rows: R x by the row kernel; MFMG_SR_PROLONG=nodes: R^T y by the node kernel (no block kernel).  Each gives
+  // the same bits as the kernel it replaces (tests/test_transfer_shapes.py); read per restrictor, not cached
+  auto env_is = [](char const *name, char const *value) {
+    char const *e = std::getenv(name);
+    return e != nullptr && std::string(e) == value;
+  };
+  s->_restrict_rows = env_is("MFMG_SR_RESTRICT", "rows");
+  const bool prolong_nodes = env_is("MFMG_SR_PROLONG", "nodes");
   {
     // planes whose values a float holds exactly ("setup value precision" float rounds R) are kept in float
     bool all_float = !planes.empty();
@@ -629,6 +639,7 @@ StructuredRestrictorDevice::create(HipHandle &handle, StructuredMesh const &mesh
     }
     if (n_regular * 2 >= n_agg)
     {
+      s->_n_regular = n_regular;
       // classes among the others (hash of the block, exact comparison with the first agglomerate of the class)
       {
         std::vector<int64_t> others;
@@ -720,7 +731,7 @@ StructuredRestrictorDevice::create(HipHandle &handle, StructuredMesh const &mesh
               any |= exc[c0 + (int64_t)agg_dims[0] * (c1 + (int64_t)agg_dims[1] * c2)];
         exc_node[nd] = any;
       }
-      if (identity && agglomerate[0] == 2 && agglomerate[1] == 2 && agglomerate[2] == 2)
+      if (identity && agglomerate[0] == 2 && agglomerate[1] == 2 && agglomerate[2] == 2 && !prolong_nodes)
       {
         // agglomerate positions all of whose (existing) agglomerates around are regular -> block kernel
         const int64_t vx = agg_dims[0] + 1, vy = agg_dims[1] + 1, vz = agg_dims[2] + 1;
@@ -789,6 +800,13 @@ SrArgs make_args(double const *planes, float const *planes_f, int32_t const *nod
 }
 } // namespace
 
+int StructuredRestrictorDevice::restrict_kernel() const
+{
+  if (_n_eig != 2 || _restrict_rows)
+    return kRestrictRows;
+  return (_a[0] == 2 && _a[1] == 2 && _a[2] == 2) ? kRestrictPair2 : kRestrictPairAny;
+}
+
 void StructuredRestrictorDevice::restrict_to_coarse(double const *x, double *y) const
 {
   ASSERT_THROW(x != nullptr && y != nullptr && x != y, "bad vectors");
@@ -796,10 +814,11 @@ void StructuredRestrictorDevice::restrict_to_coarse(double const *x, double *y) 
                        _n_eig, _patch, _exc.size() ? _exc.data() : nullptr, _exc_node.size() ? _exc_node.data() : nullptr, _table.data(),
                        _cls.size() ? _cls.data() : nullptr, _class_table.data());
   hipEvent_t stop = _handle.profiler.begin("csr_spmv_kernel", algorithmic_bytes(), _handle.stream);
-  if (_n_eig == 2)
+  const int kernel = restrict_kernel();
+  if (kernel != kRestrictRows)
   {
     const dim3 grid((unsigned int)(((_n_coarse / 2 + 255) / 256 + 7) / 8 * 8));
-    if (_a[0] == 2 && _a[1] == 2 && _a[2] == 2)
+    if (kernel == kRestrictPair2)
       hipLaunchKernelGGL(sr_restrict_pair_kernel<2>, grid, dim3(256), 0, _handle.stream, s, x, y);
     else
       hipLaunchKernelGGL(sr_restrict_pair_kernel<0>, grid, dim3(256), 0, _handle.stream, s, x, y);

@@ -28,6 +28,7 @@ public:
   int64_t n_coarse() const { return _n_coarse; }
   int64_t n_fine() const { return _n_fine; }
   int agglomerates(int d) const { return _na[d]; }
+  int agglomerate_cells(int d) const { return _a[d]; }
   int n_eigenvectors() const { return _n_eig; }
   // y_c = R x
   void restrict_to_coarse(double const *x, double *y) const;
@@ -94,10 +95,21 @@ private:
   DeviceBuffer<uint16_t> _cls;
   DeviceBuffer<double> _class_table; // [class][patch][n_eig]
   int _n_classes = 0;
+  int64_t _n_regular = 0;
+  bool _restrict_rows = false; // MFMG_SR_RESTRICT=rows: the row kernel whatever n_eig and the agglomerate
 
 public:
   int block_classes() const { return _n_classes; }
   bool float_planes() const { return _planes_f32.size() > 0; }
+  // agglomerates whose block equals the reference block `_table` (0: no table)
+  int64_t regular_agglomerates() const { return _n_regular; }
+  // agglomerate positions left to the thread-per-node part of the block kernel
+  int64_t listed_blocks() const { return (int64_t)_exc_blocks.size(); }
+  // the kernels restrict_to_coarse and prolongate launch (tests: which paths a case reaches)
+  enum RestrictKernel { kRestrictRows = 1, kRestrictPair2 = 2, kRestrictPairAny = 3 };
+  enum ProlongKernel { kProlongNodes = 1, kProlongBlock222 = 2 };
+  int restrict_kernel() const;
+  int prolong_kernel() const { return _blk_exc.size() > 0 ? kProlongBlock222 : kProlongNodes; }
 
 private:
   DeviceBuffer<int32_t> _node_dof; // DoF id of lexicographic node (empty when the numbering is lexicographic)

@@ -19,6 +19,8 @@ ERROR_INVALID_ARGUMENT = 3
 ERROR_DEVICE = 4
 NO_TRANS = 0
 TRANS = 1
+TRANS_SUBTRACT = 2   # restrictor_apply only: out -= R^T in
+RESTRICTOR_FORM_FIELDS = 11
 
 
 class MfmgError(RuntimeError):
@@ -205,6 +207,7 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_operator_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
         "mfmg_hip_hierarchy_smoother_apply": (C.c_int, [vp, i32, vp, vp]),
         "mfmg_hip_hierarchy_restrictor_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
+        "mfmg_hip_hierarchy_restrictor_form": (C.c_int, [vp, i32, P(i32), i32]),
         "mfmg_hip_hierarchy_ap_apply": (C.c_int, [vp, i32, vp, vp]),
         "mfmg_hip_hierarchy_coarse_apply": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_set_restrictor": (C.c_int, [vp, i64, i64, i64, vp, vp, vp]),
