@@ -95,11 +95,9 @@ struct mfmg_hip_hierarchy_s
   std::shared_ptr<TimerOutput> timer;
   std::unique_ptr<Hierarchy<DVector>> hierarchy;
   mfmg_hip_csr_s restrictor_view, coarse_view, amg_view, fine_view;
-  // "fine level precision" float: the matrix-free operator and its smoother in FP32 around the FP64 coarse levels
-  std::shared_ptr<MatrixFreeLaplaceDevice<float>> fine_f32;
-  DeviceBuffer<float> f32_a, f32_b, f32_c, f32_res;
   bool setup_values_float = false; // "setup value precision" of THIS hierarchy: on the handle only while one of its setups runs
-  std::shared_ptr<DVector> f32_res64, f32_bc, f32_xc, f32_corr64;
+  // "fine level precision" float: the matrix-free operator and its smoother in FP32 around the FP64 coarse levels
+  std::unique_ptr<HipFloatFineLevel> fine_f32;
 };
 
 extern "C" {
@@ -1101,7 +1099,7 @@ int mfmg_hip_hierarchy_create(mfmg_hip_context_t ctx, const char *evaluator_type
       require(type == "HipMatrixFreeMeshEvaluator", "\"fine level precision\" float needs the matrix-free evaluator");
       require(h->hierarchy->levels().size() == 2, "\"fine level precision\" float needs the two-level hierarchy");
       require(!ctx->handle->comm.enabled(), "\"fine level precision\" float is not available in a distributed run");
-      h->fine_f32 = std::make_shared<MatrixFreeLaplaceDevice<float>>(*ctx->handle, *mesh, ctx->handle->allow_cell_constant);
+      h->fine_f32.reset(new HipFloatFineLevel(*ctx->handle, *mesh, *h->hierarchy));
     }
     else
       require(precision == "double", "\"fine level precision\" must be double or float");
@@ -1138,106 +1136,13 @@ int mfmg_hip_hierarchy_apply(mfmg_hip_hierarchy_t h, const double *b, double *x)
   });
 }
 
-// Hierarchy::apply (hierarchy.hpp:246-309) with the fine level in FP32: pre-smoother, residual and post-smoother run
-// on float vectors through the FP32 instance of the matrix-free operator (same polynomial coefficients as the FP64
-// smoother), the residual is widened, restricted, solved for and prolongated in FP64, and the correction is
-// subtracted from the float iterate.
+// Hierarchy::apply with the fine level in FP32 (HipFloatFineLevel)
 int mfmg_hip_hierarchy_apply_f32(mfmg_hip_hierarchy_t h, const float *b, float *x)
 {
   return guarded([&] {
     require(h && b && x, "null argument");
     require(h->fine_f32 != nullptr, "the hierarchy was not built with \"fine level precision\" float");
-    HipHandle &hd = *h->handle;
-    auto const &levels = h->hierarchy->levels();
-    const int64_t n = level_size(h, 0), nc = level_size(h, 1);
-    auto smoother = std::dynamic_pointer_cast<HipSmoother const>(levels[0].get_smoother());
-    require(smoother != nullptr, "unexpected smoother type");
-    auto const &coef = smoother->coefficients();
-    const int d = (int)coef.size();
-    if (h->f32_a.size() == 0)
-    {
-      h->f32_a.resize(n);
-      h->f32_b.resize(n);
-      h->f32_res.resize(n);
-      h->f32_res64 = levels[0].get_operator()->build_range_vector();
-      h->f32_corr64 = levels[0].get_operator()->build_range_vector();
-    }
-    if (!h->f32_bc)
-    {
-      h->f32_bc = levels[1].get_operator()->build_range_vector();
-      h->f32_xc = levels[1].get_operator()->build_range_vector();
-    }
-    auto const &op = *h->fine_f32;
-    if (h->f32_c.size() == 0)
-      h->f32_c.resize(n);
-    // x_out <- x_in - B^-1 (A x_in - b) on two different vectors: the first K terms of the polynomial in one sweep where the
-    // FP32 operator offers it (all of them for degree <= smoother.fused_terms), else one fused kernel per term
-    const int fused = smoother->fused_terms();
-    auto smooth_to = [&](float const *x_in, float *x_out) {
-      float const *cur = x_in, *prev = nullptr;
-      int k0 = 0;
-      const int K = std::min(d, fused);
-      if (K >= 2 && coef[0].first == 0. && op.fused_sweep_available(K))
-      {
-        float alpha[3], beta[3];
-        for (int k = 0; k < K; ++k)
-        {
-          alpha[k] = (float)coef[k].first;
-          beta[k] = (float)coef[k].second;
-        }
-        if (K == d)
-        {
-          op.smoother_sweep(K, alpha, beta, b, x_in, x_out, nullptr);
-          return;
-        }
-        op.smoother_sweep(K, alpha, beta, b, x_in, h->f32_a.data(), h->f32_b.data());
-        cur = h->f32_a.data();
-        prev = h->f32_b.data();
-        k0 = K;
-      }
-      for (int k = k0; k < d; ++k)
-      {
-        // any scratch vector that is not x_k; x_{k-1} may be overwritten in place unless it is the caller's x_in
-        float *target = x_out;
-        if (k + 1 < d)
-        {
-          target = h->f32_a.data();
-          if (target == cur)
-            target = h->f32_b.data();
-        }
-        op.smoother_step(b, cur, prev, (float)coef[k].first, (float)coef[k].second, target);
-        prev = cur;
-        cur = target;
-      }
-    };
-    // the iterate alternates between x and a work vector, so that no application ends in a copy
-    float *it = x, *other = h->f32_c.data();
-    auto smooth = [&]() {
-      smooth_to(it, other);
-      std::swap(it, other);
-    };
-    if (h->hierarchy->is_preconditioner())
-      MFMG_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(float) * n, hd.stream));
-    for (unsigned int i = 0; i < h->hierarchy->n_smoothing_steps(); ++i)
-      smooth();
-    auto restrictor = levels[1].get_restrictor();
-    auto hip_restrictor = std::dynamic_pointer_cast<HipMatrixOperator const>(restrictor);
-    // b_c = R (A x - b): one pass over the FP32 vectors where the restrictor holds the rows of R A, otherwise the FP32
-    // residual, widened, and the restriction
-    if (!(hip_restrictor && hip_restrictor->restrict_residual_f32(*levels[0].get_operator(), it, b, *h->f32_bc)))
-    {
-      op.residual(it, b, h->f32_res.data());
-      vec::widen(hd, n, h->f32_res.data(), h->f32_res64->get_values());
-      restrictor->apply(*h->f32_res64, *h->f32_bc);
-    }
-    h->hierarchy->apply(*h->f32_bc, *h->f32_xc, 1);
-    restrictor->apply(*h->f32_xc, *h->f32_corr64, OperatorMode::TRANS);
-    vec::subtract_narrowed(hd, n, h->f32_corr64->get_values(), it);
-    for (unsigned int i = 0; i < h->hierarchy->n_smoothing_steps(); ++i)
-      smooth();
-    if (it != x)
-      MFMG_HIP_CHECK(hipMemcpyAsync(x, it, sizeof(float) * n, hipMemcpyDeviceToDevice, hd.stream));
-    (void)nc;
+    h->fine_f32->apply(b, x);
   });
 }
 
@@ -1500,9 +1405,6 @@ int mfmg_hip_hierarchy_set_restrictor(mfmg_hip_hierarchy_t h, int64_t n_rows, in
       h->handle->setup_values_float = h->setup_values_float;
       h->hierarchy->set_restrictor(std::make_shared<HipMatrixOperator>(m));
     }
-    // scratch vectors of apply_f32 were sized for the old coarse space
-    h->f32_bc.reset();
-    h->f32_xc.reset();
     MFMG_HIP_CHECK(hipStreamSynchronize(h->handle->stream));
   });
 }

@@ -1,4 +1,5 @@
 // Implementation of the HIP back-end classes declared in mfmg/hip_hierarchy_helpers.hpp.
+#include "mfmg/hierarchy.hpp" // (HipFloatFineLevel runs the coarse part of the cycle)
 #include "mfmg/hip_hierarchy_helpers.hpp"
 #include "probe_assembly.hpp"
 
@@ -882,6 +883,84 @@ void HipGalerkinHalfProduct::apply(DVector const &x, DVector &y, OperatorMode mo
 }
 
 // ---- HipSmoother ---------------------------------------------------------------
+namespace
+{
+// the most terms one sweep of an operator may run within smoother.fused_terms (0: none); a sweep of K terms that is available
+// is available for fewer
+template <typename Available>
+int largest_sweep(int fused_terms, Available available)
+{
+  int k = 0;
+  for (int K = 2; K <= fused_terms; ++K)
+    if (available(K))
+      k = K;
+  return k;
+}
+
+// The terms of the polynomial that run as one sweep: at most smoother.fused_terms, at most the `offered` sweep (and the sweep
+// from x_0 = 0 only where offered), and only from a first term without momentum (alpha_0 = 0: Jacobi and Chebyshev).
+SweepSchedule plan_sweeps(std::vector<std::pair<double, double>> const &coefficients, int fused_terms, int offered,
+                          bool offered_from_zero)
+{
+  SweepSchedule s;
+  const int d = (int)coefficients.size();
+  if (coefficients[0].first != 0.)
+    return s;
+  auto fits = [&](int K) { return K >= 2 && K <= offered ? K : 0; };
+  s.in_place = fits(std::min(d - 1, fused_terms));
+  s.out_of_place = fits(std::min(d, fused_terms));
+  s.from_zero = d == 3 && s.out_of_place == 3 && offered_from_zero;
+  return s;
+}
+
+// (alpha_k, beta_k) of the first n terms in the precision of the operator
+template <typename S>
+void first_terms(std::vector<std::pair<double, double>> const &coefficients, int n, S *alpha, S *beta)
+{
+  for (int k = 0; k < n; ++k)
+  {
+    alpha[k] = S(coefficients[k].first);
+    beta[k] = S(coefficients[k].second);
+  }
+}
+
+// The polynomial from x_in into x_out, for the FP64 smoother (V = DVector) and the FP32 fine level (V = float): the first
+// `swept` terms in one sweep -- into x_out when they are all of them, else x_K into scratch(0) and x_{K-1} into scratch(1) --,
+// then one launch per term.  The terms before the last land in the scratch vectors: a term may overwrite its own x_{k-1},
+// never its x_k (in place, x_in == x_out, the last term is a launch of its own).
+template <typename S, typename V, typename Scratch, typename Step, typename Sweep>
+void run_polynomial(std::vector<std::pair<double, double>> const &coefficients, int swept, V const *x_in, V *x_out, Scratch scratch,
+                    Step step, Sweep sweep)
+{
+  const int d = (int)coefficients.size();
+  V const *cur = x_in, *prev = nullptr;
+  if (swept > 0)
+  {
+    S alpha[3], beta[3];
+    first_terms(coefficients, swept, alpha, beta);
+    V *out = swept == d ? x_out : scratch(0);
+    V *out_prev = swept == d ? nullptr : scratch(1);
+    sweep(swept, alpha, beta, x_in, out, out_prev);
+    cur = out;
+    prev = out_prev;
+  }
+  for (int k = swept; k < d; ++k)
+  {
+    V *target = x_out;
+    if (k + 1 < d)
+    {
+      target = scratch(0);
+      if (target == cur)
+        target = scratch(1);
+    }
+    ASSERT_THROW(target != cur, "internal: a smoother term cannot overwrite the iterate it reads");
+    step(cur, prev, S(coefficients[k].first), S(coefficients[k].second), target);
+    prev = cur;
+    cur = target;
+  }
+}
+} // namespace
+
 HipSmoother::HipSmoother(std::shared_ptr<Operator<DVector> const> op, std::shared_ptr<ptree const> params)
     : Smoother<DVector>(op, params)
 {
@@ -900,8 +979,9 @@ HipSmoother::HipSmoother(std::shared_ptr<Operator<DVector> const> op, std::share
   {
     const std::string arith = to_lower(this->_params->get("smoother.sweep_arithmetic", "modes"));
     ASSERT_THROW(arith == "modes" || arith == "reference", "smoother.sweep_arithmetic must be modes or reference");
+    _sweep_reference = arith == "reference";
     if (auto mf = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator))
-      mf->get_mesh_evaluator()->get_device_operator()->set_fused_reference(arith == "reference");
+      mf->get_mesh_evaluator()->get_device_operator()->set_fused_reference(_sweep_reference);
   }
   if (_type == "jacobi")
   {
@@ -969,17 +1049,13 @@ HipSmoother::HipSmoother(std::shared_ptr<Operator<DVector> const> op, std::share
     // one coefficient per cell, the ghost planes it holds -- and differs between ranks whose materials differ: the ranks agree on
     // the smallest offer, in ONE collective that every rank reaches here.  Encoded as 2 K + z (z: the sweep from x_0 = 0, which
     // needs K = 3): the minimum over the ranks is the smallest K, with z set only where every rank has K = 3 and z.
-    int k = 0;
-    for (int K = 2; K <= _fused_terms; ++K)
-      if (_hip_operator->sweep_available(K))
-        k = K; // (available for K terms: also for fewer)
+    const int k = largest_sweep(_fused_terms, [&](int K) { return _hip_operator->sweep_available(K); });
     const bool z = k == 3 && _hip_operator->sweep_from_zero_available(3);
     const double mine = 2. * k + (z ? 1. : 0.);
     HipHandle &h = _hip_operator->get_hip_handle();
     const int agreed = (int)(h.comm.enabled() ? -h.allreduce_max(-mine) : mine);
-    _sweep_max = agreed / 2;
-    _sweep_from_zero = (agreed & 1) != 0;
-    ASSERT_THROW(_sweep_max <= k, "internal: the ranks agreed on a sweep this rank cannot run");
+    ASSERT_THROW(agreed / 2 <= k, "internal: the ranks agreed on a sweep this rank cannot run");
+    _schedule = plan_sweeps(_coefficients, _fused_terms, agreed / 2, (agreed & 1) != 0);
   }
 }
 
@@ -1072,90 +1148,39 @@ void HipSmoother::estimate_eigenvalues(int n_iterations, double residual, double
   max_est = w.back();
 }
 
-// terms [k0, d) of the polynomial, one fused kernel per term: `cur` = x_{k0}, `prev` = x_{k0 - 1} (null for k0 = 0); the last
-// term lands in x_out, the others alternate between the scratch vectors (a term may overwrite its own x_{k-1}, never its x_k)
-void HipSmoother::run_terms(int k0, DVector const &b, DVector const *cur, DVector const *prev, DVector &x_out) const
+DVector *HipSmoother::scratch(int i) const
 {
-  const int d = (int)_coefficients.size();
-  for (int k = k0; k < d; ++k)
-  {
-    DVector *target = &x_out;
-    if (k + 1 < d)
-    {
-      // any scratch vector that is not x_k (x_{k-1} may be overwritten in place)
-      if (!_scratch_a)
-        _scratch_a = this->_operator->build_domain_vector();
-      target = _scratch_a.get();
-      if (target == cur)
-      {
-        if (!_scratch_b)
-          _scratch_b = this->_operator->build_domain_vector();
-        target = _scratch_b.get();
-      }
-    }
-    ASSERT_THROW(target != cur, "internal: a smoother term cannot overwrite the iterate it reads");
-    _hip_operator->smoother_step(b, *cur, prev, _coefficients[k].first, _coefficients[k].second, *target);
-    prev = cur;
-    cur = target;
-  }
+  auto &s = i == 0 ? _scratch_a : _scratch_b;
+  if (!s)
+    s = this->_operator->build_domain_vector();
+  return s.get();
 }
 
-// the first K terms in one sweep where the operator offers it: x_K -> out, x_{K-1} -> out_prev
-bool HipSmoother::run_sweep(int K, DVector const &b, DVector const &x_in, DVector &out, DVector *out_prev) const
+void HipSmoother::run(int swept, DVector const &b, DVector const &x_in, DVector &x_out) const
 {
-  if (K < 2 || K > _fused_terms || K > _sweep_max)
-    return false;
-  double alpha[3], beta[3];
-  for (int k = 0; k < K; ++k)
-  {
-    alpha[k] = _coefficients[k].first;
-    beta[k] = _coefficients[k].second;
-  }
-  if (alpha[0] != 0.)
-    return false;
-  // (K <= _sweep_max: every rank takes this path, a refusal here would leave the ranks with different exchanges)
-  ASSERT_THROW(_hip_operator->smoother_sweep(K, alpha, beta, b, x_in, out, out_prev), "internal: the agreed smoother sweep was refused");
-  return true;
+  run_polynomial<double>(
+      _coefficients, swept, &x_in, &x_out, [&](int i) { return scratch(i); },
+      [&](DVector const *x, DVector const *x_prev, double alpha, double beta, DVector *out) {
+        _hip_operator->smoother_step(b, *x, x_prev, alpha, beta, *out);
+      },
+      [&](int K, double const *alpha, double const *beta, DVector const *x, DVector *out, DVector *out_prev) {
+        // (the ranks agreed on this sweep at setup: a refusal here would leave them with different exchanges)
+        ASSERT_THROW(_hip_operator->smoother_sweep(K, alpha, beta, b, *x, *out, out_prev), "internal: the agreed smoother sweep was refused");
+      });
 }
 
 void HipSmoother::apply(DVector const &b, DVector &x) const
 {
   // x <- x - B^{-1}(A x - b) with B^{-1} the Jacobi / Chebyshev polynomial.  In place, so the last term must be a launch of
-  // its own that lands in x: the terms before it run as one sweep into the scratch vectors where the operator can (d >= 3),
-  // else one fused kernel per polynomial term.
-  const int d = (int)_coefficients.size();
-  if (!_scratch_a)
-    _scratch_a = this->_operator->build_domain_vector();
-  if (d == 1)
+  // its own that lands in x: the terms before it run as one sweep into the scratch vectors where the schedule has one, else
+  // one fused kernel per polynomial term.
+  if (_coefficients.size() == 1)
   {
-    _hip_operator->smoother_step(b, x, nullptr, 0., _coefficients[0].second, *_scratch_a);
-    x = *_scratch_a;
+    _hip_operator->smoother_step(b, x, nullptr, 0., _coefficients[0].second, *scratch(0));
+    x = *scratch(0);
     return;
   }
-  if (d >= 3 && !_scratch_b)
-    _scratch_b = this->_operator->build_domain_vector();
-  if (d >= 3)
-  {
-    const int K = std::min(d - 1, _fused_terms);
-    if (K >= 2 && run_sweep(K, b, x, *_scratch_a, _scratch_b.get()))
-    {
-      run_terms(K, b, _scratch_a.get(), _scratch_b.get(), x);
-      return;
-    }
-  }
-  // term by term: x -> a -> b -> ... -> x
-  std::vector<DVector *> target(d);
-  target[d - 1] = &x;
-  for (int k = d - 2, flip = 0; k >= 0; --k, flip ^= 1)
-    target[k] = flip ? _scratch_b.get() : _scratch_a.get();
-  DVector const *cur = &x;
-  DVector const *prev = nullptr;
-  for (int k = 0; k < d; ++k)
-  {
-    _hip_operator->smoother_step(b, *cur, prev, _coefficients[k].first, _coefficients[k].second, *target[k]);
-    prev = cur;
-    cur = target[k];
-  }
+  run(_schedule.in_place, b, x, x);
 }
 
 void HipSmoother::apply_zero_guess(DVector const &b, DVector &x) const
@@ -1173,69 +1198,98 @@ void HipSmoother::apply_zero_guess(DVector const &b, DVector &x) const
                                 _hip_operator->get_diagonal_inverse(), b.get_values(), x.get_values());
 }
 
-void HipSmoother::sweep_terms(int &in_place, int &out_of_place) const
-{
-  const int d = (int)_coefficients.size();
-  in_place = out_of_place = 0;
-  if (d >= 3)
-  {
-    const int K = std::min(d - 1, _fused_terms);
-    if (K >= 2 && K <= _sweep_max)
-      in_place = K;
-  }
-  const int K = std::min(d, _fused_terms);
-  if (K >= 2 && K <= _sweep_max)
-    out_of_place = K;
-}
-
-bool HipSmoother::prefers_out_of_place() const
-{
-  const int d = (int)_coefficients.size();
-  const int K = std::min(d, _fused_terms);
-  return K >= 2 && K <= _sweep_max;
-}
-
 void HipSmoother::apply_to(DVector const &b, DVector const &x_in, DVector &x_out) const
 {
   ASSERT_THROW(x_in.get_values() != x_out.get_values(), "apply_to needs two vectors");
-  const int d = (int)_coefficients.size();
-  if (d == 1)
-  {
-    _hip_operator->smoother_step(b, x_in, nullptr, 0., _coefficients[0].second, x_out);
-    return;
-  }
-  const int K = std::min(d, _fused_terms);
-  if (K == d && run_sweep(K, b, x_in, x_out, nullptr))
-    return;
-  if (K < d && K >= 2)
-  {
-    if (!_scratch_a)
-      _scratch_a = this->_operator->build_domain_vector();
-    if (!_scratch_b)
-      _scratch_b = this->_operator->build_domain_vector();
-    if (run_sweep(K, b, x_in, *_scratch_a, _scratch_b.get()))
-    {
-      run_terms(K, b, _scratch_a.get(), _scratch_b.get(), x_out);
-      return;
-    }
-  }
-  run_terms(0, b, &x_in, nullptr, x_out);
+  run(_schedule.out_of_place, b, x_in, x_out);
 }
 
 bool HipSmoother::apply_from_zero(DVector const &b, DVector &x_out) const
 {
   // the whole polynomial as one sweep that does not read x_0 = 0 (three terms: the kernels that carry the variant)
-  const int d = (int)_coefficients.size();
-  if (d != 3 || _fused_terms < 3 || _sweep_max < 3 || !_sweep_from_zero || _coefficients[0].first != 0.)
+  if (!_schedule.from_zero)
     return false;
   double alpha[3], beta[3];
-  for (int k = 0; k < 3; ++k)
-  {
-    alpha[k] = _coefficients[k].first;
-    beta[k] = _coefficients[k].second;
-  }
+  first_terms(_coefficients, 3, alpha, beta);
   // (the ranks agreed on the sweep from zero at setup; a sweep tile set on this operator since then may still refuse it here)
   return _hip_operator->smoother_sweep_from_zero(3, alpha, beta, b, x_out);
+}
+
+// ---- HipFloatFineLevel -----------------------------------------------------------
+HipFloatFineLevel::HipFloatFineLevel(HipHandle &handle, mfmg_hip_mesh_desc const &mesh, Hierarchy<DVector> const &hierarchy)
+    : _hierarchy(hierarchy), _smoother(std::dynamic_pointer_cast<HipSmoother const>(hierarchy.levels()[0].get_smoother())),
+      _op(handle, mesh, handle.allow_cell_constant)
+{
+  ASSERT_THROW(_smoother != nullptr, "unexpected smoother type");
+  // the sweep as the FP64 smoother runs it, from what this operator offers; the pre-smoother of a preconditioner application
+  // starts from a zeroed x
+  _op.set_fused_reference(_smoother->sweep_reference());
+  const int fused = _smoother->fused_terms();
+  _schedule = plan_sweeps(_smoother->coefficients(), fused, largest_sweep(fused, [&](int K) { return _op.fused_sweep_available(K); }),
+                          false);
+}
+
+// x_out <- x_in - B^-1 (A x_in - b) on two different vectors, with the polynomial of the FP64 smoother
+void HipFloatFineLevel::smooth_to(float const *b, float const *x_in, float *x_out) const
+{
+  run_polynomial<float>(
+      _smoother->coefficients(), _schedule.out_of_place, x_in, x_out, [&](int i) { return (i == 0 ? _scratch_a : _scratch_b).data(); },
+      [&](float const *x, float const *x_prev, float alpha, float beta, float *out) { _op.smoother_step(b, x, x_prev, alpha, beta, out); },
+      [&](int K, float const *alpha, float const *beta, float const *x, float *out, float *out_prev) {
+        _op.smoother_sweep(K, alpha, beta, b, x, out, out_prev);
+      });
+}
+
+void HipFloatFineLevel::apply(float const *b, float *x) const
+{
+  HipHandle &hd = _op.handle();
+  auto const &levels = _hierarchy.levels();
+  const int64_t n = _op.n_dofs();
+  auto const &fine = *levels[0].get_operator();
+  auto const &coarse = *levels[1].get_operator();
+  if (_work.size() == 0)
+  {
+    _scratch_a.resize(n);
+    _scratch_b.resize(n);
+    _res.resize(n);
+    _work.resize(n);
+    _res64 = fine.build_range_vector();
+    _corr64 = fine.build_range_vector();
+  }
+  // (set_restrictor may have changed the coarse space since the last cycle)
+  if (!_b_coarse || _b_coarse->size() != (int64_t)coarse.grid_complexity())
+  {
+    _b_coarse = coarse.build_range_vector();
+    _x_coarse = coarse.build_range_vector();
+  }
+  // the iterate alternates between x and a work vector, so that no application ends in a copy
+  float *it = x, *other = _work.data();
+  auto smooth = [&] {
+    for (unsigned int i = 0; i < _hierarchy.n_smoothing_steps(); ++i)
+    {
+      smooth_to(b, it, other);
+      std::swap(it, other);
+    }
+  };
+  if (_hierarchy.is_preconditioner())
+    MFMG_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(float) * n, hd.stream));
+  smooth();
+  auto restrictor = levels[1].get_restrictor();
+  auto hip_restrictor = std::dynamic_pointer_cast<HipMatrixOperator const>(restrictor);
+  // b_c = R (A x - b): one pass over the FP32 vectors where the restrictor holds the rows of R A, otherwise the FP32
+  // residual, widened, and the restriction
+  if (!(hip_restrictor && hip_restrictor->restrict_residual_f32(fine, it, b, *_b_coarse)))
+  {
+    _op.residual(it, b, _res.data());
+    vec::widen(hd, n, _res.data(), _res64->get_values());
+    restrictor->apply(*_res64, *_b_coarse);
+  }
+  _hierarchy.apply(*_b_coarse, *_x_coarse, 1);
+  restrictor->apply(*_x_coarse, *_corr64, OperatorMode::TRANS);
+  vec::subtract_narrowed(hd, n, _corr64->get_values(), it);
+  smooth();
+  if (it != x)
+    MFMG_HIP_CHECK(hipMemcpyAsync(x, it, sizeof(float) * n, hipMemcpyDeviceToDevice, hd.stream));
 }
 
 // ---- HipSolver -----------------------------------------------------------------

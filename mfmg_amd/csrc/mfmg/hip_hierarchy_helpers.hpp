@@ -273,6 +273,15 @@ private:
 };
 
 // ---- smoother ------------------------------------------------------------------
+// The polynomial terms a smoother runs as ONE multi-term sweep (mf_cheb_fused.hip), planned once from the degree,
+// smoother.fused_terms and what the operator offers; the other terms are one launch each.
+struct SweepSchedule
+{
+  int in_place = 0;       // apply(): the first terms in one sweep into scratch vectors, the last term a launch into x (0: none)
+  int out_of_place = 0;   // apply_to(): the first terms in one sweep, the whole polynomial where it is that short (0: none)
+  bool from_zero = false; // apply_from_zero(): the whole polynomial in one sweep from x_0 = 0, which is not read
+};
+
 // Twin of CudaSmoother (source/cuda/cuda_smoother.cu:99-173, Jacobi) and of
 // DealIIMatrixFreeSmoother (source/dealii/dealii_matrix_free_smoother.cc:19-76, Chebyshev).
 class HipSmoother : public Smoother<DVector>
@@ -287,11 +296,17 @@ public:
   // (smoother.fused_terms, default 3), no copy back from a scratch vector
   void apply_to(DVector const &b, DVector const &x_in, DVector &x_out) const override;
   bool apply_from_zero(DVector const &b, DVector &x_out) const override;
-  bool prefers_out_of_place() const override;
+  bool prefers_out_of_place() const override { return _schedule.out_of_place > 0; }
   int fused_terms() const { return _fused_terms; }
+  // smoother.sweep_arithmetic "reference": the sweep computes with the one-term kernel's arithmetic, bit for bit
+  bool sweep_reference() const { return _sweep_reference; }
   // polynomial terms the fine smoother runs as ONE sweep: by apply() (in place: the last term is a launch of its own) and by
   // apply_to() (0: one launch per term)
-  void sweep_terms(int &in_place, int &out_of_place) const;
+  void sweep_terms(int &in_place, int &out_of_place) const
+  {
+    in_place = _schedule.in_place;
+    out_of_place = _schedule.out_of_place;
+  }
 
   int degree() const { return (int)_coefficients.size(); }
   // (alpha_k, beta_k) of the polynomial terms: x_{k+1} = x_k + alpha_k (x_k - x_{k-1}) - beta_k D^-1 (A x_k - b)
@@ -302,8 +317,9 @@ public:
 
 private:
   void estimate_eigenvalues(int n_iterations, double residual, double &min_est, double &max_est) const;
-  void run_terms(int k0, DVector const &b, DVector const *cur, DVector const *prev, DVector &x_out) const;
-  bool run_sweep(int K, DVector const &b, DVector const &x_in, DVector &out, DVector *out_prev) const;
+  // the polynomial from x_in into x_out, its first `swept` terms in one sweep (SweepSchedule)
+  void run(int swept, DVector const &b, DVector const &x_in, DVector &x_out) const;
+  DVector *scratch(int i) const; // built on first use
 
   std::shared_ptr<HipOperator const> _hip_operator;
   std::string _type;
@@ -311,11 +327,34 @@ private:
   double _lambda_min = 1., _lambda_max = 1.;
   std::vector<std::pair<double, double>> _coefficients; // (alpha_k, beta_k)
   int _fused_terms = 3; // polynomial terms per sweep (1: one launch per term)
-  // the most terms one sweep may run (0: none) and whether the sweep from a zero guess may run: what this rank's operator
-  // offers, and on a distributed context the smallest over the ranks, agreed once at setup (the sweep changes the exchanges)
-  int _sweep_max = 0;
-  bool _sweep_from_zero = false;
+  bool _sweep_reference = false;
+  SweepSchedule _schedule;
   mutable std::shared_ptr<DVector> _scratch_a, _scratch_b;
+};
+
+template <typename VectorType>
+class Hierarchy;
+
+// "fine level precision" float: Hierarchy::apply of a two-level hierarchy (hierarchy.hpp:246-309) with the fine level in FP32.
+// Pre-smoother, residual and post-smoother run on float vectors through an FP32 instance of the matrix-free operator (the
+// polynomial of the FP64 smoother); the residual is widened, restricted, solved for and prolongated in FP64, and the
+// correction is subtracted from the float iterate.  One rank.
+class HipFloatFineLevel
+{
+public:
+  HipFloatFineLevel(HipHandle &handle, mfmg_hip_mesh_desc const &mesh, Hierarchy<DVector> const &hierarchy);
+  // one V-cycle on the FP32 vectors b, x of the fine DoFs
+  void apply(float const *b, float *x) const;
+
+private:
+  void smooth_to(float const *b, float const *x_in, float *x_out) const;
+
+  Hierarchy<DVector> const &_hierarchy;
+  std::shared_ptr<HipSmoother const> _smoother;
+  MatrixFreeLaplaceDevice<float> _op;
+  SweepSchedule _schedule; // of this operator's offer: out of place only
+  mutable DeviceBuffer<float> _scratch_a, _scratch_b, _work, _res;
+  mutable std::shared_ptr<DVector> _res64, _corr64, _b_coarse, _x_coarse;
 };
 
 // ---- coarse solver -------------------------------------------------------------

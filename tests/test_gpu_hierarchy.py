@@ -1266,19 +1266,26 @@ def test_cycle_with_the_multi_term_sweep_is_the_term_by_term_cycle(ctx, n, degre
     """The fine-level Chebyshev smoother as ONE sweep over the mesh (the hierarchy alternates between x and a workspace vector,
     degree <= 3; beyond that three terms per sweep and a launch per further term) against `smoother.fused_terms 1`, a launch per
     term on chunk records with one halo lane: the same V-cycle bit for bit -- iterates and residual history, any number of
-    smoothing steps (an odd number of out-of-place applications ends in the workspace vector and is copied back)."""
+    smoothing steps (an odd number of out-of-place applications ends in the workspace vector and is copied back).  The same
+    for the fine level in FP32 (apply_f32), whose sweep follows smoother.sweep_arithmetic as well."""
     prob = M.LaplaceProblem(n, "constant", device="cuda")
     sm = {"type": "Chebyshev", "degree": degree, "smoothing_range": 20.0, "n_smoothing_steps": steps, "lambda_max": 1.9, "lambda_min": 0.095,
           "sweep_arithmetic": "reference"}
     amg = {"coarsest_size": 300, "pre_smoothing_levels": 0}
-    h_sweep = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", prob, base_params(smoother=dict(sm), solver={"type": "amg", "amg": dict(amg)}))
+
+    def hierarchies(**extra):
+        h_sweep = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", prob,
+                              base_params(smoother=dict(sm), solver={"type": "amg", "amg": dict(amg)}, **extra))
+        ctx.set_mf_fused_terms(1)
+        try:
+            h_terms = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", prob,
+                                  base_params(smoother=dict(sm, fused_terms=1), solver={"type": "amg", "amg": dict(amg)}, **extra))
+        finally:
+            ctx.set_mf_fused_terms(3)
+        return h_sweep, h_terms
+
+    h_sweep, h_terms = hierarchies()
     assert h_sweep.smoother_sweep_terms() == (min(degree - 1, 3) if degree >= 3 else 0, min(degree, 3))
-    ctx.set_mf_fused_terms(1)
-    try:
-        h_terms = M.Hierarchy(ctx, "HipMatrixFreeMeshEvaluator", prob,
-                              base_params(smoother=dict(sm, fused_terms=1), solver={"type": "amg", "amg": dict(amg)}))
-    finally:
-        ctx.set_mf_fused_terms(3)
     assert h_terms.smoother_sweep_terms() == (0, 0)
     rng = np.random.default_rng(8)
     free = prob.constrained.cpu().numpy() != 1
@@ -1296,6 +1303,15 @@ def test_cycle_with_the_multi_term_sweep_is_the_term_by_term_cycle(ctx, n, degre
         runs.append((x.clone(), y.clone()))
     assert torch.equal(runs[0][0], runs[1][0])
     assert torch.equal(runs[0][1], runs[1][1])
+    del h_sweep, h_terms
+    runs = []
+    for h in hierarchies(**{"fine level precision": "float"}):
+        x, bb = dev(x0).float(), dev(b).float()
+        for _ in range(4):
+            h.apply_f32(bb, x)
+        ctx.synchronize()
+        runs.append(x.clone())
+    assert torch.equal(runs[0], runs[1])
 
 
 @pytest.mark.parametrize("cells", [32, 64])
