@@ -11,8 +11,13 @@ res[20] / res[19] (`:74-101`); true -> CG preconditioned by the hierarchy (`:103
 hyper-cube of `laplace.n_refinements` global refinements with Q1 elements only (`laplace.fe_degree` other than 1 is
 refused; where the file names none the reference takes degree 4, `:269`, this script degree 1), and a matrix-based run whose input file asks for an Ifpack relaxation (Gauss-Seidel, the file's default) takes
 Jacobi, the CUDA back-end's smoother, with a note.
+
+`--numbering dealii` numbers the DoFs as deal.II's DoFHandler::distribute_dofs does (cells in Morton order, vertex DoFs at first
+touch), `random` by a seeded permutation; both set `"internal numbering" lexicographic` (matrix-free runs), so that the hierarchy
+runs on the kernels of the lexicographic numbering and permutes vectors at its interface.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -28,6 +33,7 @@ def main(argv=None):
     ap.add_argument("-d", "--dim", type=int, default=2)
     ap.add_argument("-m", "--matrix_free", type=int, default=0)
     ap.add_argument("-t", "--tolerance", type=float, default=1e-6)
+    ap.add_argument("--numbering", choices=["lexicographic", "dealii", "random"], default="lexicographic")
     args = ap.parse_args(argv)
     if args.dim not in (2, 3):
         raise SystemExit("dim must be 2 or 3")
@@ -58,7 +64,14 @@ def main(argv=None):
             n_coarse *= max(c // int(params.get("agglomeration", {}).get("nx", 2)), 1)
         params["solver"]["type"] = "lu_dense" if n_coarse <= 4096 else "amg"
     ctx = M.Context()
-    prob = M.LaplaceProblem(cells, material, device="cuda")
+    numbering = None
+    if args.numbering == "dealii":
+        numbering = M.dealii_numbering(cells)
+    elif args.numbering == "random":
+        numbering = torch.randperm(math.prod(c + 1 for c in cells), generator=torch.Generator().manual_seed(7))
+    if numbering is not None and args.matrix_free:
+        params["internal numbering"] = "lexicographic"
+    prob = M.LaplaceProblem(cells, material, device="cuda", dof_numbering=numbering)
     evaluator = "HipMatrixFreeMeshEvaluator" if args.matrix_free else "HipMeshEvaluator"
     h = M.Hierarchy(ctx, evaluator, prob, params)
     g = torch.Generator(device="cuda").manual_seed(1)

@@ -381,6 +381,27 @@ int mfmg_hip_hierarchy_create(mfmg_hip_context_t ctx, const char *evaluator_type
                               const mfmg_hip_mesh_desc *mesh, const char *params_info,
                               mfmg_hip_hierarchy_t *out);
 int mfmg_hip_hierarchy_destroy(mfmg_hip_hierarchy_t h);
+/* Parameter "internal numbering" (top level of `params_info`): caller (default) | lexicographic.
+ * The kernels of the fine level compute their DoF ids, run the whole Chebyshev polynomial as one sweep and restrict the residual
+ * in one pass only where the DoF numbering is lexicographic on the node grid; a mesh numbered otherwise (deal.II's
+ * DoFHandler::distribute_dofs: cells in Morton order, tests/laplace_matrix_free.hpp:269-279; any DoFRenumbering) is correct in
+ * `caller` mode but takes one launch per smoother term and an indexed access per DoF in every pass.  `lexicographic`: the
+ * hierarchy is built and run in the lexicographic numbering of the nodes -- the node -> DoF map is derived from cell_dofs as it
+ * is validated anyway -- and vectors are permuted where they cross this interface: every fine-level vector argument of the
+ * mfmg_hip_hierarchy_* calls, the columns of get_restrictor / set_restrictor and what is keyed on a DoF id (the start vector of
+ * the Chebyshev eigenvalue estimate) stay in the CALLER's numbering.  mfmg_hip_hierarchy_apply / _vmult / _apply_f32 cost two
+ * launches of the kernel "dof_permutation" (dof_permutation.hip: the gather of b -- and of x unless "is preconditioner" --
+ * and the scatter of x in place of the copy that ends the cycle), mfmg_hip_hierarchy_solve_cg two per solve whatever the
+ * iteration count; the level-wise calls permute per call.  A numbering that already is lexicographic launches nothing and gives
+ * the results of `caller` mode bit for bit.  Matrix-free evaluator, one process (MFMG_HIP_ERROR_INVALID_ARGUMENT otherwise).
+ * In this mode the handle of mfmg_hip_hierarchy_get_restrictor is a copy with renumbered columns made by that call.
+ *   lexicographic: 1 when the hierarchy was built with "internal numbering" lexicographic
+ *   permuted:      1 when vectors are permuted, 0 where the caller's numbering already was lexicographic (or in caller mode) */
+int mfmg_hip_hierarchy_internal_numbering(mfmg_hip_hierarchy_t h, int *lexicographic, int *permuted);
+/* The permutation itself, for tests and for callers that keep Krylov vectors of their own in the internal numbering:
+ * to_internal != 0: out[node] = in[caller's id of node], else out[caller's id of node] = in[node]; fp32 != 0: float vectors.
+ * `in` and `out` are different device vectors of the fine level's size.  A plain copy where nothing is permuted. */
+int mfmg_hip_hierarchy_permute(mfmg_hip_hierarchy_t h, int to_internal, int fp32, const void *in, void *out);
 /* Hierarchy::apply(b, x, 0)  (hierarchy.hpp:246-309) */
 int mfmg_hip_hierarchy_apply(mfmg_hip_hierarchy_t h, const double *b, double *x);
 /* Hierarchy::vmult(x, b)     (hierarchy.hpp:238-244) */

@@ -538,6 +538,22 @@ class Hierarchy:
         check(self._lib.mfmg_hip_hierarchy_level_size(self.handle, level, C.byref(n)))
         return n.value
 
+    def internal_numbering(self):
+        """(lexicographic, permuted): built with "internal numbering" lexicographic; vectors are permuted at the interface
+        (0 where the caller's numbering already was lexicographic)."""
+        a, b = C.c_int(), C.c_int()
+        check(self._lib.mfmg_hip_hierarchy_internal_numbering(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def permute(self, vin: torch.Tensor, vout: torch.Tensor, to_internal: bool = True):
+        """vout = vin in the internal numbering of the hierarchy (to_internal) or back in the caller's; float64 or float32
+        fine-level vectors, vin is not vout."""
+        n = self.level_size(0)
+        assert vin.dtype == vout.dtype and vin.dtype in (torch.float64, torch.float32)
+        fp32 = vin.dtype == torch.float32
+        check(self._lib.mfmg_hip_hierarchy_permute(self.handle, int(bool(to_internal)), int(fp32), _dev_ptr(vin, n, vin.dtype),
+                                                   _dev_ptr(vout, n, vout.dtype)))
+
     def apply(self, b: torch.Tensor, x: torch.Tensor):
         n = self.level_size(0)
         check(self._lib.mfmg_hip_hierarchy_apply(self.handle, _dev_ptr(b, n), _dev_ptr(x, n)))

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "cell_contraction.hpp"
+#include "dof_permutation.hpp"
 #include "halo_transport.hpp"
 #include "mfmg/hierarchy.hpp"
 
@@ -98,6 +99,25 @@ struct mfmg_hip_hierarchy_s
   bool setup_values_float = false; // "setup value precision" of THIS hierarchy: on the handle only while one of its setups runs
   // "fine level precision" float: the matrix-free operator and its smoother in FP32 around the FP64 coarse levels
   std::unique_ptr<HipFloatFineLevel> fine_f32;
+  // "internal numbering" lexicographic: the hierarchy above was built from the mesh in the lexicographic numbering of its nodes.
+  // `perm` is set where the caller's numbering is another one: vectors are then permuted where they cross this file, into and
+  // out of library-owned vectors of the fine level (built at first use)
+  bool lexicographic = false;
+  std::unique_ptr<DofPermutation> perm;
+  DeviceBuffer<double> work[2];
+  DeviceBuffer<float> work_f32[2];
+  double *workspace(int i)
+  {
+    if (work[i].size() == 0)
+      work[i].resize((size_t)perm->n_dofs());
+    return work[i].data();
+  }
+  float *workspace_f32(int i)
+  {
+    if (work_f32[i].size() == 0)
+      work_f32[i].resize((size_t)perm->n_dofs());
+    return work_f32[i].data();
+  }
 };
 
 extern "C" {
@@ -1056,6 +1076,23 @@ int mfmg_hip_hierarchy_create(mfmg_hip_context_t ctx, const char *evaluator_type
     std::unique_ptr<mfmg_hip_hierarchy_s> h(new mfmg_hip_hierarchy_s);
     h->handle = ctx->handle.get();
     std::string type(evaluator_type);
+    // "internal numbering" lexicographic: evaluator, hierarchy and FP32 fine level are built from the mesh in the lexicographic
+    // numbering of its nodes (dof_permutation.hpp); a caller's numbering that is lexicographic already changes nothing
+    const std::string numbering = params->get("internal numbering", "caller");
+    if (numbering == "lexicographic")
+    {
+      require(type == "HipMatrixFreeMeshEvaluator", "\"internal numbering\" lexicographic needs the matrix-free evaluator");
+      require(!ctx->handle->comm.enabled(), "\"internal numbering\" lexicographic is not available in a distributed run (the local "
+                                            "numbering of a rank is the library's own)");
+      h->lexicographic = true;
+      h->perm.reset(new DofPermutation(*ctx->handle, *mesh));
+      if (h->perm->identity())
+        h->perm.reset();
+      else
+        mesh = &h->perm->lexicographic_mesh();
+    }
+    else
+      require(numbering == "caller", "\"internal numbering\" must be caller or lexicographic");
     if (type == "HipMatrixFreeMeshEvaluator")
       h->evaluator = std::make_shared<HipMatrixFreeMeshEvaluator>(*ctx->handle, *mesh);
     else if (type == "HipMeshEvaluator")
@@ -1074,9 +1111,12 @@ int mfmg_hip_hierarchy_create(mfmg_hip_context_t ctx, const char *evaluator_type
         {
           keep = hd.setup_values_float;
           hd.setup_values_float = false;
+          hd.setup_caller_ids = nullptr;
         }
       } restore{*ctx->handle, h->setup_values_float};
       ctx->handle->setup_values_float = false;
+      // what the setup keys on a DoF id takes the caller's id of the node (HipSmoother::estimate_eigenvalues)
+      ctx->handle->setup_caller_ids = h->perm ? h->perm->node_dof_host().data() : nullptr;
       h->hierarchy.reset(new Hierarchy<DVector>(nullptr, h->evaluator, params, h->timer));
     }
     // "release setup matrices" true: once the hierarchy stands, the table-driven operators (A_c, the operators of the aggregation
@@ -1104,6 +1144,8 @@ int mfmg_hip_hierarchy_create(mfmg_hip_context_t ctx, const char *evaluator_type
     else
       require(precision == "double", "\"fine level precision\" must be double or float");
     MFMG_HIP_CHECK(hipStreamSynchronize(ctx->handle->stream));
+    if (h->perm)
+      h->perm->release_mesh();
     *out = h.release();
   });
 }
@@ -1126,13 +1168,69 @@ int64_t level_size(mfmg_hip_hierarchy_t h, int level)
 }
 } // namespace
 
+namespace
+{
+// Hierarchy::apply on vectors in the caller's numbering while the hierarchy runs in the lexicographic one: ONE launch gathers b
+// -- and x, unless the cycle starts from zero and never reads it --, and the copy into x that ends the cycle is the scatter
+void apply_permuted(mfmg_hip_hierarchy_t h, const double *b, double *x)
+{
+  const int64_t n = level_size(h, 0);
+  double *wb = h->workspace(0), *wx = h->workspace(1);
+  if (h->hierarchy->is_preconditioner())
+    h->perm->gather(b, wb);
+  else
+    h->perm->gather2(b, static_cast<double const *>(x), wb, wx);
+  DVector bv(*h->handle, n, wb), xv(*h->handle, n, wx);
+  const Hierarchy<DVector>::Deliver deliver = [&](DVector const &result) { h->perm->scatter(result.get_values(), x); };
+  h->hierarchy->apply(bv, xv, 0, &deliver);
+}
+} // namespace
+
 int mfmg_hip_hierarchy_apply(mfmg_hip_hierarchy_t h, const double *b, double *x)
 {
   return guarded([&] {
     require(h && b && x, "null argument");
+    if (h->perm)
+      return apply_permuted(h, b, x);
     const int64_t n = level_size(h, 0);
     DVector bv(*h->handle, n, const_cast<double *>(b)), xv(*h->handle, n, x);
     h->hierarchy->apply(bv, xv);
+  });
+}
+
+int mfmg_hip_hierarchy_internal_numbering(mfmg_hip_hierarchy_t h, int *lexicographic, int *permuted)
+{
+  return guarded([&] {
+    require(h && lexicographic && permuted, "null argument");
+    *lexicographic = h->lexicographic ? 1 : 0;
+    *permuted = h->perm ? 1 : 0;
+  });
+}
+
+int mfmg_hip_hierarchy_permute(mfmg_hip_hierarchy_t h, int to_internal, int fp32, const void *in, void *out)
+{
+  return guarded([&] {
+    require(h && in && out, "null argument");
+    require(in != out, "the permutation does not work in place");
+    if (!h->perm)
+    {
+      const size_t bytes = (size_t)level_size(h, 0) * (fp32 ? sizeof(float) : sizeof(double));
+      MFMG_HIP_CHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, h->handle->stream));
+    }
+    else if (fp32)
+    {
+      if (to_internal)
+        h->perm->gather(static_cast<float const *>(in), static_cast<float *>(out));
+      else
+        h->perm->scatter(static_cast<float const *>(in), static_cast<float *>(out));
+    }
+    else
+    {
+      if (to_internal)
+        h->perm->gather(static_cast<double const *>(in), static_cast<double *>(out));
+      else
+        h->perm->scatter(static_cast<double const *>(in), static_cast<double *>(out));
+    }
   });
 }
 
@@ -1142,6 +1240,17 @@ int mfmg_hip_hierarchy_apply_f32(mfmg_hip_hierarchy_t h, const float *b, float *
   return guarded([&] {
     require(h && b && x, "null argument");
     require(h->fine_f32 != nullptr, "the hierarchy was not built with \"fine level precision\" float");
+    if (h->perm)
+    {
+      float *wb = h->workspace_f32(0), *wx = h->workspace_f32(1);
+      if (h->hierarchy->is_preconditioner())
+        h->perm->gather(b, wb);
+      else
+        h->perm->gather2(b, static_cast<float const *>(x), wb, wx);
+      h->fine_f32->apply(wb, wx);
+      h->perm->scatter(static_cast<float const *>(wx), x);
+      return;
+    }
     h->fine_f32->apply(b, x);
   });
 }
@@ -1150,6 +1259,13 @@ int mfmg_hip_hierarchy_vmult(mfmg_hip_hierarchy_t h, double *x, const double *b)
 {
   return guarded([&] {
     require(h && b && x, "null argument");
+    if (h->perm)
+    {
+      timer_enter_subsection(h->timer, "Apply");
+      apply_permuted(h, b, x);
+      timer_leave_subsection(h->timer);
+      return;
+    }
     const int64_t n = level_size(h, 0);
     DVector bv(*h->handle, n, const_cast<double *>(b)), xv(*h->handle, n, x);
     h->hierarchy->vmult(xv, bv);
@@ -1170,7 +1286,18 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
     auto op = h->hierarchy->levels()[0].get_operator();
     auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
     const int space = hop ? hop->domain_space() : 0;
-    DVector bv(handle, n, const_cast<double *>(b)), xv(handle, n, x);
+    // "internal numbering" lexicographic: b and x are gathered once, the whole iteration -- operator, preconditioner, the four
+    // CG vectors, the dot products -- runs in the internal numbering, and x is scattered once at the end: two launches of the
+    // permutation per solve whatever the iteration count (the residual history is a list of norms)
+    double const *b_run = b;
+    double *x_run = x;
+    if (h->perm)
+    {
+      h->perm->gather2(b, static_cast<double const *>(x), h->workspace(0), h->workspace(1));
+      b_run = h->workspace(0);
+      x_run = h->workspace(1);
+    }
+    DVector bv(handle, n, const_cast<double *>(b_run)), xv(handle, n, x_run);
     DVector r(handle, n), z(handle, n), p(handle, n), ap(handle, n);
     auto dot = [&](DVector const &u, DVector const &v) { return distributed_dot(handle, space, u, v); };
     op->apply(xv, r);
@@ -1234,6 +1361,8 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
       *n_iterations = it;
     if (final_residual)
       *final_residual = res;
+    if (h->perm)
+      h->perm->scatter(static_cast<double const *>(x_run), x);
     if (!converged)
       throw std::runtime_error("CG did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
   });
@@ -1261,9 +1390,15 @@ int mfmg_hip_hierarchy_operator_apply(mfmg_hip_hierarchy_t h, int32_t level, con
     require(h && x && y, "null argument");
     require(mode == MFMG_HIP_NO_TRANS || mode == MFMG_HIP_TRANS, "unknown operator mode");
     const int64_t n = level_size(h, level);
-    DVector xv(*h->handle, n, const_cast<double *>(x)), yv(*h->handle, n, y);
+    // (the level-wise entry points permute per call: fine-level vectors in and out of the workspace)
+    const bool permute = h->perm && level == 0;
+    if (permute)
+      h->perm->gather(x, h->workspace(0));
+    DVector xv(*h->handle, n, permute ? h->workspace(0) : const_cast<double *>(x)), yv(*h->handle, n, permute ? h->workspace(1) : y);
     h->hierarchy->levels()[level].get_operator()->apply(
         xv, yv, mode == MFMG_HIP_TRANS ? OperatorMode::TRANS : OperatorMode::NO_TRANS);
+    if (permute)
+      h->perm->scatter(static_cast<double const *>(h->workspace(1)), y);
   });
 }
 
@@ -1274,8 +1409,13 @@ int mfmg_hip_hierarchy_smoother_apply(mfmg_hip_hierarchy_t h, int32_t level, con
     const int64_t n = level_size(h, level);
     auto smoother = h->hierarchy->levels()[level].get_smoother();
     require(smoother != nullptr, "this level has no smoother");
-    DVector bv(*h->handle, n, const_cast<double *>(b)), xv(*h->handle, n, x);
+    const bool permute = h->perm && level == 0;
+    if (permute)
+      h->perm->gather2(b, static_cast<double const *>(x), h->workspace(0), h->workspace(1));
+    DVector bv(*h->handle, n, permute ? h->workspace(0) : const_cast<double *>(b)), xv(*h->handle, n, permute ? h->workspace(1) : x);
     smoother->apply(bv, xv);
+    if (permute)
+      h->perm->scatter(static_cast<double const *>(h->workspace(1)), x);
   });
 }
 
@@ -1288,18 +1428,25 @@ int mfmg_hip_hierarchy_restrictor_apply(mfmg_hip_hierarchy_t h, int32_t level, c
     require(level >= 1 && level < (int)h->hierarchy->levels().size(), "restrictors live on levels >= 1");
     const int64_t n_fine = level_size(h, level - 1), n_coarse = level_size(h, level);
     auto r = h->hierarchy->levels()[level].get_restrictor();
+    const bool permute = h->perm && level == 1; // the fine side of the restrictor of level 1
     if (mode == MFMG_HIP_NO_TRANS)
     {
-      DVector iv(*h->handle, n_fine, const_cast<double *>(in)), ov(*h->handle, n_coarse, out);
+      if (permute)
+        h->perm->gather(in, h->workspace(0));
+      DVector iv(*h->handle, n_fine, permute ? h->workspace(0) : const_cast<double *>(in)), ov(*h->handle, n_coarse, out);
       r->apply(iv, ov, OperatorMode::NO_TRANS);
     }
     else
     {
-      DVector iv(*h->handle, n_coarse, const_cast<double *>(in)), ov(*h->handle, n_fine, out);
+      if (permute && mode == MFMG_HIP_TRANS_SUBTRACT)
+        h->perm->gather(static_cast<double const *>(out), h->workspace(0));
+      DVector iv(*h->handle, n_coarse, const_cast<double *>(in)), ov(*h->handle, n_fine, permute ? h->workspace(0) : out);
       if (mode == MFMG_HIP_TRANS)
         r->apply(iv, ov, OperatorMode::TRANS);
       else
         r->apply_subtract(iv, ov, OperatorMode::TRANS);
+      if (permute)
+        h->perm->scatter(static_cast<double const *>(h->workspace(0)), out);
     }
   });
 }
@@ -1334,8 +1481,12 @@ int mfmg_hip_hierarchy_ap_apply(mfmg_hip_hierarchy_t h, int32_t level, const dou
     require(h && in && out, "null argument");
     auto const &aps = h->hierarchy->ap_operators();
     require(level >= 1 && level <= (int)aps.size(), "no A R^T kept for this level (build the hierarchy with keep_ap = true)");
-    DVector iv(*h->handle, level_size(h, level), const_cast<double *>(in)), ov(*h->handle, level_size(h, level - 1), out);
+    const bool permute = h->perm && level == 1;
+    DVector iv(*h->handle, level_size(h, level), const_cast<double *>(in)),
+        ov(*h->handle, level_size(h, level - 1), permute ? h->workspace(0) : out);
     aps[level - 1]->apply(iv, ov);
+    if (permute)
+      h->perm->scatter(static_cast<double const *>(h->workspace(0)), out);
   });
 }
 
@@ -1357,8 +1508,11 @@ int mfmg_hip_hierarchy_restrict_residual(mfmg_hip_hierarchy_t h, int32_t level, 
     const int64_t n_fine = level_size(h, level - 1), n_coarse = level_size(h, level);
     auto r = h->hierarchy->levels()[level].get_restrictor();
     auto a = h->hierarchy->levels()[level - 1].get_operator();
-    DVector xv(*h->handle, n_fine, const_cast<double *>(x)), bv(*h->handle, n_fine, const_cast<double *>(b)),
-        bc(*h->handle, n_coarse, b_coarse);
+    const bool permute = h->perm && level == 1;
+    if (permute)
+      h->perm->gather2(x, b, h->workspace(0), h->workspace(1));
+    DVector xv(*h->handle, n_fine, permute ? h->workspace(0) : const_cast<double *>(x)),
+        bv(*h->handle, n_fine, permute ? h->workspace(1) : const_cast<double *>(b)), bc(*h->handle, n_coarse, b_coarse);
     if (!r->restrict_residual(*a, xv, bv, bc))
     {
       // the two steps of hierarchy.hpp:281-290
@@ -1380,6 +1534,32 @@ int mfmg_hip_hierarchy_coarse_apply(mfmg_hip_hierarchy_t h, const double *b, dou
   });
 }
 
+namespace
+{
+// columns c -> new_id[c], every row sorted again
+void renumber_columns(std::vector<int32_t> const &rp, std::vector<int32_t> &cl, std::vector<double> &vl, std::vector<int32_t> const &new_id)
+{
+  const int64_t n_rows = (int64_t)rp.size() - 1;
+#pragma omp parallel
+  {
+    std::vector<std::pair<int32_t, double>> row;
+#pragma omp for schedule(static)
+    for (int64_t r = 0; r < n_rows; ++r)
+    {
+      row.clear();
+      for (int32_t p = rp[r]; p < rp[r + 1]; ++p)
+        row.emplace_back(new_id[cl[p]], vl[p]);
+      std::sort(row.begin(), row.end(), [](auto const &a, auto const &b) { return a.first < b.first; });
+      for (int32_t p = rp[r]; p < rp[r + 1]; ++p)
+      {
+        cl[p] = row[p - rp[r]].first;
+        vl[p] = row[p - rp[r]].second;
+      }
+    }
+  }
+}
+} // namespace
+
 int mfmg_hip_hierarchy_set_restrictor(mfmg_hip_hierarchy_t h, int64_t n_rows, int64_t n_cols, int64_t nnz,
                                       const int32_t *row_ptr_host, const int32_t *col_host, const double *val_host)
 {
@@ -1393,6 +1573,17 @@ int mfmg_hip_hierarchy_set_restrictor(mfmg_hip_hierarchy_t h, int64_t n_rows, in
     std::vector<int32_t> rp(row_ptr_host, row_ptr_host + n_rows + 1);
     std::vector<int32_t> cl(col_host, col_host + nnz);
     std::vector<double> vl(val_host, val_host + nnz);
+    if (h->perm)
+    {
+      // the caller's columns are its DoF ids: the hierarchy takes the nodes
+      auto const &node_dof = h->perm->node_dof_host();
+      std::vector<int32_t> dof_node(node_dof.size());
+      for (size_t nd = 0; nd < node_dof.size(); ++nd)
+        dof_node[node_dof[nd]] = (int32_t)nd;
+      for (auto c : cl)
+        require(c >= 0 && c < n_cols, "column index out of range");
+      renumber_columns(rp, cl, vl, dof_node);
+    }
     auto m = std::make_shared<SparseMatrixDevice<double>>(*h->handle, n_rows, n_cols, std::move(rp), std::move(cl),
                                                           std::move(vl));
     {
@@ -1416,6 +1607,17 @@ int mfmg_hip_hierarchy_get_restrictor(mfmg_hip_hierarchy_t h, mfmg_hip_csr_t *r_
     require(h->hierarchy->levels().size() >= 2, "the hierarchy has a single level");
     auto r = std::dynamic_pointer_cast<HipMatrixOperator const>(h->hierarchy->levels()[1].get_restrictor());
     require(r != nullptr, "the restrictor is not a matrix operator");
+    if (h->perm)
+    {
+      // the hierarchy's columns are nodes: the caller gets a copy whose columns are its DoF ids
+      std::vector<int32_t> rp, cl;
+      std::vector<double> vl;
+      r->get_matrix()->download(rp, cl, vl);
+      renumber_columns(rp, cl, vl, h->perm->node_dof_host());
+      auto m = std::make_shared<SparseMatrixDevice<double>>(*h->handle, r->get_matrix()->m(), r->get_matrix()->n(), std::move(rp),
+                                                            std::move(cl), std::move(vl));
+      r = std::make_shared<HipMatrixOperator>(m);
+    }
     h->restrictor_view.op = std::const_pointer_cast<HipMatrixOperator>(r);
     h->restrictor_view.borrowed = true;
     *r_borrowed = &h->restrictor_view;

@@ -540,6 +540,14 @@ struct HipHandle
   // prolongators and operators of the aggregation hierarchy -- are rounded to float-representable values when they are
   // assembled; the layouts then keep them in float (half the bytes per application), arithmetic stays FP64
   bool setup_values_float = false;
+  // "internal numbering" lexicographic (parameter of the hierarchy, dof_permutation.hpp): while such a hierarchy is set up, the
+  // caller's DoF id of every lexicographic node (host array of the fine level's size) -- what is keyed on a DoF id, the start
+  // vector of the Chebyshev eigenvalue estimate, takes the caller's id so that both modes estimate the same eigenvalues
+  int32_t const *setup_caller_ids = nullptr;
+  // kernel of the DoF permutation, MFMG_DOF_PERMUTATION = brick64 | brick16 | ids, read ONCE when the handle is built
+  // (dof_permutation.hip: 0 lexicographic bricks of 64 x 8 x 4 nodes, 1 of 16 x 8 x 16, 2 blocks of consecutive caller ids: the
+  // default, the fastest of the three on deal.II's numbering)
+  int dof_permutation_kernel = 2;
   // scratch for two-stage deterministic reductions
   DeviceBuffer<double> reduce_partials;
   DeviceBuffer<double> reduce_result;
@@ -847,6 +855,11 @@ struct HipHandle
     {
       const std::string v(e);
       mf_emulate_split = v == "z" ? 1 : (v == "yz" ? 2 : ((v == "xyz" || v == "1") ? 3 : 0));
+    }
+    if (char const *e = std::getenv("MFMG_DOF_PERMUTATION"))
+    {
+      const std::string v(e);
+      dof_permutation_kernel = v == "brick64" ? 0 : (v == "brick16" ? 1 : 2);
     }
     reduce_partials.resize(4096);
     reduce_result.resize(16);

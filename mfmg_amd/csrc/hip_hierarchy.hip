@@ -1074,11 +1074,15 @@ void HipSmoother::estimate_eigenvalues(int n_iterations, double residual, double
     if (hs)
       hs->check();
     const double n_global = hs ? double(hs->n_global()) : double(n);
+    // ("internal numbering" lexicographic: entry i belongs to node i, the pattern follows the CALLER's id of that node, so that
+    // the estimate is the one of a hierarchy that runs in the caller's numbering)
+    int32_t const *caller_ids =
+        (!hs && std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator) != nullptr) ? h.setup_caller_ids : nullptr;
     std::vector<double> v(n);
     double mean = 0.;
     for (int64_t i = 0; i < n; ++i)
     {
-      const int64_t gi = hs ? hs->global_id(i) : i;
+      const int64_t gi = hs ? hs->global_id(i) : (caller_ids ? (int64_t)caller_ids[i] : i);
       if (_eig_start == "dealii")
         v[i] = double(gi % 11);
       else // splitmix64 finaliser of the DoF id, in [0, 1): white in index space whatever the row length (a

@@ -6,6 +6,8 @@
 // temporaries built once per level, no host round trips.
 #pragma once
 
+#include <functional>
+
 #include "hierarchy_helpers.hpp"
 #include "hip_hierarchy_helpers.hpp"
 #include "level.hpp"
@@ -123,7 +125,12 @@ public:
     timer_leave_subsection(_timer);
   }
 
-  void apply(VectorType const &b, VectorType &x, int level_index = 0) const
+  // `deliver` (level 0 of a hierarchy that runs in an internal numbering, dof_permutation.hpp): called with the vector that holds
+  // the result in place of the copy into x that ends the cycle -- the caller scatters it into its own vector, from wherever the
+  // iterate came to rest
+  using Deliver = std::function<void(VectorType const &)>;
+
+  void apply(VectorType const &b, VectorType &x, int level_index = 0, Deliver const *deliver = nullptr) const
   {
     auto const num_levels = _levels.size();
 
@@ -146,6 +153,8 @@ public:
       timer_enter_subsection(_timer, "Apply: coarsest level");
       auto coarse_solver = level_fine.get_solver();
       coarse_solver->apply(b, x);
+      if (deliver)
+        (*deliver)(x);
       timer_leave_subsection(_timer);
     }
     else
@@ -216,7 +225,9 @@ public:
 
       // post-smoother
       smooth();
-      if (cur != &x)
+      if (deliver)
+        (*deliver)(*cur);
+      else if (cur != &x)
         x = *cur;
       restrictor->release_rhs();
       timer_leave_subsection(_timer);

@@ -39,6 +39,54 @@ def material_property(kind: str, pts: torch.Tensor) -> torch.Tensor:
     raise NotImplementedError(f"material property '{kind}'")
 
 
+def dealii_numbering(n_cells: Sequence[int]) -> torch.Tensor:
+    """DoF ids of DoFHandler::distribute_dofs on GridGenerator::hyper_cube + refine_global for FE_Q(1), the numbering a
+    deal.II driver hands over (tests/laplace_matrix_free.hpp:243-279): cells in Morton order (x the lowest bit), vertex
+    DoFs numbered where a cell first touches them.  Returns dealii_id[lexicographic node id] (int64) for `dof_numbering`
+    of LaplaceProblem; 2^r cells per direction, 2-D and 3-D.
+
+    A node is first touched by the adjacent cell with the smallest Morton index, as that cell's vertex v: rank the nodes
+    by the smallest key morton(cell) * 2^dim + v over their adjacent cells."""
+    import numpy as np
+    n = tuple(int(v) for v in n_cells)
+    dim = len(n)
+    assert dim in (2, 3), "2-D or 3-D"
+    assert all(v == n[0] for v in n) and n[0] >= 1 and (n[0] & (n[0] - 1)) == 0, "2^r cells per direction"
+    levels = n[0].bit_length() - 1
+    N = n[0] + 1
+    # Morton code of the cell coordinate c along axis d: bit l of c at position dim * l + d
+    c = np.arange(n[0], dtype=np.int64)
+    spread = np.zeros(n[0], dtype=np.int64)
+    for l in range(levels):
+        spread |= ((c >> l) & 1) << (dim * l)
+    big = np.iinfo(np.int64).max
+    # per axis and vertex bit b: the spread code of the cell whose vertex b is node i (cell i - b), big where there is none
+    axis = []
+    for b in (0, 1):
+        a = np.full(N, big, dtype=np.int64)
+        cells = np.arange(N) - b
+        ok = (cells >= 0) & (cells < n[0])
+        a[ok] = spread[cells[ok]]
+        axis.append(a)
+    key = np.full((N,) * dim, big, dtype=np.int64)       # indexed [k][j][i] (x fastest)
+    for v in range(2 ** dim):
+        valid = np.ones((N,) * dim, dtype=bool)
+        code = np.zeros((N,) * dim, dtype=np.int64)
+        for d in range(dim):
+            a = axis[(v >> d) & 1]
+            shape = [1] * dim
+            shape[dim - 1 - d] = N
+            ad = a.reshape(shape)
+            valid &= ad != big
+            code = code + np.where(ad != big, ad << d, 0)
+        cand = np.where(valid, code * (2 ** dim) + v, big)
+        np.minimum(key, cand, out=key)
+    order = np.argsort(key.reshape(-1), kind="stable")
+    ids = np.empty(N ** dim, dtype=np.int64)
+    ids[order] = np.arange(N ** dim, dtype=np.int64)
+    return torch.from_numpy(ids)
+
+
 class LaplaceProblem:
     """Mesh arrays of the Q1 Laplace problem on [0, length]^dim with n cells per direction."""
 

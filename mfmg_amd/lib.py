@@ -198,6 +198,8 @@ def load() -> C.CDLL:
         "mfmg_hip_mf_laplace_f32_smoother_step": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_float, vp]),
         "mfmg_hip_hierarchy_create": (C.c_int, [vp, C.c_char_p, P(MeshDesc), C.c_char_p, P(vp)]),
         "mfmg_hip_hierarchy_destroy": (C.c_int, [vp]),
+        "mfmg_hip_hierarchy_internal_numbering": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
+        "mfmg_hip_hierarchy_permute": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
         "mfmg_hip_hierarchy_apply": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_apply_f32": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_vmult": (C.c_int, [vp, vp, vp]),
