@@ -263,6 +263,8 @@ int mfmg_hip_csr_stencil_classes(mfmg_hip_csr_t a, int *n_classes, int64_t *list
  * float: every one of them is representable in it -- a hierarchy built with "setup value precision" float -- so the
  * storage is lossless; products and sums stay FP64. */
 int mfmg_hip_csr_float_storage(mfmg_hip_csr_t a, int *in_float);
+/* The source vector x of the SpMV entry points below (vmult, apply, smoother_step, residual, launch) must be 16-byte
+ * aligned (any hipMalloc'ed vector is): kernels read it two doubles at a time.  The other vectors need 8 bytes. */
 /* SparseMatrixDevice::vmult  (…templates.cuh:351-371): y = A x */
 int mfmg_hip_csr_vmult(mfmg_hip_csr_t a, const double *x, double *y);
 /* CudaMatrixOperator::apply (source/cuda/cuda_matrix_operator.cu:80-91); TRANS uses the
@@ -290,6 +292,35 @@ int mfmg_hip_csr_smoother_step(mfmg_hip_csr_t a, const double *dinv, const doubl
                                const double *x_prev, double alpha, double beta, double *out);
 /* res = A x - b  (include/mfmg/common/hierarchy.hpp:284-286, negative residual) */
 int mfmg_hip_csr_residual(mfmg_hip_csr_t a, const double *x, const double *b, double *res);
+/* One SpMV with any of the fused epilogues (what vmult / residual / smoother_step and, inside a cycle, the prolongations
+ * call); b, dinv, x_prev, alpha, beta are read only by the modes that name them and may be NULL / 0 otherwise.  `out`
+ * must not alias `x`; modes SUBTRACT and ADD read `out`.  FIRST and NEXT need a square matrix. */
+#define MFMG_HIP_CSR_APPLY 0       /* out = A x */
+#define MFMG_HIP_CSR_RESIDUAL 1    /* out = A x - b */
+#define MFMG_HIP_CSR_FIRST 2       /* out = x - beta dinv (A x - b) */
+#define MFMG_HIP_CSR_NEXT 3        /* out = x + alpha (x - x_prev) - beta dinv (A x - b) */
+#define MFMG_HIP_CSR_SUBTRACT 4    /* out -= A x */
+#define MFMG_HIP_CSR_ADD 5         /* out += A x */
+#define MFMG_HIP_CSR_PLUS_SCALED 6 /* out = A x + beta dinv b */
+int mfmg_hip_csr_launch(mfmg_hip_csr_t a, int mode, const double *x, const double *b, const double *dinv, const double *x_prev,
+                        double alpha, double beta, double *out);
+/* Which kernels an application of the matrix launches as it stands (tests: which kernel a case reaches).  Filled from the
+ * record the launch itself branches on.  fields[0..21]:
+ *   0 storage variant as mfmg_hip_csr_get_kernel reports it
+ *   1 CSR kernel: 0 none, 1 lanes per row, 2 a workgroup per row, 3 LDS-cached; 2 lanes per row of the instance
+ *   3 unknowns per node, 4 stored block diagonals, 5 offsets of the full stencil (tables)
+ *   6 1 = symmetric half stored, 7 1 = planes in float
+ *   8 1 = node kernels (stencil / class tables) in use, 9 1 = the regular nodes are one of the classes
+ *  10 classes, 11 slots of the class lists (padded to wavefronts), 12 listed rows
+ *  13 route of the listed rows: 0 none, 1 tail of the class kernel (4 wavefronts per workgroup), 2 tail of the split
+ *     kernel (16), 3 a launch of their own, 4 the stored planes
+ *  14 launch of the regular nodes: 0 none, 1 one thread per node, 4 / 16 stencil split over that many wavefronts
+ *  15 launch of the classes: 0 none, 1 one thread per node, 4 / 16 split
+ *  16 stored-plane kernel: 0 none, 1 rows, 2 rows of a symmetric half, 3 symmetric half split over four wavefronts
+ *  17 row-base slots, 18 / 19 unknowns per node and offsets of the node classes of a rectangular matrix
+ *  20 whether the last launch found every vector 16-byte aligned (-1: no launch yet), 21 1 = CSR arrays released */
+#define MFMG_HIP_CSR_FORM_FIELDS 22
+int mfmg_hip_csr_form(mfmg_hip_csr_t a, int64_t *fields, int32_t n);
 
 /* ---- matrix-free Q1 Laplace operator on a logically structured hex mesh ---- */
 /* What the deal.II driver hands over (tests/laplace_matrix_free.hpp:243-313):

@@ -328,6 +328,31 @@ class SparseMatrixDevice:
                                                    _dev_ptr(x_prev, n) if x_prev is not None else None,
                                                    alpha, beta, _dev_ptr(out, n)))
 
+    def launch(self, mode: int, x, out, b=None, dinv=None, x_prev=None, alpha: float = 0.0, beta: float = 0.0):
+        """One SpMV with the fused epilogue `mode` (lib.CSR_APPLY .. lib.CSR_PLUS_SCALED); operands a mode does not
+        read may stay None."""
+        m, n = self.shape
+        opt = lambda t: _dev_ptr(t, m) if t is not None else None
+        check(self._lib.mfmg_hip_csr_launch(self.handle, mode, _dev_ptr(x, n), opt(b), opt(dinv), opt(x_prev), alpha,
+                                            beta, _dev_ptr(out, m)))
+
+    _FORM_FIELDS = ("kind", "csr_kernel", "lanes", "c", "stored_d", "full_d", "symmetric_half", "float_planes", "regular",
+                    "all_in_classes", "classes", "class_slots", "listed", "listed_route", "regular_kernel", "class_kernel",
+                    "stored_kernel", "row_base_slots", "node_class_c", "node_class_d", "pairs", "csr_released")
+    _CSR_KERNELS = {0: None, 1: "lanes", 2: "row_block", 3: "lds"}
+    _LISTED_ROUTES = {0: None, 1: "class_tail", 2: "split_tail", 3: "own_launch", 4: "stored_planes"}
+    _STORED_KERNELS = {0: None, 1: "rows", 2: "sym_rows", 3: "sym_split"}
+
+    def form(self) -> dict:
+        """Which kernels an application launches as the matrix stands (the record the launch branches on)."""
+        f = (C.c_int64 * _lib.CSR_FORM_FIELDS)()
+        check(self._lib.mfmg_hip_csr_form(self.handle, f, _lib.CSR_FORM_FIELDS))
+        d = {k: int(f[i]) for i, k in enumerate(self._FORM_FIELDS)}
+        d["csr_kernel"] = self._CSR_KERNELS[d["csr_kernel"]]
+        d["listed_route"] = self._LISTED_ROUTES[d["listed_route"]]
+        d["stored_kernel"] = self._STORED_KERNELS[d["stored_kernel"]]
+        return d
+
     def to_scipy(self):
         import scipy.sparse as sp
         m, n = self.shape

@@ -759,10 +759,18 @@ int mfmg_hip_csr_shape(mfmg_hip_csr_t a, int64_t *n_rows, int64_t *n_cols, int64
   });
 }
 
+// The node kernels gather the source vector two doubles at a time whatever its address (sparse_matrix_device.hip): a source
+// at an 8-byte-only address would make those accesses misaligned for their type, so the entry points refuse it.
+static void require_aligned_source(const double *x)
+{
+  require(reinterpret_cast<uintptr_t>(x) % 16 == 0, "the source vector of an SpMV must be 16-byte aligned");
+}
+
 int mfmg_hip_csr_vmult(mfmg_hip_csr_t a, const double *x, double *y)
 {
   return guarded([&] {
     require(a && x && y, "null argument");
+    require_aligned_source(x);
     a->op->get_matrix()->vmult(y, x);
   });
 }
@@ -772,6 +780,7 @@ int mfmg_hip_csr_apply(mfmg_hip_csr_t a, const double *x, double *y, int mode)
   return guarded([&] {
     require(a && x && y, "null argument");
     require(mode == MFMG_HIP_NO_TRANS || mode == MFMG_HIP_TRANS, "unknown operator mode");
+    require_aligned_source(x);
     if (mode == MFMG_HIP_NO_TRANS)
       a->op->get_matrix()->vmult(y, x);
     else
@@ -845,6 +854,7 @@ int mfmg_hip_csr_smoother_step(mfmg_hip_csr_t a, const double *dinv, const doubl
     require(a && dinv && b && x && out, "null argument");
     auto m = a->op->get_matrix();
     require(m->m() == m->n(), "the smoother needs a square matrix");
+    require_aligned_source(x);
     m->smoother_step(dinv, b, x, x_prev, alpha, beta, out);
   });
 }
@@ -853,7 +863,51 @@ int mfmg_hip_csr_residual(mfmg_hip_csr_t a, const double *x, const double *b, do
 {
   return guarded([&] {
     require(a && x && b && res, "null argument");
+    require_aligned_source(x);
     a->op->get_matrix()->residual(x, b, res);
+  });
+}
+
+int mfmg_hip_csr_launch(mfmg_hip_csr_t a, int mode, const double *x, const double *b, const double *dinv, const double *x_prev,
+                        double alpha, double beta, double *out)
+{
+  return guarded([&] {
+    require(a && x && out, "null argument");
+    require(mode >= MFMG_HIP_CSR_APPLY && mode <= MFMG_HIP_CSR_PLUS_SCALED, "unknown SpMV mode");
+    require_aligned_source(x);
+    a->op->get_matrix()->apply_mode(static_cast<CsrMode>(mode), x, b, dinv, x_prev, alpha, beta, out);
+  });
+}
+
+int mfmg_hip_csr_form(mfmg_hip_csr_t a, int64_t *fields, int32_t n)
+{
+  return guarded([&] {
+    require(a && fields, "null argument");
+    require(n >= MFMG_HIP_CSR_FORM_FIELDS, "csr_form needs MFMG_HIP_CSR_FORM_FIELDS fields");
+    std::fill(fields, fields + n, (int64_t)0);
+    const CsrForm f = a->op->get_matrix()->form();
+    fields[0] = f.kind;
+    fields[1] = f.csr_kernel;
+    fields[2] = f.lanes;
+    fields[3] = f.c;
+    fields[4] = f.stored_d;
+    fields[5] = f.full_d;
+    fields[6] = f.symmetric_half;
+    fields[7] = f.float_planes;
+    fields[8] = f.regular;
+    fields[9] = f.all_in_classes;
+    fields[10] = f.classes;
+    fields[11] = f.class_slots;
+    fields[12] = f.listed;
+    fields[13] = f.listed_route;
+    fields[14] = f.regular_kernel;
+    fields[15] = f.class_kernel;
+    fields[16] = f.stored_kernel;
+    fields[17] = f.row_base_slots;
+    fields[18] = f.node_class_c;
+    fields[19] = f.node_class_d;
+    fields[20] = f.pairs;
+    fields[21] = f.csr_released;
   });
 }
 

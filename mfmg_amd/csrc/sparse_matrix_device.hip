@@ -1700,10 +1700,9 @@ void SparseMatrixDevice<T>::build_block_diagonals()
       // small levels are bound by the latency of a launch, not by their rows: there the regular nodes join the lists
       // as one more class (their table is the reference stencil; a regular node has its whole stencil inside the
       // matrix, so the clamping of the class kernel never acts) and the launch of their own is dropped
-      static const int64_t regular_as_class_nodes = [] {
-        char const *e = std::getenv("MFMG_REGULAR_AS_CLASS_NODES");
-        return e ? std::atoll(e) : kRegularAsClassNodes;
-      }();
+      // (read at every construction: MFMG_REGULAR_AS_CLASS_NODES=0 gives a small matrix the regular-node launch of the large ones)
+      char const *const regular_as_class_env = std::getenv("MFMG_REGULAR_AS_CLASS_NODES");
+      const int64_t regular_as_class_nodes = regular_as_class_env ? std::atoll(regular_as_class_env) : kRegularAsClassNodes;
       if (n_classes > 0 && n_classes < kMaxClasses && n_nodes <= regular_as_class_nodes && n_regular > 0)
       {
         cls_table.insert(cls_table.end(), table.begin(), table.end());
@@ -2119,6 +2118,103 @@ void SparseMatrixDevice<T>::build_row_base(std::vector<int32_t> const &row_ptr, 
   _use_rowbase = true;
 }
 
+// The decisions of launch(), in one place: launch() takes every branch from the fields filled here.
+template <typename T>
+CsrForm SparseMatrixDevice<T>::form() const
+{
+  // (launch() tells the layouts apart by kind: that needs the four of them to exclude each other, as choose_layouts and
+  // set_kernel leave them)
+  ASSERT_THROW((int)_use_nodecls + (int)_use_rowbase + (int)_use_bdia + (int)_use_lds <= 1, "internal: more than one storage layout in use");
+  CsrForm f;
+  f.kind = kernel_kind();
+  f.pairs = _last_pairs.load(std::memory_order_relaxed);
+  f.csr_released = _csr_released ? 1 : 0;
+  auto parts_of = [&](int Df, int64_t n_nodes) {
+    const bool split = Df >= kSplitStencil;
+    const bool many_parts = Df >= 4 * kSplitStencil && n_nodes <= 131072;
+    return split && many_parts ? 16 : split ? 4 : 1;
+  };
+  if (_use_nodecls && _use_regular)
+  {
+    f.regular = 1;
+    f.c = f.node_class_c = _nc_c;
+    f.full_d = f.node_class_d = _nc_d;
+    f.classes = _nc_classes;
+    f.class_slots = (int64_t)_nc_nodes.size();
+    f.listed = (int64_t)_nc_listed.size();
+    f.class_kernel = parts_of(_nc_d, _n_rows / _nc_c);
+    f.listed_route = f.listed == 0 ? CsrForm::listed_none : f.class_kernel == 1 ? CsrForm::listed_class_tail : CsrForm::listed_split_tail;
+    return f;
+  }
+  if (_use_rowbase)
+  {
+    f.row_base_slots = _rb_slots;
+    return f;
+  }
+  if (_use_bdia)
+  {
+    f.c = _bdia_c;
+    f.stored_d = _bdia_d;
+    f.symmetric_half = _bdia_sym ? 1 : 0;
+    f.float_planes = _bdia_val_f32.size() > 0 ? 1 : 0;
+    f.regular = (_bdia_regular && _use_regular) ? 1 : 0;
+    if (f.regular)
+    {
+      f.full_d = _bdia_full_d;
+      f.all_in_classes = _bdia_all_in_classes ? 1 : 0;
+      f.classes = _bdia_n_classes;
+      f.class_slots = (int64_t)_bdia_cls_nodes.size();
+      f.listed = (int64_t)_bdia_exc_rows.size();
+      const int parts = parts_of(_bdia_full_d, _n_rows / _bdia_c);
+      f.regular_kernel = _bdia_all_in_classes ? 0 : parts;
+      f.class_kernel = _bdia_n_classes > 0 ? parts : 0;
+      // few listed rows ride at the end of the class launch, one wavefront each; without classes they have a launch of
+      // their own; many are rows of the stored planes
+      if (f.listed == 0)
+        f.listed_route = CsrForm::listed_none;
+      else if (f.listed > kListedWaveRows)
+        f.listed_route = CsrForm::listed_stored_planes;
+      else if (f.class_kernel == 0)
+        f.listed_route = CsrForm::listed_own_launch;
+      else
+        f.listed_route = f.class_kernel == 1 ? CsrForm::listed_class_tail : CsrForm::listed_split_tail;
+    }
+    if (!f.regular || f.listed_route == CsrForm::listed_stored_planes)
+      f.stored_kernel = !_bdia_sym ? CsrForm::stored_rows : f.regular ? CsrForm::stored_sym_rows : CsrForm::stored_sym_split;
+    return f;
+  }
+  if (_use_lds)
+  {
+    f.csr_kernel = CsrForm::csr_lds;
+    f.lanes = (_lanes_per_row == 8 || _lanes_per_row == 16 || _lanes_per_row == 32) ? _lanes_per_row : _lanes_per_row <= 4 ? 4 : 64;
+    return f;
+  }
+  if (_lanes_per_row == 256)
+  {
+    f.csr_kernel = CsrForm::csr_row_block;
+    f.lanes = 256;
+    return f;
+  }
+  f.csr_kernel = CsrForm::csr_lanes;
+  f.lanes = (_lanes_per_row >= 1 && _lanes_per_row <= 32 && (_lanes_per_row & (_lanes_per_row - 1)) == 0) ? _lanes_per_row : 64;
+  return f;
+}
+
+template <typename T>
+void SparseMatrixDevice<T>::apply_mode(CsrMode mode, T const *x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta,
+                                       T *out) const
+{
+  const int m = static_cast<int>(mode);
+  ASSERT_THROW(m >= 0 && m <= 6, "unknown SpMV mode");
+  const bool need_b = (m >= 1 && m <= 3) || m == 6, need_d = m == 2 || m == 3 || m == 6, need_p = m == 3;
+  ASSERT_THROW(!need_b || b != nullptr, "this SpMV mode needs b");
+  ASSERT_THROW(!need_d || dinv != nullptr, "this SpMV mode needs the inverse diagonal");
+  ASSERT_THROW(!need_p || x_prev != nullptr, "this SpMV mode needs x_prev");
+  ASSERT_THROW(!(m == 2 || m == 3) || _n_rows == _n_cols, "the smoother needs a square matrix");
+  launch(mode, x, need_b ? b : nullptr, need_d ? dinv : nullptr, need_p ? x_prev : nullptr, need_p ? alpha : T(0),
+         need_d ? beta : T(0), out);
+}
+
 template <typename T>
 void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const *dinv, T const *x_prev,
                                    T alpha, T beta, T *out) const
@@ -2153,12 +2249,14 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
   {
     auto aligned = [](void const *p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 16 == 0; };
     a.pairs = (aligned(x) && aligned(b) && aligned(dinv) && aligned(x_prev) && aligned(out)) ? 1 : 0;
+    _last_pairs.store(a.pairs, std::memory_order_relaxed);
   }
+  const CsrForm f = form(); // (every branch below is taken from it)
   hipStream_t st = _handle.stream;
   const double extra = (mode == CsrMode::apply) ? 0. : (mode == CsrMode::first) ? 3. : (mode == CsrMode::next) ? 4. : 1.;
   hipEvent_t stop =
       _handle.profiler.begin("csr_spmv_kernel", algorithmic_bytes_apply() + extra * sizeof(T) * double(_n_rows), st);
-  if (_use_nodecls && _use_regular)
+  if (f.kind == 5 && f.regular)
   {
     BdiaRegular<T> g;
     g.exc = nullptr;
@@ -2172,17 +2270,15 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     const int64_t n_slots = (int64_t)_nc_nodes.size();
     int32_t const *cn = _nc_nodes.data(), *cw = _nc_class_of_wave.data();
     T const *ct = _nc_table.data();
-    const bool split = g.Df >= kSplitStencil;
-    const bool many_parts = g.Df >= 4 * kSplitStencil && _n_rows / _nc_c <= 131072;
     int32_t const *ls = _nc_listed.data();
     const int64_t n_listed = (int64_t)_nc_listed.size();
     auto launch_nodes = [&](auto cc) {
       constexpr int C = decltype(cc)::value;
-      if (split && many_parts)
+      if (f.class_kernel == 16)
         hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 16>),
                            dim3((unsigned int)((n_slots + 63) / 64 + (n_listed + 15) / 16)), dim3(1024), 0, st, a, g, cn, cw,
                            ct, n_slots, ls, n_listed);
-      else if (split)
+      else if (f.class_kernel == 4)
         hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 4>),
                            dim3((unsigned int)((n_slots + 255) / 256 + (n_listed + 15) / 16)), dim3(1024), 0, st, a, g, cn,
                            cw, ct, n_slots, ls, n_listed);
@@ -2209,7 +2305,7 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     MFMG_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (_use_rowbase)
+  if (f.kind == 4)
   {
     hipLaunchKernelGGL(rowbase_spmv_kernel<T>, dim3((unsigned int)((_n_rows + 255) / 256)), dim3(256), 0, st, a,
                        _rb_val.data(), _rb_base.data(), _rb_offs.data(), _rb_slots, _n_cols);
@@ -2217,12 +2313,12 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     MFMG_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (_use_bdia)
+  if (f.kind == 2 || f.kind == 3)
   {
     T const *dv = _bdia_val.data();
     int32_t const *of = _bdia_offs.data();
     BdiaRegular<T> g;
-    g.exc = (_bdia_regular && _use_regular) ? _bdia_exc.data() : nullptr;
+    g.exc = f.regular ? _bdia_exc.data() : nullptr;
     g.table = _bdia_table.data();
     g.offs = _bdia_full_offs.data();
     g.Df = _bdia_full_d;
@@ -2232,36 +2328,34 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     if (g.exc != nullptr)
     {
       // regular nodes, then the classes of the others; wide stencils split over the wavefronts of a workgroup
-      const bool split = g.Df >= kSplitStencil;
-      const bool many_parts = g.Df >= 4 * kSplitStencil && _n_rows / _bdia_c <= 131072;
       const int64_t n_nodes = _n_rows / _bdia_c;
       const int64_t n_slots = (int64_t)_bdia_cls_nodes.size();
       int32_t const *cn = _bdia_cls_nodes.data(), *cw = _bdia_cls_of_wave.data();
       T const *ct = _bdia_cls_table.data();
       // few listed rows ride at the end of the class launch, one wavefront each
-      const int64_t n_tail = (_bdia_n_classes > 0 && g.n_exc <= kListedWaveRows) ? g.n_exc : 0;
+      const int64_t n_tail = (f.listed_route == CsrForm::listed_class_tail || f.listed_route == CsrForm::listed_split_tail) ? g.n_exc : 0;
       auto launch_nodes = [&](auto cc) {
         constexpr int C = decltype(cc)::value;
-        if (_bdia_all_in_classes)
+        if (f.regular_kernel == 0)
           ; // (the regular nodes are one of the classes)
-        else if (split && many_parts)
+        else if (f.regular_kernel == 16)
           hipLaunchKernelGGL((bdia_node_split_kernel<T, C, false, 16>), dim3((unsigned int)((n_nodes + 63) / 64)),
                              dim3(1024), 0, st, a, g, nullptr, nullptr, nullptr, 0, nullptr, 0);
-        else if (split)
+        else if (f.regular_kernel == 4)
           hipLaunchKernelGGL((bdia_node_split_kernel<T, C, false, 4>), dim3((unsigned int)((n_nodes + 255) / 256)),
                              dim3(1024), 0, st, a, g, nullptr, nullptr, nullptr, 0, nullptr, 0);
         else
           hipLaunchKernelGGL((bdia_regular_node_kernel<T, C>), dim3((unsigned int)((n_nodes + 255) / 256)), dim3(256), 0,
                              st, a, g);
-        if (_bdia_n_classes > 0 && split && many_parts)
+        if (f.class_kernel == 16)
           hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 16>),
                              dim3((unsigned int)((n_slots + 63) / 64 + (n_tail + 15) / 16)), dim3(1024), 0, st, a, g, cn, cw,
                              ct, n_slots, g.exc_rows, n_tail);
-        else if (_bdia_n_classes > 0 && split)
+        else if (f.class_kernel == 4)
           hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 4>),
                              dim3((unsigned int)((n_slots + 255) / 256 + (n_tail + 15) / 16)), dim3(1024), 0, st, a, g, cn,
                              cw, ct, n_slots, g.exc_rows, n_tail);
-        else if (_bdia_n_classes > 0)
+        else if (f.class_kernel == 1)
           hipLaunchKernelGGL((bdia_class_node_kernel<T, C>), dim3((unsigned int)((n_slots + 255) / 256 + (n_tail + 3) / 4)),
                              dim3(256), 0, st, a, g, cn, cw, ct, n_slots, g.exc_rows, n_tail);
       };
@@ -2280,9 +2374,9 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
         launch_nodes(std::integral_constant<int, 4>());
         break;
       }
-      if (g.n_exc <= kListedWaveRows)
+      if (f.listed_route != CsrForm::listed_stored_planes)
       {
-        if (g.n_exc > 0 && n_tail == 0)
+        if (f.listed_route == CsrForm::listed_own_launch)
           hipLaunchKernelGGL(csr_listed_rows_kernel<T>, dim3((unsigned int)((g.n_exc + 3) / 4)), dim3(256), 0, st, a,
                              g.exc_rows, g.n_exc);
         KernelProfiler::end(stop, st);
@@ -2295,10 +2389,10 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     auto stored = [&](auto const *planes, auto cc) {
       using V = std::remove_cv_t<std::remove_pointer_t<decltype(planes)>>;
       constexpr int C = decltype(cc)::value;
-      if (_bdia_sym && g.exc == nullptr)
+      if (f.stored_kernel == CsrForm::stored_sym_split)
         hipLaunchKernelGGL((bdia_sym_split_kernel<T, C, V>), dim3((unsigned int)((_n_rows + 255) / 256)), dim3(1024), 0, st, a, planes, of,
                            _bdia_d);
-      else if (_bdia_sym)
+      else if (f.stored_kernel == CsrForm::stored_sym_rows)
       {
         if (rgrid.x > 0)
           hipLaunchKernelGGL((bdia_sym_spmv_kernel<T, C, V>), rgrid, dim3(256), 0, st, a, planes, of, _bdia_d, g);
@@ -2324,7 +2418,7 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
         break;
       }
     };
-    if (_bdia_val_f32.size() > 0)
+    if (f.float_planes)
       stored_c(_bdia_val_f32.data());
     else
       stored_c(dv);
@@ -2332,14 +2426,12 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     MFMG_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (_use_lds)
+  if (f.csr_kernel == CsrForm::csr_lds)
   {
     int32_t const *bp = _blk_ptr.data(), *lg = _l2g.data();
     uint16_t const *lc = _lcol.data();
-    switch (_lanes_per_row)
+    switch (f.lanes)
     {
-    case 1:
-    case 2:
     case 4:
       launch_lds<T, 4>(a, st, bp, lg, lc, kRowsPerBlock, _lds_max_cols);
       break;
@@ -2360,7 +2452,7 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     MFMG_HIP_CHECK(hipGetLastError());
     return;
   }
-  switch (_lanes_per_row)
+  switch (f.lanes)
   {
   case 256:
     hipLaunchKernelGGL(csr_spmv_row_block_kernel<T>, dim3((unsigned int)_n_rows), dim3(256), 0, st, a);

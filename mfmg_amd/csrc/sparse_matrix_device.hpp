@@ -9,6 +9,8 @@
 
 #include "common.hpp"
 
+#include <atomic>
+
 namespace mfmg
 {
 enum class CsrMode : int
@@ -20,6 +22,55 @@ enum class CsrMode : int
   subtract = 4, // out -= A x            (x.add(-1, R^T x_c), hierarchy.hpp:297-302)
   add = 5,      // out += A x
   plus_scaled = 6 // out = A x + beta dinv b   (prolongation and damped-Jacobi post-smoothing of a correction in one step)
+};
+
+// Which kernels one application of a matrix launches (SparseMatrixDevice::form()).  launch() branches on these very fields,
+// so a test that asserts a form asserts the kernels that run.
+struct CsrForm
+{
+  enum : int
+  {
+    listed_none = 0,
+    listed_class_tail = 1,  // tail workgroups of bdia_class_node_kernel, 4 wavefronts each
+    listed_split_tail = 2,  // tail workgroups of bdia_node_split_kernel<.., CLASSES = true, P>, 16 wavefronts each
+    listed_own_launch = 3,  // csr_listed_rows_kernel
+    listed_stored_planes = 4 // the stored planes walked through the list of rows
+  };
+  enum : int
+  {
+    stored_none = 0,
+    stored_rows = 1,      // bdia_spmv_kernel
+    stored_sym_rows = 2,  // bdia_sym_spmv_kernel
+    stored_sym_split = 3  // bdia_sym_split_kernel
+  };
+  enum : int
+  {
+    csr_none = 0,
+    csr_lanes = 1,     // csr_spmv_kernel<T, lanes>
+    csr_row_block = 2, // csr_spmv_row_block_kernel
+    csr_lds = 3        // csr_spmv_lds_kernel<T, lanes>
+  };
+  int kind = 0;            // kernel_kind()
+  int csr_kernel = 0;      // csr_*; with `lanes` the instance (the LDS-cached kernel has no instance below 4)
+  int lanes = 0;
+  int c = 0;               // unknowns per node of the block-diagonal / node-class layout in use
+  int stored_d = 0;        // stored block diagonals (a symmetric matrix: offsets >= 0 only)
+  int full_d = 0;          // offsets of the full stencil (the tables of the node kernels)
+  int symmetric_half = 0;
+  int float_planes = 0;
+  int regular = 0;         // the node kernels (stencil / class tables) are in use
+  int all_in_classes = 0;  // the regular nodes are one of the classes: no launch of their own
+  int classes = 0;
+  int64_t class_slots = 0;
+  int64_t listed = 0;
+  int listed_route = 0;    // listed_*
+  int regular_kernel = 0;  // launch of the regular nodes: 0 none, 1 bdia_regular_node_kernel, 4 / 16 the split kernel, CLASSES = false
+  int class_kernel = 0;    // launch of the classes: 0 none, 1 bdia_class_node_kernel, 4 / 16 the split kernel, CLASSES = true
+  int stored_kernel = 0;   // stored_*
+  int row_base_slots = 0;
+  int node_class_c = 0, node_class_d = 0;
+  int pairs = -1;          // a.pairs of the last launch (-1: none yet)
+  int csr_released = 0;
 };
 
 template <typename T>
@@ -166,6 +217,11 @@ public:
   // rows evaluated from stored values although the matrix has regular rows, and the stencil classes next to the regular one
   int64_t listed_rows() const { return (int64_t)(_use_nodecls ? _nc_listed.size() : _bdia_exc_rows.size()); }
   int stencil_classes() const { return _use_nodecls ? _nc_classes : _bdia_n_classes; }
+  // the kernels launch() takes as the matrix stands now (and whether the vectors of the last launch were paired)
+  CsrForm form() const;
+  // out (op)= A x with the epilogue of `mode`: what vmult / residual / smoother_step / vmult_subtract / vmult_add /
+  // vmult_plus_scaled call, with the operands every mode needs checked
+  void apply_mode(CsrMode mode, T const *x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta, T *out) const;
   // algorithmic bytes of one y = A x (12 B/nnz + 4 B/row ptr + x + y)
   double algorithmic_bytes_apply() const
   {
@@ -177,6 +233,8 @@ private:
   void launch(CsrMode mode, T const *x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta,
               T *out) const;
 
+  // a.pairs of the last launch, for form() only (atomic: launches from several host threads stay free of a data race)
+  mutable std::atomic<int> _last_pairs{-1};
   HipHandle &_handle;
   int64_t _n_rows, _n_cols, _nnz;
   int _lanes_per_row;

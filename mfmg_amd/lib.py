@@ -21,6 +21,9 @@ NO_TRANS = 0
 TRANS = 1
 TRANS_SUBTRACT = 2   # restrictor_apply only: out -= R^T in
 RESTRICTOR_FORM_FIELDS = 11
+CSR_FORM_FIELDS = 22
+# modes of mfmg_hip_csr_launch
+CSR_APPLY, CSR_RESIDUAL, CSR_FIRST, CSR_NEXT, CSR_SUBTRACT, CSR_ADD, CSR_PLUS_SCALED = range(7)
 
 
 class MfmgError(RuntimeError):
@@ -178,6 +181,8 @@ def load() -> C.CDLL:
         "mfmg_hip_csr_inverse_diagonal": (C.c_int, [vp, vp]),
         "mfmg_hip_csr_smoother_step": (C.c_int, [vp, vp, vp, vp, vp, dbl, dbl, vp]),
         "mfmg_hip_csr_residual": (C.c_int, [vp, vp, vp, vp]),
+        "mfmg_hip_csr_launch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, dbl, dbl, vp]),
+        "mfmg_hip_csr_form": (C.c_int, [vp, P(i64), i32]),
         "mfmg_hip_mf_laplace_create": (C.c_int, [vp, P(MeshDesc), P(vp)]),
         "mfmg_hip_mf_laplace_destroy": (C.c_int, [vp]),
         "mfmg_hip_mf_laplace_size": (C.c_int, [vp, P(i64)]),
