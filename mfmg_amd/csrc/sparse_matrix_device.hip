@@ -48,54 +48,83 @@ struct CsrArgs
   int32_t const *kept_ptr = nullptr; // after release_csr(): val / col hold the listed rows only, row q of the list at [kept_ptr[q], kept_ptr[q + 1])
 };
 
-// the fused epilogues of a row (the modes of CsrMode)
+// Which vectors the epilogue of a mode reads at the row it writes (x there -- not the gathered x --, b, D^-1, x_prev, and
+// out as an input): what apply_mode checks and what the profiler counts.  On the device epilogue() is the statement of
+// it; store_node, which requests the operands ahead of its stores, says it once more in place: through any function, this
+// one included, its flags compile to other instruction streams in all 48 node kernels (two gain VGPRs).
+struct CsrOperands
+{
+  bool x, b, dinv, xprev, out;
+};
+constexpr CsrOperands operands_of(CsrMode m)
+{
+  const bool smoother = m == CsrMode::first || m == CsrMode::next;
+  return {smoother, smoother || m == CsrMode::residual || m == CsrMode::plus_scaled, smoother || m == CsrMode::plus_scaled,
+          m == CsrMode::next, m == CsrMode::subtract || m == CsrMode::add};
+}
+
+// The fused epilogues (the modes of CsrMode): out at one row from the sum of the row.  The operands come as their vectors
+// and the position i in them, the sum by address: each is read inside the case that uses it (the vectors a mode does not
+// read are null pointers).  Passed as values they would be read in front of the switch, and the node kernels compile to
+// other instruction streams.  No other mode reaches a kernel (apply_mode and the C ABI reject it), so `default` needs no
+// code of its own: it stays on the last case, since an unreachable default changes the compare tree of every kernel with
+// an epilogue and costs the LDS-cached kernels 4 to 6 VGPRs.
+template <typename T>
+__device__ __forceinline__ T epilogue(CsrMode mode, T const *sum, T const *x, T const *b, T const *dinv, T const *xprev,
+                                      T const *old, int64_t i, T alpha, T beta)
+{
+  T o;
+  switch (mode)
+  {
+  case CsrMode::apply:
+    o = *sum;
+    break;
+  case CsrMode::residual:
+    o = *sum - b[i];
+    break;
+  case CsrMode::first:
+    o = x[i] - beta * dinv[i] * (*sum - b[i]);
+    break;
+  case CsrMode::next:
+    o = x[i] + alpha * (x[i] - xprev[i]) - beta * dinv[i] * (*sum - b[i]);
+    break;
+  case CsrMode::subtract:
+    o = old[i] - *sum;
+    break;
+  case CsrMode::plus_scaled:
+    o = *sum + beta * dinv[i] * b[i];
+    break;
+  case CsrMode::add:
+  default:
+    o = old[i] + *sum;
+    break;
+  }
+  return o;
+}
+
+// the epilogue of one row
 template <typename T>
 __device__ __forceinline__ void store_row(CsrArgs<T> const &a, int64_t row, T sum)
 {
-  T o;
-  switch (a.mode)
-  {
-  case 0:
-    o = sum;
-    break;
-  case 1:
-    o = sum - a.b[row];
-    break;
-  case 2:
-    o = a.x[row] - a.beta * a.dinv[row] * (sum - a.b[row]);
-    break;
-  case 3:
-  {
-    const T xr = a.x[row];
-    o = xr + a.alpha * (xr - a.xprev[row]) - a.beta * a.dinv[row] * (sum - a.b[row]);
-    break;
-  }
-  case 4:
-    o = a.out[row] - sum;
-    break;
-  case 6:
-    o = sum + a.beta * a.dinv[row] * a.b[row];
-    break;
-  default:
-    o = a.out[row] + sum;
-    break;
-  }
-  a.out[row] = o;
+  a.out[row] = epilogue(static_cast<CsrMode>(a.mode), &sum, a.x, a.b, a.dinv, a.xprev, a.out, row, a.alpha, a.beta);
 }
 
 // The epilogue of the C rows of one NODE (the node kernels below).  Row by row (store_row) the operands of the second row
 // could only be requested after the store of the first -- nothing tells the compiler that out does not alias x, b or D^-1 --,
 // one more dependent round trip in kernels that are bound by their latency.  Here every operand of the node is requested
 // before the first store, and for C = 2 in FP64 the rows 2 n, 2 n + 1 are ONE 16-byte access per operand (a.pairs: the
-// vectors are 16-byte aligned, checked at launch).  Same operations in the same order as store_row: same bits.
+// vectors are 16-byte aligned, checked at launch).  Both halves and store_row evaluate the one epilogue(): same bits.
 template <typename T, int C>
 __device__ __forceinline__ void store_node(CsrArgs<T> const &a, int64_t node, T const (&sum)[C])
 {
   const int64_t row0 = node * C;
   T xr[C], br[C], dr[C], pr[C], orr[C];
-  const int mode = a.mode;
-  const bool need_x = mode == 2 || mode == 3, need_b = (mode >= 1 && mode <= 3) || mode == 6, need_d = need_x || mode == 6,
-             need_p = mode == 3, need_o = mode == 4 || mode == 5;
+  const CsrMode mode = static_cast<CsrMode>(a.mode);
+  // (operands_of(mode), written in place: see there)
+  const bool need_x = mode == CsrMode::first || mode == CsrMode::next,
+             need_b = (mode >= CsrMode::residual && mode <= CsrMode::next) || mode == CsrMode::plus_scaled,
+             need_d = need_x || mode == CsrMode::plus_scaled, need_p = mode == CsrMode::next,
+             need_o = mode == CsrMode::subtract || mode == CsrMode::add;
   if constexpr (C == 2 && sizeof(T) == 8)
   {
     if (a.pairs)
@@ -118,32 +147,7 @@ __device__ __forceinline__ void store_node(CsrArgs<T> const &a, int64_t node, T 
       T o[C];
 #pragma unroll
       for (int rc = 0; rc < C; ++rc)
-      {
-        switch (mode)
-        {
-        case 0:
-          o[rc] = sum[rc];
-          break;
-        case 1:
-          o[rc] = sum[rc] - br[rc];
-          break;
-        case 2:
-          o[rc] = xr[rc] - a.beta * dr[rc] * (sum[rc] - br[rc]);
-          break;
-        case 3:
-          o[rc] = xr[rc] + a.alpha * (xr[rc] - pr[rc]) - a.beta * dr[rc] * (sum[rc] - br[rc]);
-          break;
-        case 4:
-          o[rc] = orr[rc] - sum[rc];
-          break;
-        case 6:
-          o[rc] = sum[rc] + a.beta * dr[rc] * br[rc];
-          break;
-        default:
-          o[rc] = orr[rc] + sum[rc];
-          break;
-        }
-      }
+        o[rc] = epilogue(mode, sum + rc, xr, br, dr, pr, orr, rc, a.alpha, a.beta);
       *reinterpret_cast<double2 *>(a.out + row0) = make_double2(o[0], o[1]);
       return;
     }
@@ -165,34 +169,7 @@ __device__ __forceinline__ void store_node(CsrArgs<T> const &a, int64_t node, T 
   }
 #pragma unroll
   for (int rc = 0; rc < C; ++rc)
-  {
-    T o;
-    switch (mode)
-    {
-    case 0:
-      o = sum[rc];
-      break;
-    case 1:
-      o = sum[rc] - br[rc];
-      break;
-    case 2:
-      o = xr[rc] - a.beta * dr[rc] * (sum[rc] - br[rc]);
-      break;
-    case 3:
-      o = xr[rc] + a.alpha * (xr[rc] - pr[rc]) - a.beta * dr[rc] * (sum[rc] - br[rc]);
-      break;
-    case 4:
-      o = orr[rc] - sum[rc];
-      break;
-    case 6:
-      o = sum[rc] + a.beta * dr[rc] * br[rc];
-      break;
-    default:
-      o = orr[rc] + sum[rc];
-      break;
-    }
-    a.out[row0 + rc] = o;
-  }
+    a.out[row0 + rc] = epilogue(mode, sum + rc, xr, br, dr, pr, orr, rc, a.alpha, a.beta);
 }
 
 template <typename T, int LPR>
@@ -212,37 +189,7 @@ __global__ void csr_spmv_kernel(CsrArgs<T> a)
   for (int off = LPR / 2; off > 0; off >>= 1)
     sum += __shfl_xor(sum, off);
   if (row < a.n_rows && sub == 0)
-  {
-    T o;
-    switch (a.mode)
-    {
-    case 0:
-      o = sum;
-      break;
-    case 1:
-      o = sum - a.b[row];
-      break;
-    case 2:
-      o = a.x[row] - a.beta * a.dinv[row] * (sum - a.b[row]);
-      break;
-    case 3:
-    {
-      const T xr = a.x[row];
-      o = xr + a.alpha * (xr - a.xprev[row]) - a.beta * a.dinv[row] * (sum - a.b[row]);
-      break;
-    }
-    case 4:
-      o = a.out[row] - sum;
-      break;
-    case 6:
-      o = sum + a.beta * a.dinv[row] * a.b[row];
-      break;
-    default:
-      o = a.out[row] + sum;
-      break;
-    }
-    a.out[row] = o;
-  }
+    store_row(a, row, sum);
 }
 
 // Few, long rows (the transfer operators and the triangular inverses at the bottom of the aggregation hierarchy:
@@ -301,37 +248,7 @@ __global__ void csr_spmv_lds_kernel(CsrArgs<T> a, int32_t const *blk_ptr, int32_
     for (int off = LPR / 2; off > 0; off >>= 1)
       sum += __shfl_xor(sum, off);
     if (row < row1 && sub == 0)
-    {
-      T o;
-      switch (a.mode)
-      {
-      case 0:
-        o = sum;
-        break;
-      case 1:
-        o = sum - a.b[row];
-        break;
-      case 2:
-        o = a.x[row] - a.beta * a.dinv[row] * (sum - a.b[row]);
-        break;
-      case 3:
-      {
-        const T xr = a.x[row];
-        o = xr + a.alpha * (xr - a.xprev[row]) - a.beta * a.dinv[row] * (sum - a.b[row]);
-        break;
-      }
-      case 4:
-        o = a.out[row] - sum;
-        break;
-      case 6:
-        o = sum + a.beta * a.dinv[row] * a.b[row];
-        break;
-      default:
-        o = a.out[row] + sum;
-        break;
-      }
-      a.out[row] = o;
-    }
+      store_row(a, row, sum);
   }
 }
 
@@ -400,35 +317,7 @@ __global__ __launch_bounds__(256) void bdia_spmv_kernel(CsrArgs<T> a, V const *v
     }
   }
   const int64_t row = r;
-  T o;
-  switch (a.mode)
-  {
-  case 0:
-    o = sum;
-    break;
-  case 1:
-    o = sum - a.b[row];
-    break;
-  case 2:
-    o = a.x[row] - a.beta * a.dinv[row] * (sum - a.b[row]);
-    break;
-  case 3:
-  {
-    const T xr = a.x[row];
-    o = xr + a.alpha * (xr - a.xprev[row]) - a.beta * a.dinv[row] * (sum - a.b[row]);
-    break;
-  }
-  case 4:
-    o = a.out[row] - sum;
-    break;
-  case 6:
-    o = sum + a.beta * a.dinv[row] * a.b[row];
-    break;
-  default:
-    o = a.out[row] + sum;
-    break;
-  }
-  a.out[row] = o;
+  store_row(a, row, sum);
 }
 
 // Row-base storage for rectangular stencil-like matrices whose values do not repeat (prolongators of a problem with a
@@ -457,10 +346,6 @@ __global__ __launch_bounds__(256) void rowbase_spmv_kernel(CsrArgs<T> a, T const
   store_row(a, r, sum);
 }
 
-// Symmetric matrices keep only the block diagonals with offset >= 0 (half the bytes from HBM): the entry
-// A[(n,c)][(n-o,cc)] of a lower diagonal is read as its transpose A[(n-o,cc)][(n,c)] = val[o][c][(n-o) C + cc],
-// i.e. the same plane a lower-numbered row streams as its upper part -- a second read of data that passed
-// through the caches o rows earlier.  One thread per row, fixed summation order (upper part, then lower part).
 // regular rows (see build_block_diagonals): the stencil comes from a table, only x is read
 template <typename T>
 struct BdiaRegular
@@ -706,6 +591,11 @@ __global__ __launch_bounds__(256) void csr_listed_rows_kernel(CsrArgs<T> a, int3
   listed_row_wave(a, rows, n_listed, (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6, threadIdx.x & 63);
 }
 
+// Symmetric matrices keep only the block diagonals with offset >= 0 (half the bytes from HBM): the entry
+// A[(n,c)][(n-o,cc)] of a lower diagonal is read as its transpose A[(n-o,cc)][(n,c)] = val[o][c][(n-o) C + cc],
+// i.e. the same plane a lower-numbered row streams as its upper part -- a second read of data that passed
+// through the caches o rows earlier.  One thread per row, fixed summation order (upper part, then lower part):
+// bdia_sym_spmv_kernel.  bdia_sym_split_kernel:
 // The same sums for a whole matrix with the block diagonals dealt to the four quarters of a 1024-thread workgroup
 // (256 consecutive rows): four times the wavefronts, each with a quarter of the dependent loads; no branches
 // around the loads (a neighbour outside the matrix is read at a clamped position and its entry replaced by 0), the
@@ -788,36 +678,7 @@ __global__ __launch_bounds__(256) void bdia_sym_spmv_kernel(CsrArgs<T> a, V cons
         sum += T(vq[cc]) * a.x[nb * C + cc];
     }
   }
-  const int64_t row = r;
-  T o;
-  switch (a.mode)
-  {
-  case 0:
-    o = sum;
-    break;
-  case 1:
-    o = sum - a.b[row];
-    break;
-  case 2:
-    o = a.x[row] - a.beta * a.dinv[row] * (sum - a.b[row]);
-    break;
-  case 3:
-  {
-    const T xr = a.x[row];
-    o = xr + a.alpha * (xr - a.xprev[row]) - a.beta * a.dinv[row] * (sum - a.b[row]);
-    break;
-  }
-  case 4:
-    o = a.out[row] - sum;
-    break;
-  case 6:
-    o = sum + a.beta * a.dinv[row] * a.b[row];
-    break;
-  default:
-    o = a.out[row] + sum;
-    break;
-  }
-  a.out[row] = o;
+  store_row(a, r, sum);
 }
 
 // ---- layout analysis on the device -----------------------------------------------------------------------
@@ -1090,6 +951,42 @@ constexpr int kMaxStoredBlockDiagonals = 160;
 constexpr int64_t kRegularAsClassNodes = 5000000; // nodes up to which regular nodes are evaluated as one more class (one launch instead of two: at 2.1 M nodes 54 against 38 + 23 us)
 constexpr int kSplitStencil = 48;        // block diagonals from which a node's stencil is split over four wavefronts
 constexpr int64_t kListedWaveRows = 32768; // listed rows up to which each gets a wavefront of its own
+
+// f(std::integral_constant<int, c>()) for the unknowns per node c = 1 .. 4 of a layout
+template <typename F>
+void with_node_width(int c, F &&f)
+{
+  switch (c)
+  {
+  case 1:
+    f(std::integral_constant<int, 1>());
+    break;
+  case 2:
+    f(std::integral_constant<int, 2>());
+    break;
+  case 3:
+    f(std::integral_constant<int, 3>());
+    break;
+  default:
+    f(std::integral_constant<int, 4>());
+    break;
+  }
+}
+
+// f(std::integral_constant<int, l>()) for the lanes per row l = L, 2 L, .. 32 of a CSR kernel; any other value: 64
+template <int L, typename F>
+void with_lanes(int lanes, F &&f)
+{
+  if constexpr (L < 64)
+  {
+    if (lanes == L)
+      f(std::integral_constant<int, L>());
+    else
+      with_lanes<2 * L>(lanes, f);
+  }
+  else
+    f(std::integral_constant<int, 64>());
+}
 
 template <typename T, int LPR>
 void launch_lds(CsrArgs<T> const &a, hipStream_t st, int32_t const *blk_ptr, int32_t const *l2g, uint16_t const *lcol,
@@ -2206,13 +2103,13 @@ void SparseMatrixDevice<T>::apply_mode(CsrMode mode, T const *x, T const *b, T c
 {
   const int m = static_cast<int>(mode);
   ASSERT_THROW(m >= 0 && m <= 6, "unknown SpMV mode");
-  const bool need_b = (m >= 1 && m <= 3) || m == 6, need_d = m == 2 || m == 3 || m == 6, need_p = m == 3;
-  ASSERT_THROW(!need_b || b != nullptr, "this SpMV mode needs b");
-  ASSERT_THROW(!need_d || dinv != nullptr, "this SpMV mode needs the inverse diagonal");
-  ASSERT_THROW(!need_p || x_prev != nullptr, "this SpMV mode needs x_prev");
-  ASSERT_THROW(!(m == 2 || m == 3) || _n_rows == _n_cols, "the smoother needs a square matrix");
-  launch(mode, x, need_b ? b : nullptr, need_d ? dinv : nullptr, need_p ? x_prev : nullptr, need_p ? alpha : T(0),
-         need_d ? beta : T(0), out);
+  const CsrOperands need = operands_of(mode);
+  ASSERT_THROW(!need.b || b != nullptr, "this SpMV mode needs b");
+  ASSERT_THROW(!need.dinv || dinv != nullptr, "this SpMV mode needs the inverse diagonal");
+  ASSERT_THROW(!need.xprev || x_prev != nullptr, "this SpMV mode needs x_prev");
+  ASSERT_THROW(!need.x || _n_rows == _n_cols, "the smoother needs a square matrix");
+  launch(mode, x, need.b ? b : nullptr, need.dinv ? dinv : nullptr, need.xprev ? x_prev : nullptr, need.xprev ? alpha : T(0),
+         need.dinv ? beta : T(0), out);
 }
 
 template <typename T>
@@ -2253,9 +2150,27 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
   }
   const CsrForm f = form(); // (every branch below is taken from it)
   hipStream_t st = _handle.stream;
-  const double extra = (mode == CsrMode::apply) ? 0. : (mode == CsrMode::first) ? 3. : (mode == CsrMode::next) ? 4. : 1.;
+  // vectors of n_rows entries counted beyond x and out: b or the old out 1, x at the row and D^-1 of the smoother 2, x_prev
+  // 1 (the D^-1 of plus_scaled was never counted: kept, the recorded bandwidths stay comparable)
+  const CsrOperands need = operands_of(mode);
+  const double extra = (need.b || need.out ? 1. : 0.) + (need.x ? 2. : 0.) + (need.xprev ? 1. : 0.);
   hipEvent_t stop =
       _handle.profiler.begin("csr_spmv_kernel", algorithmic_bytes_apply() + extra * sizeof(T) * double(_n_rows), st);
+  // the launch of the classes of a node layout with C unknowns per node: f.class_kernel wavefronts share a node's stencil;
+  // the tail workgroups behind the class lists take the listed rows `tail`, one wavefront each
+  auto launch_classes = [&](auto cc, BdiaRegular<T> const &g, int32_t const *nodes, int32_t const *class_of_wave, T const *table,
+                            int64_t n_slots, int32_t const *tail, int64_t n_tail) {
+    constexpr int C = decltype(cc)::value;
+    if (f.class_kernel == 16)
+      hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 16>), dim3((unsigned int)((n_slots + 63) / 64 + (n_tail + 15) / 16)),
+                         dim3(1024), 0, st, a, g, nodes, class_of_wave, table, n_slots, tail, n_tail);
+    else if (f.class_kernel == 4)
+      hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 4>), dim3((unsigned int)((n_slots + 255) / 256 + (n_tail + 15) / 16)),
+                         dim3(1024), 0, st, a, g, nodes, class_of_wave, table, n_slots, tail, n_tail);
+    else if (f.class_kernel == 1)
+      hipLaunchKernelGGL((bdia_class_node_kernel<T, C>), dim3((unsigned int)((n_slots + 255) / 256 + (n_tail + 3) / 4)), dim3(256),
+                         0, st, a, g, nodes, class_of_wave, table, n_slots, tail, n_tail);
+  };
   if (f.kind == 5 && f.regular)
   {
     BdiaRegular<T> g;
@@ -2267,56 +2182,16 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     g.Df = _nc_d;
     g.base = _nc_base.data();
     g.n_col_nodes = _n_cols / _nc_c;
-    const int64_t n_slots = (int64_t)_nc_nodes.size();
-    int32_t const *cn = _nc_nodes.data(), *cw = _nc_class_of_wave.data();
-    T const *ct = _nc_table.data();
-    int32_t const *ls = _nc_listed.data();
-    const int64_t n_listed = (int64_t)_nc_listed.size();
-    auto launch_nodes = [&](auto cc) {
-      constexpr int C = decltype(cc)::value;
-      if (f.class_kernel == 16)
-        hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 16>),
-                           dim3((unsigned int)((n_slots + 63) / 64 + (n_listed + 15) / 16)), dim3(1024), 0, st, a, g, cn, cw,
-                           ct, n_slots, ls, n_listed);
-      else if (f.class_kernel == 4)
-        hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 4>),
-                           dim3((unsigned int)((n_slots + 255) / 256 + (n_listed + 15) / 16)), dim3(1024), 0, st, a, g, cn,
-                           cw, ct, n_slots, ls, n_listed);
-      else
-        hipLaunchKernelGGL((bdia_class_node_kernel<T, C>), dim3((unsigned int)((n_slots + 255) / 256 + (n_listed + 3) / 4)),
-                           dim3(256), 0, st, a, g, cn, cw, ct, n_slots, ls, n_listed);
-    };
-    switch (_nc_c)
-    {
-    case 1:
-      launch_nodes(std::integral_constant<int, 1>());
-      break;
-    case 2:
-      launch_nodes(std::integral_constant<int, 2>());
-      break;
-    case 3:
-      launch_nodes(std::integral_constant<int, 3>());
-      break;
-    default:
-      launch_nodes(std::integral_constant<int, 4>());
-      break;
-    }
-    KernelProfiler::end(stop, st);
-    MFMG_HIP_CHECK(hipGetLastError());
-    return;
+    with_node_width(_nc_c, [&](auto cc) {
+      launch_classes(cc, g, _nc_nodes.data(), _nc_class_of_wave.data(), _nc_table.data(), (int64_t)_nc_nodes.size(),
+                     _nc_listed.data(), (int64_t)_nc_listed.size());
+    });
   }
-  if (f.kind == 4)
-  {
+  else if (f.kind == 4)
     hipLaunchKernelGGL(rowbase_spmv_kernel<T>, dim3((unsigned int)((_n_rows + 255) / 256)), dim3(256), 0, st, a,
                        _rb_val.data(), _rb_base.data(), _rb_offs.data(), _rb_slots, _n_cols);
-    KernelProfiler::end(stop, st);
-    MFMG_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if (f.kind == 2 || f.kind == 3)
+  else if (f.kind == 2 || f.kind == 3)
   {
-    T const *dv = _bdia_val.data();
-    int32_t const *of = _bdia_offs.data();
     BdiaRegular<T> g;
     g.exc = f.regular ? _bdia_exc.data() : nullptr;
     g.table = _bdia_table.data();
@@ -2329,156 +2204,63 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     {
       // regular nodes, then the classes of the others; wide stencils split over the wavefronts of a workgroup
       const int64_t n_nodes = _n_rows / _bdia_c;
-      const int64_t n_slots = (int64_t)_bdia_cls_nodes.size();
-      int32_t const *cn = _bdia_cls_nodes.data(), *cw = _bdia_cls_of_wave.data();
-      T const *ct = _bdia_cls_table.data();
       // few listed rows ride at the end of the class launch, one wavefront each
       const int64_t n_tail = (f.listed_route == CsrForm::listed_class_tail || f.listed_route == CsrForm::listed_split_tail) ? g.n_exc : 0;
-      auto launch_nodes = [&](auto cc) {
+      with_node_width(_bdia_c, [&](auto cc) {
         constexpr int C = decltype(cc)::value;
-        if (f.regular_kernel == 0)
-          ; // (the regular nodes are one of the classes)
-        else if (f.regular_kernel == 16)
+        if (f.regular_kernel == 16)
           hipLaunchKernelGGL((bdia_node_split_kernel<T, C, false, 16>), dim3((unsigned int)((n_nodes + 63) / 64)),
                              dim3(1024), 0, st, a, g, nullptr, nullptr, nullptr, 0, nullptr, 0);
         else if (f.regular_kernel == 4)
           hipLaunchKernelGGL((bdia_node_split_kernel<T, C, false, 4>), dim3((unsigned int)((n_nodes + 255) / 256)),
                              dim3(1024), 0, st, a, g, nullptr, nullptr, nullptr, 0, nullptr, 0);
-        else
+        else if (f.regular_kernel == 1)
           hipLaunchKernelGGL((bdia_regular_node_kernel<T, C>), dim3((unsigned int)((n_nodes + 255) / 256)), dim3(256), 0,
                              st, a, g);
-        if (f.class_kernel == 16)
-          hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 16>),
-                             dim3((unsigned int)((n_slots + 63) / 64 + (n_tail + 15) / 16)), dim3(1024), 0, st, a, g, cn, cw,
-                             ct, n_slots, g.exc_rows, n_tail);
-        else if (f.class_kernel == 4)
-          hipLaunchKernelGGL((bdia_node_split_kernel<T, C, true, 4>),
-                             dim3((unsigned int)((n_slots + 255) / 256 + (n_tail + 15) / 16)), dim3(1024), 0, st, a, g, cn,
-                             cw, ct, n_slots, g.exc_rows, n_tail);
-        else if (f.class_kernel == 1)
-          hipLaunchKernelGGL((bdia_class_node_kernel<T, C>), dim3((unsigned int)((n_slots + 255) / 256 + (n_tail + 3) / 4)),
-                             dim3(256), 0, st, a, g, cn, cw, ct, n_slots, g.exc_rows, n_tail);
-      };
-      switch (_bdia_c)
-      {
-      case 1:
-        launch_nodes(std::integral_constant<int, 1>());
-        break;
-      case 2:
-        launch_nodes(std::integral_constant<int, 2>());
-        break;
-      case 3:
-        launch_nodes(std::integral_constant<int, 3>());
-        break;
-      default:
-        launch_nodes(std::integral_constant<int, 4>());
-        break;
-      }
-      if (f.listed_route != CsrForm::listed_stored_planes)
-      {
-        if (f.listed_route == CsrForm::listed_own_launch)
-          hipLaunchKernelGGL(csr_listed_rows_kernel<T>, dim3((unsigned int)((g.n_exc + 3) / 4)), dim3(256), 0, st, a,
-                             g.exc_rows, g.n_exc);
-        KernelProfiler::end(stop, st);
-        MFMG_HIP_CHECK(hipGetLastError());
-        return;
-      }
+        // (f.regular_kernel == 0: the regular nodes are one of the classes)
+        launch_classes(cc, g, _bdia_cls_nodes.data(), _bdia_cls_of_wave.data(), _bdia_cls_table.data(),
+                       (int64_t)_bdia_cls_nodes.size(), g.exc_rows, n_tail);
+      });
+      if (f.listed_route == CsrForm::listed_own_launch)
+        hipLaunchKernelGGL(csr_listed_rows_kernel<T>, dim3((unsigned int)((g.n_exc + 3) / 4)), dim3(256), 0, st, a,
+                           g.exc_rows, g.n_exc);
     }
-    const dim3 rgrid((unsigned int)(((g.exc != nullptr ? g.n_exc : _n_rows) + 255) / 256));
-    // the stored planes: in T, or in float where every value is representable in it (half the bytes, sums in T)
-    auto stored = [&](auto const *planes, auto cc) {
-      using V = std::remove_cv_t<std::remove_pointer_t<decltype(planes)>>;
-      constexpr int C = decltype(cc)::value;
-      if (f.stored_kernel == CsrForm::stored_sym_split)
-        hipLaunchKernelGGL((bdia_sym_split_kernel<T, C, V>), dim3((unsigned int)((_n_rows + 255) / 256)), dim3(1024), 0, st, a, planes, of,
-                           _bdia_d);
-      else if (f.stored_kernel == CsrForm::stored_sym_rows)
-      {
-        if (rgrid.x > 0)
-          hipLaunchKernelGGL((bdia_sym_spmv_kernel<T, C, V>), rgrid, dim3(256), 0, st, a, planes, of, _bdia_d, g);
-      }
-      else if (rgrid.x > 0)
-        hipLaunchKernelGGL((bdia_spmv_kernel<T, C, V>), rgrid, dim3(256), 0, st, a, planes, of, _bdia_d,
-                           g.exc != nullptr ? g.exc_rows : nullptr, g.n_exc);
-    };
-    auto stored_c = [&](auto const *planes) {
-      switch (_bdia_c)
-      {
-      case 1:
-        stored(planes, std::integral_constant<int, 1>());
-        break;
-      case 2:
-        stored(planes, std::integral_constant<int, 2>());
-        break;
-      case 3:
-        stored(planes, std::integral_constant<int, 3>());
-        break;
-      default:
-        stored(planes, std::integral_constant<int, 4>());
-        break;
-      }
-    };
-    if (f.float_planes)
-      stored_c(_bdia_val_f32.data());
-    else
-      stored_c(dv);
-    KernelProfiler::end(stop, st);
-    MFMG_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if (f.csr_kernel == CsrForm::csr_lds)
-  {
-    int32_t const *bp = _blk_ptr.data(), *lg = _l2g.data();
-    uint16_t const *lc = _lcol.data();
-    switch (f.lanes)
+    if (f.stored_kernel != CsrForm::stored_none)
     {
-    case 4:
-      launch_lds<T, 4>(a, st, bp, lg, lc, kRowsPerBlock, _lds_max_cols);
-      break;
-    case 8:
-      launch_lds<T, 8>(a, st, bp, lg, lc, kRowsPerBlock, _lds_max_cols);
-      break;
-    case 16:
-      launch_lds<T, 16>(a, st, bp, lg, lc, kRowsPerBlock, _lds_max_cols);
-      break;
-    case 32:
-      launch_lds<T, 32>(a, st, bp, lg, lc, kRowsPerBlock, _lds_max_cols);
-      break;
-    default:
-      launch_lds<T, 64>(a, st, bp, lg, lc, kRowsPerBlock, _lds_max_cols);
-      break;
+      // the stored planes (all rows, or the listed ones of a matrix with regular rows): in T, or in float where every value
+      // is representable in it (half the bytes, sums in T)
+      const dim3 rgrid((unsigned int)(((g.exc != nullptr ? g.n_exc : _n_rows) + 255) / 256));
+      auto stored = [&](auto const *planes) {
+        using V = std::remove_cv_t<std::remove_pointer_t<decltype(planes)>>;
+        with_node_width(_bdia_c, [&](auto cc) {
+          constexpr int C = decltype(cc)::value;
+          if (f.stored_kernel == CsrForm::stored_sym_split)
+            hipLaunchKernelGGL((bdia_sym_split_kernel<T, C, V>), dim3((unsigned int)((_n_rows + 255) / 256)), dim3(1024), 0, st, a,
+                               planes, _bdia_offs.data(), _bdia_d);
+          else if (rgrid.x == 0)
+            ; // (no row left to the planes)
+          else if (f.stored_kernel == CsrForm::stored_sym_rows)
+            hipLaunchKernelGGL((bdia_sym_spmv_kernel<T, C, V>), rgrid, dim3(256), 0, st, a, planes, _bdia_offs.data(), _bdia_d, g);
+          else
+            hipLaunchKernelGGL((bdia_spmv_kernel<T, C, V>), rgrid, dim3(256), 0, st, a, planes, _bdia_offs.data(), _bdia_d,
+                               g.exc != nullptr ? g.exc_rows : nullptr, g.n_exc);
+        });
+      };
+      if (f.float_planes)
+        stored(_bdia_val_f32.data());
+      else
+        stored(_bdia_val.data());
     }
-    KernelProfiler::end(stop, st);
-    MFMG_HIP_CHECK(hipGetLastError());
-    return;
   }
-  switch (f.lanes)
-  {
-  case 256:
+  else if (f.csr_kernel == CsrForm::csr_lds)
+    // (form() reports 4 lanes at least: the LDS-cached kernel has no instance below)
+    with_lanes<4>(f.lanes, [&](auto l) {
+      launch_lds<T, decltype(l)::value>(a, st, _blk_ptr.data(), _l2g.data(), _lcol.data(), kRowsPerBlock, _lds_max_cols);
+    });
+  else if (f.csr_kernel == CsrForm::csr_row_block)
     hipLaunchKernelGGL(csr_spmv_row_block_kernel<T>, dim3((unsigned int)_n_rows), dim3(256), 0, st, a);
-    break;
-  case 1:
-    launch_lpr<T, 1>(a, st);
-    break;
-  case 2:
-    launch_lpr<T, 2>(a, st);
-    break;
-  case 4:
-    launch_lpr<T, 4>(a, st);
-    break;
-  case 8:
-    launch_lpr<T, 8>(a, st);
-    break;
-  case 16:
-    launch_lpr<T, 16>(a, st);
-    break;
-  case 32:
-    launch_lpr<T, 32>(a, st);
-    break;
-  default:
-    launch_lpr<T, 64>(a, st);
-    break;
-  }
+  else
+    with_lanes<1>(f.lanes, [&](auto l) { launch_lpr<T, decltype(l)::value>(a, st); });
   KernelProfiler::end(stop, st);
   MFMG_HIP_CHECK(hipGetLastError());
 }
