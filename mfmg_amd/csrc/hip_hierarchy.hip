@@ -642,20 +642,12 @@ HipMatrixFreeOperator::HipMatrixFreeOperator(std::shared_ptr<HipMatrixFreeMeshEv
 // One operator application of a distributed run: the tiles that do not read a ghost plane run while the
 // boundary planes travel on the second stream; the tiles next to the ghost planes follow (slabs: at most four z-tiles;
 // boxes: a shell of tiles along all three axes).
-void HipMatrixFreeOperator::apply_mode(MfMode mode, double const *x, double const *b, double const *x_prev,
-                                       double alpha, double beta, double *out) const
+void HipMatrixFreeOperator::apply_mode(MfMode mode, MfOperands<double> const &v) const
 {
   HipHandle &handle = get_hip_handle();
   auto op = _mesh_evaluator->get_device_operator();
-  auto whole = [&] {
-    if (mode == MfMode::apply)
-      op->vmult(x, out);
-    else if (mode == MfMode::residual)
-      op->residual(x, b, out);
-    else
-      op->smoother_step(b, x, x_prev, alpha, beta, out);
-  };
-  // The shell around the interior tiles is ONE launch over a compact list of its tiles (launch_outside: z slabs, y slabs, x
+  auto whole = [&] { op->launch_region(mode, v, MfTileRegion::whole()); };
+  // The shell around the interior tiles is ONE launch over a compact list of its tiles (MfTileRegion::outside_of: z slabs, y slabs, x
   // slabs and the tail columns; consecutive workgroups, consecutive tiles, so that the XCDs share it evenly), enqueued on the
   // EXCHANGE stream behind the unpacking: it runs beside the interior tiles and its workgroups fill the slots the interior
   // launch leaves while it drains.  Measured on one GPU with the launches of the corner rank of a 2 x 2 x 2 grid and no exchange
@@ -671,29 +663,29 @@ void HipMatrixFreeOperator::apply_mode(MfMode mode, double const *x, double cons
   auto shell = [&](int const lo[3], int const hi[3], int const nt[3]) {
     if (!shell_slabs && !shell_after)
     {
-      op->launch_outside(mode, x, b, x_prev, alpha, beta, out, lo, hi, handle.exchange_stream());
+      op->launch_region(mode, v, MfTileRegion::outside_of(lo, hi, handle.exchange_stream()));
       handle.join_exchange_stream();
       return;
     }
     handle.exchange_end(1);
     if (shell_after)
     {
-      op->launch_outside(mode, x, b, x_prev, alpha, beta, out, lo, hi);
+      op->launch_region(mode, v, MfTileRegion::outside_of(lo, hi));
       return;
     }
+    // the slabs of mf_shell_slabs, low side then high side (z, y, x each), then the tail columns over all z-tiles
     const int zero[3] = {0, 0, 0};
-    // z slabs over all columns and rows, y slabs between them, x slabs between those, then the tail columns over all z-tiles
+    int slab[6][6];
+    mf_shell_slabs(lo, hi, nt, slab);
     for (int side = 0; side < 2; ++side)
-    {
-      int b0[3] = {0, 0, side == 0 ? 0 : hi[2]}, b1[3] = {nt[0], nt[1], side == 0 ? lo[2] : nt[2]};
-      op->launch_tiles(mode, x, b, x_prev, alpha, beta, out, b0, b1, true, false);
-      int c0[3] = {0, side == 0 ? 0 : hi[1], lo[2]}, c1[3] = {nt[0], side == 0 ? lo[1] : nt[1], hi[2]};
-      op->launch_tiles(mode, x, b, x_prev, alpha, beta, out, c0, c1, true, false);
-      int d0[3] = {side == 0 ? 0 : hi[0], lo[1], lo[2]}, d1[3] = {side == 0 ? lo[0] : nt[0], hi[1], hi[2]};
-      op->launch_tiles(mode, x, b, x_prev, alpha, beta, out, d0, d1, true, false);
-    }
+      for (int q = side; q < 6; q += 2)
+        if (!mf_slab_empty(slab[q]))
+        {
+          const int b0[3] = {slab[q][0], slab[q][2], slab[q][4]}, b1[3] = {slab[q][1], slab[q][3], slab[q][5]};
+          op->launch_region(mode, v, MfTileRegion::box(b0, b1));
+        }
     if (op->has_tail())
-      op->launch_tiles(mode, x, b, x_prev, alpha, beta, out, zero, nt, false, true);
+      op->launch_region(mode, v, MfTileRegion::box(zero, nt, false, true));
   };
   if (!handle.comm.enabled())
   {
@@ -710,7 +702,7 @@ void HipMatrixFreeOperator::apply_mode(MfMode mode, double const *x, double cons
         const int lo[3] = {0, 0, 0};
         const int hi[3] = {nt[0] - (emu == 3 ? 1 : 0), nt[1] - (emu == 1 ? 0 : 1), nt[2] - 1};
         handle.fork_exchange_stream(); // (what an exchange_begin does to the two streams, without the exchange)
-        op->launch_tiles(mode, x, b, x_prev, alpha, beta, out, lo, hi, true, false);
+        op->launch_region(mode, v, MfTileRegion::box(lo, hi));
         shell(lo, hi, nt);
         return;
       }
@@ -739,12 +731,12 @@ void HipMatrixFreeOperator::apply_mode(MfMode mode, double const *x, double cons
   }
   if (!interior)
   {
-    handle.exchange(1, const_cast<double *>(x));
+    handle.exchange(1, const_cast<double *>(v.x));
     whole();
     return;
   }
-  handle.exchange_begin(1, const_cast<double *>(x));
-  op->launch_tiles(mode, x, b, x_prev, alpha, beta, out, lo, hi, true, false);
+  handle.exchange_begin(1, const_cast<double *>(v.x));
+  op->launch_region(mode, v, MfTileRegion::box(lo, hi));
   shell(lo, hi, nt);
 }
 
@@ -756,7 +748,7 @@ void HipMatrixFreeOperator::apply_local(DVector const &x, DVector &y) const
 void HipMatrixFreeOperator::vmult(DVector &dst, DVector const &src) const
 {
   ASSERT_THROW(dst.size() == src.size(), "vector sizes do not match the operator");
-  apply_mode(MfMode::apply, src.get_values(), nullptr, nullptr, 0., 0., dst.get_values());
+  apply_mode(MfMode::apply, {src.get_values(), nullptr, nullptr, 0., 0., dst.get_values()});
 }
 
 void HipMatrixFreeOperator::apply(DVector const &x, DVector &y, OperatorMode mode) const
@@ -807,14 +799,14 @@ size_t HipMatrixFreeOperator::operator_complexity() const
 
 void HipMatrixFreeOperator::residual(DVector const &x, DVector const &b, DVector &res) const
 {
-  apply_mode(MfMode::residual, x.get_values(), b.get_values(), nullptr, 0., 0., res.get_values());
+  apply_mode(MfMode::residual, {x.get_values(), b.get_values(), nullptr, 0., 0., res.get_values()});
 }
 
 void HipMatrixFreeOperator::smoother_step(DVector const &b, DVector const &x, DVector const *x_prev, double alpha,
                                           double beta, DVector &out) const
 {
-  apply_mode((x_prev == nullptr || alpha == 0.) ? MfMode::first : MfMode::next, x.get_values(), b.get_values(),
-             x_prev ? x_prev->get_values() : nullptr, alpha, beta, out.get_values());
+  double const *xp = x_prev ? x_prev->get_values() : nullptr;
+  apply_mode(mf_smoother_mode(xp, alpha), {x.get_values(), b.get_values(), xp, alpha, beta, out.get_values()});
 }
 
 bool HipMatrixFreeOperator::sweep_available(int n_terms) const

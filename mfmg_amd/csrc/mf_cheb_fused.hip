@@ -37,8 +37,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
-#include <set>
 #include <string>
 #include <utility>
 
@@ -75,6 +73,18 @@ struct IntTag
 {
   static constexpr int value = V;
 };
+
+// a run-time number of smoother terms as the template argument K (with_tile_rows, mf_device.hpp)
+template <typename F>
+void with_terms(int n_terms, F &&f)
+{
+  if (n_terms == 1)
+    f(std::integral_constant<int, 1>());
+  else if (n_terms == 2)
+    f(std::integral_constant<int, 2>());
+  else
+    f(std::integral_constant<int, 3>());
+}
 
 // The cell kernel in MODE SPACE (one coefficient per cell).  Per direction a Q1 cell acts on (u0, u1) through s = u0 + u1 and
 // d = u1 - u0 alone: the 1-D stiffness matrix is diag(0, 1), the mass matrices diag(1/2, 1/6) and f diag(1, 1/3) on (s, d), and the
@@ -845,13 +855,7 @@ void MatrixFreeLaplaceDevice<T>::choose_fused_tile(int n_terms, int &nw, int &ty
   ASSERT_THROW(ry >= 1, "tile of the multi-term sweep too small for its halo rows");
   if (tz > 0)
     return;
-  static const int n_cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      v = 256;
-    return v > 0 ? v : 256;
-  }();
-  const int64_t slots = (int64_t)n_cus * (8 / nw);
+  const int64_t slots = (int64_t)mf_n_cus() * (8 / nw);
   const int64_t nty = (_N[1] + ry - 1) / ry;
   const int64_t tiles_xy = (narrow_last_column() && fused_narrow_capable(n_terms, ty)) ? (int64_t)(_ncols - 1) * nty + (nty + 1) / 2 : (int64_t)_ncols * nty;
   double best = 0.;
@@ -900,16 +904,8 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
   a.rec_bytes = (unsigned int)_rec_bytes;
   a.dinv_in_record = _dinv_in_record ? 1 : 0;
   {
-    const double vol = _h[0] * _h[1] * _h[2];
-    const double m00 = MFMG_GA * MFMG_GA + MFMG_GB * MFMG_GB, m01 = 2. * MFMG_GA * MFMG_GB;
-    const double f[3] = {vol / 8. / (_h[0] * _h[0]), vol / 8. / (_h[1] * _h[1]), vol / 8. / (_h[2] * _h[2])};
-    a.fax = T(2. * f[0] * m00);
-    a.fbx = T(2. * f[0] * m01);
-    a.fay = T(2. * f[1] * m00);
-    a.fby = T(2. * f[1] * m01);
-    a.faz = T(2. * f[2] * m00);
-    a.fbz = T(2. * f[2] * m01);
-    a.kd = T(2. * m00 * m00 * (f[0] + f[1] + f[2]));
+    double f[3];
+    mf_cell_factors(a, _h, f);
     // the cell matrix on the modes (cell_row_modes): stiffness diag(0, 1), masses diag(1/2, 1/6) and f diag(1, 1/3)
     a.lam[0] = T(f[0] / 2.);
     a.lam[1] = T(f[1] / 2.);
@@ -935,9 +931,9 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
   a.wide_tiles = (a.ncols - (narrow ? 1u : 0u)) * a.ntiles_y * a.ntiles_z;
   const uint64_t n_tiles = (uint64_t)a.wide_tiles + (uint64_t)a.ntiles_y2 * a.ntiles_z;
   ASSERT_THROW(n_tiles < (1ull << 30), "tile of the multi-term sweep too small for this mesh (grid size limit)");
-  const unsigned int n_blocks = (unsigned int)(n_tiles >= 64 ? ((n_tiles + 7) / 8) * 8 : n_tiles);
+  const unsigned int n_blocks = mf_xcd_grid(n_tiles);
   const size_t lds = ((size_t)nw * ring_planes(n_terms) * (ty + 1) + (size_t)2 * nw * 4) * 64 * sizeof(T);
-  ASSERT_THROW(lds <= 160 * 1024, "tile of the multi-term sweep too large for the LDS");
+  ASSERT_THROW(lds <= kMfMaxLds, "tile of the multi-term sweep too large for the LDS");
   hipStream_t st = _handle.stream;
   // Algorithmic bytes of the launch: what its n_terms smoother terms require as launches of their own (x, out, one id, the
   // coefficient, b, x_prev: mf_laplace.hpp) -- the figure the one-term kernel is priced on, so that the two compare.  What the
@@ -947,105 +943,47 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
     bytes += required_bytes_apply() + epilogue_bytes(k == 0 ? 2 : 3);
   hipEvent_t stop = _handle.profiler.begin("mf_cheb_fused_kernel", bytes, st);
   static const bool narrow_split = std::getenv("MFMG_MF_FUSED_NARROW") && std::string(std::getenv("MFMG_MF_FUSED_NARROW")) == "split";
-  auto go = [&](auto kernel, unsigned int blocks) {
-    static std::mutex attr_mutex;
-    static std::set<std::pair<const void *, int>> attr_set;
-    int dev = 0;
-    MFMG_HIP_CHECK(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lock(attr_mutex);
-      if (attr_set.insert({reinterpret_cast<const void *>(kernel), dev}).second)
-        MFMG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * nw), lds, st, a);
-  };
-  auto grid = [](uint64_t n) { return (unsigned int)(n >= 64 ? ((n + 7) / 8) * 8 : n); };
+  auto go = [&](auto kernel, unsigned int blocks) { mf_launch(kernel, MfGrid{blocks, nw, lds, st}, a); };
   // a kernel that carries both bodies (joint) or the wide-only kernel followed by the narrow-only one (split)
   auto go_narrow = [&](auto joint, auto wide, auto narrow_only) {
     if (!narrow_split)
       go(joint, n_blocks);
     else
     {
-      go(wide, grid(a.wide_tiles));
-      go(narrow_only, grid((uint64_t)a.ntiles_y2 * a.ntiles_z));
+      go(wide, mf_xcd_grid(a.wide_tiles));
+      go(narrow_only, mf_xcd_grid((uint64_t)a.ntiles_y2 * a.ntiles_z));
     }
   };
   // the arithmetic of the cell kernel: mode space (default) or the bit-for-bit twin of the one-term kernel (set_fused_reference)
   const bool modes = !_fused_reference_arithmetic;
-  auto pick = [&](auto kt, auto dt, auto mt) {
-    constexpr int KK = decltype(kt)::value;
-    constexpr bool DR = decltype(dt)::value != 0;
-    constexpr bool MO = decltype(mt)::value != 0;
-    // (fused_narrow_capable: these two shapes carry the second body)
-    if constexpr (KK == 3)
-      if (narrow && ty == 3)
-      {
-        go_narrow(mf_cheb_fused_kernel<T, 3, 3, DR, MO, 0, true>, mf_cheb_fused_kernel<T, 3, 3, DR, MO>, mf_cheb_fused_narrow_kernel<T, 3, 3, DR, MO>);
-        return;
-      }
-    if constexpr (KK == 2)
-      if (narrow && ty == 4)
-      {
-        go_narrow(mf_cheb_fused_kernel<T, 2, 4, DR, MO, 0, true>, mf_cheb_fused_kernel<T, 2, 4, DR, MO>, mf_cheb_fused_narrow_kernel<T, 2, 4, DR, MO>);
-        return;
-      }
-    if (ty == 2)
-      go(mf_cheb_fused_kernel<T, KK, 2, DR, MO>, n_blocks);
-    else if (ty == 3)
-      go(mf_cheb_fused_kernel<T, KK, 3, DR, MO>, n_blocks);
-    else
-      go(mf_cheb_fused_kernel<T, KK, 4, DR, MO>, n_blocks);
-  };
-  auto pick_k = [&](auto kt) {
-    if (_dinv_in_record)
-    {
-      if (modes)
-        pick(kt, IntTag<1>{}, IntTag<1>{});
-      else
-        pick(kt, IntTag<1>{}, IntTag<0>{});
-    }
-    else
-    {
-      if (modes)
-        pick(kt, IntTag<0>{}, IntTag<1>{});
-      else
-        pick(kt, IntTag<0>{}, IntTag<0>{});
-    }
-  };
   static const int dbg = std::getenv("MFMG_MF_FUSED_DBG") ? std::atoi(std::getenv("MFMG_MF_FUSED_DBG")) : 0;
-  if (zero_guess)
-  {
-    // (n_terms = 3, ty = 3, mode-space arithmetic: checked above)
-    if (_dinv_in_record)
-    {
-      if (narrow)
-        go_narrow(mf_cheb_fused_kernel<T, 3, 3, true, true, 0, true, true>, mf_cheb_fused_kernel<T, 3, 3, true, true, 0, false, true>,
-                  mf_cheb_fused_narrow_kernel<T, 3, 3, true, true, true>);
-      else
-        go(mf_cheb_fused_kernel<T, 3, 3, true, true, 0, false, true>, n_blocks);
-    }
-    else
-    {
-      if (narrow)
-        go_narrow(mf_cheb_fused_kernel<T, 3, 3, false, true, 0, true, true>, mf_cheb_fused_kernel<T, 3, 3, false, true, 0, false, true>,
-                  mf_cheb_fused_narrow_kernel<T, 3, 3, false, true, true>);
-      else
-        go(mf_cheb_fused_kernel<T, 3, 3, false, true, 0, false, true>, n_blocks);
-    }
-  }
-  else if (dbg > 0 && n_terms == 3 && ty == 3 && !_dinv_in_record && std::is_same<T, double>::value)
-  {
-    if (dbg == 1)
-      go(mf_cheb_fused_kernel<T, 3, 3, false, true, 1>, n_blocks);
-    else
-      go(mf_cheb_fused_kernel<T, 3, 3, false, true, 2>, n_blocks);
-  }
-  else if (n_terms == 1)
-    pick_k(IntTag<1>{});
-  else if (n_terms == 2)
-    pick_k(IntTag<2>{});
+  // the kernel <K, TY, DREC, MODES> with or without the body of a narrow last column (fused_narrow_capable: two shapes carry it)
+  // and, from a zero guess, its ZERO0 form (fused_zero_guess_available: one shape has it)
+  auto sweep = [&](auto kt, auto tt, auto dt, auto mt) {
+    constexpr int K = decltype(kt)::value, TY = decltype(tt)::value;
+    constexpr bool DR = decltype(dt)::value, MO = decltype(mt)::value;
+    auto with_guess = [&](auto zt) {
+      constexpr bool Z0 = decltype(zt)::value;
+      if constexpr (fused_narrow_capable(K, TY))
+        if (narrow)
+          return go_narrow(mf_cheb_fused_kernel<T, K, TY, DR, MO, 0, true, Z0>, mf_cheb_fused_kernel<T, K, TY, DR, MO, 0, false, Z0>,
+                           mf_cheb_fused_narrow_kernel<T, K, TY, DR, MO, Z0>);
+      go(mf_cheb_fused_kernel<T, K, TY, DR, MO, 0, false, Z0>, n_blocks);
+    };
+    if constexpr (K == 3 && TY == 3 && MO)
+      if (zero_guess)
+        return with_guess(std::true_type());
+    with_guess(std::false_type());
+  };
+  // (timing experiments, FP64: the kernels without barrier / without division)
+  if (dbg > 0 && !zero_guess && n_terms == 3 && ty == 3 && !_dinv_in_record && std::is_same<T, double>::value)
+    with_flag(dbg == 1, [&](auto one) { go(mf_cheb_fused_kernel<T, 3, 3, false, true, decltype(one)::value ? 1 : 2>, n_blocks); });
   else
-    pick_k(IntTag<3>{});
+    with_terms(n_terms, [&](auto kt) {
+      with_tile_rows<4>(ty, [&](auto tt) {
+        with_flag(_dinv_in_record, [&](auto dt) { with_flag(modes, [&](auto mt) { sweep(kt, tt, dt, mt); }); });
+      });
+    });
   MFMG_HIP_CHECK(hipGetLastError());
   KernelProfiler::end(stop, st);
 }

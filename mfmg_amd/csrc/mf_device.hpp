@@ -1,11 +1,15 @@
 // Device-side pieces shared by the kernels of the matrix-free Q1 Laplace operator (mf_laplace.hip: one polynomial term per
 // launch; mf_cheb_fused.hip: several terms of the Chebyshev smoother per sweep): the chunk-record geometry, the cell kernels, the
-// lane shifts, the addressing helpers and the kernel argument blocks.  Included by those two translation units only.
+// lane shifts, the addressing helpers and the kernel argument blocks; at the end the host-side helpers of their launches.
+// Included by those two translation units only.
 #pragma once
 
 #include "mf_laplace.hpp"
 
+#include <mutex>
+#include <set>
 #include <type_traits>
+#include <utility>
 
 namespace mfmg
 {
@@ -39,7 +43,7 @@ struct MfArgs
 
 // n_boxes > 0: the tiles of the main part of a launch are those of up to six boxes of (column, y, z) tiles, one after the other
 // (box q: the tiles bx_end[q - 1] .. bx_end[q] - 1 of the list) -- the shell around the interior tiles of a distributed run as
-// ONE launch (launch_outside).  Consecutive workgroups take consecutive tiles of the list: the shell is spread evenly over the
+// ONE launch (MfTileRegion::outside).  Consecutive workgroups take consecutive tiles of the list: the shell is spread evenly over the
 // XCDs (leaving the interior out of the full list instead gave two of the eight XCDs the whole x slab: 170 us for 30 % of the
 // tiles).  An argument of its own, not part of MfArgs: the two argument blocks of a launch are selected field by field.
 struct MfBoxes
@@ -301,4 +305,91 @@ __device__ __forceinline__ T mf_epilogue(MfArgs<T> const &a, int id0, T x0, T yv
   return (a.mode == 2) ? fmadd<T>(wgt, r, x0) : fmadd<T>(wgt, r, fmadd<T>(a.alpha, x0 - lxp, x0));
 }
 } // namespace
+
+// ---- host side: what the launches of both translation units share ------------------------------------------------
+// compute units of the current device (256 where it cannot be asked)
+inline int mf_n_cus()
+{
+  static const int n_cus = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      v = 256;
+    return v > 0 ? v : 256;
+  }();
+  return n_cus;
+}
+
+// workgroups for n tiles: rounded up to a multiple of 8 for the XCD-contiguous tile order of the kernels
+inline unsigned int mf_xcd_grid(uint64_t n_tiles) { return (unsigned int)(n_tiles >= 64 ? ((n_tiles + 7) / 8) * 8 : n_tiles); }
+
+// Launch of a workgroup of nw wavefronts that may use the whole LDS.  The attribute is per kernel AND device; every kernel
+// instantiation decays to the same function-pointer type, so the record of what has been set is keyed on the pointer (a flag per
+// instantiation of a generic lambda or of this template would be shared by all kernels of one signature) and lives in a
+// function that is no template.  Operators are used from several host threads: behind a mutex.
+constexpr size_t kMfMaxLds = 160 * 1024;
+inline void mf_allow_max_lds(const void *kernel)
+{
+  static std::mutex attr_mutex;
+  static std::set<std::pair<const void *, int>> attr_set;
+  int dev = 0;
+  MFMG_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(attr_mutex);
+  if (attr_set.insert({kernel, dev}).second)
+    MFMG_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMfMaxLds));
+}
+struct MfGrid
+{
+  unsigned int blocks;
+  int nw;
+  size_t lds;
+  hipStream_t stream;
+};
+template <typename Kernel, typename... Args>
+void mf_launch(Kernel kernel, MfGrid const &g, Args const &...args)
+{
+  mf_allow_max_lds(reinterpret_cast<const void *>(kernel));
+  hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(64 * g.nw), g.lds, g.stream, args...);
+}
+
+// The factors of the cell kernels with one coefficient per cell, for MfArgs and MfFusedArgs alike (in double, rounded to the
+// kernel's type here: the one-term kernel and the sweep must see the same bits).  Returns f[d] = |cell| / 8 / h_d^2.
+template <typename Args>
+void mf_cell_factors(Args &a, double const h[3], double f[3])
+{
+  using T = decltype(a.kd);
+  const double vol = h[0] * h[1] * h[2];
+  const double m00 = MFMG_GA * MFMG_GA + MFMG_GB * MFMG_GB, m01 = 2. * MFMG_GA * MFMG_GB;
+  for (int d = 0; d < 3; ++d)
+    f[d] = vol / 8. / (h[d] * h[d]);
+  a.fax = T(2. * f[0] * m00);
+  a.fbx = T(2. * f[0] * m01);
+  a.fay = T(2. * f[1] * m00);
+  a.fby = T(2. * f[1] * m01);
+  a.faz = T(2. * f[2] * m00);
+  a.fbz = T(2. * f[2] * m01);
+  a.kd = T(2. * m00 * m00 * (f[0] + f[1] + f[2]));
+}
+
+// Run-time values as template arguments of a kernel: f(std::integral_constant<int, TY>()) for ty cell rows per wavefront
+// (`other`: the argument of every ty that has no instance of its own), f(std::true_type / std::false_type()) for a flag.
+template <int other, typename F>
+void with_tile_rows(int ty, F &&f)
+{
+  if (ty == 2)
+    f(std::integral_constant<int, 2>());
+  else if (ty == 3)
+    f(std::integral_constant<int, 3>());
+  else if (ty == 4)
+    f(std::integral_constant<int, 4>());
+  else
+    f(std::integral_constant<int, other>());
+}
+template <typename F>
+void with_flag(bool v, F &&f)
+{
+  if (v)
+    f(std::true_type());
+  else
+    f(std::false_type());
+}
 } // namespace mfmg

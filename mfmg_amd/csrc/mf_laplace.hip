@@ -1152,7 +1152,7 @@ void MatrixFreeLaplaceDevice<T>::init_2d(mfmg_hip_mesh_desc const &mesh)
 }
 
 template <typename T>
-void MatrixFreeLaplaceDevice<T>::launch_2d(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out) const
+void MatrixFreeLaplaceDevice<T>::launch_2d(MfMode mode, MfOperands<T> const &v) const
 {
   Mf2dArgs<T> a{};
   a.cell_dofs = _cd2.data();
@@ -1161,13 +1161,13 @@ void MatrixFreeLaplaceDevice<T>::launch_2d(MfMode mode, T const *x, T const *b, 
   a.node_dof = _node_dof2.data();
   a.nx = _n[0];
   a.ny = _n[1];
-  a.x = x;
-  a.b = b;
+  a.x = v.x;
+  a.b = v.b;
   a.dinv = _dinv.data();
-  a.xprev = x_prev;
-  a.out = out;
-  a.alpha = alpha;
-  a.beta = beta;
+  a.xprev = v.x_prev;
+  a.out = v.out;
+  a.alpha = v.alpha;
+  a.beta = v.beta;
   a.mode = (int)mode;
   Mf2dTable tab;
   for (int t = 0; t < 64; ++t)
@@ -1184,24 +1184,16 @@ void MatrixFreeLaplaceDevice<T>::launch_2d(MfMode mode, T const *x, T const *b, 
 // tile of the list that still gives every CU two rounds of wavefronts is taken (large tiles re-read less halo,
 // but a launch of fewer than two rounds pays its ramp up and down in full).
 template <typename T>
-void MatrixFreeLaplaceDevice<T>::choose_tile(int &nw, int &ty, int &tz) const
+MfTile MatrixFreeLaplaceDevice<T>::choose_tile() const
 {
-  nw = _tile_waves;
-  ty = _tile_y;
-  tz = _tile_z;
+  int nw = _tile_waves, ty = _tile_y, tz = _tile_z;
   if (nw > 0 && ty > 0 && tz > 0)
-    return;
+    return {nw, ty, tz};
   static const int pref_general[][3] = {{8, 2, 16}, {4, 3, 8}, {4, 2, 8}, {2, 2, 8}, {2, 2, 4}, {1, 2, 4}};
   static const int pref_compact[][3] = {{8, 3, 16}, {4, 3, 8}, {4, 3, 8}, {4, 2, 8}, {2, 2, 4}, {1, 2, 4}};
   const int(*pref)[3] = _compact ? pref_compact : pref_general;
   constexpr int n_pref = 6;
-  static const int n_cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      v = 256;
-    return v > 0 ? v : 256;
-  }();
-  const int64_t waves_wanted = (int64_t)2 * 16 * n_cus; // two rounds of 4 wavefronts per SIMD
+  const int64_t waves_wanted = (int64_t)2 * 16 * mf_n_cus(); // two rounds of 4 wavefronts per SIMD
   int pick = n_pref - 1;
   for (int c = 0; c < n_pref; ++c)
   {
@@ -1222,6 +1214,7 @@ void MatrixFreeLaplaceDevice<T>::choose_tile(int &nw, int &ty, int &tz) const
     tz = pref[pick][2];
   if (nw * ty < 2)
     ty = 2;
+  return {nw, ty, tz};
 }
 
 // Tiling along z.  A launch of a few rounds of workgroups pays for its last round: when the list of tiles runs out the
@@ -1279,38 +1272,27 @@ int const *MatrixFreeLaplaceDevice<T>::z_tiling(int tz, bool graded, int &n_tile
 }
 
 template <typename T>
-bool MatrixFreeLaplaceDevice<T>::make_args(MfArgs<T> &a, unsigned int &n_blocks, MfMode mode, T const *x, T const *b,
-                                           T const *x_prev, T alpha, T beta, T *out, int nw, int ty, int tz,
-                                           int const *ztab, int z_tile_begin, int z_tile_end, int const *xy_range) const
+void MatrixFreeLaplaceDevice<T>::make_args(MfArgs<T> &a, MfMode mode, MfOperands<T> const &v, MfTile const &tile, int const *ztab,
+                                           int all_z) const
 {
   a.rec = _rec.data();
-  a.x = x;
-  a.b = b;
+  a.x = v.x;
+  a.b = v.b;
   a.dinv = _dinv.data();
-  a.xprev = x_prev;
-  a.out = out;
+  a.xprev = v.x_prev;
+  a.out = v.out;
   a.Nx = _N[0];
   a.Ny = _N[1];
   a.Nz = _N[2];
-  a.TY = ty;
-  a.TZ = tz;
-  const double vol = _h[0] * _h[1] * _h[2];
-  a.fx = T(vol / 8. / (_h[0] * _h[0]));
-  a.fy = T(vol / 8. / (_h[1] * _h[1]));
-  a.fz = T(vol / 8. / (_h[2] * _h[2]));
-  {
-    const double m00 = MFMG_GA * MFMG_GA + MFMG_GB * MFMG_GB, m01 = 2. * MFMG_GA * MFMG_GB;
-    const double f[3] = {vol / 8. / (_h[0] * _h[0]), vol / 8. / (_h[1] * _h[1]), vol / 8. / (_h[2] * _h[2])};
-    a.fax = T(2. * f[0] * m00);
-    a.fbx = T(2. * f[0] * m01);
-    a.fay = T(2. * f[1] * m00);
-    a.fby = T(2. * f[1] * m01);
-    a.faz = T(2. * f[2] * m00);
-    a.fbz = T(2. * f[2] * m01);
-    a.kd = T(2. * m00 * m00 * (f[0] + f[1] + f[2]));
-  }
-  a.alpha = alpha;
-  a.beta = beta;
+  a.TY = tile.ty;
+  a.TZ = tile.tz;
+  double f[3];
+  mf_cell_factors(a, _h, f);
+  a.fx = T(f[0]);
+  a.fy = T(f[1]);
+  a.fz = T(f[2]);
+  a.alpha = v.alpha;
+  a.beta = v.beta;
   a.mode = static_cast<int>(mode);
   a.rec_bytes = (unsigned int)_rec_bytes;
   a.own = _own;
@@ -1320,293 +1302,181 @@ bool MatrixFreeLaplaceDevice<T>::make_args(MfArgs<T> &a, unsigned int &n_blocks,
   a.ncols = _ncols;
   a.ncols_active = _tail ? _ncols - 1 : _ncols;
   // ty cell rows per wavefront, nw ty - 1 owned DoF rows per workgroup
-  a.ntiles_y = (_N[1] + nw * ty - 2) / (nw * ty - 1);
-  a.col0 = a.ty0 = 0;
+  a.ntiles_y = (_N[1] + tile.nw * tile.ty - 2) / (tile.nw * tile.ty - 1);
+  a.ntiles_z = (unsigned int)all_z;
+  a.col0 = a.ty0 = a.z_tile0 = 0;
   a.ztab = ztab;
-  n_blocks = 0;
-  if (xy_range)
-  {
-    // a sub-range of the column and y-tiles: {col begin, col end, y-tile begin, y-tile end}
-    ASSERT_THROW(xy_range[0] >= 0 && xy_range[1] <= (int)a.ncols_active && xy_range[2] >= 0 && xy_range[3] <= (int)a.ntiles_y,
-                 "tile range outside the tiling");
-    if (xy_range[0] >= xy_range[1] || xy_range[2] >= xy_range[3])
-      return false;
-    a.col0 = (unsigned int)xy_range[0];
-    a.ncols_active = (unsigned int)(xy_range[1] - xy_range[0]);
-    a.ty0 = (unsigned int)xy_range[2];
-    a.ntiles_y = (unsigned int)(xy_range[3] - xy_range[2]);
-  }
-  if (z_tile_begin >= z_tile_end)
-    return false;
-  a.z_tile0 = (unsigned int)z_tile_begin;
-  a.ntiles_z = (unsigned int)(z_tile_end - z_tile_begin);
-  const uint64_t n_tiles = (uint64_t)a.ncols_active * a.ntiles_y * a.ntiles_z;
-  ASSERT_THROW(n_tiles < (1ull << 30), "operator tile too small for this mesh (grid size limit)");
-  // rounded up to a multiple of 8 for the XCD-contiguous tile order
-  n_blocks = (unsigned int)(n_tiles >= 64 ? ((n_tiles + 7) / 8) * 8 : n_tiles);
-  return true;
 }
 
-template <typename T>
-void MatrixFreeLaplaceDevice<T>::run(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out,
-                                     int nw, int ty, int tz, int z_tile_begin, int z_tile_end, int const *xy_range, bool with_main,
-                                     bool with_tail, int const *exclude, hipStream_t on_stream) const
+namespace
 {
+// restricts a launch to the box [begin, end) of its (column, y, z) tiles; returns its workgroups (0: the box is empty)
+template <typename T>
+unsigned int select_tiles(MfArgs<T> &a, int const begin[3], int const end[3])
+{
+  if (begin[0] >= end[0] || begin[1] >= end[1] || begin[2] >= end[2])
+    return 0;
+  a.col0 = (unsigned int)begin[0];
+  a.ncols_active = (unsigned int)(end[0] - begin[0]);
+  a.ty0 = (unsigned int)begin[1];
+  a.ntiles_y = (unsigned int)(end[1] - begin[1]);
+  a.z_tile0 = (unsigned int)begin[2];
+  a.ntiles_z = (unsigned int)(end[2] - begin[2]);
+  const uint64_t n_tiles = (uint64_t)a.ncols_active * a.ntiles_y * a.ntiles_z;
+  ASSERT_THROW(n_tiles < (1ull << 30), "operator tile too small for this mesh (grid size limit)");
+  return mf_xcd_grid(n_tiles);
+}
+} // namespace
+
+// One launch: the tiles of `region` (checked by launch_region) of the mesh and of the slab of its tail columns.
+template <typename T>
+void MatrixFreeLaplaceDevice<T>::run(MfMode mode, MfOperands<T> const &v, MfTile const &tile, MfTileRegion const &region) const
+{
+  const int nw = tile.nw, ty = tile.ty, tz = tile.tz;
   ASSERT_THROW(nw >= 1 && nw <= 8, "1..8 wavefronts per workgroup");
   ASSERT_THROW(ty >= 1 && tz >= 1 && nw * ty >= 2, "operator tile too small");
   MfArgs<T> am, at;
   MfBoxes boxes;
-  unsigned int main_blocks = 0, tail_blocks = 0;
-  // the whole mesh: graded z-tiles; a range of z-tiles: the uniform tiling the caller counts in
+  // the whole mesh: graded z-tiles; a region of tiles: the uniform tiling the caller counts in
   static const bool graded_env = !(std::getenv("MFMG_MF_GRADED_TILES") && std::string(std::getenv("MFMG_MF_GRADED_TILES")) == "0");
-  const bool whole = z_tile_begin == 0 && z_tile_end < 0 && exclude == nullptr;
   int all_z = 0;
-  int const *ztab = z_tiling(tz, whole && graded_env, all_z);
-  if (z_tile_end < 0)
-    z_tile_end = all_z;
-  ASSERT_THROW(z_tile_begin >= 0 && z_tile_end <= all_z, "z-tile range outside the tiling");
-  const bool have_main = make_args(am, main_blocks, mode, x, b, x_prev, alpha, beta, out, nw, ty, tz, ztab, z_tile_begin, z_tile_end, xy_range);
-  if (!have_main && !_tail)
-    return;
-  if (!with_main)
-    main_blocks = 0;
+  int const *ztab = z_tiling(tz, region.whole_mesh && graded_env, all_z);
+  make_args(am, mode, v, tile, ztab, all_z);
   at = am;
-  if (exclude)
+  const int zero[3] = {0, 0, 0}, nt[3] = {(int)am.ncols_active, (int)am.ntiles_y, all_z};
+  const bool in_box = !region.whole_mesh && !region.outside;
+  unsigned int main_blocks = select_tiles(am, in_box ? region.begin : zero, in_box ? region.end : nt), tail_blocks = 0;
+  if (region.outside)
   {
-    // the tiles of the uniform tiling outside the box {lo[3], hi[3]}: z slabs over all columns and rows, y slabs between them,
-    // x slabs between those (the tail columns are not column tiles: they are the `at` part of the launch as always)
-    const int nt[3] = {(int)am.ncols_active, (int)am.ntiles_y, (int)am.ntiles_z};
-    int lo[3], hi[3];
-    for (int d = 0; d < 3; ++d)
-    {
-      lo[d] = std::min(std::max(exclude[d], 0), nt[d]);
-      hi[d] = std::min(std::max(exclude[3 + d], lo[d]), nt[d]);
-    }
-    const int box[6][6] = {{0, nt[0], 0, nt[1], 0, lo[2]},         {0, nt[0], 0, nt[1], hi[2], nt[2]},
-                           {0, nt[0], 0, lo[1], lo[2], hi[2]},     {0, nt[0], hi[1], nt[1], lo[2], hi[2]},
-                           {0, lo[0], lo[1], hi[1], lo[2], hi[2]}, {hi[0], nt[0], lo[1], hi[1], lo[2], hi[2]}};
+    // (the tail columns are not column tiles: they are the `at` part of the launch as always)
+    int slab[6][6];
+    mf_shell_slabs(region.begin, region.end, nt, slab);
     unsigned int end = 0;
     for (int q = 0; q < 6; ++q)
     {
-      const int ncq = box[q][1] - box[q][0], nyq = box[q][3] - box[q][2], nzq = box[q][5] - box[q][4];
-      const bool empty = ncq <= 0 || nyq <= 0 || nzq <= 0;
+      const bool empty = mf_slab_empty(slab[q]);
       if (!empty)
-        end += (unsigned int)ncq * nyq * nzq;
+        end += (unsigned int)(slab[q][1] - slab[q][0]) * (slab[q][3] - slab[q][2]) * (slab[q][5] - slab[q][4]);
       boxes.bx_end[q] = end;
-      boxes.bx_c0[q] = (unsigned int)box[q][0];
-      boxes.bx_nc[q] = empty ? 1u : (unsigned int)ncq;
-      boxes.bx_y0[q] = (unsigned int)box[q][2];
-      boxes.bx_ny[q] = empty ? 1u : (unsigned int)nyq;
-      boxes.bx_z0[q] = (unsigned int)box[q][4];
+      boxes.bx_c0[q] = (unsigned int)slab[q][0];
+      boxes.bx_nc[q] = empty ? 1u : (unsigned int)(slab[q][1] - slab[q][0]);
+      boxes.bx_y0[q] = (unsigned int)slab[q][2];
+      boxes.bx_ny[q] = empty ? 1u : (unsigned int)(slab[q][3] - slab[q][2]);
+      boxes.bx_z0[q] = (unsigned int)slab[q][4];
     }
     boxes.n_boxes = 6;
-    main_blocks = with_main ? (end >= 64 ? ((end + 7) / 8) * 8 : end) : 0;
+    main_blocks = mf_xcd_grid(end);
   }
-  if (_tail && with_tail) // the columns of the last chunk: same tile shape, same layers (same table: Nz is the same), first in the grid
-    _tail->make_args(at, tail_blocks, mode, x, b, x_prev, alpha, beta, out, nw, ty, tz, ztab, z_tile_begin, z_tile_end, nullptr);
+  if (!region.main_part)
+    main_blocks = 0;
+  if (_tail && region.tail_part) // the columns of the last chunk: same tile shape, same layers (same table: Nz is the same), first in the grid
+  {
+    _tail->make_args(at, mode, v, tile, ztab, all_z);
+    const int tb[3] = {0, 0, in_box ? region.begin[2] : 0}, te[3] = {(int)at.ncols_active, (int)at.ntiles_y, in_box ? region.end[2] : all_z};
+    tail_blocks = select_tiles(at, tb, te);
+  }
   if (main_blocks + tail_blocks == 0)
     return;
   const size_t lds = ((size_t)nw * (3 * ty + 1) + (size_t)2 * nw * 3) * 64 * sizeof(T) + (size_t)nw * (ty + 1) * 64 * sizeof(int);
-  ASSERT_THROW(lds <= 160 * 1024, "operator tile too large for the LDS");
-  const dim3 grid(main_blocks + tail_blocks);
-  const dim3 block(64 * nw);
-  hipStream_t st = on_stream ? on_stream : _handle.stream;
-  auto go = [&](auto kernel) {
-    // (the attribute is per kernel AND device; every instantiation decays to the same function-pointer type, so the
-    // record of what has been set is keyed on the pointer -- a flag per lambda instantiation would be shared by all variants)
-    static std::mutex attr_mutex;
-    static std::set<std::pair<const void *, int>> attr_set;
-    int dev = 0;
-    MFMG_HIP_CHECK(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lock(attr_mutex);
-      if (attr_set.insert({reinterpret_cast<const void *>(kernel), dev}).second)
-        MFMG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024));
-    }
-    hipLaunchKernelGGL(kernel, grid, block, lds, st, am, at, tail_blocks, boxes);
-  };
+  ASSERT_THROW(lds <= kMfMaxLds, "operator tile too large for the LDS");
+  const MfGrid grid{main_blocks + tail_blocks, nw, lds, region.stream ? region.stream : _handle.stream};
+  auto go = [&](auto kernel) { mf_launch(kernel, grid, am, at, tail_blocks, boxes); };
+  // (experiments: MFMG_MF_BATCH=n asks for n rows per request batch where that instance exists)
+  static const int batch_env = std::getenv("MFMG_MF_BATCH") ? std::atoi(std::getenv("MFMG_MF_BATCH")) : 0;
   // both parts of the launch must read their ids the same way
   const bool affine = ids_computed();
-  if (_compact)
-  {
-    if (ty == 2)
-      go(mf_laplace_kernel<T, 2, true, 2>);
-    else if (ty == 3)
-      go(mf_laplace_kernel<T, 3, true, 3>);
-    else if (ty == 4)
-      go(mf_laplace_kernel<T, 4, true, 4>);
-    else
-      go(mf_laplace_kernel<T, 0, true, 1>);
-  }
-  else
-  {
-    // (experiments: MFMG_MF_BATCH=n asks for n rows per request batch where that instance exists)
-    static const int batch_env = std::getenv("MFMG_MF_BATCH") ? std::atoi(std::getenv("MFMG_MF_BATCH")) : 0;
-    if (ty == 2 && batch_env == 2)
-      go(mf_laplace_kernel<T, 2, false, 2>);
-    else if (ty == 3 && batch_env == 3)
-      go(mf_laplace_kernel<T, 3, false, 3>);
-    else if (ty == 4 && batch_env == 2)
-      go(mf_laplace_kernel<T, 4, false, 2>);
-    else if (affine && ty == 2)
-      go(mf_laplace_kernel<T, 2, false, 1, true>);
-    else if (affine && ty == 3)
-      go(mf_laplace_kernel<T, 3, false, 1, true>);
-    else if (affine && ty == 4)
-      go(mf_laplace_kernel<T, 4, false, 1, true>);
-    else if (affine)
-      go(mf_laplace_kernel<T, 0, false, 1, true>);
-    else if (ty == 2)
-      go(mf_laplace_kernel<T, 2, false, 1>);
-    else if (ty == 3)
-      go(mf_laplace_kernel<T, 3, false, 1>);
-    else if (ty == 4)
-      go(mf_laplace_kernel<T, 4, false, 1>);
-    else
-      go(mf_laplace_kernel<T, 0, false, 1>);
-  }
+  with_tile_rows<0>(ty, [&](auto rows) {
+    constexpr int TYC = decltype(rows)::value;
+    // rows per request batch.  One coefficient per cell: all rows of the wavefront; eight: one, or what MFMG_MF_BATCH asks for
+    // where that instance exists -- (2, 2), (3, 3), (4, 2)
+    constexpr int kBatchCompact = TYC == 0 ? 1 : TYC, kBatchEnv = TYC == 4 ? 2 : TYC;
+    if (_compact)
+      return go(mf_laplace_kernel<T, TYC, true, kBatchCompact>);
+    if constexpr (kBatchEnv > 1)
+      if (batch_env == kBatchEnv)
+        return go(mf_laplace_kernel<T, TYC, false, kBatchEnv>);
+    with_flag(affine, [&](auto aff) { go(mf_laplace_kernel<T, TYC, false, 1, decltype(aff)::value>); });
+  });
   MFMG_HIP_CHECK(hipGetLastError());
 }
 
 template <typename T>
-void MatrixFreeLaplaceDevice<T>::check_vectors(MfMode mode, T const *x, T const *b, T const *x_prev, T const *out) const
+void MatrixFreeLaplaceDevice<T>::check_vectors(MfMode mode, MfOperands<T> const &v) const
 {
-  ASSERT_THROW(x != nullptr && out != nullptr, "null vector");
-  ASSERT_THROW(x != out, "the operator kernel cannot run in place (out aliases x)");
+  ASSERT_THROW(v.x != nullptr && v.out != nullptr, "null vector");
+  ASSERT_THROW(v.x != v.out, "the operator kernel cannot run in place (out aliases x)");
   if (mode != MfMode::apply)
-    ASSERT_THROW(b != nullptr, "null right-hand side");
+    ASSERT_THROW(v.b != nullptr, "null right-hand side");
   if (mode == MfMode::next)
-    ASSERT_THROW(x_prev != nullptr, "null x_prev");
-}
-
-template <typename T>
-int MatrixFreeLaplaceDevice<T>::tile_layers() const
-{
-  int nw, ty, tz;
-  choose_tile(nw, ty, tz);
-  return tz;
-}
-
-template <typename T>
-int MatrixFreeLaplaceDevice<T>::n_z_tiles() const
-{
-  const int tz = tile_layers();
-  return (_N[2] + tz - 1) / tz;
-}
-
-template <typename T>
-void MatrixFreeLaplaceDevice<T>::launch_z_range(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta,
-                                                T *out, int z_tile_begin, int z_tile_end) const
-{
-  check_vectors(mode, x, b, x_prev, out);
-  ASSERT_THROW(_dim == 3, "z-tile ranges belong to the 3-D operator");
-  if (mode == MfMode::next && (x_prev == nullptr || alpha == T(0)))
-    mode = MfMode::first;
-  int nw, ty, tz;
-  choose_tile(nw, ty, tz);
-  const int all_z = (_N[2] + tz - 1) / tz;
-  if (z_tile_begin >= z_tile_end)
-    return;
-  const double share = double(z_tile_end - z_tile_begin) / double(all_z);
-  hipEvent_t stop = _handle.profiler.begin("mf_laplace_kernel", share * (required_bytes_apply() + epilogue_bytes((int)mode)),
-                                           _handle.stream);
-  run(mode, x, b, x_prev, alpha, beta, out, nw, ty, tz, z_tile_begin, z_tile_end);
-  KernelProfiler::end(stop, _handle.stream);
+    ASSERT_THROW(v.x_prev != nullptr, "null x_prev");
 }
 
 template <typename T>
 void MatrixFreeLaplaceDevice<T>::tiling(int n_tiles[3], int rows[3]) const
 {
-  int nw, ty, tz;
-  choose_tile(nw, ty, tz);
+  const MfTile t = choose_tile();
   n_tiles[0] = _tail ? _ncols - 1 : _ncols;
   rows[0] = _own;
-  rows[1] = nw * ty - 1;
+  rows[1] = t.nw * t.ty - 1;
   n_tiles[1] = (_N[1] + rows[1] - 1) / rows[1];
-  rows[2] = tz;
-  n_tiles[2] = (_N[2] + tz - 1) / tz;
+  rows[2] = t.tz;
+  n_tiles[2] = (_N[2] + t.tz - 1) / t.tz;
 }
 
 template <typename T>
-void MatrixFreeLaplaceDevice<T>::launch_tiles(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out,
-                                              int const begin[3], int const end[3], bool main_part, bool tail_part) const
+double MatrixFreeLaplaceDevice<T>::dof_share(MfTileRegion const &r, int const nt[3], int const rows[3]) const
 {
-  check_vectors(mode, x, b, x_prev, out);
-  ASSERT_THROW(_dim == 3, "tile ranges belong to the 3-D operator");
-  if (mode == MfMode::next && (x_prev == nullptr || alpha == T(0)))
-    mode = MfMode::first;
-  int nw, ty, tz;
-  choose_tile(nw, ty, tz);
-  int nt[3], rows[3];
-  tiling(nt, rows);
-  if (begin[2] >= end[2])
-    return;
-  const bool m = main_part && begin[0] < end[0] && begin[1] < end[1], t = tail_part && _tail != nullptr;
-  if (!m && !t)
-    return;
-  // share of the DoFs this launch updates (for the profiler's bytes)
-  const double zshare = double(end[2] - begin[2]) / double(nt[2]);
+  if (r.whole_mesh)
+    return 1.;
+  if (r.outside)
+  {
+    double inside = 1.;
+    for (int d = 0; d < 3; ++d)
+      inside *= double(r.end[d] - r.begin[d]) * (d == 0 ? double(rows[0]) / double(_N[0]) : 1. / double(nt[d]));
+    return std::max(0., 1. - inside);
+  }
+  const double zshare = double(r.end[2] - r.begin[2]) / double(nt[2]);
   const double tail_cols = _tail ? double(_N[0] - (_ncols - 1) * _own) : 0.;
   double share = 0.;
-  if (m)
-    share += zshare * (double(end[0] - begin[0]) * _own / double(_N[0])) * (double(end[1] - begin[1]) / double(nt[1]));
-  if (t)
+  if (r.main_part)
+    share += zshare * (double(r.end[0] - r.begin[0]) * _own / double(_N[0])) * (double(r.end[1] - r.begin[1]) / double(nt[1]));
+  if (r.tail_part && _tail)
     share += zshare * tail_cols / double(_N[0]);
-  hipEvent_t stop = _handle.profiler.begin("mf_laplace_kernel", std::min(1., share) * (required_bytes_apply() + epilogue_bytes((int)mode)),
-                                           _handle.stream);
-  const int xy[4] = {begin[0], end[0], begin[1], end[1]};
-  run(mode, x, b, x_prev, alpha, beta, out, nw, ty, tz, begin[2], end[2], xy, m, t);
-  KernelProfiler::end(stop, _handle.stream);
+  return std::min(1., share);
 }
 
-// Everything launch_tiles(begin, end, main) leaves: the tiles of the uniform tiling OUTSIDE the box [begin, end) and the tail
-// columns, as ONE launch (the workgroups of the excluded tiles leave at once).  Launched slab by slab -- up to six launches
-// and the tail, each a fraction of a round of workgroups and as long as one workgroup lives -- the shell of a box rank cost
-// more than the interior it surrounds.
+// The one entry of every launch.  A box launched slab by slab -- up to six launches and the tail, each a fraction of a round
+// of workgroups and as long as one workgroup lives -- cost the shell of a box rank more than the interior it surrounds: hence
+// `outside`, ONE launch whose workgroups of the excluded tiles do not exist (MfBoxes).
 template <typename T>
-void MatrixFreeLaplaceDevice<T>::launch_outside(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out,
-                                                int const begin[3], int const end[3], hipStream_t on_stream) const
+void MatrixFreeLaplaceDevice<T>::launch_region(MfMode mode, MfOperands<T> const &v, MfTileRegion const &region) const
 {
-  check_vectors(mode, x, b, x_prev, out);
-  ASSERT_THROW(_dim == 3, "tile ranges belong to the 3-D operator");
-  if (mode == MfMode::next && (x_prev == nullptr || alpha == T(0)))
-    mode = MfMode::first;
-  int nw, ty, tz;
-  choose_tile(nw, ty, tz);
-  int nt[3], rows[3];
-  tiling(nt, rows);
-  double inside = 1.;
-  for (int d = 0; d < 3; ++d)
-  {
-    ASSERT_THROW(begin[d] >= 0 && begin[d] <= end[d] && end[d] <= nt[d], "tile range outside the tiling");
-    inside *= double(end[d] - begin[d]) * (d == 0 ? double(rows[0]) / double(_N[0]) : 1. / double(nt[d]));
-  }
-  hipStream_t st = on_stream ? on_stream : _handle.stream;
-  hipEvent_t stop = _handle.profiler.begin("mf_laplace_kernel", std::max(0., 1. - inside) * (required_bytes_apply() + epilogue_bytes((int)mode)), st);
-  const int ex[6] = {begin[0], begin[1], begin[2], end[0], end[1], end[2]};
-  run(mode, x, b, x_prev, alpha, beta, out, nw, ty, tz, 0, -1, nullptr, true, true, ex, st);
-  KernelProfiler::end(stop, st);
-}
-
-template <typename T>
-void MatrixFreeLaplaceDevice<T>::launch(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha,
-                                        T beta, T *out) const
-{
-  check_vectors(mode, x, b, x_prev, out);
+  check_vectors(mode, v);
+  if (mode == MfMode::next)
+    mode = mf_smoother_mode(v.x_prev, v.alpha);
   if (_dim == 2)
   {
-    if (mode == MfMode::next && (x_prev == nullptr || alpha == T(0)))
-      mode = MfMode::first;
-    launch_2d(mode, x, b, x_prev, alpha, beta, out);
+    ASSERT_THROW(region.whole_mesh, "tile ranges belong to the 3-D operator");
+    launch_2d(mode, v);
     return;
   }
-  int nw, ty, tz;
-  choose_tile(nw, ty, tz);
+  const MfTile tile = choose_tile();
+  int nt[3] = {0, 0, 0}, rows[3] = {0, 0, 0};
+  if (!region.whole_mesh)
+  {
+    tiling(nt, rows);
+    for (int d = 0; d < 3; ++d)
+      ASSERT_THROW(region.begin[d] >= 0 && region.begin[d] <= region.end[d] && region.end[d] <= nt[d], "tile range outside the tiling");
+    // a box without tiles of the parts asked for: no launch
+    const bool main_part = region.main_part && region.begin[0] < region.end[0] && region.begin[1] < region.end[1];
+    if (!region.outside && (region.begin[2] >= region.end[2] || !(main_part || (region.tail_part && _tail))))
+      return;
+  }
   // bytes the layout requires per launch (mf_laplace.hpp), plus the b / D^-1 / x_prev reads of the epilogue
-  hipEvent_t stop = _handle.profiler.begin("mf_laplace_kernel", required_bytes_apply() + epilogue_bytes((int)mode), _handle.stream);
-  run(mode, x, b, x_prev, alpha, beta, out, nw, ty, tz);
-  KernelProfiler::end(stop, _handle.stream);
+  hipStream_t st = region.stream ? region.stream : _handle.stream;
+  hipEvent_t stop = _handle.profiler.begin("mf_laplace_kernel", dof_share(region, nt, rows) * (required_bytes_apply() + epilogue_bytes((int)mode)), st);
+  run(mode, v, tile, region);
+  KernelProfiler::end(stop, st);
 }
 
 template class MatrixFreeLaplaceDevice<double>;

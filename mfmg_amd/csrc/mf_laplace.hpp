@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 
+#include <algorithm>
 #include <memory>
 
 namespace mfmg
@@ -40,6 +41,82 @@ struct AffineIds
 template <typename T>
 struct MfArgs; // kernel arguments (mf_laplace.hip)
 
+// The vectors and scalars of one launch: out = the epilogue of the mode on A x (b, x_prev, alpha, beta where the mode reads them).
+template <typename T>
+struct MfOperands
+{
+  T const *x, *b, *x_prev;
+  T alpha, beta;
+  T *out;
+};
+
+// A smoother term without momentum (no x_prev, or alpha = 0) is a `first` term: it reads no x_prev.
+template <typename T>
+inline MfMode mf_smoother_mode(T const *x_prev, T alpha)
+{
+  return (x_prev == nullptr || alpha == T(0)) ? MfMode::first : MfMode::next;
+}
+
+// tile of one workgroup: nw wavefronts of ty cell rows each, tz layers
+struct MfTile
+{
+  int nw, ty, tz;
+};
+
+// Which tiles of tiling() a launch covers (every DoF is owned by exactly one tile, so regions that cover all tiles once give
+// the full result): the box [begin, end) of (column, y, z) tiles, or everything outside it -- the shell around the interior
+// tiles of a distributed run, the tail columns included, as ONE launch.  main_part / tail_part (boxes only): the column tiles
+// of the box / the columns of a nearly empty last chunk, which are no column tiles (all y, the z-tiles of the box).
+// whole_mesh: every tile and the tail; the only region that runs on the graded z-tiling (z_tiling), its box is not read.
+struct MfTileRegion
+{
+  int begin[3] = {0, 0, 0}, end[3] = {0, 0, 0};
+  bool whole_mesh = false, outside = false;
+  bool main_part = true, tail_part = true;
+  hipStream_t stream = nullptr; // nullptr: the context's (the shell of a distributed run goes to the exchange stream)
+
+  static MfTileRegion whole()
+  {
+    MfTileRegion r;
+    r.whole_mesh = true;
+    return r;
+  }
+  static MfTileRegion box(int const begin[3], int const end[3], bool main_part = true, bool tail_part = false)
+  {
+    MfTileRegion r;
+    std::copy(begin, begin + 3, r.begin);
+    std::copy(end, end + 3, r.end);
+    r.main_part = main_part;
+    r.tail_part = tail_part;
+    return r;
+  }
+  static MfTileRegion outside_of(int const begin[3], int const end[3], hipStream_t stream = nullptr)
+  {
+    MfTileRegion r = box(begin, end, true, true);
+    r.outside = true;
+    r.stream = stream;
+    return r;
+  }
+};
+
+// The shell of tiles around the box [lo, hi) of an nt[0] x nt[1] x nt[2] tiling as six slabs {c0, c1, y0, y1, z0, z1}: the z
+// slabs over all columns and rows (below, above), the y slabs between them, the x slabs between those; lo and hi are clamped
+// to the tiling, a slab may be empty (see mf_slab_empty).
+inline void mf_shell_slabs(int const lo_in[3], int const hi_in[3], int const nt[3], int slab[6][6])
+{
+  int lo[3], hi[3];
+  for (int d = 0; d < 3; ++d)
+  {
+    lo[d] = std::min(std::max(lo_in[d], 0), nt[d]);
+    hi[d] = std::min(std::max(hi_in[d], lo[d]), nt[d]);
+  }
+  const int s[6][6] = {{0, nt[0], 0, nt[1], 0, lo[2]},         {0, nt[0], 0, nt[1], hi[2], nt[2]},
+                       {0, nt[0], 0, lo[1], lo[2], hi[2]},     {0, nt[0], hi[1], nt[1], lo[2], hi[2]},
+                       {0, lo[0], lo[1], hi[1], lo[2], hi[2]}, {hi[0], nt[0], lo[1], hi[1], lo[2], hi[2]}};
+  std::copy(&s[0][0], &s[0][0] + 36, &slab[0][0]);
+}
+inline bool mf_slab_empty(int const slab[6]) { return slab[1] <= slab[0] || slab[3] <= slab[2] || slab[5] <= slab[4]; }
+
 template <typename T>
 class MatrixFreeLaplaceDevice
 {
@@ -58,42 +135,21 @@ public:
   int n_cells(int d) const { return _n[d]; }
   double cell_size(int d) const { return _h[d]; }
 
-  void vmult(T const *x, T *y) const { launch(MfMode::apply, x, nullptr, nullptr, T(0), T(0), y); }
-  void residual(T const *x, T const *b, T *res) const
-  {
-    launch(MfMode::residual, x, b, nullptr, T(0), T(0), res);
-  }
+  void vmult(T const *x, T *y) const { launch(MfMode::apply, {x, nullptr, nullptr, T(0), T(0), y}); }
+  void residual(T const *x, T const *b, T *res) const { launch(MfMode::residual, {x, b, nullptr, T(0), T(0), res}); }
   // out = x + alpha (x - x_prev) - beta dinv (A x - b); out must not alias x
   void smoother_step(T const *b, T const *x, T const *x_prev, T alpha, T beta, T *out) const
   {
-    if (x_prev == nullptr || alpha == T(0))
-      launch(MfMode::first, x, b, nullptr, T(0), beta, out);
-    else
-      launch(MfMode::next, x, b, x_prev, alpha, beta, out);
+    launch(mf_smoother_mode(x_prev, alpha), {x, b, x_prev, alpha, beta, out});
   }
 
-  // The same operations restricted to the z-tiles [z_tile_begin, z_tile_end) of the current tiling (every
-  // DoF is owned by exactly one tile, so ranges that cover all tiles once give the full result): tiles
-  // [0, n_z_tiles()) ; tile t owns the DoF layers [t tile_layers(), (t+1) tile_layers()) and reads the layers
-  // one below and one above them.
-  int n_z_tiles() const;
-  int tile_layers() const;
-  void launch_z_range(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out, int z_tile_begin,
-                      int z_tile_end) const;
-  // ... and to a box of tiles along all three axes (a box decomposition overlaps its exchange with the tiles that read
-  // no ghost plane along any axis): n_tiles / rows per axis -- column tiles of `rows[0]` DoF columns, y-tiles of rows[1] DoF
-  // rows, z-tiles of rows[2] layers; tile t of an axis owns [t rows, (t + 1) rows) and reads one plane below and above.
-  // The columns of a nearly empty last chunk are not part of the column tiles: they are the `tail_part` (all y, the
-  // z-tiles of the range), `main_part` the tiles [begin, end).
+  // The same operations on a region of the tiles (a box decomposition overlaps its exchange with the tiles that read no ghost
+  // plane along any axis).  tiling: n_tiles / rows per axis -- column tiles of rows[0] DoF columns, y-tiles of rows[1] DoF rows,
+  // z-tiles of rows[2] layers; tile t of an axis owns [t rows, (t + 1) rows) and reads one plane below and above.  The columns
+  // of a nearly empty last chunk are not part of the column tiles (MfTileRegion: tail_part).  An empty region launches nothing.
   void tiling(int n_tiles[3], int rows[3]) const;
   bool has_tail() const { return _tail != nullptr; }
-  void launch_tiles(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out, int const begin[3],
-                    int const end[3], bool main_part, bool tail_part) const;
-  // ... and everything such a box leaves (the tiles outside [begin, end) and the tail columns) as ONE launch
-  // (on_stream: another stream than the context's -- the shell of a distributed run is launched on the exchange stream, behind
-  // the unpacking of the ghost planes, and runs BESIDE the interior tiles)
-  void launch_outside(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out, int const begin[3],
-                      int const end[3], hipStream_t on_stream = nullptr) const;
+  void launch_region(MfMode mode, MfOperands<T> const &v, MfTileRegion const &region) const;
 
   // Several smoother terms in ONE sweep (mf_cheb_fused.hip): x_1 = x - beta[0] dinv (A x - b), then
   // x_s = x_{s-1} + alpha[s-1] (x_{s-1} - x_{s-2}) - beta[s-1] dinv (A x_{s-1} - b) up to s = n_terms (2 or 3); out = x_{n_terms},
@@ -106,7 +162,7 @@ public:
   // the last chunk column owns at most 32 - 2 halo DoF columns: the sweep kernels of the default tile shapes (three terms 8 x 3
   // rows, two terms 4 x 4) run it two y-tiles per workgroup, one per half of the wavefront
   bool narrow_last_column() const { return _narrow_last; }
-  static bool fused_narrow_capable(int n_terms, int ty) { return (n_terms == 3 && ty == 3) || (n_terms == 2 && ty == 4); }
+  static constexpr bool fused_narrow_capable(int n_terms, int ty) { return (n_terms == 3 && ty == 3) || (n_terms == 2 && ty == 4); }
   void smoother_sweep(int n_terms, T const *alpha, T const *beta, T const *b, T const *x, T *out, T *out_prev) const;
   // tile of the sweep: nw wavefronts of ty cell rows, tz owned layers (0, 0, 0: chosen from the mesh)
   void set_fused_tile(int nw, int ty, int tz)
@@ -135,7 +191,13 @@ public:
   }
   void set_tile_waves(int nw) { _tile_waves = nw; }
   // the tile the next launch uses
-  void get_tile(int &nw, int &ty, int &tz) const { choose_tile(nw, ty, tz); }
+  void get_tile(int &nw, int &ty, int &tz) const
+  {
+    const MfTile t = choose_tile();
+    nw = t.nw;
+    ty = t.ty;
+    tz = t.tz;
+  }
   HipHandle &handle() const { return _handle; }
 
   // Bytes of one operator application y = A x.
@@ -166,13 +228,12 @@ public:
   }
 
 private:
-  void launch(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out) const;
-  void run(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out, int nw, int ty, int tz,
-           int z_tile_begin = 0, int z_tile_end = -1, int const *xy_range = nullptr, bool with_main = true,
-           bool with_tail = true, int const *exclude = nullptr, hipStream_t on_stream = nullptr) const;
-  bool make_args(MfArgs<T> &a, unsigned int &n_blocks, MfMode mode, T const *x, T const *b, T const *x_prev, T alpha,
-                 T beta, T *out, int nw, int ty, int tz, int const *ztab, int z_tile_begin, int z_tile_end,
-                 int const *xy_range) const;
+  void launch(MfMode mode, MfOperands<T> const &v) const { launch_region(mode, v, MfTileRegion::whole()); }
+  void run(MfMode mode, MfOperands<T> const &v, MfTile const &tile, MfTileRegion const &region) const;
+  // every tile of this part (the mesh, or the slab of its tail columns) over the z-tiles of `ztab`
+  void make_args(MfArgs<T> &a, MfMode mode, MfOperands<T> const &v, MfTile const &tile, int const *ztab, int all_z) const;
+  // share of the DoFs the region updates (for the profiler's bytes)
+  double dof_share(MfTileRegion const &region, int const n_tiles[3], int const rows[3]) const;
   // layers of the z-tiles (device table, built once per tz): graded = shorter tiles at the end of every XCD's run
   int const *z_tiling(int tz, bool graded, int &n_tiles) const;
   struct ZTiling
@@ -181,16 +242,16 @@ private:
     DeviceBuffer<int> dev;
   };
   mutable ZTiling _zt_uniform, _zt_graded;
-  void check_vectors(MfMode mode, T const *x, T const *b, T const *x_prev, T const *out) const;
+  void check_vectors(MfMode mode, MfOperands<T> const &v) const;
   // dim = 2 (mf_laplace.hip): a plain owner-computes kernel on the caller's arrays
   void init_2d(mfmg_hip_mesh_desc const &mesh);
-  void launch_2d(MfMode mode, T const *x, T const *b, T const *x_prev, T alpha, T beta, T *out) const;
+  void launch_2d(MfMode mode, MfOperands<T> const &v) const;
   int _dim = 3;
   DeviceBuffer<int32_t> _cd2, _node_dof2;
   DeviceBuffer<T> _co2;
   DeviceBuffer<uint8_t> _cn2;
   double _k2[64] = {};
-  void choose_tile(int &nw, int &ty, int &tz) const;
+  MfTile choose_tile() const;
   void choose_fused_tile(int n_terms, int &nw, int &ty, int &tz) const;
   int _fused_tile[3] = {0, 0, 0};
   bool _fused_reference_arithmetic = false;
