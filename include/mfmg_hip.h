@@ -465,8 +465,9 @@ int mfmg_hip_hierarchy_restrictor_apply(mfmg_hip_hierarchy_t h, int32_t level, c
  *   6 agglomerates evaluated from the reference block table, 7 further block classes, 8 agglomerate positions listed
  *     for the thread-per-node part of the 2 x 2 x 2 prolongation kernel
  *   9 restriction kernel: 1 rows, 2 pairs of 2 x 2 x 2 agglomerates, 3 pairs of any agglomerate
- *  10 prolongation kernel: 1 one thread per node, 2 the 2 x 2 x 2 block kernel */
-#define MFMG_HIP_RESTRICTOR_FORM_FIELDS 11
+ *  10 prolongation kernel: 1 one thread per node, 2 the 2 x 2 x 2 block kernel
+ *  11 the block kernel in its marching form (0: a thread per agglomerate position, MFMG_SR_PROLONG=block) */
+#define MFMG_HIP_RESTRICTOR_FORM_FIELDS 12
 int mfmg_hip_hierarchy_restrictor_form(mfmg_hip_hierarchy_t h, int32_t level, int32_t *fields, int32_t n);
 /* out = (A R^T) in for the A R^T the coarse operator of `level` was formed from -- `fast_multiply_transpose()` when the
  * parameter `fast_ap` is true (include/mfmg/common/hierarchy.hpp:214-221), `a->multiply_transpose(restrictor)` otherwise.

@@ -617,7 +617,8 @@ class Hierarchy:
             return {"structured": False}
         return {"structured": True, "n_eig": f[1], "a": (f[2], f[3], f[4]), "float_planes": bool(f[5]),
                 "table_agglomerates": f[6], "n_classes": f[7], "listed_blocks": f[8],
-                "restrict": self._RESTRICT_KERNELS[f[9]], "prolong": self._PROLONG_KERNELS[f[10]]}
+                "restrict": self._RESTRICT_KERNELS[f[9]], "prolong": self._PROLONG_KERNELS[f[10]],
+                "prolong_march": bool(f[11])}
 
     def ap_apply(self, level: int, vin, vout):
         """vout = (A R^T) vin for the A R^T of `level` (hierarchies built with keep_ap = true)."""

@@ -1526,6 +1526,7 @@ int mfmg_hip_hierarchy_restrictor_form(mfmg_hip_hierarchy_t h, int32_t level, in
     fields[8] = (int32_t)s->listed_blocks();
     fields[9] = s->restrict_kernel();
     fields[10] = s->prolong_kernel();
+    fields[11] = s->prolong_march() ? 1 : 0;
   });
 }
 

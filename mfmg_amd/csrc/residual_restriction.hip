@@ -565,6 +565,9 @@ bool StructuredRestrictorDevice::build_residual_restriction(std::function<void(d
   _rr_segs = segs;
   _rr_main_last = main_last;
   _rr_classes = n_classes;
+  // (read when the tables are built, as the switches of restrict / prolong are: two restrictors of one process can differ)
+  char const *kernel = std::getenv("MFMG_RR_KERNEL");
+  _rr_rows = kernel != nullptr && std::string(kernel) == "rows";
   return true;
 }
 
@@ -593,10 +596,7 @@ void StructuredRestrictorDevice::restrict_residual_any(TI const *x, TI const *b,
   s.segs = _rr_segs;
   s.main_last = _rr_main_last;
   // MFMG_RR_KERNEL=rows: the row-wise kernel of rounds 2-3 (a wavefront per agglomerate row, no LDS) for comparisons
-  static const bool tile_form = [] {
-    char const *e = std::getenv("MFMG_RR_KERNEL");
-    return !(e && std::string(e) == "rows");
-  }();
+  const bool tile_form = !_rr_rows;
   hipEvent_t stop = _handle.profiler.begin("residual_restriction", 2. * sizeof(TI) * double(_n_fine) + 8. * double(_n_coarse), _handle.stream);
   if (tile_form)
   {

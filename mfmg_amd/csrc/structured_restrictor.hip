@@ -171,6 +171,8 @@ __global__ __launch_bounds__(256) void sr_restrict_pair_kernel(SrArgs s, double 
   reinterpret_cast<double2 *>(y)[ag] = make_double2(sum0, sum1);
 }
 
+// (sr_prolong_listed222_part below forms the same sum for 2 x 2 x 2 agglomerates with two eigenvectors with its requests in one
+// batch: candidate order, m, the plane index p0 / 2 and the choice table / class table / planes must stay in step with this)
 // (R^T y) at fine node `node`: a node lies in at most two agglomerates per direction, the one it starts
 // (position m = i mod a) and, on an agglomerate boundary, the previous one (position m = a); fixed order
 // (z, y, x candidates, then eigenvectors)
@@ -246,6 +248,25 @@ __global__ __launch_bounds__(256) void sr_prolong_kernel(SrArgs s, double const 
   out[id] = subtract ? out[id] - sum : sum;
 }
 
+// the nodes of the listed agglomerate positions: a thread per node (the first workgroups of the block kernel)
+template <bool SUB>
+__device__ __forceinline__ void sr_prolong_listed_part(SrArgs const &s, double const *y, double *out, int32_t const *blocks, int64_t n_blocks)
+{
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= 8 * n_blocks)
+    return;
+  const int64_t v = blocks[t >> 3];
+  const int d = (int)(t & 7);
+  const int vx = s.na[0] + 1, vy = s.na[1] + 1;
+  const int i = 2 * (int)(v % vx) + (d & 1), j = 2 * (int)((v / vx) % vy) + ((d >> 1) & 1),
+            k = 2 * (int)(v / ((int64_t)vx * vy)) + (d >> 2);
+  if (i >= s.N[0] || j >= s.N[1] || k >= s.N[2])
+    return;
+  const int64_t node = i + (int64_t)s.N[0] * (j + (int64_t)s.N[1] * k);
+  const double sum = sr_node_value(s, y, node);
+  out[node] = SUB ? out[node] - sum : sum;
+}
+
 // 2 x 2 x 2 agglomerates, two eigenvectors, lexicographic numbering, table-driven blocks: one thread per
 // agglomerate position (na + 1 per direction) finishes the 2 x 2 x 2 nodes at the low corner of its agglomerate.
 // The y pairs of the (at most) eight agglomerates around are fetched once for the eight nodes, the table
@@ -274,19 +295,7 @@ __global__ __launch_bounds__(256) void sr_prolong_block222_kernel(SrArgs s, doub
   ctable_t *table = reinterpret_cast<ctable_t *>(reinterpret_cast<uintptr_t>(s.table));
   if (blockIdx.x < listed_blocks)
   {
-    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (t >= 8 * n_blocks)
-      return;
-    const int64_t v = blocks[t >> 3];
-    const int d = (int)(t & 7);
-    const int vx = s.na[0] + 1, vy = s.na[1] + 1;
-    const int i = 2 * (int)(v % vx) + (d & 1), j = 2 * (int)((v / vx) % vy) + ((d >> 1) & 1),
-              k = 2 * (int)(v / ((int64_t)vx * vy)) + (d >> 2);
-    if (i >= s.N[0] || j >= s.N[1] || k >= s.N[2])
-      return;
-    const int64_t node = i + (int64_t)s.N[0] * (j + (int64_t)s.N[1] * k);
-    const double sum = sr_node_value(s, y, node);
-    out[node] = subtract ? out[node] - sum : sum;
+    sr_prolong_listed_part<SUB>(s, y, out, blocks, n_blocks);
     return;
   }
   const int64_t t = (int64_t)(blockIdx.x - listed_blocks) * blockDim.x + threadIdx.x;
@@ -366,6 +375,358 @@ __global__ __launch_bounds__(256) void sr_prolong_block222_kernel(SrArgs s, doub
       *reinterpret_cast<sr_pair *>(orow[dyz]) = v;
     else
       orow[dyz][0] = v.x;
+  }
+}
+
+// The listed positions for the marching kernel: a thread per node and the sums of sr_node_value again (2 x 2 x 2 agglomerates, two
+// eigenvectors, lexicographic ids), but every request of a thread leaves before the first answer is used.  sr_node_value asks
+// for the class of an agglomerate, then for its block entry, then for the y pair, candidate after candidate behind branches:
+// some twenty dependent round trips per wavefront, and on the bench mesh the 9 % of the nodes that lie at the faces of the box
+// took as long as all the others.  Here: the position, then y pairs, classes and out for all eight candidates at once
+// (agglomerates outside the mesh at a clamped index), then the eight block entries, then the sum -- over the candidates that
+// exist, in the same order, so the same bits.
+template <bool SUB>
+__device__ __forceinline__ void sr_prolong_listed222_part(SrArgs const &s, double const *y, double *out, int32_t const *blocks, int64_t n_blocks,
+                                                          unsigned int block)
+{
+  const int64_t t = block * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= 8 * n_blocks)
+    return;
+  const int64_t v = blocks[t >> 3];
+  const int d = (int)(t & 7);
+  const int vx = s.na[0] + 1, vy = s.na[1] + 1;
+  const int idx[3] = {2 * (int)(v % vx) + (d & 1), 2 * (int)((v / vx) % vy) + ((d >> 1) & 1), 2 * (int)(v / ((int64_t)vx * vy)) + (d >> 2)};
+  if (idx[0] >= s.N[0] || idx[1] >= s.N[1] || idx[2] >= s.N[2])
+    return;
+  const int64_t node = idx[0] + (int64_t)s.N[0] * (idx[1] + (int64_t)s.N[1] * idx[2]);
+  // candidate agglomerates per direction, as in sr_node_value: [0] the one the node starts, [1] the previous one
+  int ag[3][2], mm[3][2];
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+  {
+    ag[q][0] = idx[q] / 2 < s.na[q] ? idx[q] / 2 : -1;
+    mm[q][0] = idx[q] % 2;
+    ag[q][1] = (idx[q] % 2 == 0 && idx[q] / 2 >= 1) ? idx[q] / 2 - 1 : -1;
+    mm[q][1] = 2;
+  }
+  const bool table = s.exc_node != nullptr && s.exc_node[node] == 0;
+  const double o = SUB ? out[node] : 0.;
+  bool valid[8];
+  int64_t agc[8];
+  int m[8];
+  double2 yv[8], pv[8];
+  unsigned int cl[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+  {
+    const int cz = c >> 2, cy = (c >> 1) & 1, cx = c & 1;
+    valid[c] = ag[2][cz] >= 0 && ag[1][cy] >= 0 && ag[0][cx] >= 0;
+    agc[c] = valid[c] ? ag[0][cx] + (int64_t)s.na[0] * (ag[1][cy] + (int64_t)s.na[1] * ag[2][cz]) : 0;
+    m[c] = mm[0][cx] + 3 * (mm[1][cy] + 3 * mm[2][cz]);
+    yv[c] = reinterpret_cast<double2 const *>(y)[agc[c]];
+    cl[c] = s.cls != nullptr ? s.cls[agc[c]] : 0xffffu;
+  }
+  double2 const *table2 = reinterpret_cast<double2 const *>(s.table), *class2 = reinterpret_cast<double2 const *>(s.class_table),
+                *planes2 = reinterpret_cast<double2 const *>(s.planes);
+  const size_t stride = (size_t)s.n_coarse / 2;
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+  {
+    // one request whatever the source: the reference table, the class table, or the planes (kept in float: below)
+    double2 const *src = table2 + m[c];
+    if (!table && cl[c] != 0xffffu)
+      src = class2 + (size_t)cl[c] * s.patch + m[c];
+    else if (!table && planes2 != nullptr)
+      src = planes2 + (size_t)m[c] * stride + agc[c];
+    pv[c] = *src;
+  }
+  if (s.planes_f != nullptr)
+  {
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (valid[c] && !table && cl[c] == 0xffffu)
+        pv[c] = sr_plane_pair(s, (size_t)m[c] * stride + agc[c]);
+  }
+  double sum = 0.;
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+    if (valid[c])
+    {
+      sum += pv[c].x * yv[c].x;
+      sum += pv[c].y * yv[c].y;
+    }
+  out[node] = SUB ? o - sum : sum;
+}
+
+// ---- the same as a march -------------------------------------------------------------------------------------------------
+// The block kernel asks for the y pair of an agglomerate from eight threads and lives for one round trip.  Here a wavefront
+// owns 64 consecutive agglomerate positions of one row (vj) and marches through `len` layers of positions (vk):
+//   y    : a lane requests the pairs of its own agglomerate column in the rows vj and vj - 1, once per layer, 16 bytes each;
+//          the column before (vi - 1) is the previous lane's (DPP wave shift; lane 0 gets it from a wave-uniform request), the
+//          layer before (vk - 1) is carried in registers from the step before.  A pair is requested by two wavefronts of
+//          neighbouring rows (the same workgroup) instead of eight threads.
+//   out  : the four node rows of layer vk + 1 and that layer's pairs are requested before the sums of layer vk are formed
+//          (buffer descriptors: a per-lane offset that never changes and a scalar offset per row), so that two layers of
+//          requests are in flight per wavefront and a wait stands only in front of the first use.
+//   pairs: node rows start 8 bytes further on from row to row (odd row lengths), so in the rows at an odd distance from the
+//          start of the vector a lane takes the nodes (2 vi - 1, 2 vi) instead of (2 vi, 2 vi + 1) -- the last node of the
+//          position before and the first of its own, both formed from the very pairs it holds anyway -- and every 16-byte
+//          access of a row is aligned: a wavefront reads and writes one contiguous, aligned kilobyte per row; the first node
+//          of such a row and the last node of the others are single 8-byte stores (head and tail).
+// A node is read and written by the one lane that owns it; a lane at either end of a row reads its pair one node further
+// inside and drops the foreign half, and the last step of a march requests its own layer once more and drops all of it.  Every sum is formed in the order of sr_node_value (the same bits as the block kernel).
+// Waves share nothing (no LDS, no barrier): the ones of a workgroup are neighbouring rows, for the vector cache.
+constexpr int kMarchWaves = 4; // rows vj of a workgroup
+
+struct SrMarch
+{
+  int lo[3], hi[3]; // box of the agglomerate positions the tables serve (the march covers it; positions in the list are masked)
+  int strips, wgs_y, chunks, len;
+  unsigned int n_wgs, blocks; // workgroups with work / in the grid (a multiple of 8)
+  unsigned int y_bytes, out_bytes;
+};
+
+typedef unsigned int sr_v4u __attribute__((ext_vector_type(4)));
+typedef unsigned int sr_v2u __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ sr_pair sr_ld_pair(__amdgpu_buffer_rsrc_t r, unsigned int voff, unsigned int soff)
+{
+  const sr_v4u v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
+  sr_pair p;
+  p.x = __hiloint2double((int)v.y, (int)v.x);
+  p.y = __hiloint2double((int)v.w, (int)v.z);
+  return p;
+}
+__device__ __forceinline__ void sr_st_pair(sr_pair p, __amdgpu_buffer_rsrc_t r, unsigned int voff, unsigned int soff)
+{
+  sr_v4u v;
+  v.x = (unsigned int)__double2loint(p.x), v.y = (unsigned int)__double2hiint(p.x);
+  v.z = (unsigned int)__double2loint(p.y), v.w = (unsigned int)__double2hiint(p.y);
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
+}
+__device__ __forceinline__ void sr_st_one(double d, __amdgpu_buffer_rsrc_t r, unsigned int voff, unsigned int soff)
+{
+  sr_v2u v;
+  v.x = (unsigned int)__double2loint(d), v.y = (unsigned int)__double2hiint(d);
+  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
+}
+// value the previous lane of the wavefront holds (DPP wave shift; lane 0 keeps its own)
+__device__ __forceinline__ double sr_prev_lane(double v)
+{
+  const int hi = __double2hiint(v), lo = __double2loint(v);
+  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false),
+                          __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false));
+}
+
+// y pairs of one layer of agglomerates around a lane: [0] its own column, [1] the column before; [.][sy]: rows vj - sy
+struct SrLayer
+{
+  sr_pair c[2][2];
+};
+
+// (R^T y) at the node at offset (DX, DY, DZ) in its agglomerate position: `a0` are the pairs of the agglomerate column the
+// position starts, `a1` those of the column before (which holds the node only for DX = 0); [0] the layer vk, [1] vk - 1.
+// The terms in the order of sr_node_value / the block kernel.
+template <int DX, int DY, int DZ, typename Table>
+__device__ __forceinline__ double sr_march_sum(Table table, sr_pair const (&a0)[2][2], sr_pair const (&a1)[2][2])
+{
+  double sum = 0.;
+#pragma unroll
+  for (int sz = 0; sz < 2; ++sz)
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy)
+#pragma unroll
+      for (int sx = 0; sx < 2; ++sx)
+      {
+        if ((sx && DX) || (sy && DY) || (sz && DZ))
+          continue;
+        const int m = (sx ? 2 : DX) + 3 * ((sy ? 2 : DY) + 3 * (sz ? 2 : DZ));
+        const sr_pair yv = sx ? a1[sz][sy] : a0[sz][sy];
+        sum += table[2 * m] * yv.x;
+        sum += table[2 * m + 1] * yv.y;
+      }
+  return sum;
+}
+
+template <bool SUB>
+__global__ __launch_bounds__(64 * kMarchWaves) void sr_prolong_march222_kernel(SrArgs s, SrMarch g, double const *y, double *out,
+                                                                               uint8_t const *blk_exc, int32_t const *blocks,
+                                                                               int64_t n_blocks)
+{
+  // the marches first: few workgroups that live long; the listed positions fill the rest of the device beside them
+  if (blockIdx.x >= g.blocks)
+  {
+    sr_prolong_listed222_part<SUB>(s, y, out, blocks, n_blocks, blockIdx.x - g.blocks);
+    return;
+  }
+  typedef __attribute__((address_space(4))) const double ctable_t;
+  ctable_t *table = reinterpret_cast<ctable_t *>(reinterpret_cast<uintptr_t>(s.table));
+  // a contiguous run of workgroups per XCD: neighbouring rows and neighbouring chunks of layers share y pairs (workgroups are
+  // dealt to the 8 XCDs of the MI300 / MI355X in turn, as the restriction kernels above assume; on a part with another count the
+  // mapping is still one to one -- `blocks` is a multiple of 8 -- and only the sharing is lost)
+  const unsigned int mb = blockIdx.x;
+  const unsigned int bid = (mb & 7) * (g.blocks >> 3) + (mb >> 3);
+  if (bid >= g.n_wgs)
+    return;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  const int strip = (int)(bid % (unsigned int)g.strips), wy = (int)((bid / (unsigned int)g.strips) % (unsigned int)g.wgs_y),
+            ch = (int)(bid / (unsigned int)(g.strips * g.wgs_y));
+  const int vj = g.lo[1] + wy * kMarchWaves + w;
+  const int vk0 = g.lo[2] + ch * g.len, vk1 = min(vk0 + g.len, g.hi[2] + 1);
+  if (vj > g.hi[1] || vk0 >= vk1)
+    return; // (waves share nothing: no barrier is left waiting)
+  const int na0 = s.na[0], na1 = s.na[1], na2 = s.na[2], N0 = s.N[0], N1 = s.N[1], N2 = s.N[2];
+  const int vi0 = g.lo[0] + 64 * strip, vi = vi0 + lane;
+  const int vic = min(vi, na0); // (lanes beyond the row: clamped requests, no stores)
+  const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(y), 0, g.y_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(out, 0, g.out_bytes, 0x00020000);
+  // y: per-lane offset of the own agglomerate column, wave-uniform one of the column before lane 0; agglomerates outside
+  // the mesh are requested at a clamped index and contribute exact zeros, as in the block kernel
+  const unsigned int yo_own = 16u * (unsigned int)min(vic, na0 - 1);
+  unsigned int yo_halo = 16u * (unsigned int)min(max(vi0 - 1, 0), na0 - 1);
+  // (kept in a vector register of its own: moved there from a scalar before every request it took the place of a register that
+  // an earlier request had yet to fill, with a wait for ALL outstanding requests in front of the move)
+  asm volatile("" : "+v"(yo_halo));
+  const bool has_own = vi < na0, has_halo = vi0 >= 1;
+  const unsigned int y_row[2] = {(unsigned int)min(vj, na1 - 1), (unsigned int)max(vj - 1, 0)};
+  const bool has_row[2] = {vj < na1, vj >= 1};
+  // out: first node of the lane's pair in the rows at an even / odd distance from the start of the vector, and the same
+  // clamped into the row for the request
+  const int n_first[2] = {2 * vic, 2 * vic - 1};
+  unsigned int oo_ld[2], oo_st[2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+  {
+    oo_ld[p] = 8u * (unsigned int)min(max(n_first[p], 0), N0 - 2);
+    oo_st[p] = 8u * (unsigned int)max(n_first[p], 0);
+  }
+  const bool at_head = vic == 0, at_tail = vic == na0; // pair (-1, 0) of an odd row, pair (N0 - 1, N0) of an even one
+  const int vx = na0 + 1, vy = na1 + 1;
+
+  struct Raw
+  {
+    sr_pair own[2], halo[2]; // y pairs of a layer as requested: rows vj, vj - 1
+    sr_pair o[4];            // out: node rows (dy, dz) of the layer
+    unsigned int exc[2];     // blk_exc of the positions vi, vi - 1
+  };
+  auto request_y = [&](Raw &r, int vk) {
+    const unsigned int kc = (unsigned int)min(max(vk, 0), na2 - 1);
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy)
+    {
+      const unsigned int soff = 16u * (unsigned int)na0 * (y_row[sy] + (unsigned int)na1 * kc);
+      r.own[sy] = sr_ld_pair(rs_y, yo_own, soff);
+      r.halo[sy] = sr_ld_pair(rs_y, yo_halo, soff);
+    }
+  };
+  auto request_out = [&](Raw &r, int vk) {
+    const int64_t pos = (int64_t)vx * (vj + (int64_t)vy * vk);
+    r.exc[0] = blk_exc[pos + vic];
+    r.exc[1] = blk_exc[pos + max(vic - 1, 0)];
+    if constexpr (SUB)
+    {
+#pragma unroll
+      for (int dyz = 0; dyz < 4; ++dyz)
+      {
+        const int dy = dyz & 1, dz = dyz >> 1;
+        const unsigned int row = (unsigned int)min(2 * vj + dy, N1 - 1) + (unsigned int)N1 * (unsigned int)min(2 * vk + dz, N2 - 1);
+        r.o[dyz] = sr_ld_pair(rs_o, oo_ld[dy ^ dz], 8u * (unsigned int)N0 * row);
+      }
+    }
+  };
+  // the pairs of layer vk around the lane, from what was requested
+  auto layer_of = [&](Raw const &r, int vk) {
+    const bool has_k = vk >= 0 && vk < na2;
+    SrLayer L;
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy)
+    {
+      const bool ho = has_own && has_row[sy] && has_k, hh = has_halo && has_row[sy] && has_k;
+      const sr_pair own{ho ? r.own[sy].x : 0., ho ? r.own[sy].y : 0.};
+      const sr_pair halo{hh ? r.halo[sy].x : 0., hh ? r.halo[sy].y : 0.};
+      const double px = sr_prev_lane(own.x), py = sr_prev_lane(own.y);
+      L.c[0][sy] = own;
+      L.c[1][sy] = sr_pair{lane == 0 ? halo.x : px, lane == 0 ? halo.y : py};
+    }
+    return L;
+  };
+  // the four node rows of layer vk: sums, then out
+  auto finish = [&](Raw const &r, SrLayer const &cur, SrLayer const &prev, int vk) {
+    sr_pair a_own[2][2], a_prev[2][2]; // [layer vk - sz][row vj - sy]
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy)
+    {
+      a_own[0][sy] = cur.c[0][sy], a_own[1][sy] = prev.c[0][sy];
+      a_prev[0][sy] = cur.c[1][sy], a_prev[1][sy] = prev.c[1][sy];
+    }
+    const bool live_p = vi <= na0 && r.exc[0] == 0, live_m = vi >= 1 && vi <= na0 && r.exc[1] == 0;
+#pragma unroll
+    for (int dyz = 0; dyz < 4; ++dyz)
+    {
+      const int dy = dyz & 1, dz = dyz >> 1;
+      if (2 * vj + dy >= N1 || 2 * vk + dz >= N2)
+        continue; // (wave-uniform)
+      const int odd = dy ^ dz;
+      double s0, s1;
+      bool w0, w1;
+      if (odd)
+      {
+        s0 = dyz == 1 ? sr_march_sum<1, 1, 0>(table, a_prev, a_prev) : sr_march_sum<1, 0, 1>(table, a_prev, a_prev);
+        s1 = dyz == 1 ? sr_march_sum<0, 1, 0>(table, a_own, a_prev) : sr_march_sum<0, 0, 1>(table, a_own, a_prev);
+        w0 = live_m, w1 = live_p;
+      }
+      else
+      {
+        s0 = dyz == 0 ? sr_march_sum<0, 0, 0>(table, a_own, a_prev) : sr_march_sum<0, 1, 1>(table, a_own, a_prev);
+        s1 = dyz == 0 ? sr_march_sum<1, 0, 0>(table, a_own, a_own) : sr_march_sum<1, 1, 1>(table, a_own, a_own);
+        w0 = live_p, w1 = live_p && vi < na0;
+      }
+      sr_pair v{s0, s1};
+      if constexpr (SUB)
+      {
+        sr_pair o = r.o[dyz];
+        if (odd && at_head)
+          o.y = o.x; // requested (0, 1) for (-1, 0)
+        if (!odd && at_tail)
+          o.x = o.y; // requested (N0 - 2, N0 - 1) for (N0 - 1, N0)
+        v.x = o.x - s0, v.y = o.y - s1;
+      }
+      const unsigned int soff = 8u * (unsigned int)N0 * ((unsigned int)(2 * vj + dy) + (unsigned int)N1 * (unsigned int)(2 * vk + dz));
+      if (w0 && w1)
+        sr_st_pair(v, rs_o, oo_st[odd], soff);
+      else if (w0)
+        sr_st_one(v.x, rs_o, oo_st[odd], soff);
+      else if (w1)
+        sr_st_one(v.y, rs_o, 8u * (unsigned int)(n_first[odd] + 1), soff);
+    }
+  };
+
+  // one step: the requests of layer vk + 1 leave into `next` before `now` (requested a step ago) is first used; the two sets of
+  // registers and the two layers of pairs change roles from step to step (no copies: a copy would wait for the data)
+  // (the last step of a march asks for its own layer again: a request under a condition would make the compiler copy the
+  // registers it fills where the two paths join, and a copy waits for the data)
+  auto step = [&](Raw const &now, Raw &next, SrLayer const &below, SrLayer &here, int vk) {
+    const int vn = min(vk + 1, vk1 - 1);
+    request_y(next, vn);
+    request_out(next, vn);
+    here = layer_of(now, vk);
+    finish(now, here, below, vk);
+  };
+  Raw ra, rb;
+  SrLayer la, lb;
+  request_y(rb, vk0 - 1);
+  request_y(ra, vk0);
+  request_out(ra, vk0);
+  lb = layer_of(rb, vk0 - 1);
+  for (int vk = vk0;; vk += 2)
+  {
+    step(ra, rb, lb, la, vk);
+    if (vk + 1 >= vk1)
+      break;
+    step(rb, ra, la, lb, vk + 1);
+    if (vk + 2 >= vk1)
+      break;
   }
 }
 } // namespace
@@ -456,6 +817,12 @@ StructuredRestrictorDevice::create(HipHandle &handle, StructuredMesh const &mesh
   };
   s->_restrict_rows = env_is("MFMG_SR_RESTRICT", "rows");
   const bool prolong_nodes = env_is("MFMG_SR_PROLONG", "nodes");
+  // MFMG_SR_PROLONG=block: the block kernel with a thread per agglomerate position instead of its marching form (the same bits,
+  // tests/test_transfer_march_kernels.py; for that comparison and for timing one against the other); MFMG_SR_MARCH_LAYERS: the
+  // layers of a march (default: chosen for the grid).  The march addresses both vectors through 32-bit byte offsets
+  s->_prolong_march = !env_is("MFMG_SR_PROLONG", "block") && 8 * (int64_t)mesh.n_dofs < (int64_t(1) << 32) && 8 * R.n_rows < (int64_t(1) << 32);
+  if (char const *e = std::getenv("MFMG_SR_MARCH_LAYERS"))
+    s->_march_layers = std::max(0, std::atoi(e));
   {
     // planes whose values a float holds exactly ("setup value precision" float rounds R) are kept in float
     bool all_float = !planes.empty();
@@ -750,9 +1117,59 @@ StructuredRestrictorDevice::create(HipHandle &handle, StructuredMesh const &mesh
           blk_exc[t] = any;
         }
         std::vector<int32_t> exc_blocks;
+        int lo[3] = {1 << 30, 1 << 30, 1 << 30}, hi[3] = {-1, -1, -1};
         for (int64_t t = 0; t < vx * vy * vz; ++t)
           if (blk_exc[t])
             exc_blocks.push_back((int32_t)t);
+          else
+          {
+            const int v[3] = {(int)(t % vx), (int)((t / vx) % vy), (int)(t / (vx * vy))};
+            for (int d = 0; d < 3; ++d)
+            {
+              lo[d] = std::min(lo[d], v[d]);
+              hi[d] = std::max(hi[d], v[d]);
+            }
+          }
+        for (int d = 0; d < 3; ++d)
+        {
+          s->_march_lo[d] = lo[d];
+          s->_march_hi[d] = hi[d];
+        }
+        if (hi[0] >= lo[0])
+        {
+          // grid of the marches.  The lane after the last position of a row takes that position's last node in the odd rows.
+          s->_march_strips = (std::min(hi[0] + 1, agg_dims[0]) - lo[0] + 1 + 63) / 64;
+          s->_march_wgs_y = (hi[1] - lo[1] + 1 + kMarchWaves - 1) / kMarchWaves;
+          const int layers = hi[2] - lo[2] + 1;
+          // Layers of a march: as many chunks as give every CU ONE workgroup of marches, in whole rounds -- one per CU streams as
+          // fast as four (the marches are bound by bytes: profiles/r07_a), and the rest of the CU is for the listed positions,
+          // which are bound by latency and run beside them.  A march passes its layers plus the fill of its pipeline; one
+          // shorter than kMarchMin layers re-reads too many y pairs at its start.
+          int n_cus = 0, dev = 0;
+          if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
+            n_cus = 256;
+          constexpr int kMarchMin = 8;
+          int len = s->_march_layers > 0 ? std::min(s->_march_layers, layers) : 0;
+          if (len == 0)
+          {
+            double best = 0.;
+            for (int nk = 1; nk <= layers; ++nk)
+            {
+              const int t = (layers + nk - 1) / nk;
+              if ((layers + t - 1) / t != nk || (nk > 1 && t < kMarchMin))
+                continue;
+              const int64_t wgs = (int64_t)s->_march_strips * s->_march_wgs_y * nk;
+              const double cost = double((wgs + n_cus - 1) / n_cus) * (t + 2.);
+              if (len == 0 || cost < best)
+              {
+                best = cost;
+                len = t;
+              }
+            }
+          }
+          s->_march_len = len;
+          s->_march_chunks = (layers + len - 1) / len;
+        }
         s->_blk_exc.upload(blk_exc.data(), blk_exc.size(), handle.stream);
         s->_exc_blocks.upload(exc_blocks.data(), exc_blocks.size(), handle.stream);
       }
@@ -838,7 +1255,41 @@ void StructuredRestrictorDevice::prolongate(double const *y, double *out, bool s
                        _cls.size() ? _cls.data() : nullptr, _class_table.data());
   hipEvent_t stop = _handle.profiler.begin("csr_spmv_kernel", algorithmic_bytes() + (subtract ? 8. * double(_n_fine) : 0.),
                                            _handle.stream);
-  if (_blk_exc.size() > 0)
+  if (prolong_march())
+  {
+    const int64_t n_listed = (int64_t)_exc_blocks.size();
+    unsigned int listed_blocks = (unsigned int)((8 * n_listed + 255) / 256);
+    SrMarch g;
+    std::memset(&g, 0, sizeof(g));
+    for (int d = 0; d < 3; ++d)
+    {
+      g.lo[d] = _march_lo[d];
+      g.hi[d] = _march_hi[d];
+    }
+    g.strips = _march_strips, g.wgs_y = _march_wgs_y, g.chunks = _march_chunks, g.len = _march_len;
+    g.n_wgs = (unsigned int)(g.strips * g.wgs_y * g.chunks);
+    g.blocks = (g.n_wgs + 7) / 8 * 8;
+    g.y_bytes = (unsigned int)(8 * _n_coarse);
+    g.out_bytes = (unsigned int)(8 * _n_fine);
+#ifdef MFMG_SR_TIMING_PARTS
+    // a measurement build only (-DMFMG_SR_TIMING_PARTS=1 or 2 in CXXFLAGS; wrong results): the launch without its list / without
+    // its marches, for the split timings of profiles/r07_a and r07_b
+    if (MFMG_SR_TIMING_PARTS == 1)
+      listed_blocks = 0;
+    else
+      g.blocks = 0, g.n_wgs = 0;
+#endif
+    const dim3 grid(listed_blocks + g.blocks);
+    if (grid.x == 0)
+      ; // (nothing to launch: only a measurement build gets here, every position is table-driven or in the list)
+    else if (subtract)
+      hipLaunchKernelGGL(sr_prolong_march222_kernel<true>, grid, dim3(64 * kMarchWaves), 0, _handle.stream, s, g, y, out, _blk_exc.data(),
+                         _exc_blocks.data(), n_listed);
+    else
+      hipLaunchKernelGGL(sr_prolong_march222_kernel<false>, grid, dim3(64 * kMarchWaves), 0, _handle.stream, s, g, y, out, _blk_exc.data(),
+                         _exc_blocks.data(), n_listed);
+  }
+  else if (_blk_exc.size() > 0)
   {
     const int64_t n_pos = (int64_t)_blk_exc.size(), n_listed = (int64_t)_exc_blocks.size();
     const unsigned int listed_blocks = (unsigned int)((8 * n_listed + 255) / 256);

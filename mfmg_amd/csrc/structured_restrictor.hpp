@@ -97,6 +97,12 @@ private:
   int _n_classes = 0;
   int64_t _n_regular = 0;
   bool _restrict_rows = false; // MFMG_SR_RESTRICT=rows: the row kernel whatever n_eig and the agglomerate
+  // the block kernel as a march (structured_restrictor.hip): the box of agglomerate positions the tables serve (empty: hi < lo)
+  // and the layers of a march (0: chosen per launch grid); MFMG_SR_PROLONG=block keeps the thread-per-position kernel
+  bool _prolong_march = false;
+  int _march_lo[3] = {0, 0, 0}, _march_hi[3] = {-1, -1, -1};
+  int _march_layers = 0;
+  int _march_strips = 0, _march_wgs_y = 0, _march_chunks = 0, _march_len = 0; // grid of the marches, fixed at construction
 
 public:
   int block_classes() const { return _n_classes; }
@@ -110,6 +116,8 @@ public:
   enum ProlongKernel { kProlongNodes = 1, kProlongBlock222 = 2 };
   int restrict_kernel() const;
   int prolong_kernel() const { return _blk_exc.size() > 0 ? kProlongBlock222 : kProlongNodes; }
+  // the block kernel in its marching form (a wavefront per row of positions, layers in turn) instead of a thread per position
+  bool prolong_march() const { return _blk_exc.size() > 0 && _prolong_march; }
 
 private:
   DeviceBuffer<int32_t> _node_dof; // DoF id of lexicographic node (empty when the numbering is lexicographic)
@@ -120,5 +128,6 @@ private:
   DeviceBuffer<uint16_t> _rr_seg_class;  // per wavefront of the main part (64 agglomerates of one row): its class
   DeviceBuffer<int32_t> _rr_listed;      // agglomerates left to the thread-per-agglomerate part
   int _rr_segs = 0, _rr_classes = 0, _rr_main_last = 0;
+  bool _rr_rows = false; // MFMG_RR_KERNEL=rows when the tables were built
 };
 } // namespace mfmg

@@ -20,7 +20,7 @@ ERROR_DEVICE = 4
 NO_TRANS = 0
 TRANS = 1
 TRANS_SUBTRACT = 2   # restrictor_apply only: out -= R^T in
-RESTRICTOR_FORM_FIELDS = 11
+RESTRICTOR_FORM_FIELDS = 12
 CSR_FORM_FIELDS = 22
 # modes of mfmg_hip_csr_launch
 CSR_APPLY, CSR_RESIDUAL, CSR_FIRST, CSR_NEXT, CSR_SUBTRACT, CSR_ADD, CSR_PLUS_SCALED = range(7)
