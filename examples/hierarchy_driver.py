@@ -15,6 +15,10 @@ Jacobi, the CUDA back-end's smoother, with a note.
 `--numbering dealii` numbers the DoFs as deal.II's DoFHandler::distribute_dofs does (cells in Morton order, vertex DoFs at first
 touch), `random` by a seeded permutation; both set `"internal numbering" lexicographic` (matrix-free runs), so that the hierarchy
 runs on the kernels of the lexicographic numbering and permutes vectors at its interface.
+
+`--solver fgmres` (with `"is preconditioner" true`) solves with the flexible GMRES driver in place of CG: the hierarchy may then
+be a non-symmetric cycle (`solver.amg.pre_smoothing_levels 0`), and `--preconditioner-precision float` runs its fine level in
+FP32 under the FP64 iteration (sets `"fine level precision" float`; matrix-free, two levels).  `--restart` is the basis size.
 """
 import argparse
 import math
@@ -34,9 +38,14 @@ def main(argv=None):
     ap.add_argument("-m", "--matrix_free", type=int, default=0)
     ap.add_argument("-t", "--tolerance", type=float, default=1e-6)
     ap.add_argument("--numbering", choices=["lexicographic", "dealii", "random"], default="lexicographic")
+    ap.add_argument("--solver", choices=["cg", "fgmres"], default="cg")
+    ap.add_argument("--restart", type=int, default=30)
+    ap.add_argument("--preconditioner-precision", choices=["double", "float"], default="double")
     args = ap.parse_args(argv)
     if args.dim not in (2, 3):
         raise SystemExit("dim must be 2 or 3")
+    if args.preconditioner_precision == "float" and args.solver != "fgmres":
+        raise SystemExit("--preconditioner-precision float needs --solver fgmres (CG wants a fixed, symmetric preconditioner)")
     params = M.info_to_params(open(args.filename).read())
     if not args.matrix_free and params.get("use_raw_ml", False):
         raise SystemExit("use_raw_ml: ML is not part of the HIP build")
@@ -71,6 +80,8 @@ def main(argv=None):
         numbering = torch.randperm(math.prod(c + 1 for c in cells), generator=torch.Generator().manual_seed(7))
     if numbering is not None and args.matrix_free:
         params["internal numbering"] = "lexicographic"
+    if args.preconditioner_precision == "float":
+        params["fine level precision"] = "float"
     prob = M.LaplaceProblem(cells, material, device="cuda", dof_numbering=numbering)
     evaluator = "HipMatrixFreeMeshEvaluator" if args.matrix_free else "HipMeshEvaluator"
     h = M.Hierarchy(ctx, evaluator, prob, params)
@@ -93,7 +104,11 @@ def main(argv=None):
         g2 = torch.Generator(device="cuda").manual_seed(2)
         b = torch.rand(prob.n_dofs, dtype=torch.float64, device="cuda", generator=g2) * (prob.constrained == 0)
         x.zero_()
-        its, hist = h.solve_cg(b, x, tolerance=args.tolerance, max_iterations=prob.n_dofs)
+        if args.solver == "fgmres":
+            its, hist = h.solve_fgmres(b, x, tolerance=args.tolerance, max_iterations=prob.n_dofs, restart=args.restart,
+                                       preconditioner=args.preconditioner_precision)
+        else:
+            its, hist = h.solve_cg(b, x, tolerance=args.tolerance, max_iterations=prob.n_dofs)
         print(f"Converging after {its} iterations.")
         rate = its
     print(h.timer_report())

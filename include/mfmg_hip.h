@@ -450,6 +450,35 @@ int mfmg_hip_hierarchy_vmult(mfmg_hip_hierarchy_t h, double *x, const double *b)
 int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance,
                                 int32_t max_iterations, int32_t *n_iterations, double *final_residual,
                                 double *residual_history, int32_t history_len);
+/* Right-preconditioned flexible GMRES(restart), dealii::SolverFGMRES: the preconditioner may be non-symmetric (the cycle with
+ * solver.amg.pre_smoothing_levels 0) and may change from one iteration to the next (a preconditioner rounded to float), neither
+ * of which CG admits.  Same stopping rule and outputs as mfmg_hip_hierarchy_solve_cg: the absolute l2 norm of the residual -- here
+ * the residual norm |g_{j+1}| of the least-squares problem, which is what residual_history receives per iteration -- against
+ * `tolerance`; ||r_0|| <= tolerance returns 0 iterations with x unchanged; MFMG_HIP_ERROR_RUNTIME without convergence, outputs
+ * filled, x updated with what was reached.  x += Z y after `restart` (>= 1) vectors, then the true residual is recomputed and
+ * tested (it is not a history entry of its own); a breakdown h_{j+1,j} = 0 ends the cycle with the update, and the true residual
+ * recomputed after it -- not the estimate, which a singular Hessenberg matrix makes zero too -- is that iteration's history entry
+ * and decides convergence.  An allocation of the basis that fails returns an error and leaves no basis behind: retry with a
+ * smaller restart.
+ *   preconditioner_fp32 0: z = Hierarchy::vmult(v); 1: the FP32 fine level (mfmg_hip_hierarchy_apply_f32) on the narrowed v, its
+ *   result widened -- the outer iteration, operator and basis stay FP64 (needs "fine level precision" float, otherwise
+ *   MFMG_HIP_ERROR_INVALID_ARGUMENT).  Either preconditioner starts from zero whatever "is preconditioner" says.
+ * Orthogonalisation: classical Gram-Schmidt twice with the fused kernels of krylov_basis.hpp; one device-to-host copy per
+ * iteration.  The basis (2 restart + 1 vectors, restart capped by max_iterations) is owned by the hierarchy and kept for the next
+ * solve.  "internal numbering" lexicographic: two launches of "dof_permutation" per solve.  One process
+ * (MFMG_HIP_ERROR_INVALID_ARGUMENT on a context with a communicator). */
+int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance,
+                                    int32_t max_iterations, int32_t restart, int32_t preconditioner_fp32,
+                                    int32_t *n_iterations, double *final_residual,
+                                    double *residual_history, int32_t history_len);
+/* The kernels of that orthogonalisation on their own (tests).  V, Z: column-major device arrays with leading dimension ld >= n,
+ * columns 0 .. j; h_out (j + 1 doubles), norm_out (1), y (j + 1): device memory.  16-byte loads where V, w (x) are 16-byte aligned
+ * and ld is even, scalar ones otherwise.
+ *   orthogonalize: `passes` times { c = V^T w; w -= V c }; h_out = the sum of the c, norm_out = ||w|| of the result
+ *   combine:       x += sum_i y[i] Z_i */
+int mfmg_hip_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int64_t ld, int32_t j, const double *V, double *w,
+                                  double *h_out, double *norm_out, int32_t passes);
+int mfmg_hip_krylov_combine(mfmg_hip_context_t ctx, int64_t n, int64_t ld, int32_t j, const double *Z, const double *y, double *x);
 int mfmg_hip_hierarchy_n_levels(mfmg_hip_hierarchy_t h, int32_t *n_levels);
 int mfmg_hip_hierarchy_level_size(mfmg_hip_hierarchy_t h, int32_t level, int64_t *n);
 /* Level::get_operator()->apply (level.hpp:30-33) */

@@ -200,6 +200,24 @@ class Context:
     def sadd(self, x: torch.Tensor, s: float, a: float, v: torch.Tensor):
         check(self._lib.mfmg_hip_vector_sadd(self.handle, x.numel(), s, a, _dev_ptr(v, x.numel()), _dev_ptr(x)))
 
+    def krylov_orthogonalize(self, V: torch.Tensor, w: torch.Tensor, n_columns: int, passes: int = 2):
+        """The fused Gram-Schmidt kernels of solve_fgmres on their own: `passes` times { c = V^T w; w -= V c } in place, against
+        the first n_columns columns of V ([columns, ld] contiguous: column-major with leading dimension ld >= len(w)).
+        Returns (h, norm): device tensors with the summed coefficients and ||w|| of the result."""
+        n, ld = w.numel(), V.shape[1]
+        assert 1 <= n_columns <= V.shape[0] and ld >= n
+        h = torch.empty(n_columns, dtype=torch.float64, device=w.device)
+        norm = torch.empty(1, dtype=torch.float64, device=w.device)
+        check(self._lib.mfmg_hip_krylov_orthogonalize(self.handle, n, ld, n_columns - 1, _dev_ptr(V), _dev_ptr(w), _dev_ptr(h),
+                                                      _dev_ptr(norm), passes))
+        return h, norm
+
+    def krylov_combine(self, Z: torch.Tensor, y: torch.Tensor, x: torch.Tensor):
+        """x += sum_i y[i] Z[i] in one pass (Z: [columns, ld] contiguous, ld >= len(x); y on the device)."""
+        n, ld = x.numel(), Z.shape[1]
+        assert 1 <= y.numel() <= Z.shape[0] and ld >= n
+        check(self._lib.mfmg_hip_krylov_combine(self.handle, n, ld, y.numel() - 1, _dev_ptr(Z), _dev_ptr(y), _dev_ptr(x)))
+
     def cell_contraction(self, u: torch.Tensor, c: torch.Tensor, v: torch.Tensor, cell_size, variant: str = "mfma"):
         """v[m, cell] = c[cell] * sum_k K_ref[m, k] u[k, cell] (BASELINE.json configs[4]); u, v: [8, n] contiguous CUDA
         tensors, float32 or float64; variant "valu" or "mfma"."""
@@ -750,6 +768,21 @@ class Hierarchy:
         check(self._lib.mfmg_hip_hierarchy_solve_cg(self.handle, _dev_ptr(b, n), _dev_ptr(x, n), tolerance, max_iterations,
                                                     C.byref(it), C.byref(res), hist.ctypes.data_as(C.POINTER(C.c_double)),
                                                     len(hist)))
+        return it.value, hist[: it.value + 1]
+
+    def solve_fgmres(self, b, x, tolerance: float = 1e-6, max_iterations: int = 1000, restart: int = 30,
+                     preconditioner: str = "double"):
+        """dealii::SolverFGMRES: right-preconditioned flexible GMRES(restart) on the fine operator with this hierarchy as
+        preconditioner -- which may be non-symmetric (solver.amg.pre_smoothing_levels 0) or, with preconditioner="float", the
+        FP32 fine level ("fine level precision" float) under the FP64 iteration.  Returns (iterations, residual history)."""
+        if preconditioner not in ("double", "float"):
+            raise _lib.MfmgInvalidArgument('preconditioner must be "double" or "float"')
+        n = self.level_size(0)
+        it, res = C.c_int32(), C.c_double()
+        hist = np.zeros(max(max_iterations, 0) + 1)
+        check(self._lib.mfmg_hip_hierarchy_solve_fgmres(self.handle, _dev_ptr(b, n), _dev_ptr(x, n), tolerance, max_iterations,
+                                                        restart, 1 if preconditioner == "float" else 0, C.byref(it), C.byref(res),
+                                                        hist.ctypes.data_as(C.POINTER(C.c_double)), len(hist)))
         return it.value, hist[: it.value + 1]
 
     def operator_tile(self):

@@ -8,6 +8,7 @@
 #include "cell_contraction.hpp"
 #include "dof_permutation.hpp"
 #include "halo_transport.hpp"
+#include "krylov_basis.hpp"
 #include "mfmg/hierarchy.hpp"
 
 using namespace mfmg;
@@ -89,6 +90,64 @@ struct mfmg_hip_host_amg_s
   std::vector<AmgLevelHost> levels;
 };
 
+// What mfmg_hip_hierarchy_solve_fgmres keeps between solves: the basis V[ld x (columns + 1)], the preconditioned vectors
+// Z[ld x columns] (krylov_basis.hpp), the float vectors around an FP32 preconditioner, the Hessenberg column / y on the device
+// and their pinned host mirror.  Grown on demand, never shrunk: a solve allocates nothing once its restart length has been seen.
+struct KrylovWorkspace
+{
+  int64_t ld = 0;
+  int columns = 0;
+  DeviceBuffer<double> V, Z, coefficients; // coefficients: [0, columns]: h_0 .. h_j, ||w||; [columns + 1, 2 columns]: y
+  DeviceBuffer<float> v_f32, z_f32;
+  std::unique_ptr<krylov::Scratch> scratch;
+  double *host = nullptr; // pinned, as `coefficients`
+  // An allocation that fails (the basis is 2 m + 1 fine vectors) throws out of here with the workspace EMPTY (ld = columns = 0,
+  // no buffer): the next solve allocates afresh, it never runs on a half-built workspace.
+  void reserve(int64_t n, int m, bool fp32)
+  {
+    const int64_t want_ld = krylov::leading_dimension(n);
+    if (want_ld != ld || m > columns)
+    {
+      MemoryKind kind("Krylov basis");
+      release(); // (before the larger one is allocated)
+      V.resize((size_t)want_ld * (m + 1));
+      Z.resize((size_t)want_ld * m);
+      coefficients.resize((size_t)2 * m + 2);
+      scratch.reset(new krylov::Scratch(m + 1));
+      MFMG_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&host), ((size_t)2 * m + 2) * sizeof(double)));
+      ld = want_ld; // only now: everything above stands
+      columns = m;
+    }
+    if (fp32 && (v_f32.size() != (size_t)ld || z_f32.size() != (size_t)ld))
+    {
+      MemoryKind kind("Krylov basis");
+      v_f32.release();
+      z_f32.release();
+      v_f32.resize((size_t)ld);
+      z_f32.resize((size_t)ld);
+    }
+  }
+  void release()
+  {
+    ld = 0;
+    columns = 0;
+    release_host();
+    V.release();
+    Z.release();
+    coefficients.release();
+    v_f32.release();
+    z_f32.release();
+    scratch.reset();
+  }
+  void release_host()
+  {
+    if (host)
+      (void)hipHostFree(host);
+    host = nullptr;
+  }
+  ~KrylovWorkspace() { release_host(); }
+};
+
 struct mfmg_hip_hierarchy_s
 {
   HipHandle *handle = nullptr;
@@ -106,6 +165,7 @@ struct mfmg_hip_hierarchy_s
   std::unique_ptr<DofPermutation> perm;
   DeviceBuffer<double> work[2];
   DeviceBuffer<float> work_f32[2];
+  KrylovWorkspace krylov;
   double *workspace(int i)
   {
     if (work[i].size() == 0)
@@ -1419,6 +1479,199 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
       h->perm->scatter(static_cast<double const *>(x_run), x);
     if (!converged)
       throw std::runtime_error("CG did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
+  });
+}
+
+// Right-preconditioned flexible GMRES(restart) as dealii::SolverFGMRES runs it (third-party, restated): r = b - A x, v_0 = r / ||r||;
+// step j: z_j = M^-1 v_j, w = A z_j, w orthogonalised against v_0 .. v_j (classical Gram-Schmidt twice, krylov_basis.hpp),
+// v_{j+1} = w / ||w||; the Hessenberg column goes through the Givens rotations on the host, |g_{j+1}| is the residual norm of the
+// least-squares problem and is what SolverControl sees; x += Z y when it is small enough or the basis is full.
+int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance, int32_t max_iterations,
+                                    int32_t restart, int32_t preconditioner_fp32, int32_t *n_iterations, double *final_residual,
+                                    double *residual_history, int32_t history_len)
+{
+  return guarded([&] {
+    require(h && b && x, "null argument");
+    require(tolerance >= 0. && max_iterations >= 0, "bad stopping criterion");
+    require(restart >= 1, "the restart length must be at least 1");
+    require(preconditioner_fp32 == 0 || preconditioner_fp32 == 1, "preconditioner_fp32 must be 0 or 1");
+    HipHandle &handle = *h->handle;
+    require(!handle.comm.enabled(), "mfmg_hip_hierarchy_solve_fgmres is not available in a distributed run");
+    const bool fp32 = preconditioner_fp32 != 0;
+    require(!fp32 || h->fine_f32 != nullptr, "preconditioner_fp32 needs a hierarchy built with \"fine level precision\" float");
+    const int64_t n = level_size(h, 0);
+    const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
+    KrylovWorkspace &ws = h->krylov;
+    try
+    {
+      ws.reserve(n, m, fp32);
+    }
+    catch (...)
+    {
+      ws.release();
+      (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
+      throw;
+    }
+    const int64_t ld = ws.ld;
+    krylov::Scratch &scratch = *ws.scratch;
+    double *const V = ws.V.data(), *const Z = ws.Z.data(), *const hcol = ws.coefficients.data(), *const y_dev = hcol + ws.columns + 1;
+    double *const y_host = ws.host + ws.columns + 1;
+    float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
+    auto op = h->hierarchy->levels()[0].get_operator();
+    // "internal numbering" lexicographic: as in mfmg_hip_hierarchy_solve_cg -- b and x are gathered once, the basis, the operator
+    // and the preconditioner live in the internal numbering, x is scattered once: two launches of the permutation per solve
+    double const *b_run = b;
+    double *x_run = x;
+    if (h->perm)
+    {
+      h->perm->gather2(b, static_cast<double const *>(x), h->workspace(0), h->workspace(1));
+      b_run = h->workspace(0);
+      x_run = h->workspace(1);
+    }
+    DVector bv(handle, n, const_cast<double *>(b_run)), xv(handle, n, x_run);
+    auto fetch = [&](int count) { // the first `count` device coefficients: the one round trip of an iteration
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, hcol, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+    };
+    // v_0 = r / ||r|| with r = b - A x (and its float copy); returns ||r||
+    auto start_cycle = [&] {
+      DVector r(handle, n, V);
+      op->apply(xv, r);
+      r.sadd(-1., 1., bv);
+      krylov::basis_norm_partials(handle, scratch, n, V);
+      krylov::basis_scale_store(handle, scratch, n, V, V, v_f32, hcol);
+      fetch(1);
+      return ws.host[0];
+    };
+    auto precondition = [&](int j) { // z_j = M^-1 v_j, from a zero start whatever "is preconditioner" says
+      const bool zero_first = !h->hierarchy->is_preconditioner();
+      if (fp32)
+      {
+        if (zero_first)
+          MFMG_HIP_CHECK(hipMemsetAsync(ws.z_f32.data(), 0, sizeof(float) * n, handle.stream));
+        h->fine_f32->apply(v_f32, ws.z_f32.data());
+        vec::widen(handle, n, ws.z_f32.data(), Z + j * ld);
+        return;
+      }
+      DVector vj(handle, n, V + j * ld), zj(handle, n, Z + j * ld);
+      if (zero_first)
+        zj = 0.;
+      h->hierarchy->vmult(zj, vj);
+    };
+    auto record = [&](int k, double v) {
+      if (residual_history && k < history_len)
+        residual_history[k] = v;
+    };
+    double res = start_cycle();
+    int it = 0;
+    record(0, res);
+    bool converged = res <= tolerance;
+    // the triangular factor of the Hessenberg matrix, column-major with m + 1 rows, the rotations and the rotated right-hand side
+    std::vector<double> R((size_t)(m + 1) * m), cs(m), sn(m), g(m + 1);
+    while (!converged && it < max_iterations)
+    {
+      std::fill(g.begin(), g.end(), 0.);
+      g[0] = res;
+      int k = 0; // columns of this cycle
+      bool breakdown = false;
+      while (k < m && it < max_iterations && !converged && !breakdown)
+      {
+        const int j = k;
+        precondition(j);
+        double *const w = V + (int64_t)(j + 1) * ld;
+        {
+          DVector zj(handle, n, Z + j * ld), wv(handle, n, w);
+          op->apply(zj, wv);
+        }
+        for (int pass = 0; pass < 2; ++pass)
+        {
+          krylov::basis_dots(handle, scratch, n, ld, j + 1, V, w, scratch.pass_coefficients.data(), hcol, pass == 1);
+          krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass == 1);
+        }
+        krylov::basis_scale_store(handle, scratch, n, w, w, v_f32, hcol + j + 1);
+        fetch(j + 2);
+        double *const c = &R[(size_t)j * (m + 1)];
+        std::copy(ws.host, ws.host + j + 2, c);
+        for (int i = 0; i < j; ++i)
+        {
+          const double t = cs[i] * c[i] + sn[i] * c[i + 1];
+          c[i + 1] = -sn[i] * c[i] + cs[i] * c[i + 1];
+          c[i] = t;
+        }
+        // h_{j+1,j} = 0: the Krylov space is exhausted -- v_{j+1} is zero (basis_scale_store), the cycle ends with the update
+        breakdown = c[j + 1] == 0.;
+        const double d = std::hypot(c[j], c[j + 1]);
+        cs[j] = d > 0. ? c[j] / d : 1.;
+        sn[j] = d > 0. ? c[j + 1] / d : 0.;
+        c[j] = d;
+        c[j + 1] = 0.;
+        g[j + 1] = -sn[j] * g[j];
+        g[j] = cs[j] * g[j];
+        res = std::abs(g[j + 1]);
+        ++k;
+        ++it;
+        // a breakdown is not taken at its word (a singular Hessenberg matrix also gives |g_{j+1}| = 0): the cycle ends, and the
+        // residual recomputed below is what is recorded and tested
+        if (!breakdown)
+          record(it, res);
+        converged = !breakdown && res <= tolerance;
+      }
+      // x += Z y with R y = g (a zero pivot -- a singular Hessenberg matrix -- contributes nothing: no division by zero)
+      for (int i = k - 1; i >= 0; --i)
+      {
+        double s = g[i];
+        for (int l = i + 1; l < k; ++l)
+          s -= R[(size_t)l * (m + 1) + i] * y_host[l];
+        const double pivot = R[(size_t)i * (m + 1) + i];
+        y_host[i] = pivot != 0. ? s / pivot : 0.;
+      }
+      MFMG_HIP_CHECK(hipMemcpyAsync(y_dev, y_host, sizeof(double) * k, hipMemcpyHostToDevice, handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (y_host is written again by the next cycle / the next solve)
+      krylov::basis_combine(handle, n, ld, k, Z, y_dev, x_run);
+      // after a restart and after a breakdown the residual is the true one, recomputed
+      if (!converged && (it < max_iterations || breakdown))
+      {
+        res = start_cycle();
+        converged = res <= tolerance;
+        if (breakdown)
+          record(it, res);
+      }
+    }
+    if (n_iterations)
+      *n_iterations = it;
+    if (final_residual)
+      *final_residual = res;
+    if (h->perm)
+      h->perm->scatter(static_cast<double const *>(x_run), x);
+    if (!converged)
+      throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
+  });
+}
+
+int mfmg_hip_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int64_t ld, int32_t j, const double *V, double *w, double *h_out,
+                                  double *norm_out, int32_t passes)
+{
+  return guarded([&] {
+    require(ctx && V && w && h_out && norm_out, "null argument");
+    require(n >= 1 && ld >= n && j >= 0 && passes >= 1, "bad shape");
+    HipHandle &handle = *ctx->handle;
+    krylov::Scratch scratch(j + 1);
+    for (int pass = 0; pass < passes; ++pass)
+    {
+      krylov::basis_dots(handle, scratch, n, ld, j + 1, V, w, scratch.pass_coefficients.data(), h_out, pass > 0);
+      krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass + 1 == passes);
+    }
+    krylov::basis_scale_store(handle, scratch, n, w, nullptr, nullptr, norm_out);
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the scratch goes away)
+  });
+}
+
+int mfmg_hip_krylov_combine(mfmg_hip_context_t ctx, int64_t n, int64_t ld, int32_t j, const double *Z, const double *y, double *x)
+{
+  return guarded([&] {
+    require(ctx && Z && y && x, "null argument");
+    require(n >= 1 && ld >= n && j >= 0, "bad shape");
+    krylov::basis_combine(*ctx->handle, n, ld, j + 1, Z, y, x);
   });
 }
 

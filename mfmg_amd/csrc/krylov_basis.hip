@@ -1,0 +1,390 @@
+// Fused orthogonalisation kernels of the flexible GMRES driver (krylov_basis.hpp).
+//
+// Streaming kernels, wave64, 256 threads: a thread owns W = 2 consecutive entries (one 16-byte access per vector; W = 1 where a
+// pointer or the leading dimension is not 16-byte aligned) and walks the vector with a grid stride.  The columns are taken in
+// groups of kGroup = 8: the loads of a group -- 8 x 16 bytes per thread -- are all issued before the first of them is used, so a
+// wavefront keeps 8 KiB of column data in flight beside w (requests in flight, not bytes, bound the streaming kernels here).
+// Every product enters its sum through one fma: a term of w - sum h_i V_i is rounded once.
+// Reductions: per-thread partial -> __shfl_xor butterfly -> LDS across the 4 waves -> one partial per block and column; a second
+// launch sums the partials of a column in a fixed order.  The grid depends on n alone.
+#include "krylov_basis.hpp"
+
+namespace mfmg
+{
+namespace krylov
+{
+namespace
+{
+constexpr int kWaves = block_size / 64;
+
+template <int W>
+__device__ __forceinline__ void load(double const *p, double (&r)[W])
+{
+  if constexpr (W == 2)
+  {
+    const double2 t = *reinterpret_cast<double2 const *>(p);
+    r[0] = t.x;
+    r[1] = t.y;
+  }
+  else
+    r[0] = *p;
+}
+
+template <int W>
+__device__ __forceinline__ void store(double *p, double const (&r)[W])
+{
+  if constexpr (W == 2)
+    *reinterpret_cast<double2 *>(p) = make_double2(r[0], r[1]);
+  else
+    *p = r[0];
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    v += __shfl_xor(v, off);
+  return v;
+}
+
+// the entries past the last whole group of W (n odd, W = 2) belong to the first thread of the grid
+__device__ __forceinline__ bool owns_tail() { return blockIdx.x == 0 && threadIdx.x == 0; }
+
+// ---- dots ----------------------------------------------------------------------------------------------------------------------
+template <int W, int NC>
+__device__ __forceinline__ void dots_body(int64_t n, int64_t ld, double const *__restrict__ V, double const *__restrict__ w,
+                                          double *__restrict__ partials, double (*wsum)[kWaves])
+{
+  double acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    acc[c] = 0.;
+  const int64_t n_units = n / W, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < n_units; u += stride)
+  {
+    const int64_t e = u * W;
+    double v[NC][W], ww[W];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      load<W>(V + c * ld + e, v[c]);
+    load<W>(w + e, ww);
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+    {
+#pragma unroll
+      for (int k = 0; k < W; ++k)
+        acc[c] = fma(v[c][k], ww[k], acc[c]);
+    }
+  }
+  if (owns_tail())
+    for (int64_t e = n_units * W; e < n; ++e)
+    {
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        acc[c] = fma(V[c * ld + e], w[e], acc[c]);
+    }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+  {
+    const double t = wave_sum(acc[c]);
+    if (lane == 0)
+      wsum[c][wave] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC)
+  {
+    double t = 0.;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k)
+      t += wsum[threadIdx.x][k];
+    partials[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+// blockIdx.y: the group of kGroup columns; partials[column][block]
+template <int W>
+__global__ __launch_bounds__(block_size) void dots_kernel(int64_t n, int64_t ld, int n_columns, double const *__restrict__ V,
+                                                           double const *__restrict__ w, double *__restrict__ partials)
+{
+  __shared__ double wsum[kGroup][kWaves];
+  const int c0 = blockIdx.y * kGroup;
+  const int nc = min(kGroup, n_columns - c0);
+  V += (int64_t)c0 * ld;
+  partials += (int64_t)c0 * gridDim.x;
+  switch (nc) // (the same in every thread of the grid row)
+  {
+  case 1: dots_body<W, 1>(n, ld, V, w, partials, wsum); break;
+  case 2: dots_body<W, 2>(n, ld, V, w, partials, wsum); break;
+  case 3: dots_body<W, 3>(n, ld, V, w, partials, wsum); break;
+  case 4: dots_body<W, 4>(n, ld, V, w, partials, wsum); break;
+  case 5: dots_body<W, 5>(n, ld, V, w, partials, wsum); break;
+  case 6: dots_body<W, 6>(n, ld, V, w, partials, wsum); break;
+  case 7: dots_body<W, 7>(n, ld, V, w, partials, wsum); break;
+  default: dots_body<W, 8>(n, ld, V, w, partials, wsum); break;
+  }
+}
+
+// one block per column: the partials of the column in a fixed order
+__global__ __launch_bounds__(block_size) void dots_finish_kernel(int n_partials, double const *__restrict__ partials,
+                                                                  double *__restrict__ h_pass, double *__restrict__ h_total, int accumulate)
+{
+  __shared__ double wsum[kWaves];
+  double const *p = partials + (int64_t)blockIdx.x * n_partials;
+  double acc = 0.;
+  for (int i = threadIdx.x; i < n_partials; i += blockDim.x)
+    acc += p[i];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0)
+    wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    double t = 0.;
+    for (int k = 0; k < kWaves; ++k)
+      t += wsum[k];
+    h_pass[blockIdx.x] = t;
+    h_total[blockIdx.x] = accumulate ? h_total[blockIdx.x] + t : t;
+  }
+}
+
+// ---- update / combine: out = out + sign * sum_i c[i] V_i -------------------------------------------------------------------------
+template <int W, int NC>
+__device__ __forceinline__ void axpy_group(double (&acc)[W], double const *__restrict__ V, int64_t ld, double const *__restrict__ c,
+                                           double sign)
+{
+  double v[NC][W];
+#pragma unroll
+  for (int i = 0; i < NC; ++i)
+    load<W>(V + i * ld, v[i]);
+#pragma unroll
+  for (int i = 0; i < NC; ++i)
+  {
+    const double a = sign * c[i];
+#pragma unroll
+    for (int k = 0; k < W; ++k)
+      acc[k] = fma(a, v[i][k], acc[k]);
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void axpy_columns(double (&acc)[W], double const *__restrict__ V, int64_t ld, int n_columns,
+                                             double const *__restrict__ c, double sign)
+{
+  int g = 0;
+  for (; g + kGroup <= n_columns; g += kGroup)
+    axpy_group<W, kGroup>(acc, V + (int64_t)g * ld, ld, c + g, sign);
+  V += (int64_t)g * ld;
+  c += g;
+  switch (n_columns - g)
+  {
+  case 1: axpy_group<W, 1>(acc, V, ld, c, sign); break;
+  case 2: axpy_group<W, 2>(acc, V, ld, c, sign); break;
+  case 3: axpy_group<W, 3>(acc, V, ld, c, sign); break;
+  case 4: axpy_group<W, 4>(acc, V, ld, c, sign); break;
+  case 5: axpy_group<W, 5>(acc, V, ld, c, sign); break;
+  case 6: axpy_group<W, 6>(acc, V, ld, c, sign); break;
+  case 7: axpy_group<W, 7>(acc, V, ld, c, sign); break;
+  default: break;
+  }
+}
+
+template <int W, bool kNorm>
+__global__ __launch_bounds__(block_size) void axpy_kernel(int64_t n, int64_t ld, int n_columns, double const *__restrict__ V,
+                                                           double const *__restrict__ c, double sign, double *__restrict__ out,
+                                                           double *__restrict__ norm_partials)
+{
+  __shared__ double wsum[kWaves];
+  double nrm = 0.;
+  const int64_t n_units = n / W, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < n_units; u += stride)
+  {
+    const int64_t e = u * W;
+    double acc[W];
+    load<W>(out + e, acc);
+    axpy_columns<W>(acc, V + e, ld, n_columns, c, sign);
+    store<W>(out + e, acc);
+    if (kNorm)
+    {
+#pragma unroll
+      for (int k = 0; k < W; ++k)
+        nrm = fma(acc[k], acc[k], nrm);
+    }
+  }
+  if (owns_tail())
+    for (int64_t e = n_units * W; e < n; ++e)
+    {
+      double acc[1] = {out[e]};
+      axpy_columns<1>(acc, V + e, ld, n_columns, c, sign);
+      out[e] = acc[0];
+      if (kNorm)
+        nrm = fma(acc[0], acc[0], nrm);
+    }
+  if (kNorm)
+  {
+    nrm = wave_sum(nrm);
+    if ((threadIdx.x & 63) == 0)
+      wsum[threadIdx.x >> 6] = nrm;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+      double t = 0.;
+      for (int k = 0; k < kWaves; ++k)
+        t += wsum[k];
+      norm_partials[blockIdx.x] = t;
+    }
+  }
+}
+
+// ---- scale_store ---------------------------------------------------------------------------------------------------------------
+// Every block sums the norm partials itself, all in the same order: the same norm in every block, no launch in between.
+template <int W>
+__global__ __launch_bounds__(block_size) void scale_store_kernel(int64_t n, int n_partials, double const *__restrict__ partials,
+                                                                  double const *w, double *v_next, float *__restrict__ v_next_f32,
+                                                                  double *__restrict__ norm_out)
+{
+  __shared__ double wsum[kWaves];
+  double acc = 0.;
+  for (int i = threadIdx.x; i < n_partials; i += blockDim.x)
+    acc += partials[i];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0)
+    wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  double total = 0.;
+#pragma unroll
+  for (int k = 0; k < kWaves; ++k)
+    total += wsum[k];
+  const double norm = sqrt(total);
+  if (owns_tail())
+    norm_out[0] = norm;
+  if (v_next == nullptr)
+    return;
+  const double inv = norm > 0. ? 1. / norm : 0.;
+  const int64_t n_units = n / W, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < n_units; u += stride)
+  {
+    const int64_t e = u * W;
+    double r[W];
+    load<W>(w + e, r);
+#pragma unroll
+    for (int k = 0; k < W; ++k)
+      r[k] *= inv;
+    store<W>(v_next + e, r);
+    if (v_next_f32 != nullptr)
+    {
+      if constexpr (W == 2)
+        *reinterpret_cast<float2 *>(v_next_f32 + e) = make_float2((float)r[0], (float)r[1]);
+      else
+        v_next_f32[e] = (float)r[0];
+    }
+  }
+  if (owns_tail())
+    for (int64_t e = n_units * W; e < n; ++e)
+    {
+      const double r = w[e] * inv;
+      v_next[e] = r;
+      if (v_next_f32 != nullptr)
+        v_next_f32[e] = (float)r;
+    }
+}
+
+bool aligned16(void const *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+void check_columns(int64_t n, int64_t ld, int n_columns)
+{
+  ASSERT_THROW(n >= 1 && n_columns >= 0, "krylov basis: empty vector or negative column count");
+  ASSERT_THROW(n_columns == 0 || ld >= n, "krylov basis: the leading dimension is smaller than the vectors");
+}
+} // namespace
+
+unsigned int reduction_blocks(int64_t n) { return n_blocks_for((n + 1) / 2, block_size, kMaxBlocks); }
+
+void basis_dots(HipHandle &h, Scratch &s, int64_t n, int64_t ld, int n_columns, double const *V, double const *w, double *h_pass,
+                double *h_total, bool accumulate)
+{
+  check_columns(n, ld, n_columns);
+  if (n_columns == 0)
+    return;
+  ASSERT_THROW(n_columns <= s.capacity, "krylov basis: more columns than the scratch was built for");
+  const unsigned int nb = reduction_blocks(n);
+  const dim3 grid(nb, (unsigned)((n_columns + kGroup - 1) / kGroup));
+  const int n_groups = (int)grid.y;
+  hipEvent_t stop = h.profiler.begin("basis_dots", 8. * double(n) * (n_columns + n_groups), h.stream);
+  if (aligned16(V) && aligned16(w) && ld % 2 == 0)
+    hipLaunchKernelGGL(dots_kernel<2>, grid, dim3(block_size), 0, h.stream, n, ld, n_columns, V, w, s.dot_partials.data());
+  else
+    hipLaunchKernelGGL(dots_kernel<1>, grid, dim3(block_size), 0, h.stream, n, ld, n_columns, V, w, s.dot_partials.data());
+  hipLaunchKernelGGL(dots_finish_kernel, dim3(n_columns), dim3(block_size), 0, h.stream, (int)nb, s.dot_partials.data(), h_pass, h_total,
+                     accumulate ? 1 : 0);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+namespace
+{
+template <bool kNorm>
+void launch_axpy(HipHandle &h, int64_t n, int64_t ld, int n_columns, double const *V, double const *c, double sign, double *out,
+                 double *norm_partials)
+{
+  const dim3 grid(reduction_blocks(n));
+  if (aligned16(V) && aligned16(out) && ld % 2 == 0)
+    hipLaunchKernelGGL((axpy_kernel<2, kNorm>), grid, dim3(block_size), 0, h.stream, n, ld, n_columns, V, c, sign, out, norm_partials);
+  else
+    hipLaunchKernelGGL((axpy_kernel<1, kNorm>), grid, dim3(block_size), 0, h.stream, n, ld, n_columns, V, c, sign, out, norm_partials);
+}
+} // namespace
+
+void basis_update(HipHandle &h, Scratch &s, int64_t n, int64_t ld, int n_columns, double const *V, double const *c, double *w,
+                  bool with_norm)
+{
+  check_columns(n, ld, n_columns);
+  hipEvent_t stop = h.profiler.begin("basis_update", 8. * double(n) * (n_columns + 2), h.stream);
+  if (with_norm)
+    launch_axpy<true>(h, n, ld, n_columns, V, c, -1., w, s.norm_partials.data());
+  else
+    launch_axpy<false>(h, n, ld, n_columns, V, c, -1., w, nullptr);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void basis_norm_partials(HipHandle &h, Scratch &s, int64_t n, double const *w)
+{
+  // (w, w) of the dots kernel with w as its only column: the partials of column 0 are the norm's
+  check_columns(n, n, 1);
+  const dim3 grid(reduction_blocks(n));
+  if (aligned16(w))
+    hipLaunchKernelGGL(dots_kernel<2>, grid, dim3(block_size), 0, h.stream, n, n, 1, w, w, s.norm_partials.data());
+  else
+    hipLaunchKernelGGL(dots_kernel<1>, grid, dim3(block_size), 0, h.stream, n, n, 1, w, w, s.norm_partials.data());
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void basis_scale_store(HipHandle &h, Scratch &s, int64_t n, double const *w, double *v_next, float *v_next_f32, double *norm_out)
+{
+  check_columns(n, n, 0);
+  const int nb = (int)reduction_blocks(n);
+  const dim3 grid(v_next == nullptr ? 1u : (unsigned)nb);
+  hipEvent_t stop = h.profiler.begin("basis_scale_store", v_next == nullptr ? 0. : double(n) * (16. + (v_next_f32 ? 4. : 0.)), h.stream);
+  if (aligned16(w) && aligned16(v_next) && (reinterpret_cast<uintptr_t>(v_next_f32) & 7u) == 0)
+    hipLaunchKernelGGL(scale_store_kernel<2>, grid, dim3(block_size), 0, h.stream, n, nb, s.norm_partials.data(), w, v_next, v_next_f32,
+                       norm_out);
+  else
+    hipLaunchKernelGGL(scale_store_kernel<1>, grid, dim3(block_size), 0, h.stream, n, nb, s.norm_partials.data(), w, v_next, v_next_f32,
+                       norm_out);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void basis_combine(HipHandle &h, int64_t n, int64_t ld, int n_columns, double const *Z, double const *y, double *x)
+{
+  check_columns(n, ld, n_columns);
+  if (n_columns == 0)
+    return;
+  hipEvent_t stop = h.profiler.begin("basis_combine", 8. * double(n) * (n_columns + 2), h.stream);
+  launch_axpy<false>(h, n, ld, n_columns, Z, y, 1., x, nullptr);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+} // namespace krylov
+} // namespace mfmg

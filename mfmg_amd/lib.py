@@ -209,6 +209,9 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_apply_f32": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_vmult": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_solve_cg": (C.c_int, [vp, vp, vp, C.c_double, C.c_int32, P(C.c_int32), P(C.c_double), P(C.c_double), C.c_int32]),
+        "mfmg_hip_hierarchy_solve_fgmres": (C.c_int, [vp, vp, vp, dbl, i32, i32, i32, P(i32), P(dbl), P(dbl), i32]),
+        "mfmg_hip_krylov_orthogonalize": (C.c_int, [vp, i64, i64, i32, vp, vp, vp, vp, i32]),
+        "mfmg_hip_krylov_combine": (C.c_int, [vp, i64, i64, i32, vp, vp, vp]),
         "mfmg_hip_hierarchy_n_levels": (C.c_int, [vp, P(i32)]),
         "mfmg_hip_hierarchy_level_size": (C.c_int, [vp, i32, P(i64)]),
         "mfmg_hip_hierarchy_operator_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
