@@ -370,7 +370,9 @@ int mfmg_hip_mf_laplace_smoother_sweep(mfmg_hip_mf_laplace_t op, int n_terms, co
  * neighbouring cells: ~30 % fewer FP64 operations, the same operator with its own rounding (1e-15 per cell).  on != 0: the
  * arithmetic of the one-term kernel, bit for bit (tests compare the two kernels that way). */
 int mfmg_hip_mf_laplace_set_sweep_reference(mfmg_hip_mf_laplace_t op, int on);
-/* tile of the sweep: n_waves wavefronts of tile_y cell rows (2, 3 or 4), tile_z owned layers; 0, 0, 0 = chosen from the mesh */
+/* tile of the sweep: n_waves (1 .. 8) wavefronts of tile_y cell rows (2, 3 or 4), tile_z owned layers; 0, 0, 0 = chosen from the mesh.
+ * 12 wavefronts of 2 rows: the shape of the three-term FP64 sweep with D^-1 derived in the kernel (its default; 8, 3 is the shape
+ * of before); a sweep that has no such kernel keeps its default tile when asked for it */
 int mfmg_hip_mf_laplace_set_sweep_tile(mfmg_hip_mf_laplace_t op, int n_waves, int tile_y, int tile_z);
 int mfmg_hip_mf_laplace_get_sweep_tile(mfmg_hip_mf_laplace_t op, int n_terms, int *n_waves, int *tile_y, int *tile_z);
 /* FP32 instance of the same operator (BASELINE.json configs[4]; the coefficient table is converted once,

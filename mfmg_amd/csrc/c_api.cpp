@@ -1082,7 +1082,8 @@ int mfmg_hip_mf_laplace_set_sweep_tile(mfmg_hip_mf_laplace_t op, int n_waves, in
 {
   return guarded([&] {
     require(op != nullptr, "null operator");
-    require(n_waves >= 0 && n_waves <= 8 && tile_y >= 0 && tile_y <= 4 && tile_z >= 0 && tile_z <= 4096, "sweep tile out of range");
+    require(((n_waves >= 0 && n_waves <= 8) || (n_waves == 12 && tile_y == 2)) && tile_y >= 0 && tile_y <= 4 && tile_z >= 0 && tile_z <= 4096,
+            "sweep tile out of range");
     op->op->set_fused_tile(n_waves, tile_y, tile_z);
   });
 }
@@ -2064,7 +2065,7 @@ int mfmg_hip_hierarchy_set_sweep_tile(mfmg_hip_hierarchy_t h, int n_waves, int t
 {
   return guarded([&] {
     require(h != nullptr, "null argument");
-    require(n_waves >= 0 && n_waves <= 8 && tile_y >= 0 && tile_y <= 4 && tile_z >= 0, "bad tile");
+    require(((n_waves >= 0 && n_waves <= 8) || (n_waves == 12 && tile_y == 2)) && tile_y >= 0 && tile_y <= 4 && tile_z >= 0, "bad tile");
     auto op = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(h->hierarchy->levels()[0].get_operator());
     require(op != nullptr, "the fine-level operator is not matrix-free");
     op->get_mesh_evaluator()->get_device_operator()->set_fused_tile(n_waves, tile_y, tile_z);

@@ -131,10 +131,14 @@ __device__ __forceinline__ void cell_row_modes(T Pl0, T Pl1, T Ql0, T Ql1, T Pu0
 }
 
 // ring s holds x_s: three slots where a later stage still reads the own value of the layer two below (the momentum term of
-// stage s + 2), two for the last one
-__host__ __device__ constexpr int ring_depth(int s, int K) { return s <= K - 2 ? 3 : 2; }
-__host__ __device__ constexpr int ring_planes(int K) { return K == 1 ? 2 : (K == 2 ? 5 : 8); }
-__host__ __device__ constexpr int ring_base(int s, int K) { return s == 0 ? 0 : (s == 1 ? ring_depth(0, K) : ring_depth(0, K) + ring_depth(1, K)); }
+// stage s + 2), two for the last one.  carry: the shape keeps that value in registers instead (twelve wavefronts of two rows:
+// three slots per ring would take 192 KiB), and every ring is two slots deep.
+__host__ __device__ constexpr int ring_depth(int s, int K, bool carry = false) { return (!carry && s <= K - 2) ? 3 : 2; }
+__host__ __device__ constexpr int ring_planes(int K, bool carry = false) { return carry ? 2 * K : (K == 1 ? 2 : (K == 2 ? 5 : 8)); }
+__host__ __device__ constexpr int ring_base(int s, int K, bool carry = false)
+{
+  return carry ? 2 * s : (s == 0 ? 0 : (s == 1 ? ring_depth(0, K) : ring_depth(0, K) + ring_depth(1, K)));
+}
 
 // Global memory through buffer descriptors: a request is "descriptor (4 SGPRs, built once per array from the kernel
 // arguments) + uniform 32-bit byte offset (an SGPR: row and layer) + per-lane 32-bit byte offset (one VGPR, loop invariant)".
@@ -175,21 +179,27 @@ struct BufIO<float>
 // everywhere.
 // ZERO0: x_0 = 0 (the pre-smoother of a preconditioner application, hierarchy.hpp:253-259): stage 1 is x_1 = beta_1 D^-1 b -- no
 // operator application, nothing read of x_0, no exchange between the wavefronts; the same bits as the sweep run on a zeroed vector.
-template <typename T, int K, int TY, bool DREC, bool MODES, int DBG = 0, bool NARROW = false, bool ZERO0 = false>
+// NWC: the number of wavefronts where the kernel fixes it (0: that of the launch).  Such a kernel also CARRIES the momentum
+// operand: x_{S-2} of a DoF is the x_{S-1} that stage S - 1 read of it one super-pass earlier, kept in registers from there
+// (xn at the stage that reads it, xq one super-pass later: a renaming like that of bq and dq) instead of in a third slot of
+// its ring.  The x_0 layer requested two ahead then lands over the slot of layer c1, which stage 1 has read by the end of the
+// super-pass.
+template <typename T, int K, int TY, bool DREC, bool MODES, int DBG = 0, bool NARROW = false, bool ZERO0 = false, int NWC = 0>
 __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsigned int w)
 {
 #pragma clang fp contract(off)
   constexpr int R = TY + 1; // node rows of a wavefront
+  constexpr bool CARRY = NWC > 0;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int NW = blockDim.x >> 6;
+  const int NW = NWC > 0 ? NWC : blockDim.x >> 6;
   // LDS: per wavefront the rings x_0 .. x_{K-1} ([planes][R rows][64 lanes]); then the exports [2][NW][4][64]
-  T *ring = reinterpret_cast<T *>(smem_raw) + (size_t)wv * (ring_planes(K) * R * 64) + lane;
+  T *ring = reinterpret_cast<T *>(smem_raw) + (size_t)wv * (ring_planes(K, CARRY) * R * 64) + lane;
   // the same planes as the NEXT lane sees them (the last lane: its own, what a DPP shift with the source as old value returns): the
   // x_{s-1} values of the neighbour column are read from the ring, not shifted through the vector ALU, which bounds the sweep
   T const *ring_next = ring + (lane == 63 ? 0 : 1);
-  T *xport = reinterpret_cast<T *>(smem_raw) + (size_t)NW * (ring_planes(K) * R * 64) + lane;
+  T *xport = reinterpret_cast<T *>(smem_raw) + (size_t)NW * (ring_planes(K, CARRY) * R * 64) + lane;
 
   // (tile w of the list: the kernel has dealt the list to the XCDs in contiguous runs)
   const int wcols = a.ntiles_y2 > 0 ? (int)a.ncols - 1 : (int)a.ncols; // chunk columns with tiles of their own width
@@ -319,8 +329,8 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
   };
   // ring slot sl of ring s, node row r: the slot of node layer n is (n - cb) mod the depth of the ring; the march hands a stage
   // pass its slots as constants of the position in its trip (march below)
-  auto ring_at = [&](int s, int sl, int r) -> T * { return ring + ((ring_base(s, K) + sl) * R + r) * 64; };
-  auto ring_next_at = [&](int s, int sl, int r) -> T const * { return ring_next + ((ring_base(s, K) + sl) * R + r) * 64; };
+  auto ring_at = [&](int s, int sl, int r) -> T * { return ring + ((ring_base(s, K, CARRY) + sl) * R + r) * 64; };
+  auto ring_next_at = [&](int s, int sl, int r) -> T const * { return ring_next + ((ring_base(s, K, CARRY) + sl) * R + r) * 64; };
 
   // ---- per-lane state carried from super-pass to super-pass (stage s + 1 uses entry s)
   T bq[K][R];  // b of the DoF (row r, layer of the stage)
@@ -328,13 +338,15 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
   T cq[K][TY]; // coefficient of the cell (row q, cell layer of the stage)
   T pt[K][R];  // z-carry of the partial sums
   T pcs[R];    // z-carry of the coefficient sums (D^-1 on the fly)
+  T xn[K][R];  // CARRY: x_s of the DoF as stage s + 1 reads it in this super-pass (entry s)
+  T xq[K][R];  // CARRY: the same of the super-pass before: the momentum operand of stage s + 2
   T clo = T(0), chi = T(0); // coefficients of the cell rows below / above the wavefront's own, stage-1 layer (D^-1 of the shared rows)
 #pragma unroll
   for (int s = 0; s < K; ++s)
   {
 #pragma unroll
     for (int r = 0; r < R; ++r)
-      bq[s][r] = dq[s][r] = pt[s][r] = T(0);
+      bq[s][r] = dq[s][r] = pt[s][r] = xn[s][r] = xq[s][r] = T(0);
 #pragma unroll
     for (int q = 0; q < TY; ++q)
       cq[s][q] = T(0);
@@ -396,6 +408,8 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       }
       const T l = *ring_at(S - 1, sl(S - 1, 0), r), u = *ring_at(S - 1, sl(S - 1, 1), r);
       xown[r] = l;
+      if constexpr (CARRY && S < K)
+        xn[S - 1][r] = l;
       if constexpr (S == 1)
       {
         // x_0 sits in the ring as it was read; Dirichlet and out-of-mesh values enter the cells as zero
@@ -570,7 +584,11 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       {
         // x_{S-1} and x_{S-2} of the DoF (zero where it is not free: the result is dropped there)
         const T xo = xown[r];
-        const T xoo = (S == 2 && ZERO0) ? T(0) : *ring_at(S - 2, sl(S - 2, 0), r);
+        T xoo = T(0);
+        if constexpr (CARRY)
+          xoo = xq[S - 2][r]; // (zero from a zero guess)
+        else if constexpr (!(S == 2 && ZERO0))
+          xoo = *ring_at(S - 2, sl(S - 2, 0), r);
         const T xoo_m = (S == 2) ? ((lane_free && ((rows_free >> r) & 1u) && lo_free) ? xoo : T(0)) : xoo; // (x_0 sits in its ring unmasked)
         const T xs = fmadd<T>(-(k_beta(S - 1) * dq[S - 1][r]), yv - bq[S - 1][r], fmadd<T>(k_alpha(S - 1), xo - xoo_m, xo));
         if constexpr (S < K)
@@ -696,6 +714,12 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     for (int r = 0; r < R; ++r)
     {
       bq[0][r] = pfb[r];
+      if constexpr (CARRY)
+      {
+#pragma unroll
+        for (int s = 0; s + 2 <= K; ++s)
+          xq[s][r] = xn[s][r];
+      }
       if constexpr (DREC)
         dq[0][r] = pfd[r];
       if constexpr (!ZERO0)
@@ -721,7 +745,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
   auto sl_at = [&](auto jt) {
     constexpr int j = decltype(jt)::value;
     return [&](int s, int k) {
-      if (ring_depth(s, K) == 3)
+      if (ring_depth(s, K, CARRY) == 3)
         return K % 3 == 0 ? ((j + k) % 3 + 3) % 3 : (base3 + j + k + 3) % 3;
       return K % 2 == 0 ? ((j + k) & 1) : ((base2 + j + k) & 1);
     };
@@ -775,6 +799,35 @@ __global__ __launch_bounds__(512, 2) void mf_cheb_fused_kernel(MfFusedArgs<T> a)
   mf_cheb_fused_body<T, K, TY, DREC, MODES, DBG, false, ZERO0>(a, w);
 }
 
+// Twelve wavefronts of TY = 2 rows, three per SIMD: the rows of eight of three (the same y-tiling, the same pairing of a narrow
+// last column) at three quarters of the per-row state each.  Three terms, FP64, D^-1 from the coefficient sums; at most 168
+// VGPRs, and the rings two slots deep (mf_cheb_fused_body, NWC) so that 12 x (6 x 3) + 96 planes of 512 B = 156 KiB fit the LDS.
+constexpr int kWgWaves12 = 12, kWgRows12 = 2;
+constexpr bool kWg12ByDefault = true; // the tile of a sweep that can take it (choose_fused_tile)
+template <typename T, bool MODES, bool NARROW_TOO, bool ZERO0>
+__global__ __launch_bounds__(64 * kWgWaves12, 3) void mf_cheb_fused_wg12_kernel(MfFusedArgs<T> a)
+{
+  // (the tile order of mf_cheb_fused_kernel)
+  const unsigned int n_tiles = NARROW_TOO ? a.wide_tiles + a.ntiles_y2 * a.ntiles_z : a.wide_tiles;
+  unsigned int w = blockIdx.x;
+  if (n_tiles >= 64)
+  {
+    const unsigned int per_xcd = (n_tiles + 7) / 8;
+    w = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    if (w >= n_tiles)
+      return;
+  }
+  if constexpr (NARROW_TOO)
+  {
+    if (w >= a.wide_tiles)
+    {
+      mf_cheb_fused_body<T, 3, kWgRows12, false, MODES, 0, true, ZERO0, kWgWaves12>(a, w);
+      return;
+    }
+  }
+  mf_cheb_fused_body<T, 3, kWgRows12, false, MODES, 0, false, ZERO0, kWgWaves12>(a, w);
+}
+
 // The tiles of a narrow last chunk column alone, launched behind the wide-only kernel on the same stream (MFMG_MF_FUSED_NARROW=split;
 // each kernel gets the register budget of its own body).  The default carries both bodies in one launch: at 257^3 all tiles of
 // the sweep fit one round of the chip, and a second launch queues its tiles behind the first.
@@ -819,20 +872,33 @@ bool MatrixFreeLaplaceDevice<T>::fused_zero_guess_available(int n_terms) const
     return false;
   int nw, ty, tz;
   choose_fused_tile(n_terms, nw, ty, tz);
-  return ty == 3;
+  return ty == 3 || nw == kWgWaves12;
 }
 
 // tile of the sweep: NW wavefronts of TY cell rows, TZ owned layers.  One workgroup of eight wavefronts per CU (two per
 // SIMD: the per-lane state takes ~200 VGPRs) or two of four; the height is chosen so that the workgroups fill whole
-// rounds of the chip -- a workgroup lives for K TZ + K^2 stage passes, a part-filled round costs a full one.
+// rounds of the chip -- a workgroup lives for K TZ + K^2 stage passes, a part-filled round costs a full one.  Three terms in
+// FP64 with D^-1 from the coefficient sums also have twelve wavefronts of two rows (three per SIMD, mf_cheb_fused_wg12_kernel):
+// asked of a sweep that has no such kernel (two terms, FP32, D^-1 in the records), that shape leaves the sweep on its default.
+template <typename T>
+bool MatrixFreeLaplaceDevice<T>::fused_wg12_capable(int n_terms) const
+{
+  return std::is_same<T, double>::value && n_terms == 3 && !_dinv_in_record;
+}
+
 template <typename T>
 void MatrixFreeLaplaceDevice<T>::choose_fused_tile(int n_terms, int &nw, int &ty, int &tz) const
 {
   // (measured at 257^3 DoFs: three terms 8 x 3 rows -- four rows per wavefront spill --, two terms 4 x 4: two independent
-  // workgroups per CU, 0.31 against 0.34 ms)
+  // workgroups per CU, 0.31 against 0.34 ms; three terms in FP64 12 x 2 rows against 8 x 3: 0.345 against 0.364 ms)
   nw = n_terms == 2 ? 4 : 8;
   ty = n_terms == 2 ? 4 : 3;
   tz = 0;
+  if (kWg12ByDefault && fused_wg12_capable(n_terms))
+  {
+    nw = kWgWaves12;
+    ty = kWgRows12;
+  }
   static const std::string env = std::getenv("MFMG_MF_FUSED_TILE") ? std::getenv("MFMG_MF_FUSED_TILE") : "";
   if (_fused_tile[0] > 0)
   {
@@ -850,14 +916,20 @@ void MatrixFreeLaplaceDevice<T>::choose_fused_tile(int n_terms, int &nw, int &ty
       tz = v[2];
     }
   }
-  ASSERT_THROW(nw >= 1 && nw <= 8 && (ty == 2 || ty == 3 || ty == 4), "tile of the multi-term sweep: 1..8 wavefronts of 2, 3 or 4 rows");
+  if (nw == kWgWaves12 && ty == kWgRows12 && !fused_wg12_capable(n_terms))
+  {
+    nw = n_terms == 2 ? 4 : 8;
+    ty = n_terms == 2 ? 4 : 3;
+  }
+  ASSERT_THROW(((nw >= 1 && nw <= 8) || (nw == kWgWaves12 && ty == kWgRows12)) && (ty == 2 || ty == 3 || ty == 4),
+               "tile of the multi-term sweep: 1..8 wavefronts of 2, 3 or 4 rows, or 12 of 2");
   const int ry = nw * ty - 2 * n_terms + 1;
   ASSERT_THROW(ry >= 1, "tile of the multi-term sweep too small for its halo rows");
   if (tz > 0)
     return;
-  const int64_t slots = (int64_t)mf_n_cus() * (8 / nw);
+  const int64_t slots = (int64_t)mf_n_cus() * (nw > 8 ? 1 : 8 / nw); // (more than eight wavefronts: one workgroup per CU)
   const int64_t nty = (_N[1] + ry - 1) / ry;
-  const int64_t tiles_xy = (narrow_last_column() && fused_narrow_capable(n_terms, ty)) ? (int64_t)(_ncols - 1) * nty + (nty + 1) / 2 : (int64_t)_ncols * nty;
+  const int64_t tiles_xy = (narrow_last_column() && fused_narrow_capable(n_terms, ty, nw)) ? (int64_t)(_ncols - 1) * nty + (nty + 1) / 2 : (int64_t)_ncols * nty;
   double best = 0.;
   for (int nz = 1; nz <= _N[2]; ++nz)
   {
@@ -926,13 +998,15 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
   a.rec_total_bytes = (unsigned int)_rec.size();
   // a narrow last chunk column (mf_laplace.hip: at most 32 - 2 halo owned columns) is swept two y-tiles per workgroup by the
   // kernels that carry the body for it
-  const bool narrow = narrow_last_column() && fused_narrow_capable(n_terms, ty);
+  // (twelve wavefronts in the reference arithmetic: both bodies in one kernel do not fit its 168 VGPRs, ordinary tiles there)
+  const bool narrow = narrow_last_column() && fused_narrow_capable(n_terms, ty, nw) && !(nw == kWgWaves12 && _fused_reference_arithmetic);
   a.ntiles_y2 = narrow ? (a.ntiles_y + 1) / 2 : 0u;
   a.wide_tiles = (a.ncols - (narrow ? 1u : 0u)) * a.ntiles_y * a.ntiles_z;
   const uint64_t n_tiles = (uint64_t)a.wide_tiles + (uint64_t)a.ntiles_y2 * a.ntiles_z;
   ASSERT_THROW(n_tiles < (1ull << 30), "tile of the multi-term sweep too small for this mesh (grid size limit)");
   const unsigned int n_blocks = mf_xcd_grid(n_tiles);
-  const size_t lds = ((size_t)nw * ring_planes(n_terms) * (ty + 1) + (size_t)2 * nw * 4) * 64 * sizeof(T);
+  const bool wg12 = nw == kWgWaves12; // (choose_fused_tile: three terms of two rows, FP64, D^-1 from the coefficient sums)
+  const size_t lds = ((size_t)nw * ring_planes(n_terms, wg12) * (ty + 1) + (size_t)2 * nw * 4) * 64 * sizeof(T);
   ASSERT_THROW(lds <= kMfMaxLds, "tile of the multi-term sweep too large for the LDS");
   hipStream_t st = _handle.stream;
   // Algorithmic bytes of the launch: what its n_terms smoother terms require as launches of their own (x, out, one id, the
@@ -976,7 +1050,21 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
     with_guess(std::false_type());
   };
   // (timing experiments, FP64: the kernels without barrier / without division)
-  if (dbg > 0 && !zero_guess && n_terms == 3 && ty == 3 && !_dinv_in_record && std::is_same<T, double>::value)
+  if (wg12)
+  {
+    // (one launch also where the narrow tiles are asked to be split off: the shape has no kernels of one body)
+    if constexpr (std::is_same<T, double>::value)
+      with_flag(narrow, [&](auto nt) {
+        constexpr bool NT = decltype(nt)::value;
+        if (!modes)
+          go(mf_cheb_fused_wg12_kernel<T, false, false, false>, n_blocks);
+        else if (zero_guess)
+          go(mf_cheb_fused_wg12_kernel<T, true, NT, true>, n_blocks);
+        else
+          go(mf_cheb_fused_wg12_kernel<T, true, NT, false>, n_blocks);
+      });
+  }
+  else if (dbg > 0 && !zero_guess && n_terms == 3 && ty == 3 && !_dinv_in_record && std::is_same<T, double>::value)
     with_flag(dbg == 1, [&](auto one) { go(mf_cheb_fused_kernel<T, 3, 3, false, true, decltype(one)::value ? 1 : 2>, n_blocks); });
   else
     with_terms(n_terms, [&](auto kt) {
@@ -992,6 +1080,8 @@ template bool MatrixFreeLaplaceDevice<double>::fused_zero_guess_available(int) c
 template bool MatrixFreeLaplaceDevice<float>::fused_zero_guess_available(int) const;
 template bool MatrixFreeLaplaceDevice<double>::fused_sweep_available(int) const;
 template bool MatrixFreeLaplaceDevice<float>::fused_sweep_available(int) const;
+template bool MatrixFreeLaplaceDevice<double>::fused_wg12_capable(int) const;
+template bool MatrixFreeLaplaceDevice<float>::fused_wg12_capable(int) const;
 template void MatrixFreeLaplaceDevice<double>::choose_fused_tile(int, int &, int &, int &) const;
 template void MatrixFreeLaplaceDevice<float>::choose_fused_tile(int, int &, int &, int &) const;
 template void MatrixFreeLaplaceDevice<double>::smoother_sweep(int, double const *, double const *, double const *, double const *, double *,

@@ -162,7 +162,10 @@ public:
   // the last chunk column owns at most 32 - 2 halo DoF columns: the sweep kernels of the default tile shapes (three terms 8 x 3
   // rows, two terms 4 x 4) run it two y-tiles per workgroup, one per half of the wavefront
   bool narrow_last_column() const { return _narrow_last; }
-  static constexpr bool fused_narrow_capable(int n_terms, int ty) { return (n_terms == 3 && ty == 3) || (n_terms == 2 && ty == 4); }
+  static constexpr bool fused_narrow_capable(int n_terms, int ty, int nw = 8)
+  {
+    return (n_terms == 3 && ty == 3 && nw <= 8) || (n_terms == 2 && ty == 4 && nw <= 8) || (n_terms == 3 && ty == 2 && nw == 12);
+  }
   void smoother_sweep(int n_terms, T const *alpha, T const *beta, T const *b, T const *x, T *out, T *out_prev) const;
   // tile of the sweep: nw wavefronts of ty cell rows, tz owned layers (0, 0, 0: chosen from the mesh)
   void set_fused_tile(int nw, int ty, int tz)
@@ -253,6 +256,7 @@ private:
   double _k2[64] = {};
   MfTile choose_tile() const;
   void choose_fused_tile(int n_terms, int &nw, int &ty, int &tz) const;
+  bool fused_wg12_capable(int n_terms) const; // the sweep has the kernel of twelve wavefronts of two rows
   int _fused_tile[3] = {0, 0, 0};
   bool _fused_reference_arithmetic = false;
 
