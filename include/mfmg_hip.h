@@ -392,6 +392,14 @@ int mfmg_hip_mf_laplace_f32_sweep_available(mfmg_hip_mf_laplace_f32_t op, int n_
 int mfmg_hip_mf_laplace_f32_set_sweep_reference(mfmg_hip_mf_laplace_f32_t op, int on);
 int mfmg_hip_mf_laplace_f32_smoother_sweep(mfmg_hip_mf_laplace_f32_t op, int n_terms, const float *alpha, const float *beta,
                                            const float *b, const float *x, float *out, float *out_prev);
+/* The tiles of the FP32 instance, as the entry points of the same names without _f32 below and above (same ranges).  The float sweep
+ * has no kernel of 12 wavefronts of 2 rows: asked for it, it keeps its default tile (8 x 3 rows at three terms, 4 x 4 at two). */
+int mfmg_hip_mf_laplace_f32_set_tile(mfmg_hip_mf_laplace_f32_t op, int tile_y, int tile_z);
+int mfmg_hip_mf_laplace_f32_set_tile_waves(mfmg_hip_mf_laplace_f32_t op, int n_waves);
+int mfmg_hip_mf_laplace_f32_get_tile(mfmg_hip_mf_laplace_f32_t op, int *n_waves, int *tile_y, int *tile_z);
+int mfmg_hip_mf_laplace_f32_set_sweep_tile(mfmg_hip_mf_laplace_f32_t op, int n_waves, int tile_y, int tile_z);
+int mfmg_hip_mf_laplace_f32_get_sweep_tile(mfmg_hip_mf_laplace_f32_t op, int n_terms, int *n_waves, int *tile_y, int *tile_z);
+int mfmg_hip_mf_laplace_f32_diagonal_in_record(mfmg_hip_mf_laplace_f32_t op, int *in_record);
 /* tuning knob: owned DoF rows / planes per workgroup tile (0 = heuristic) */
 int mfmg_hip_mf_laplace_set_tile(mfmg_hip_mf_laplace_t op, int tile_y, int tile_z);
 /* wavefronts per workgroup (1..8) stacked in y that hand their boundary sums on through LDS (0 = heuristic) */
@@ -517,6 +525,10 @@ int mfmg_hip_hierarchy_set_restrictor(mfmg_hip_hierarchy_t h, int64_t n_rows, in
  * one-pass form, 0 when the two-step form is in use. */
 int mfmg_hip_hierarchy_restrict_residual(mfmg_hip_hierarchy_t h, int32_t level, const double *x, const double *b, double *b_coarse);
 int mfmg_hip_hierarchy_residual_restriction_classes(mfmg_hip_hierarchy_t h, int32_t level, int32_t *n_classes);
+/* The one-pass form on float x and b, as the FP32 fine level (mfmg_hip_hierarchy_apply_f32) runs it: x and b are widened as they
+ * are loaded, all arithmetic and b_coarse are FP64.  There is no two-step form behind this entry (that one rounds the residual to
+ * float): MFMG_HIP_ERROR_NOT_IMPLEMENTED where the one-pass form is not built (*_classes == 0) or the context has a communicator. */
+int mfmg_hip_hierarchy_restrict_residual_f32(mfmg_hip_hierarchy_t h, int32_t level, const float *x, const float *b, double *b_coarse);
 /* restrictor / coarse operator download for inspection: query sizes with *_shape first */
 int mfmg_hip_hierarchy_get_restrictor(mfmg_hip_hierarchy_t h, mfmg_hip_csr_t *r_borrowed);
 int mfmg_hip_hierarchy_get_coarse_operator(mfmg_hip_hierarchy_t h, mfmg_hip_csr_t *ac_borrowed);

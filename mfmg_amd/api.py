@@ -526,11 +526,36 @@ class MatrixFreeLaplaceF32:
         k = len(alpha)
         a = (C.c_float * k)(*[float(v) for v in alpha])
         be = (C.c_float * k)(*[float(v) for v in beta])
-        check(self._lib.mfmg_hip_mf_laplace_f32_smoother_sweep(self.handle, k, a, be, self._p(b), self._p(x), self._p(out),
-                                                               self._p(out_prev) if out_prev is not None else None))
+        # (x = None reaches the C entry as a null pointer, which it refuses: the sweep from a zero guess is FP64 only)
+        check(self._lib.mfmg_hip_mf_laplace_f32_smoother_sweep(self.handle, k, a, be, self._p(b), self._p(x) if x is not None else None,
+                                                               self._p(out), self._p(out_prev) if out_prev is not None else None))
 
     def set_sweep_reference(self, on: bool):
         check(self._lib.mfmg_hip_mf_laplace_f32_set_sweep_reference(self.handle, int(bool(on))))
+
+    def set_sweep_tile(self, waves: int, ty: int, tz: int):
+        check(self._lib.mfmg_hip_mf_laplace_f32_set_sweep_tile(self.handle, waves, ty, tz))
+
+    def get_sweep_tile(self, n_terms: int):
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_f32_get_sweep_tile(self.handle, int(n_terms), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def get_tile(self):
+        """(waves, ty, tz) of the next launch."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_f32_get_tile(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def set_tile(self, ty: int, tz: int, waves: int = None):
+        check(self._lib.mfmg_hip_mf_laplace_f32_set_tile(self.handle, ty, tz))
+        if waves is not None:
+            check(self._lib.mfmg_hip_mf_laplace_f32_set_tile_waves(self.handle, waves))
+
+    def diagonal_in_record(self) -> bool:
+        v = C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_f32_diagonal_in_record(self.handle, C.byref(v)))
+        return bool(v.value)
 
     def cell_constant_layout(self) -> bool:
         v = C.c_int()
@@ -712,6 +737,13 @@ class Hierarchy:
         nf, nc = self.level_size(level - 1), self.level_size(level)
         check(self._lib.mfmg_hip_hierarchy_restrict_residual(self.handle, level, _dev_ptr(x, nf), _dev_ptr(b, nf),
                                                              _dev_ptr(b_coarse, nc)))
+
+    def restrict_residual_f32(self, x: torch.Tensor, b: torch.Tensor, b_coarse: torch.Tensor, level: int = 1):
+        """The one-pass form on float32 x and b (b_coarse is float64), as apply_f32 runs it; raises MfmgNotImplementedError where
+        that form is not built or the context has a communicator -- there is no two-step form behind it."""
+        nf, nc = self.level_size(level - 1), self.level_size(level)
+        check(self._lib.mfmg_hip_hierarchy_restrict_residual_f32(self.handle, level, _dev_ptr(x, nf, torch.float32),
+                                                                 _dev_ptr(b, nf, torch.float32), _dev_ptr(b_coarse, nc)))
 
     def residual_restriction_classes(self, level: int = 1) -> int:
         """Agglomerate classes of the one-pass residual restriction; 0 when the two-step form is in use."""

@@ -1157,6 +1157,54 @@ int mfmg_hip_mf_laplace_f32_smoother_sweep(mfmg_hip_mf_laplace_f32_t op, int n_t
   });
 }
 
+// the tiles of the FP32 instance: the entry points of the FP64 one, same ranges
+int mfmg_hip_mf_laplace_f32_get_tile(mfmg_hip_mf_laplace_f32_t op, int *n_waves, int *tile_y, int *tile_z)
+{
+  return guarded([&] {
+    require(op && n_waves && tile_y && tile_z, "null argument");
+    op->op->get_tile(*n_waves, *tile_y, *tile_z);
+  });
+}
+int mfmg_hip_mf_laplace_f32_set_tile_waves(mfmg_hip_mf_laplace_f32_t op, int n_waves)
+{
+  return guarded([&] {
+    require(op != nullptr, "null operator");
+    require(n_waves >= 0 && n_waves <= 8, "0..8 wavefronts per workgroup");
+    op->op->set_tile_waves(n_waves);
+  });
+}
+int mfmg_hip_mf_laplace_f32_set_tile(mfmg_hip_mf_laplace_f32_t op, int tile_y, int tile_z)
+{
+  return guarded([&] {
+    require(op != nullptr, "null argument");
+    require(tile_y >= 0 && tile_z >= 0 && tile_y <= 64 && tile_z <= 1024, "tile size out of range");
+    op->op->set_tile(tile_y, tile_z);
+  });
+}
+int mfmg_hip_mf_laplace_f32_set_sweep_tile(mfmg_hip_mf_laplace_f32_t op, int n_waves, int tile_y, int tile_z)
+{
+  return guarded([&] {
+    require(op != nullptr, "null operator");
+    require(((n_waves >= 0 && n_waves <= 8) || (n_waves == 12 && tile_y == 2)) && tile_y >= 0 && tile_y <= 4 && tile_z >= 0 && tile_z <= 4096,
+            "sweep tile out of range");
+    op->op->set_fused_tile(n_waves, tile_y, tile_z);
+  });
+}
+int mfmg_hip_mf_laplace_f32_get_sweep_tile(mfmg_hip_mf_laplace_f32_t op, int n_terms, int *n_waves, int *tile_y, int *tile_z)
+{
+  return guarded([&] {
+    require(op && n_waves && tile_y && tile_z, "null argument");
+    op->op->get_fused_tile(n_terms, *n_waves, *tile_y, *tile_z);
+  });
+}
+int mfmg_hip_mf_laplace_f32_diagonal_in_record(mfmg_hip_mf_laplace_f32_t op, int *in_record)
+{
+  return guarded([&] {
+    require(op && in_record, "null argument");
+    *in_record = op->op->diagonal_in_record() ? 1 : 0;
+  });
+}
+
 int mfmg_hip_mf_laplace_get_tile(mfmg_hip_mf_laplace_t op, int *n_waves, int *tile_y, int *tile_z)
 {
   return guarded([&] {
@@ -1829,6 +1877,25 @@ int mfmg_hip_hierarchy_restrict_residual(mfmg_hip_hierarchy_t h, int32_t level, 
       a->residual(xv, bv, res);
       r->apply(res, bc);
     }
+  });
+}
+
+int mfmg_hip_hierarchy_restrict_residual_f32(mfmg_hip_hierarchy_t h, int32_t level, const float *x, const float *b, double *b_coarse)
+{
+  return guarded([&] {
+    require(h && x && b && b_coarse, "null argument");
+    require(level >= 1 && level < (int)h->hierarchy->levels().size(), "restrictors live on levels >= 1");
+    auto r = std::dynamic_pointer_cast<HipMatrixOperator const>(h->hierarchy->levels()[level].get_restrictor());
+    auto a = h->hierarchy->levels()[level - 1].get_operator();
+    // (no two-step form here: it rounds the residual to float, so it is not what this entry names)
+    if (!r || !r->has_residual_restriction() || h->handle->comm.enabled())
+      ASSERT_THROW_NOT_IMPLEMENTED("the one-pass residual restriction on float vectors is not available for this level");
+    const bool permute = h->perm && level == 1;
+    if (permute)
+      h->perm->gather2(x, b, h->workspace_f32(0), h->workspace_f32(1));
+    DVector bc(*h->handle, level_size(h, level), b_coarse);
+    if (!r->restrict_residual_f32(*a, permute ? h->workspace_f32(0) : x, permute ? h->workspace_f32(1) : b, bc))
+      ASSERT_THROW_NOT_IMPLEMENTED("the one-pass residual restriction on float vectors is not available for this level");
   });
 }
 

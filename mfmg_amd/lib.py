@@ -194,6 +194,12 @@ def load() -> C.CDLL:
         "mfmg_hip_mf_laplace_set_tile": (C.c_int, [vp, C.c_int, C.c_int]),
         "mfmg_hip_mf_laplace_set_tile_waves": (C.c_int, [vp, C.c_int]),
         "mfmg_hip_mf_laplace_get_tile": (C.c_int, [vp, P(C.c_int), P(C.c_int), P(C.c_int)]),
+        "mfmg_hip_mf_laplace_f32_set_tile": (C.c_int, [vp, C.c_int, C.c_int]),
+        "mfmg_hip_mf_laplace_f32_set_tile_waves": (C.c_int, [vp, C.c_int]),
+        "mfmg_hip_mf_laplace_f32_get_tile": (C.c_int, [vp, P(C.c_int), P(C.c_int), P(C.c_int)]),
+        "mfmg_hip_mf_laplace_f32_set_sweep_tile": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "mfmg_hip_mf_laplace_f32_get_sweep_tile": (C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]),
+        "mfmg_hip_mf_laplace_f32_diagonal_in_record": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_mf_laplace_f32_create": (C.c_int, [vp, P(MeshDesc), P(vp)]),
         "mfmg_hip_mf_laplace_f32_destroy": (C.c_int, [vp]),
         "mfmg_hip_mf_laplace_f32_cell_constant_layout": (C.c_int, [vp, P(C.c_int)]),
@@ -245,6 +251,7 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_coarse_amg_levels": (C.c_int, [vp, P(i32)]),
         "mfmg_hip_hierarchy_coarse_amg_gather_level": (C.c_int, [vp, P(i32)]),
         "mfmg_hip_hierarchy_restrict_residual": (C.c_int, [vp, i32, vp, vp, vp]),
+        "mfmg_hip_hierarchy_restrict_residual_f32": (C.c_int, [vp, i32, vp, vp, vp]),
         "mfmg_hip_hierarchy_residual_restriction_classes": (C.c_int, [vp, i32, P(i32)]),
         "mfmg_hip_hierarchy_coarse_amg_get": (C.c_int, [vp, i32, i32, P(vp)]),
         "mfmg_hip_hierarchy_coarse_amg_smoother": (C.c_int, [vp, i32, P(i32), P(dbl), P(dbl)]),
