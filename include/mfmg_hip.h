@@ -475,8 +475,11 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
  *   MFMG_HIP_ERROR_INVALID_ARGUMENT).  Either preconditioner starts from zero whatever "is preconditioner" says.
  * Orthogonalisation: classical Gram-Schmidt twice with the fused kernels of krylov_basis.hpp; one device-to-host copy per
  * iteration.  The basis (2 restart + 1 vectors, restart capped by max_iterations) is owned by the hierarchy and kept for the next
- * solve.  "internal numbering" lexicographic: two launches of "dof_permutation" per solve.  One process
- * (MFMG_HIP_ERROR_INVALID_ARGUMENT on a context with a communicator). */
+ * solve.  "internal numbering" lexicographic: two launches of "dof_permutation" per solve.
+ * On a context with a communicator b and x are the rank's local vectors (ghost entries are don't-care on entry), the basis is sized
+ * by the local vectors, dots and norms run over the owned entries and are summed over the ranks: three all-reduces per iteration
+ * through the registered transport (the coefficients of the two Gram-Schmidt passes, ||w||^2), and no other host round trip.  All
+ * ranks return the same iteration count and history.  preconditioner_fp32 1 is MFMG_HIP_ERROR_INVALID_ARGUMENT there. */
 int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance,
                                     int32_t max_iterations, int32_t restart, int32_t preconditioner_fp32,
                                     int32_t *n_iterations, double *final_residual,
@@ -489,6 +492,14 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
 int mfmg_hip_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int64_t ld, int32_t j, const double *V, double *w,
                                   double *h_out, double *norm_out, int32_t passes);
 int mfmg_hip_krylov_combine(mfmg_hip_context_t ctx, int64_t n, int64_t ld, int32_t j, const double *Z, const double *y, double *x);
+/* orthogonalize over the OWNED entries of a rank's local vectors alone: V, w hold the lexicographic box of local_nodes[3] nodes
+ * (x fastest) with `comps` entries per node, of which the nodes [own0, own0 + own_n) per axis are owned; ld >= the entries of the
+ * local box.  h_out and norm_out are sums over the owned entries; the ghost entries of V and w never enter a result and those of w
+ * are not written.  The kernels of one rank of a distributed mfmg_hip_hierarchy_solve_fgmres, launched on a context WITHOUT a
+ * communicator (MFMG_HIP_ERROR_INVALID_ARGUMENT otherwise): the sum over the ranks is the identity (tests). */
+int mfmg_hip_krylov_orthogonalize_box(mfmg_hip_context_t ctx, const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n,
+                                      int32_t comps, int64_t ld, int32_t j, const double *V, double *w, double *h_out,
+                                      double *norm_out, int32_t passes);
 int mfmg_hip_hierarchy_n_levels(mfmg_hip_hierarchy_t h, int32_t *n_levels);
 int mfmg_hip_hierarchy_level_size(mfmg_hip_hierarchy_t h, int32_t level, int64_t *n);
 /* Level::get_operator()->apply (level.hpp:30-33) */

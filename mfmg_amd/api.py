@@ -200,14 +200,25 @@ class Context:
     def sadd(self, x: torch.Tensor, s: float, a: float, v: torch.Tensor):
         check(self._lib.mfmg_hip_vector_sadd(self.handle, x.numel(), s, a, _dev_ptr(v, x.numel()), _dev_ptr(x)))
 
-    def krylov_orthogonalize(self, V: torch.Tensor, w: torch.Tensor, n_columns: int, passes: int = 2):
+    def krylov_orthogonalize(self, V: torch.Tensor, w: torch.Tensor, n_columns: int, passes: int = 2, box=None):
         """The fused Gram-Schmidt kernels of solve_fgmres on their own: `passes` times { c = V^T w; w -= V c } in place, against
         the first n_columns columns of V ([columns, ld] contiguous: column-major with leading dimension ld >= len(w)).
-        Returns (h, norm): device tensors with the summed coefficients and ||w|| of the result."""
+        Returns (h, norm): device tensors with the summed coefficients and ||w|| of the result.
+        box = (local_nodes, own0, own_n, comps): the vectors are a rank's local ones -- the lexicographic box of local_nodes
+        (x, y, z) nodes with comps entries each -- and everything runs over the owned nodes [own0, own0 + own_n) alone (the
+        kernels of a distributed solve_fgmres; ghost entries are neither used nor written)."""
         n, ld = w.numel(), V.shape[1]
         assert 1 <= n_columns <= V.shape[0] and ld >= n
         h = torch.empty(n_columns, dtype=torch.float64, device=w.device)
         norm = torch.empty(1, dtype=torch.float64, device=w.device)
+        if box is not None:
+            local_nodes, own0, own_n, comps = box
+            i3 = C.c_int64 * 3
+            assert n == comps * local_nodes[0] * local_nodes[1] * local_nodes[2]
+            check(self._lib.mfmg_hip_krylov_orthogonalize_box(self.handle, i3(*local_nodes), i3(*own0), i3(*own_n), comps, ld,
+                                                              n_columns - 1, _dev_ptr(V), _dev_ptr(w), _dev_ptr(h), _dev_ptr(norm),
+                                                              passes))
+            return h, norm
         check(self._lib.mfmg_hip_krylov_orthogonalize(self.handle, n, ld, n_columns - 1, _dev_ptr(V), _dev_ptr(w), _dev_ptr(h),
                                                       _dev_ptr(norm), passes))
         return h, norm
@@ -806,7 +817,8 @@ class Hierarchy:
                      preconditioner: str = "double"):
         """dealii::SolverFGMRES: right-preconditioned flexible GMRES(restart) on the fine operator with this hierarchy as
         preconditioner -- which may be non-symmetric (solver.amg.pre_smoothing_levels 0) or, with preconditioner="float", the
-        FP32 fine level ("fine level precision" float) under the FP64 iteration.  Returns (iterations, residual history)."""
+        FP32 fine level ("fine level precision" float) under the FP64 iteration.  Returns (iterations, residual history).
+        On a context with a HaloTransport b and x are the rank's local vectors; every rank gets the same count and history."""
         if preconditioner not in ("double", "float"):
             raise _lib.MfmgInvalidArgument('preconditioner must be "double" or "float"')
         n = self.level_size(0)

@@ -1535,6 +1535,13 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
 // step j: z_j = M^-1 v_j, w = A z_j, w orthogonalised against v_0 .. v_j (classical Gram-Schmidt twice, krylov_basis.hpp),
 // v_{j+1} = w / ||w||; the Hessenberg column goes through the Givens rotations on the host, |g_{j+1}| is the residual norm of the
 // least-squares problem and is what SolverControl sees; x += Z y when it is small enough or the basis is full.
+// Several ranks: the vectors are the ranks' local ones, b, x and the basis handed to the operator and the cycle as
+// mfmg_hip_hierarchy_solve_cg hands them (ghost entries are exchanged by whoever reads them, and are don't-care here).  Dots and
+// norms run over the owned entries (krylov::OwnedBox of the fine space) and are summed over the ranks on the host: per iteration
+// one all-reduce of the j + 1 coefficients per Gram-Schmidt pass and one of ||w||^2, three in all.  The Hessenberg column is
+// then on the host already.  EVERY control decision below -- convergence, breakdown, restart, the end of the iteration -- is
+// taken from all-reduced values alone (`res`, the column, the iteration count), so all ranks take the same branch: a rank that
+// left the loop by itself would leave the others waiting in the next exchange.
 int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance, int32_t max_iterations,
                                     int32_t restart, int32_t preconditioner_fp32, int32_t *n_iterations, double *final_residual,
                                     double *residual_history, int32_t history_len)
@@ -1545,8 +1552,8 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
     require(restart >= 1, "the restart length must be at least 1");
     require(preconditioner_fp32 == 0 || preconditioner_fp32 == 1, "preconditioner_fp32 must be 0 or 1");
     HipHandle &handle = *h->handle;
-    require(!handle.comm.enabled(), "mfmg_hip_hierarchy_solve_fgmres is not available in a distributed run");
     const bool fp32 = preconditioner_fp32 != 0;
+    // (also what refuses the FP32 preconditioner in a distributed run: such a hierarchy cannot be built there)
     require(!fp32 || h->fine_f32 != nullptr, "preconditioner_fp32 needs a hierarchy built with \"fine level precision\" float");
     const int64_t n = level_size(h, 0);
     const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
@@ -1567,6 +1574,33 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
     double *const y_host = ws.host + ws.columns + 1;
     float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
     auto op = h->hierarchy->levels()[0].get_operator();
+    const bool distributed = handle.comm.enabled();
+    krylov::OwnedBox box;
+    if (distributed)
+    {
+      auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
+      const int space = hop ? hop->domain_space() : 0;
+      if (space <= 0 || !handle.comm.spaces[space].configured())
+        throw std::runtime_error("the fine operator of a distributed run has no halo space");
+      if (!handle.comm.transport)
+        throw std::runtime_error("no halo transport was registered with the context");
+      box = krylov::OwnedBox(handle.comm.spaces[space]);
+      if (box.n_local() != n)
+        throw std::runtime_error("internal: the fine halo space does not describe the fine vectors");
+    }
+    // `count` doubles at `dev` summed over the ranks: to the host (ws.host), one all-reduce, back to `dev`; the sums stay in ws.host
+    auto allreduce = [&](double *dev, int count) {
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+      handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
+      MFMG_HIP_CHECK(hipMemcpyAsync(dev, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
+    };
+    // ||w||^2 over the owned entries of all ranks from this rank's s.norm_partials: on the device (scratch.norm_squared) and returned
+    auto norm_squared_of_all = [&] {
+      krylov::basis_norm_finish(handle, scratch, box);
+      allreduce(scratch.norm_squared.data(), 1);
+      return ws.host[0];
+    };
     // "internal numbering" lexicographic: as in mfmg_hip_hierarchy_solve_cg -- b and x are gathered once, the basis, the operator
     // and the preconditioner live in the internal numbering, x is scattered once: two launches of the permutation per solve
     double const *b_run = b;
@@ -1587,6 +1621,13 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
       DVector r(handle, n, V);
       op->apply(xv, r);
       r.sadd(-1., 1., bv);
+      if (distributed)
+      {
+        krylov::basis_norm_partials(handle, scratch, box, V);
+        const double norm = std::sqrt(norm_squared_of_all());
+        krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), V, V, nullptr);
+        return norm;
+      }
       krylov::basis_norm_partials(handle, scratch, n, V);
       krylov::basis_scale_store(handle, scratch, n, V, V, v_f32, hcol);
       fetch(1);
@@ -1632,15 +1673,33 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
           DVector zj(handle, n, Z + j * ld), wv(handle, n, w);
           op->apply(zj, wv);
         }
-        for (int pass = 0; pass < 2; ++pass)
-        {
-          krylov::basis_dots(handle, scratch, n, ld, j + 1, V, w, scratch.pass_coefficients.data(), hcol, pass == 1);
-          krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass == 1);
-        }
-        krylov::basis_scale_store(handle, scratch, n, w, w, v_f32, hcol + j + 1);
-        fetch(j + 2);
         double *const c = &R[(size_t)j * (m + 1)];
-        std::copy(ws.host, ws.host + j + 2, c);
+        if (distributed)
+        {
+          // the column h_0 .. h_j, ||w|| is summed over the ranks on its way: no fetch
+          double *const pc = scratch.pass_coefficients.data();
+          for (int pass = 0; pass < 2; ++pass)
+          {
+            krylov::basis_dots(handle, scratch, box, ld, j + 1, V, w, pc, pc, false);
+            allreduce(pc, j + 1);
+            for (int i = 0; i <= j; ++i)
+              c[i] = pass == 0 ? ws.host[i] : c[i] + ws.host[i];
+            krylov::basis_update(handle, scratch, box, ld, j + 1, V, pc, w, pass == 1);
+          }
+          c[j + 1] = std::sqrt(norm_squared_of_all());
+          krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), w, w, nullptr);
+        }
+        else
+        {
+          for (int pass = 0; pass < 2; ++pass)
+          {
+            krylov::basis_dots(handle, scratch, n, ld, j + 1, V, w, scratch.pass_coefficients.data(), hcol, pass == 1);
+            krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass == 1);
+          }
+          krylov::basis_scale_store(handle, scratch, n, w, w, v_f32, hcol + j + 1);
+          fetch(j + 2);
+          std::copy(ws.host, ws.host + j + 2, c);
+        }
         for (int i = 0; i < j; ++i)
         {
           const double t = cs[i] * c[i] + sn[i] * c[i + 1];
@@ -1711,6 +1770,38 @@ int mfmg_hip_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int64_t ld,
       krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass + 1 == passes);
     }
     krylov::basis_scale_store(handle, scratch, n, w, nullptr, nullptr, norm_out);
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the scratch goes away)
+  });
+}
+
+int mfmg_hip_krylov_orthogonalize_box(mfmg_hip_context_t ctx, const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n,
+                                      int32_t comps, int64_t ld, int32_t j, const double *V, double *w, double *h_out, double *norm_out,
+                                      int32_t passes)
+{
+  return guarded([&] {
+    require(ctx && local_nodes && own0 && own_n && V && w && h_out && norm_out, "null argument");
+    require(comps >= 1 && j >= 0 && passes >= 1, "bad shape");
+    HipHandle &handle = *ctx->handle;
+    require(!handle.comm.enabled(), "mfmg_hip_krylov_orthogonalize_box runs the kernels of one rank: a context without a communicator");
+    krylov::OwnedBox box;
+    box.comps = comps;
+    for (int d = 0; d < 3; ++d)
+    {
+      require(own0[d] >= 0 && own_n[d] >= 1 && own0[d] + own_n[d] <= local_nodes[d], "the owned box leaves the local box");
+      box.local[d] = local_nodes[d];
+      box.own0[d] = own0[d];
+      box.own_n[d] = own_n[d];
+    }
+    require(ld >= box.n_local(), "bad shape");
+    krylov::Scratch scratch(j + 1);
+    for (int pass = 0; pass < passes; ++pass)
+    {
+      krylov::basis_dots(handle, scratch, box, ld, j + 1, V, w, scratch.pass_coefficients.data(), h_out, pass > 0);
+      krylov::basis_update(handle, scratch, box, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass + 1 == passes);
+    }
+    // (one rank: the sum over the ranks is the identity)
+    krylov::basis_norm_finish(handle, scratch, box);
+    krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), w, nullptr, norm_out);
     MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the scratch goes away)
   });
 }

@@ -182,7 +182,12 @@ public:
   }
   void allreduce(double *host_values, int n, int op, hipStream_t stream) override
   {
-    ASSERT_THROW(n >= 1 && n <= 16, "all-reduce of at most 16 scalars");
+    ASSERT_THROW(n >= 1, "all-reduce of at least one scalar");
+    if ((size_t)n > _scalars.size()) // (the coefficients of a Gram-Schmidt pass: as many as the basis has columns)
+    {
+      MFMG_HIP_CHECK(hipStreamSynchronize(stream));
+      _scalars.resize((size_t)n);
+    }
     MFMG_HIP_CHECK(hipMemcpyAsync(_scalars.data(), host_values, n * sizeof(double), hipMemcpyHostToDevice, stream));
     rccl_check(rccl().AllReduce(_scalars.data(), _scalars.data(), (size_t)n, ncclFloat64, op == 1 ? ncclMax : ncclSum, _comm, stream),
                "ncclAllReduce");

@@ -7,6 +7,14 @@
 // Every product enters its sum through one fma: a term of w - sum h_i V_i is rounded once.
 // Reductions: per-thread partial -> __shfl_xor butterfly -> LDS across the 4 waves -> one partial per block and column; a second
 // launch sums the partials of a column in a fixed order.  The grid depends on n alone.
+//
+// Owned-box kernels (OwnedBox): the owned entries are rows of row_len doubles, stride_y / stride_z apart, and a row may start at an
+// odd entry.  A thread owns one SLOT of a row: with W = 2 a 16-byte ALIGNED pair of the local vector, of which the head slot of a
+// row that starts odd and the tail slot of one that ends odd hold one owned entry each -- no 16-byte access is made at an address
+// that is not 16-byte aligned.  The ghost half of such a pair is loaded with it and never used (a select, not a product: it may be
+// NaN) and never stored (the two edge slots store 8 bytes).  Every row gets row_len / 2 + 1 slots, the most it can need; a slot
+// past the row idles.  The grid stride is carried through (slot, y, z) in mixed radix, its digits computed on the host: no
+// division in the loop.  The grid depends on the box alone.
 #include "krylov_basis.hpp"
 
 namespace mfmg
@@ -50,6 +58,29 @@ __device__ __forceinline__ double wave_sum(double v)
 // the entries past the last whole group of W (n odd, W = 2) belong to the first thread of the grid
 __device__ __forceinline__ bool owns_tail() { return blockIdx.x == 0 && threadIdx.x == 0; }
 
+// the sums of a block: partials[column][block] = sum over the block's threads of acc[column], waves in a fixed order
+template <int NC>
+__device__ __forceinline__ void block_column_sums(double const (&acc)[NC], double *__restrict__ partials, double (*wsum)[kWaves])
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+  {
+    const double t = wave_sum(acc[c]);
+    if (lane == 0)
+      wsum[c][wave] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC)
+  {
+    double t = 0.;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k)
+      t += wsum[threadIdx.x][k];
+    partials[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = t;
+  }
+}
+
 // ---- dots ----------------------------------------------------------------------------------------------------------------------
 template <int W, int NC>
 __device__ __forceinline__ void dots_body(int64_t n, int64_t ld, double const *__restrict__ V, double const *__restrict__ w,
@@ -83,23 +114,7 @@ __device__ __forceinline__ void dots_body(int64_t n, int64_t ld, double const *_
       for (int c = 0; c < NC; ++c)
         acc[c] = fma(V[c * ld + e], w[e], acc[c]);
     }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-  {
-    const double t = wave_sum(acc[c]);
-    if (lane == 0)
-      wsum[c][wave] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < NC)
-  {
-    double t = 0.;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k)
-      t += wsum[threadIdx.x][k];
-    partials[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = t;
-  }
+  block_column_sums<NC>(acc, partials, wsum);
 }
 
 // blockIdx.y: the group of kGroup columns; partials[column][block]
@@ -289,6 +304,212 @@ __global__ __launch_bounds__(block_size) void scale_store_kernel(int64_t n, int 
     }
 }
 
+// ---- owned-box kernels -----------------------------------------------------------------------------------------------------------
+// The rows of an OwnedBox (whole axes joined) and the walk of one launch over their slots
+struct RowWalk
+{
+  int64_t base, row_len, stride_y, stride_z, n_y, n_z; // row (y, z) = the entries [s, s + row_len), s = base + y stride_y + z stride_z
+  int64_t n_local;                                     // entries of the local vector: a pair that ends past it is not loaded
+  int64_t slots;                                       // slots per row
+  int64_t d_slot, d_y, d_z;                            // the grid stride in slots = d_slot + slots (d_y + n_y d_z)
+};
+
+template <int W>
+struct Cursor
+{
+  int64_t slot, y, z;
+  __device__ __forceinline__ explicit Cursor(RowWalk const &g)
+  {
+    const int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, row = u / g.slots;
+    slot = u % g.slots;
+    y = row % g.n_y;
+    z = row / g.n_y;
+  }
+  __device__ __forceinline__ bool inside(RowWalk const &g) const { return z < g.n_z; }
+  __device__ __forceinline__ void advance(RowWalk const &g)
+  {
+    slot += g.d_slot;
+    y += g.d_y;
+    z += g.d_z;
+    if (slot >= g.slots)
+    {
+      slot -= g.slots;
+      ++y;
+    }
+    if (y >= g.n_y)
+    {
+      y -= g.n_y;
+      ++z;
+    }
+  }
+  // first entry of the slot (W = 2: even) and which of its W entries the row holds
+  __device__ __forceinline__ int64_t entries(RowWalk const &g, bool (&in)[W]) const
+  {
+    const int64_t s = g.base + y * g.stride_y + z * g.stride_z;
+    if constexpr (W == 1)
+    {
+      in[0] = true; // (slots = row_len)
+      return s + slot;
+    }
+    else
+    {
+      const int64_t e = ((s >> 1) + slot) << 1; // (e + 1 >= s)
+      in[0] = e >= s && e < s + g.row_len;
+      in[1] = e + 1 < s + g.row_len;
+      return e;
+    }
+  }
+};
+
+// the products of one slot: WL = the width of the loads (WL < W: the one pair that ends past the vector, its first entry alone)
+template <int W, int WL, int NC>
+__device__ __forceinline__ void dots_slot(double (&acc)[NC], bool const (&in)[W], double const *__restrict__ V, int64_t ld,
+                                          double const *__restrict__ w)
+{
+  double v[NC][WL], ww[WL];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    load<WL>(V + c * ld, v[c]);
+  load<WL>(w, ww);
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+  {
+#pragma unroll
+    for (int k = 0; k < WL; ++k)
+    {
+      const double t = fma(v[c][k], ww[k], acc[c]);
+      acc[c] = in[k] ? t : acc[c]; // (not a product with 0: a ghost entry may hold NaN)
+    }
+  }
+}
+
+template <int W, int NC>
+__device__ __forceinline__ void box_dots_body(RowWalk const &g, int64_t ld, double const *__restrict__ V, double const *__restrict__ w,
+                                              double *__restrict__ partials, double (*wsum)[kWaves])
+{
+  double acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    acc[c] = 0.;
+  for (Cursor<W> cur(g); cur.inside(g); cur.advance(g))
+  {
+    bool in[W];
+    const int64_t e = cur.entries(g, in);
+    if (!in[0] && !in[W - 1])
+      continue;
+    if (W == 1 || e + 1 < g.n_local)
+      dots_slot<W, W, NC>(acc, in, V + e, ld, w + e);
+    else
+      dots_slot<W, 1, NC>(acc, in, V + e, ld, w + e);
+  }
+  block_column_sums<NC>(acc, partials, wsum);
+}
+
+template <int W>
+__global__ __launch_bounds__(block_size) void box_dots_kernel(RowWalk g, int64_t ld, int n_columns, double const *__restrict__ V,
+                                                               double const *__restrict__ w, double *__restrict__ partials)
+{
+  __shared__ double wsum[kGroup][kWaves];
+  const int c0 = blockIdx.y * kGroup;
+  const int nc = min(kGroup, n_columns - c0);
+  V += (int64_t)c0 * ld;
+  partials += (int64_t)c0 * gridDim.x;
+  switch (nc)
+  {
+  case 1: box_dots_body<W, 1>(g, ld, V, w, partials, wsum); break;
+  case 2: box_dots_body<W, 2>(g, ld, V, w, partials, wsum); break;
+  case 3: box_dots_body<W, 3>(g, ld, V, w, partials, wsum); break;
+  case 4: box_dots_body<W, 4>(g, ld, V, w, partials, wsum); break;
+  case 5: box_dots_body<W, 5>(g, ld, V, w, partials, wsum); break;
+  case 6: box_dots_body<W, 6>(g, ld, V, w, partials, wsum); break;
+  case 7: box_dots_body<W, 7>(g, ld, V, w, partials, wsum); break;
+  default: box_dots_body<W, 8>(g, ld, V, w, partials, wsum); break;
+  }
+}
+
+// the owned entries of a slot stored: both halves of a pair in one 16-byte store, an edge slot its one entry
+template <int W>
+__device__ __forceinline__ void store_owned(double *p, double const (&r)[W], bool const (&in)[W])
+{
+  if (in[0] && in[W - 1])
+    store<W>(p, r);
+  else if (in[0])
+    p[0] = r[0];
+  else if (in[W - 1])
+    p[W - 1] = r[W - 1];
+}
+
+template <int W, bool kNorm>
+__global__ __launch_bounds__(block_size) void box_axpy_kernel(RowWalk g, int64_t ld, int n_columns, double const *__restrict__ V,
+                                                               double const *__restrict__ c, double sign, double *__restrict__ out,
+                                                               double *__restrict__ norm_partials)
+{
+  __shared__ double wsum[1][kWaves];
+  double nrm[1] = {0.};
+  for (Cursor<W> cur(g); cur.inside(g); cur.advance(g))
+  {
+    bool in[W];
+    const int64_t e = cur.entries(g, in);
+    if (!in[0] && !in[W - 1])
+      continue;
+    double acc[W];
+    if (W == 1 || e + 1 < g.n_local)
+    {
+      // (a ghost half is computed with its pair -- the entries of a pair do not meet -- and dropped)
+      load<W>(out + e, acc);
+      axpy_columns<W>(acc, V + e, ld, n_columns, c, sign);
+    }
+    else
+    {
+      double first[1] = {out[e]};
+      axpy_columns<1>(first, V + e, ld, n_columns, c, sign);
+      acc[0] = first[0];
+      acc[W - 1] = first[0];
+    }
+    store_owned<W>(out + e, acc, in);
+    if (kNorm)
+    {
+#pragma unroll
+      for (int k = 0; k < W; ++k)
+      {
+        const double t = fma(acc[k], acc[k], nrm[0]);
+        nrm[0] = in[k] ? t : nrm[0];
+      }
+    }
+  }
+  if (kNorm)
+    block_column_sums<1>(nrm, norm_partials, wsum);
+}
+
+// norm_squared: ||w||^2 over all ranks, one device scalar (the partials of a rank are not the norm: the caller summed them)
+template <int W>
+__global__ __launch_bounds__(block_size) void box_scale_store_kernel(RowWalk g, double const *__restrict__ norm_squared, double const *w,
+                                                                      double *v_next, double *__restrict__ norm_out)
+{
+  const double norm = sqrt(norm_squared[0]);
+  if (owns_tail() && norm_out != nullptr)
+    norm_out[0] = norm;
+  if (v_next == nullptr)
+    return;
+  const double inv = norm > 0. ? 1. / norm : 0.;
+  for (Cursor<W> cur(g); cur.inside(g); cur.advance(g))
+  {
+    bool in[W];
+    const int64_t e = cur.entries(g, in);
+    if (!in[0] && !in[W - 1])
+      continue;
+    double r[W];
+    if (W == 1 || e + 1 < g.n_local)
+      load<W>(w + e, r);
+    else
+      r[0] = r[W - 1] = w[e];
+#pragma unroll
+    for (int k = 0; k < W; ++k)
+      r[k] *= inv;
+    store_owned<W>(v_next + e, r, in);
+  }
+}
+
 bool aligned16(void const *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 void check_columns(int64_t n, int64_t ld, int n_columns)
@@ -372,6 +593,142 @@ void basis_scale_store(HipHandle &h, Scratch &s, int64_t n, double const *w, dou
   else
     hipLaunchKernelGGL(scale_store_kernel<1>, grid, dim3(block_size), 0, h.stream, n, nb, s.norm_partials.data(), w, v_next, v_next_f32,
                        norm_out);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+// ---- owned-box launches ---------------------------------------------------------------------------------------------------------
+namespace
+{
+void check_box(OwnedBox const &b, int64_t ld, int n_columns)
+{
+  ASSERT_THROW(b.comps >= 1 && n_columns >= 0, "krylov basis: no component or a negative column count");
+  for (int d = 0; d < 3; ++d)
+    ASSERT_THROW(b.own0[d] >= 0 && b.own_n[d] >= 1 && b.own0[d] + b.own_n[d] <= b.local[d], "krylov basis: the owned box leaves the local box");
+  ASSERT_THROW(n_columns == 0 || ld >= b.n_local(), "krylov basis: the leading dimension is smaller than the vectors");
+}
+
+// rows of the box, an axis that is owned whole joined with the next one (x and y whole: one run); slots of a row
+void rows_of(OwnedBox const &b, RowWalk &g)
+{
+  g.stride_y = b.local[0] * b.comps;
+  g.stride_z = g.stride_y * b.local[1];
+  g.base = b.own0[0] * b.comps + b.own0[1] * g.stride_y + b.own0[2] * g.stride_z;
+  g.row_len = b.own_n[0] * b.comps;
+  g.n_y = b.own_n[1];
+  g.n_z = b.own_n[2];
+  g.n_local = b.n_local();
+  if (b.own_n[0] == b.local[0])
+  {
+    g.row_len *= g.n_y;
+    g.n_y = 1;
+    if (b.own_n[1] == b.local[1])
+    {
+      g.row_len *= g.n_z;
+      g.n_z = 1;
+    }
+  }
+}
+
+RowWalk row_walk(OwnedBox const &b, int W, unsigned int n_blocks)
+{
+  RowWalk g;
+  rows_of(b, g);
+  g.slots = W == 2 ? g.row_len / 2 + 1 : g.row_len;
+  const int64_t stride = (int64_t)n_blocks * block_size, rows = stride / g.slots;
+  g.d_slot = stride % g.slots;
+  g.d_y = rows % g.n_y;
+  g.d_z = rows / g.n_y;
+  return g;
+}
+} // namespace
+
+unsigned int reduction_blocks(OwnedBox const &box)
+{
+  RowWalk g;
+  rows_of(box, g);
+  return n_blocks_for((g.row_len / 2 + 1) * g.n_y * g.n_z, block_size, kMaxBlocks); // (the slots of the 16-byte kernels, for both)
+}
+
+void basis_dots(HipHandle &h, Scratch &s, OwnedBox const &box, int64_t ld, int n_columns, double const *V, double const *w,
+                double *h_pass, double *h_total, bool accumulate)
+{
+  check_box(box, ld, n_columns);
+  if (n_columns == 0)
+    return;
+  ASSERT_THROW(n_columns <= s.capacity, "krylov basis: more columns than the scratch was built for");
+  const unsigned int nb = reduction_blocks(box);
+  const dim3 grid(nb, (unsigned)((n_columns + kGroup - 1) / kGroup));
+  hipEvent_t stop = h.profiler.begin("basis_dots_box", 8. * double(box.n_owned()) * (n_columns + (int)grid.y), h.stream);
+  if (aligned16(V) && aligned16(w) && ld % 2 == 0)
+    hipLaunchKernelGGL(box_dots_kernel<2>, grid, dim3(block_size), 0, h.stream, row_walk(box, 2, nb), ld, n_columns, V, w, s.dot_partials.data());
+  else
+    hipLaunchKernelGGL(box_dots_kernel<1>, grid, dim3(block_size), 0, h.stream, row_walk(box, 1, nb), ld, n_columns, V, w, s.dot_partials.data());
+  hipLaunchKernelGGL(dots_finish_kernel, dim3(n_columns), dim3(block_size), 0, h.stream, (int)nb, s.dot_partials.data(), h_pass, h_total,
+                     accumulate ? 1 : 0);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+namespace
+{
+template <bool kNorm>
+void launch_box_axpy(HipHandle &h, OwnedBox const &box, int64_t ld, int n_columns, double const *V, double const *c, double *out,
+                     double *norm_partials)
+{
+  const unsigned int nb = reduction_blocks(box);
+  if (aligned16(V) && aligned16(out) && ld % 2 == 0)
+    hipLaunchKernelGGL((box_axpy_kernel<2, kNorm>), dim3(nb), dim3(block_size), 0, h.stream, row_walk(box, 2, nb), ld, n_columns, V, c, -1., out,
+                       norm_partials);
+  else
+    hipLaunchKernelGGL((box_axpy_kernel<1, kNorm>), dim3(nb), dim3(block_size), 0, h.stream, row_walk(box, 1, nb), ld, n_columns, V, c, -1., out,
+                       norm_partials);
+}
+} // namespace
+
+void basis_update(HipHandle &h, Scratch &s, OwnedBox const &box, int64_t ld, int n_columns, double const *V, double const *c,
+                  double *w, bool with_norm)
+{
+  check_box(box, ld, n_columns);
+  hipEvent_t stop = h.profiler.begin("basis_update_box", 8. * double(box.n_owned()) * (n_columns + 2), h.stream);
+  if (with_norm)
+    launch_box_axpy<true>(h, box, ld, n_columns, V, c, w, s.norm_partials.data());
+  else
+    launch_box_axpy<false>(h, box, ld, n_columns, V, c, w, nullptr);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void basis_norm_partials(HipHandle &h, Scratch &s, OwnedBox const &box, double const *w)
+{
+  // as the contiguous one: (w, w) of the dots kernel with w as its only column
+  check_box(box, box.n_local(), 1);
+  const unsigned int nb = reduction_blocks(box);
+  if (aligned16(w))
+    hipLaunchKernelGGL(box_dots_kernel<2>, dim3(nb), dim3(block_size), 0, h.stream, row_walk(box, 2, nb), box.n_local(), 1, w, w,
+                       s.norm_partials.data());
+  else
+    hipLaunchKernelGGL(box_dots_kernel<1>, dim3(nb), dim3(block_size), 0, h.stream, row_walk(box, 1, nb), box.n_local(), 1, w, w,
+                       s.norm_partials.data());
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void basis_norm_finish(HipHandle &h, Scratch &s, OwnedBox const &box)
+{
+  hipLaunchKernelGGL(dots_finish_kernel, dim3(1), dim3(block_size), 0, h.stream, (int)reduction_blocks(box), s.norm_partials.data(),
+                     s.norm_squared.data(), s.norm_squared.data(), 0);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void basis_scale_store(HipHandle &h, OwnedBox const &box, double const *norm_squared, double const *w, double *v_next, double *norm_out)
+{
+  check_box(box, box.n_local(), 0);
+  const unsigned int nb = v_next == nullptr ? 1u : reduction_blocks(box);
+  hipEvent_t stop = h.profiler.begin("basis_scale_store_box", v_next == nullptr ? 0. : 16. * double(box.n_owned()), h.stream);
+  if (aligned16(w) && aligned16(v_next))
+    hipLaunchKernelGGL(box_scale_store_kernel<2>, dim3(nb), dim3(block_size), 0, h.stream, row_walk(box, 2, nb), norm_squared, w, v_next, norm_out);
+  else
+    hipLaunchKernelGGL(box_scale_store_kernel<1>, dim3(nb), dim3(block_size), 0, h.stream, row_walk(box, 1, nb), norm_squared, w, v_next, norm_out);
   KernelProfiler::end(stop, h.stream);
   MFMG_HIP_CHECK(hipGetLastError());
 }

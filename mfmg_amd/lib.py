@@ -218,6 +218,7 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_solve_fgmres": (C.c_int, [vp, vp, vp, dbl, i32, i32, i32, P(i32), P(dbl), P(dbl), i32]),
         "mfmg_hip_krylov_orthogonalize": (C.c_int, [vp, i64, i64, i32, vp, vp, vp, vp, i32]),
         "mfmg_hip_krylov_combine": (C.c_int, [vp, i64, i64, i32, vp, vp, vp]),
+        "mfmg_hip_krylov_orthogonalize_box": (C.c_int, [vp, P(i64), P(i64), P(i64), i32, i64, i32, vp, vp, vp, vp, i32]),
         "mfmg_hip_hierarchy_n_levels": (C.c_int, [vp, P(i32)]),
         "mfmg_hip_hierarchy_level_size": (C.c_int, [vp, i32, P(i64)]),
         "mfmg_hip_hierarchy_operator_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
