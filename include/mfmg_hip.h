@@ -158,6 +158,23 @@ int mfmg_hip_context_exchange_volume(mfmg_hip_context_t ctx, int64_t *n_doubles_
 /* one halo exchange of a device vector of `space` (1 fine DoFs, 2 first coarse level, 3.. aggregation levels):
  * reverse = 0 owner -> ghost, 1 ghost -> owner (added).  The cycle does this by itself; exposed for tests. */
 int mfmg_hip_context_exchange(mfmg_hip_context_t ctx, int32_t space, double *vector, int reverse);
+/* The forward exchange (owner -> ghost) of a FLOAT device vector of the fine DoF space, `width` planes deep (1 to 3, at most the
+ * ghost planes every rank holds below: 2, or 4 with two ghost agglomerates).  The packing kernel widens the entries into the
+ * staging buffers of the double exchange and the unpacking kernel narrows them (exact both ways), so the transports, the
+ * callbacks and the messages are those of a double vector of the space: the same peers and counts, 8 bytes per entry on the
+ * wire.  A slab packs too.  space must be 1 (MFMG_HIP_ERROR_INVALID_ARGUMENT otherwise).  What the FP32 fine level does by itself;
+ * exposed for tests. */
+int mfmg_hip_context_exchange_f32(mfmg_hip_context_t ctx, int32_t space, float *vector, int width);
+/* Host only (no context, no GPU; tests): the messages of one box exchange `width` layers deep of a local box of local_nodes[3] nodes
+ * (x fastest, `comps` entries per node) that owns [own0, own0 + own_n) per axis and has a neighbour below / above along the axes
+ * with has_low / has_high set, on rank `rank` of a grid[3] arrangement.  n_messages (<= 26), peers and counts (26 entries
+ * each) describe the group; send_entries / recv_entries (both NULL, or `capacity` >= the sum of the counts entries each) receive
+ * for every entry of the packed buffer its position in the local vector: where the packing kernel reads it (owned boundary
+ * layers) and where the unpacking kernel writes what arrived in its place (ghost layers). */
+int mfmg_hip_halo_box_messages(const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n, const int32_t *has_low,
+                               const int32_t *has_high, int32_t comps, int32_t width, int32_t rank, const int32_t *grid,
+                               int32_t *n_messages, int32_t *peers, int64_t *counts, int64_t *send_entries, int64_t *recv_entries,
+                               int64_t capacity);
 /* sum over the ranks of the dot product over the owned entries of two vectors of `space` */
 int mfmg_hip_context_owned_dot(mfmg_hip_context_t ctx, int32_t space, const double *x, const double *y, double *result);
 /* Distributed runs: overlap the exchange of the fine-level ghost planes with the operator tiles that do not read
@@ -449,8 +466,19 @@ int mfmg_hip_hierarchy_apply(mfmg_hip_hierarchy_t h, const double *b, double *x)
 /* The same cycle with the fine level in FP32 (BASELINE.json configs[4]): float device vectors; pre-smoother,
  * residual and post-smoother through the FP32 instance of the matrix-free operator, restriction, coarse solve and
  * prolongation in FP64.  Needs the parameter "fine level precision" float at creation (matrix-free evaluator, two
- * levels, one process). */
+ * levels).  On a context with a communicator b and x are the rank's local float vectors (ghost entries are don't-care on entry):
+ * the FP32 operator exchanges x like the FP64 one -- one plane per application beside the interior tiles, once per sweep as many
+ * planes deep as the sweep has terms, b one plane less once per cycle -- widened to double on the wire
+ * (mfmg_hip_context_exchange_f32); the ranks agree at creation on the sweep every rank's FP32 operator offers.  b_c = R (A x - b)
+ * takes the two-step form there: the FP32 residual, widened, and the FP64 restriction with its own exchange. */
 int mfmg_hip_hierarchy_apply_f32(mfmg_hip_hierarchy_t h, const float *b, float *x);
+/* The FP32 operator of that level on its own (tests): mode 0 out = A x, 1 out = A x - b, 2 out = x + alpha (x - x_prev) - beta
+ * D^-1 (A x - b) (x_prev NULL or alpha 0: no momentum).  Owned entries; on ranks the ghost entries of x are exchanged by the call.
+ * Not with permuted vectors ("internal numbering" lexicographic on a renumbered mesh).  *_sweep_terms_f32: the terms the FP32
+ * smoother runs as one sweep (0: a launch per term), the same on every rank. */
+int mfmg_hip_hierarchy_operator_f32(mfmg_hip_hierarchy_t h, int mode, const float *x, const float *b, const float *x_prev, float alpha,
+                                    float beta, float *out);
+int mfmg_hip_hierarchy_sweep_terms_f32(mfmg_hip_hierarchy_t h, int *terms_out_of_place);
 int mfmg_hip_hierarchy_vmult(mfmg_hip_hierarchy_t h, double *x, const double *b);
 /* Outer Krylov driver of tests/hierarchy_driver.cc:103-116: dealii::SolverCG on the fine-level operator with
  * Hierarchy::vmult as preconditioner, SolverControl(max_iterations, tolerance) on the absolute l2 norm of the
@@ -479,7 +507,8 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
  * On a context with a communicator b and x are the rank's local vectors (ghost entries are don't-care on entry), the basis is sized
  * by the local vectors, dots and norms run over the owned entries and are summed over the ranks: three all-reduces per iteration
  * through the registered transport (the coefficients of the two Gram-Schmidt passes, ||w||^2), and no other host round trip.  All
- * ranks return the same iteration count and history.  preconditioner_fp32 1 is MFMG_HIP_ERROR_INVALID_ARGUMENT there. */
+ * ranks return the same iteration count and history.  preconditioner_fp32 1 there: v is narrowed and z widened over the whole local
+ * vector, the FP32 level exchanges the ghost entries it reads; the basis, the dots and the three all-reduces are unchanged. */
 int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance,
                                     int32_t max_iterations, int32_t restart, int32_t preconditioner_fp32,
                                     int32_t *n_iterations, double *final_residual,

@@ -200,6 +200,12 @@ class Context:
     def sadd(self, x: torch.Tensor, s: float, a: float, v: torch.Tensor):
         check(self._lib.mfmg_hip_vector_sadd(self.handle, x.numel(), s, a, _dev_ptr(v, x.numel()), _dev_ptr(x)))
 
+    def exchange_f32(self, space: int, v: torch.Tensor, width: int = 1):
+        """One forward halo exchange (owner -> ghost) of a float32 vector of the fine DoF space (space 1), `width` planes deep;
+        the FP32 fine level does this by itself (for tests).  Nothing happens without a HaloTransport."""
+        assert v.dtype == torch.float32 and v.is_contiguous()
+        check(self._lib.mfmg_hip_context_exchange_f32(self.handle, int(space), v.data_ptr(), int(width)))
+
     def krylov_orthogonalize(self, V: torch.Tensor, w: torch.Tensor, n_columns: int, passes: int = 2, box=None):
         """The fused Gram-Schmidt kernels of solve_fgmres on their own: `passes` times { c = V^T w; w -= V c } in place, against
         the first n_columns columns of V ([columns, ld] contiguous: column-major with leading dimension ld >= len(w)).
@@ -638,9 +644,24 @@ class Hierarchy:
         check(self._lib.mfmg_hip_hierarchy_apply(self.handle, _dev_ptr(b, n), _dev_ptr(x, n)))
 
     def apply_f32(self, b: torch.Tensor, x: torch.Tensor):
-        """The same cycle on float32 vectors with the fine level in FP32 (parameter "fine level precision": "float")."""
+        """The same cycle on float32 vectors with the fine level in FP32 (parameter "fine level precision": "float").  On a
+        context with a HaloTransport b and x are the rank's local float vectors (ghost entries are don't-care on entry)."""
         n = self.level_size(0)
         check(self._lib.mfmg_hip_hierarchy_apply_f32(self.handle, _dev_ptr(b, n, torch.float32), _dev_ptr(x, n, torch.float32)))
+
+    def operator_f32(self, mode: str, x: torch.Tensor, out: torch.Tensor, b=None, x_prev=None, alpha: float = 0.0, beta: float = 0.0):
+        """The FP32 operator of the fine level on its own (tests): mode "vmult" out = A x, "residual" out = A x - b, "step"
+        out = x + alpha (x - x_prev) - beta D^-1 (A x - b).  On ranks the call exchanges the ghost entries of x."""
+        n = self.level_size(0)
+        p = lambda t: 0 if t is None else _dev_ptr(t, n, torch.float32)
+        check(self._lib.mfmg_hip_hierarchy_operator_f32(self.handle, {"vmult": 0, "residual": 1, "step": 2}[mode], p(x), p(b), p(x_prev),
+                                                        float(alpha), float(beta), p(out)))
+
+    def sweep_terms_f32(self) -> int:
+        """Terms the FP32 smoother runs as one sweep (0: a launch per term); the same on every rank."""
+        k = C.c_int()
+        check(self._lib.mfmg_hip_hierarchy_sweep_terms_f32(self.handle, C.byref(k)))
+        return k.value
 
     def vmult(self, x: torch.Tensor, b: torch.Tensor):
         n = self.level_size(0)
@@ -818,7 +839,8 @@ class Hierarchy:
         """dealii::SolverFGMRES: right-preconditioned flexible GMRES(restart) on the fine operator with this hierarchy as
         preconditioner -- which may be non-symmetric (solver.amg.pre_smoothing_levels 0) or, with preconditioner="float", the
         FP32 fine level ("fine level precision" float) under the FP64 iteration.  Returns (iterations, residual history).
-        On a context with a HaloTransport b and x are the rank's local vectors; every rank gets the same count and history."""
+        On a context with a HaloTransport b and x are the rank's local vectors; every rank gets the same count and history
+        (either preconditioner)."""
         if preconditioner not in ("double", "float"):
             raise _lib.MfmgInvalidArgument('preconditioner must be "double" or "float"')
         n = self.level_size(0)

@@ -464,6 +464,73 @@ int mfmg_hip_context_exchange(mfmg_hip_context_t ctx, int32_t space, double *vec
   });
 }
 
+// host only: the messages of a box exchange and where their entries lie in the local vector (halo_box_messages, halo_region_entry)
+int mfmg_hip_halo_box_messages(const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n, const int32_t *has_low,
+                               const int32_t *has_high, int32_t comps, int32_t width, int32_t rank, const int32_t *grid,
+                               int32_t *n_messages, int32_t *peers, int64_t *counts, int64_t *send_entries, int64_t *recv_entries,
+                               int64_t capacity)
+{
+  return guarded([&] {
+    require(local_nodes && own0 && own_n && has_low && has_high && grid && n_messages && peers && counts, "null argument");
+    require(comps >= 1 && width >= 1, "bad space");
+    HaloSpace s;
+    s.comps = comps;
+    s.width = width;
+    for (int d = 0; d < 3; ++d)
+    {
+      require(own0[d] >= 0 && own_n[d] >= width && own0[d] + own_n[d] <= local_nodes[d], "the owned box lies outside the local box");
+      require(!has_low[d] || own0[d] >= width, "fewer ghost layers below than the exchange is wide");
+      require(!has_high[d] || local_nodes[d] - own0[d] - own_n[d] >= width, "fewer ghost layers above than the exchange is wide");
+    }
+    s.n_xy[0] = local_nodes[0];
+    s.n_xy[1] = local_nodes[1];
+    s.n_layers = local_nodes[2];
+    s.layer_elems = comps * local_nodes[0] * local_nodes[1];
+    for (int d = 0; d < 2; ++d)
+    {
+      s.own0_xy[d] = own0[d];
+      s.own_n_xy[d] = own_n[d];
+      s.low_xy[d] = has_low[d] != 0;
+      s.high_xy[d] = has_high[d] != 0;
+    }
+    s.owned_begin = own0[2];
+    s.owned_count = own_n[2];
+    s.has_low = has_low[2] != 0;
+    s.has_high = has_high[2] != 0;
+    HaloRegions own, ghost;
+    int p[26];
+    int64_t c[26];
+    const int stride[3] = {1, grid[0], grid[0] * grid[1]};
+    const int64_t total = halo_box_messages(s, rank, stride, own, ghost, p, c);
+    *n_messages = own.count;
+    std::copy(p, p + own.count, peers);
+    std::copy(c, c + own.count, counts);
+    if (send_entries == nullptr && recv_entries == nullptr)
+      return;
+    require(send_entries && recv_entries && capacity >= total, "entry arrays shorter than the messages");
+    for (int64_t i = 0; i < total; ++i)
+    {
+      send_entries[i] = halo_region_entry(own, comps, s.n_xy[0], s.n_xy[1], i);
+      recv_entries[i] = halo_region_entry(ghost, comps, s.n_xy[0], s.n_xy[1], i);
+    }
+  });
+}
+
+int mfmg_hip_context_exchange_f32(mfmg_hip_context_t ctx, int32_t space, float *vector, int width)
+{
+  return guarded([&] {
+    require(ctx != nullptr && vector != nullptr, "null argument");
+    HipHandle &h = *ctx->handle;
+    require(space == 1, "float vectors are exchanged in the fine DoF space (1) only");
+    // (the same answer on every rank: every rank holds low_ghost_cells planes below and three above where it has a neighbour)
+    require(width >= 1 && width <= 3 && width <= h.comm.low_ghost_cells, "width: 1 to 3 planes, at most the ghost planes every rank holds");
+    if (!h.comm.enabled())
+      return;
+    (void)h.space_checked(space);
+    h.exchange_on(h.fine_space(width), vector, h.stream, h.stream, false);
+  });
+}
+
 int mfmg_hip_context_owned_dot(mfmg_hip_context_t ctx, int32_t space, const double *x, const double *y, double *result)
 {
   return guarded([&] {
@@ -1301,7 +1368,6 @@ int mfmg_hip_hierarchy_create(mfmg_hip_context_t ctx, const char *evaluator_type
       // built here: the mesh arrays of the caller need not outlive this call
       require(type == "HipMatrixFreeMeshEvaluator", "\"fine level precision\" float needs the matrix-free evaluator");
       require(h->hierarchy->levels().size() == 2, "\"fine level precision\" float needs the two-level hierarchy");
-      require(!ctx->handle->comm.enabled(), "\"fine level precision\" float is not available in a distributed run");
       h->fine_f32.reset(new HipFloatFineLevel(*ctx->handle, *mesh, *h->hierarchy));
     }
     else
@@ -1415,6 +1481,35 @@ int mfmg_hip_hierarchy_apply_f32(mfmg_hip_hierarchy_t h, const float *b, float *
       return;
     }
     h->fine_f32->apply(b, x);
+  });
+}
+
+int mfmg_hip_hierarchy_sweep_terms_f32(mfmg_hip_hierarchy_t h, int *terms_out_of_place)
+{
+  return guarded([&] {
+    require(h && terms_out_of_place, "null argument");
+    require(h->fine_f32 != nullptr, "the hierarchy was not built with \"fine level precision\" float");
+    *terms_out_of_place = h->fine_f32->sweep_terms();
+  });
+}
+
+// the FP32 operator of the fine level on its own (tests)
+int mfmg_hip_hierarchy_operator_f32(mfmg_hip_hierarchy_t h, int mode, const float *x, const float *b, const float *x_prev, float alpha,
+                                    float beta, float *out)
+{
+  return guarded([&] {
+    require(h && x && out, "null argument");
+    require(h->fine_f32 != nullptr, "the hierarchy was not built with \"fine level precision\" float");
+    require(mode >= 0 && mode <= 2, "mode: 0 out = A x, 1 out = A x - b, 2 a smoother term");
+    require(mode == 0 || b != nullptr, "null argument");
+    require(x != out && x_prev != out, "the operator does not work in place");
+    require(!h->perm, "the level-wise FP32 operator takes the internal numbering: not with permuted vectors");
+    if (mode == 0)
+      h->fine_f32->vmult(x, out);
+    else if (mode == 1)
+      h->fine_f32->residual(x, b, out);
+    else
+      h->fine_f32->smoother_step(b, x, x_prev, alpha, beta, out);
   });
 }
 
@@ -1553,7 +1648,6 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
     require(preconditioner_fp32 == 0 || preconditioner_fp32 == 1, "preconditioner_fp32 must be 0 or 1");
     HipHandle &handle = *h->handle;
     const bool fp32 = preconditioner_fp32 != 0;
-    // (also what refuses the FP32 preconditioner in a distributed run: such a hierarchy cannot be built there)
     require(!fp32 || h->fine_f32 != nullptr, "preconditioner_fp32 needs a hierarchy built with \"fine level precision\" float");
     const int64_t n = level_size(h, 0);
     const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
@@ -1626,6 +1720,9 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
         krylov::basis_norm_partials(handle, scratch, box, V);
         const double norm = std::sqrt(norm_squared_of_all());
         krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), V, V, nullptr);
+        // (the whole local vector: what its ghost entries hold is exchanged over by the FP32 level where it reads them)
+        if (fp32)
+          vec::narrow(handle, n, V, v_f32);
         return norm;
       }
       krylov::basis_norm_partials(handle, scratch, n, V);
@@ -1688,6 +1785,8 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
           }
           c[j + 1] = std::sqrt(norm_squared_of_all());
           krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), w, w, nullptr);
+          if (fp32)
+            vec::narrow(handle, n, w, v_f32);
         }
         else
         {

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mfmg_hip.h"
@@ -439,6 +440,60 @@ struct HaloRegions
   int64_t off[27];
 };
 
+// The messages of one box exchange of `s` (HipHandle::exchange_box), `width` = s.width layers deep: every existing neighbour at an
+// offset o in {-1, 0, 1}^3, z slowest, gets message r -- peers[r] = rank + o . stride, counts[r] entries.  own: the regions of
+// the owned boundary layers next to the neighbours, ghost: those of the ghost layers beyond them, both with the same offsets
+// into the packed buffer.  Returns the entries of all messages.  A slab (no neighbour along x or y) has the messages of its
+// contiguous form: the lower neighbour first, the `width` layers over all of x and y.
+inline int64_t halo_box_messages(HaloSpace const &s, int rank, int const stride[3], HaloRegions &own, HaloRegions &ghost, int peers[26],
+                                 int64_t counts[26])
+{
+  int64_t total = 0;
+  own.count = ghost.count = 0;
+  for (int oz = -1; oz <= 1; ++oz)
+    for (int oy = -1; oy <= 1; ++oy)
+      for (int ox = -1; ox <= 1; ++ox)
+      {
+        const int o[3] = {ox, oy, oz};
+        if (ox == 0 && oy == 0 && oz == 0)
+          continue;
+        bool exists = true;
+        for (int d = 0; d < 3; ++d)
+          if ((o[d] < 0 && !s.low(d)) || (o[d] > 0 && !s.high(d)))
+            exists = false;
+        if (!exists)
+          continue;
+        const int r = own.count;
+        int64_t n = s.comps;
+        for (int d = 0; d < 3; ++d)
+        {
+          const int o0 = (int)s.own0(d), o1 = (int)(s.own0(d) + s.own_n(d)), w = s.width;
+          own.b[r][d] = o[d] < 0 ? o0 : (o[d] > 0 ? o1 - w : o0);
+          ghost.b[r][d] = o[d] < 0 ? o0 - w : (o[d] > 0 ? o1 : o0);
+          own.n[r][d] = ghost.n[r][d] = o[d] == 0 ? o1 - o0 : w;
+          n *= own.n[r][d];
+        }
+        own.off[r] = ghost.off[r] = total;
+        peers[r] = rank + ox * stride[0] + oy * stride[1] + oz * stride[2];
+        counts[r] = n;
+        total += n;
+        own.count = ghost.count = r + 1;
+      }
+  own.off[own.count] = ghost.off[own.count] = total;
+  return total;
+}
+
+// entry i of the packed buffer of `t`: its position in the lexicographic array of nx x ny x . nodes with `comps` entries each
+__host__ __device__ inline int64_t halo_region_entry(HaloRegions const &t, int comps, int64_t nx, int64_t ny, int64_t i)
+{
+  int r = 0;
+  while (r + 1 < t.count && i >= t.off[r + 1])
+    ++r;
+  const int64_t q = i - t.off[r], rx = (int64_t)t.n[r][0] * comps;
+  const int64_t x = q % rx, j = (q / rx) % t.n[r][1], k = q / (rx * t.n[r][1]);
+  return ((k + t.b[r][2]) * ny + (j + t.b[r][1])) * nx * comps + (int64_t)t.b[r][0] * comps + x;
+}
+
 // Point-to-point transport between neighbours + the few collectives of the setup.  Two implementations:
 // RCCL send/recv over xGMI on the caller's stream (one process per GPU), and host callbacks (the library stages
 // through pinned host buffers; gloo in the tests, where several ranks share one card).
@@ -506,6 +561,9 @@ struct HaloRegions;
 struct HaloSpace;
 // the regions of a vector of space `s` against the packed buffer: mode 0 buf = v (pack), 1 v = buf (unpack), 2 v += buf (vector_ops.hip)
 void halo_regions_copy(double *v, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode, hipStream_t stream);
+// ... of a FLOAT vector against the same buffer of doubles: mode 0 buf = v widened (pack), 1 v = buf narrowed (unpack).  float ->
+// double -> float is exact, and the wire carries what it carries for a double vector of the space: same messages, same counts.
+void halo_regions_copy(float *v, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode, hipStream_t stream);
 // the owned sub-box (or the whole local box) of a vector of space `s` against the contiguous buf: mode 0 buf = v, 1 v = buf
 void halo_box_copy(double *v, HaloSpace const &s, bool owned_only, double *buf, int mode, hipStream_t stream);
 void gather_indexed(int64_t n, double const *in, int32_t const *index, double *out, hipStream_t stream); // out[i] = in[index[i]]
@@ -626,44 +684,20 @@ struct HipHandle
   // o in {-1, 0, 1}^3 gets one message.  Along an axis with o_d = -1 / +1 the message spans the `width` owned layers next to that
   // neighbour (forward: sent; reverse: added to) resp. the `width` ghost layers beyond them (forward: received; reverse: sent);
   // along an axis with o_d = 0 it spans the owned range.
-  void exchange_box(HaloSpace const &s, double *v, bool reverse, hipStream_t st)
+  // (T = float, forward only: the regions are widened into the same staging buffers and narrowed out of them)
+  template <typename T>
+  void exchange_box(HaloSpace const &s, T *v, bool reverse, hipStream_t st)
   {
+    static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "halo exchange of double or float vectors");
+    if (!std::is_same<T, double>::value && reverse)
+      throw std::runtime_error("internal: float vectors have no reverse-add exchange");
     HaloRegions own, ghost;
     int peers[26];
     int64_t counts[26];
-    int64_t total = 0;
-    for (int oz = -1; oz <= 1; ++oz)
-      for (int oy = -1; oy <= 1; ++oy)
-        for (int ox = -1; ox <= 1; ++ox)
-        {
-          const int o[3] = {ox, oy, oz};
-          if (ox == 0 && oy == 0 && oz == 0)
-            continue;
-          bool exists = true;
-          for (int d = 0; d < 3; ++d)
-            if ((o[d] < 0 && !s.low(d)) || (o[d] > 0 && !s.high(d)))
-              exists = false;
-          if (!exists)
-            continue;
-          const int r = own.count;
-          int64_t n = s.comps;
-          for (int d = 0; d < 3; ++d)
-          {
-            const int o0 = (int)s.own0(d), o1 = (int)(s.own0(d) + s.own_n(d)), w = s.width;
-            own.b[r][d] = o[d] < 0 ? o0 : (o[d] > 0 ? o1 - w : o0);
-            ghost.b[r][d] = o[d] < 0 ? o0 - w : (o[d] > 0 ? o1 : o0);
-            own.n[r][d] = ghost.n[r][d] = o[d] == 0 ? o1 - o0 : w;
-            n *= own.n[r][d];
-          }
-          own.off[r] = ghost.off[r] = total;
-          peers[r] = comm.rank + ox * comm.stride(0) + oy * comm.stride(1) + oz * comm.stride(2);
-          counts[r] = n;
-          total += n;
-          own.count = ghost.count = r + 1;
-        }
+    const int stride[3] = {comm.stride(0), comm.stride(1), comm.stride(2)};
+    const int64_t total = halo_box_messages(s, comm.rank, stride, own, ghost, peers, counts);
     if (own.count == 0)
       return;
-    own.off[own.count] = ghost.off[own.count] = total;
     int64_t each = 0;
     double *send = staging_reserve((total + 1) / 2 + 1, st, each), *recv = send + 2 * each;
     double const *send_ptr[26];
@@ -683,31 +717,38 @@ struct HipHandle
   // contiguous runs of the vector (lexicographic layers): the transport sends from and receives into the vector itself
   // -- no packing, no staging copies (round 2 moved every layer through a staging buffer: four device copies per exchange).
   // A box packs the regions of all its neighbours (exchange_box).
-  void exchange_on(HaloSpace const &s, double *v, hipStream_t pack_stream, hipStream_t st, bool split)
+  // A float vector always takes the packed path, a slab's too: its layers are no contiguous runs of doubles.  The messages are
+  // those of the double vector of the space (halo_box_messages).
+  template <typename T>
+  void exchange_on(HaloSpace const &s, T *v, hipStream_t pack_stream, hipStream_t st, bool split)
   {
-    const int64_t n = (int64_t)s.width * s.layer_elems;
-    double const *send_low = v + s.owned_begin * s.layer_elems, *send_high = v + (s.owned_begin + s.owned_count - s.width) * s.layer_elems;
-    double *recv_low = v + (s.owned_begin - s.width) * s.layer_elems, *recv_high = v + (s.owned_begin + s.owned_count) * s.layer_elems;
     if (split)
     {
       // the boundary layers are final on `pack_stream` at this point: the transport stream may read them from here on
       MFMG_HIP_CHECK(hipEventRecord(ev_packed, pack_stream));
       MFMG_HIP_CHECK(hipStreamWaitEvent(st, ev_packed, 0));
     }
-    if (s.split_xy())
+    if (s.split_xy() || !std::is_same<T, double>::value)
     {
       exchange_box(s, v, false, st);
       return;
     }
-    if (!s.has_low && !s.has_high)
-      return;
-    comm.transport->sendrecv(comm.rank - comm.stride(2), comm.rank + comm.stride(2), send_low, recv_low, s.has_low ? n : 0, send_high,
-                             recv_high, s.has_high ? n : 0, st);
-    ++comm.n_exchanges;
-    comm.n_doubles_sent += (s.has_low ? n : 0) + (s.has_high ? n : 0);
+    if constexpr (std::is_same<T, double>::value)
+    {
+      const int64_t n = (int64_t)s.width * s.layer_elems;
+      double const *send_low = v + s.owned_begin * s.layer_elems, *send_high = v + (s.owned_begin + s.owned_count - s.width) * s.layer_elems;
+      double *recv_low = v + (s.owned_begin - s.width) * s.layer_elems, *recv_high = v + (s.owned_begin + s.owned_count) * s.layer_elems;
+      if (!s.has_low && !s.has_high)
+        return;
+      comm.transport->sendrecv(comm.rank - comm.stride(2), comm.rank + comm.stride(2), send_low, recv_low, s.has_low ? n : 0, send_high,
+                               recv_high, s.has_high ? n : 0, st);
+      ++comm.n_exchanges;
+      comm.n_doubles_sent += (s.has_low ? n : 0) + (s.has_high ? n : 0);
+    }
   }
   // refresh the ghost layers of a distributed vector (no-op on one rank / for local spaces)
-  void exchange(int space, double *v)
+  template <typename T>
+  void exchange(int space, T *v)
   {
     if (!comm.enabled() || space <= 0)
       return;
@@ -719,7 +760,8 @@ struct HipHandle
   //          transport and unpacks into the ghost layers;
   //   end:   `stream` waits for the unpacking.
   // Between the two calls `stream` must not read the ghost layers of `v` nor write its boundary layers.
-  void exchange_begin(int space, double *v)
+  template <typename T>
+  void exchange_begin(int space, T *v)
   {
     if (!comm.enabled() || space <= 0)
       return;
@@ -763,13 +805,15 @@ struct HipHandle
   // A whole exchange on the exchange stream, behind what `stream` has enqueued so far; `stream` goes on and waits for it with
   // exchange_async_wait() where it needs the ghost entries (the right-hand side of a cycle: prefetch_rhs).  In between `stream`
   // must not read the ghost entries of `v` nor write its boundary layers.
-  void exchange_async(int space, double *v)
+  template <typename T>
+  void exchange_async(int space, T *v)
   {
     if (!comm.enabled() || space <= 0)
       return;
     exchange_async(space_checked(space), v);
   }
-  void exchange_async(HaloSpace const &s, double *v)
+  template <typename T>
+  void exchange_async(HaloSpace const &s, T *v)
   {
     hipStream_t cs = exchange_stream();
     if (ev_async == nullptr)

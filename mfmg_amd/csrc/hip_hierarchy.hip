@@ -642,10 +642,13 @@ HipMatrixFreeOperator::HipMatrixFreeOperator(std::shared_ptr<HipMatrixFreeMeshEv
 // One operator application of a distributed run: the tiles that do not read a ghost plane run while the
 // boundary planes travel on the second stream; the tiles next to the ghost planes follow (slabs: at most four z-tiles;
 // boxes: a shell of tiles along all three axes).
-void HipMatrixFreeOperator::apply_mode(MfMode mode, MfOperands<double> const &v) const
+// One body for the FP64 operator of the hierarchy and the FP32 operator of HipFloatFineLevel: the same regions, the same exchanges
+// on the same streams (a float x travels widened, HipHandle::exchange_on).
+namespace
 {
-  HipHandle &handle = get_hip_handle();
-  auto op = _mesh_evaluator->get_device_operator();
+template <typename T>
+void distributed_apply_mode(HipHandle &handle, MatrixFreeLaplaceDevice<T> const *op, MfMode mode, MfOperands<T> const &v)
+{
   auto whole = [&] { op->launch_region(mode, v, MfTileRegion::whole()); };
   // The shell around the interior tiles is ONE launch over a compact list of its tiles (MfTileRegion::outside_of: z slabs, y slabs, x
   // slabs and the tail columns; consecutive workgroups, consecutive tiles, so that the XCDs share it evenly), enqueued on the
@@ -731,13 +734,19 @@ void HipMatrixFreeOperator::apply_mode(MfMode mode, MfOperands<double> const &v)
   }
   if (!interior)
   {
-    handle.exchange(1, const_cast<double *>(v.x));
+    handle.exchange(1, const_cast<T *>(v.x));
     whole();
     return;
   }
-  handle.exchange_begin(1, const_cast<double *>(v.x));
+  handle.exchange_begin(1, const_cast<T *>(v.x));
   op->launch_region(mode, v, MfTileRegion::box(lo, hi));
   shell(lo, hi, nt);
+}
+} // namespace
+
+void HipMatrixFreeOperator::apply_mode(MfMode mode, MfOperands<double> const &v) const
+{
+  distributed_apply_mode<double>(get_hip_handle(), _mesh_evaluator->get_device_operator().get(), mode, v);
 }
 
 void HipMatrixFreeOperator::apply_local(DVector const &x, DVector &y) const
@@ -1221,8 +1230,83 @@ HipFloatFineLevel::HipFloatFineLevel(HipHandle &handle, mfmg_hip_mesh_desc const
   // starts from a zeroed x
   _op.set_fused_reference(_smoother->sweep_reference());
   const int fused = _smoother->fused_terms();
-  _schedule = plan_sweeps(_smoother->coefficients(), fused, largest_sweep(fused, [&](int K) { return _op.fused_sweep_available(K); }),
-                          false);
+  int offered = largest_sweep(fused, [&](int K) { return _op.fused_sweep_available(K); });
+  // Several ranks: the sweep decides the exchanges (x once per sweep, as many planes deep as it has terms; b one plane less), so
+  // the ranks run the sweep that every one of them offers -- this operator's offer, not the FP64 smoother's agreement: the
+  // materials of the ranks may differ, and the float sweep has other tiles.  ONE collective that every rank reaches here.
+  // (... and on the sweep from x_0 = 0 that spares the first pre-smoothing step of a preconditioner application the exchange of x,
+  // encoded as in HipSmoother: 2 K + z.  One rank keeps zeroing x: its cycle is what it was.)
+  bool from_zero = false;
+  if (handle.comm.enabled())
+  {
+    const double mine = 2. * offered + (offered == 3 && _op.fused_zero_guess_available(3) ? 1. : 0.);
+    const int agreed = (int)-handle.allreduce_max(-mine);
+    ASSERT_THROW(agreed / 2 <= offered && agreed / 2 <= handle.comm.sweep_terms(), "internal: the ranks agreed on a sweep this rank cannot run");
+    offered = agreed / 2;
+    from_zero = (agreed & 1) != 0;
+  }
+  _schedule = plan_sweeps(_smoother->coefficients(), fused, offered, from_zero);
+  // (several ranks: a polynomial longer than the agreed sweep starts with that sweep -- two terms where the ranks hold one ghost
+  // agglomerate below -- and goes on term by term, as the in-place FP64 smoother does there)
+  if (handle.comm.enabled() && _schedule.out_of_place == 0 && offered >= 2 && _smoother->coefficients()[0].first == 0. &&
+      (int)_smoother->coefficients().size() > offered)
+    _schedule.out_of_place = std::min(offered, fused);
+  _b_ghost_width = handle.comm.enabled() && _schedule.out_of_place > 0 ? _schedule.out_of_place - 1 : 0;
+}
+
+// One application of the FP32 operator.  Several ranks: as HipMatrixFreeOperator::apply_mode -- x is exchanged one plane deep, the
+// tiles that read no ghost plane run beside the exchange, the shell behind it.
+void HipFloatFineLevel::launch(MfMode mode, MfOperands<float> const &v) const
+{
+  if (_op.handle().comm.enabled())
+    distributed_apply_mode<float>(_op.handle(), &_op, mode, v);
+  else
+    _op.launch_region(mode, v, MfTileRegion::whole());
+}
+
+void HipFloatFineLevel::vmult(float const *x, float *y) const { launch(MfMode::apply, {x, nullptr, nullptr, 0.f, 0.f, y}); }
+
+void HipFloatFineLevel::residual(float const *x, float const *b, float *res) const
+{
+  launch(MfMode::residual, {x, b, nullptr, 0.f, 0.f, res});
+}
+
+void HipFloatFineLevel::smoother_step(float const *b, float const *x, float const *x_prev, float alpha, float beta, float *out) const
+{
+  launch(mf_smoother_mode(x_prev, alpha), {x, b, x_prev, alpha, beta, out});
+}
+
+// the ghost entries of b, `width` planes deep, current on the compute stream (the sweep reads b at the ghost DoFs it computes)
+void HipFloatFineLevel::need_b_ghosts(float const *b, int width) const
+{
+  HipHandle &hd = _op.handle();
+  if (_b_in_flight == b)
+  {
+    hd.exchange_async_wait();
+    _b_fresh = b;
+    _b_in_flight = nullptr;
+  }
+  if (_b_fresh != b || _b_fresh_width < width)
+  {
+    hd.exchange_on(hd.fine_space(std::max(width, _b_ghost_width)), const_cast<float *>(b), hd.stream, hd.stream, false);
+    _b_fresh_width = std::max(width, _b_ghost_width);
+    _b_fresh = _b_of_cycle == b ? b : nullptr; // (fresh only while the cycle that owns this vector is running)
+  }
+}
+
+// Several smoother terms in one sweep.  Several ranks: as HipMatrixFreeOperator::smoother_sweep -- x travels n_terms planes deep,
+// once; b n_terms - 1 planes deep, once per cycle; the ghost DoFs next to the box are computed redundantly.
+void HipFloatFineLevel::smoother_sweep(int n_terms, float const *alpha, float const *beta, float const *b, float const *x, float *out,
+                                       float *out_prev) const
+{
+  HipHandle &hd = _op.handle();
+  if (hd.comm.enabled())
+  {
+    ASSERT_THROW(n_terms <= hd.comm.sweep_terms(), "internal: more terms per sweep than the ranks hold ghost planes for");
+    hd.exchange_on(hd.fine_space(n_terms), const_cast<float *>(x), hd.stream, hd.stream, false);
+    need_b_ghosts(b, n_terms - 1);
+  }
+  _op.smoother_sweep(n_terms, alpha, beta, b, x, out, out_prev);
 }
 
 // x_out <- x_in - B^-1 (A x_in - b) on two different vectors, with the polynomial of the FP64 smoother
@@ -1230,9 +1314,9 @@ void HipFloatFineLevel::smooth_to(float const *b, float const *x_in, float *x_ou
 {
   run_polynomial<float>(
       _smoother->coefficients(), _schedule.out_of_place, x_in, x_out, [&](int i) { return (i == 0 ? _scratch_a : _scratch_b).data(); },
-      [&](float const *x, float const *x_prev, float alpha, float beta, float *out) { _op.smoother_step(b, x, x_prev, alpha, beta, out); },
+      [&](float const *x, float const *x_prev, float alpha, float beta, float *out) { smoother_step(b, x, x_prev, alpha, beta, out); },
       [&](int K, float const *alpha, float const *beta, float const *x, float *out, float *out_prev) {
-        _op.smoother_sweep(K, alpha, beta, b, x, out, out_prev);
+        smoother_sweep(K, alpha, beta, b, x, out, out_prev);
       });
 }
 
@@ -1243,12 +1327,17 @@ void HipFloatFineLevel::apply(float const *b, float *x) const
   const int64_t n = _op.n_dofs();
   auto const &fine = *levels[0].get_operator();
   auto const &coarse = *levels[1].get_operator();
+  const bool distributed = hd.comm.enabled();
   if (_work.size() == 0)
   {
     _scratch_a.resize(n);
     _scratch_b.resize(n);
     _res.resize(n);
     _work.resize(n);
+    if (distributed)
+      // (ghost entries beyond what an exchange refreshes are read by no kernel's result, but they are read: no NaN there)
+      for (DeviceBuffer<float> *buf : {&_scratch_a, &_scratch_b, &_res, &_work})
+        MFMG_HIP_CHECK(hipMemsetAsync(buf->data(), 0, sizeof(float) * n, hd.stream));
     _res64 = fine.build_range_vector();
     _corr64 = fine.build_range_vector();
   }
@@ -1258,25 +1347,52 @@ void HipFloatFineLevel::apply(float const *b, float *x) const
     _b_coarse = coarse.build_range_vector();
     _x_coarse = coarse.build_range_vector();
   }
+  // Several ranks: the ghost entries of b the sweeps read travel on the exchange stream from the start of the cycle, as the FP64
+  // cycle sends them (HipMatrixOperator::prefetch_rhs); the first sweep waits for them.  Without sweeps nobody reads them.
+  _b_of_cycle = b;
+  _b_fresh = _b_in_flight = nullptr;
+  if (distributed && _b_ghost_width > 0 && hd.overlap_exchange && _hierarchy.n_smoothing_steps() > 0)
+  {
+    hd.exchange_async(hd.fine_space(_b_ghost_width), const_cast<float *>(b));
+    _b_fresh_width = _b_ghost_width;
+    _b_in_flight = b;
+  }
   // the iterate alternates between x and a work vector, so that no application ends in a copy
   float *it = x, *other = _work.data();
+  unsigned int first_step = 0;
   auto smooth = [&] {
-    for (unsigned int i = 0; i < _hierarchy.n_smoothing_steps(); ++i)
+    for (unsigned int i = first_step; i < _hierarchy.n_smoothing_steps(); ++i)
     {
       smooth_to(b, it, other);
       std::swap(it, other);
     }
+    first_step = 0;
   };
   if (_hierarchy.is_preconditioner())
-    MFMG_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(float) * n, hd.stream));
+  {
+    if (_schedule.from_zero && _hierarchy.n_smoothing_steps() > 0)
+    {
+      // (several ranks, agreed at construction) the first pre-smoothing step as one sweep that does not read x_0 = 0: x is zero on
+      // every rank, its ghost entries need no exchange; b as in smoother_sweep
+      float alpha[3], beta[3];
+      first_terms(_smoother->coefficients(), 3, alpha, beta);
+      ASSERT_THROW(_op.fused_zero_guess_available(3), "internal: the agreed sweep from zero was refused");
+      need_b_ghosts(b, 2);
+      _op.smoother_sweep(3, alpha, beta, b, nullptr, other, nullptr);
+      std::swap(it, other);
+      first_step = 1;
+    }
+    else
+      MFMG_HIP_CHECK(hipMemsetAsync(x, 0, sizeof(float) * n, hd.stream));
+  }
   smooth();
   auto restrictor = levels[1].get_restrictor();
   auto hip_restrictor = std::dynamic_pointer_cast<HipMatrixOperator const>(restrictor);
-  // b_c = R (A x - b): one pass over the FP32 vectors where the restrictor holds the rows of R A, otherwise the FP32
-  // residual, widened, and the restriction
+  // b_c = R (A x - b): one pass over the FP32 vectors where the restrictor holds the rows of R A (one rank), otherwise the FP32
+  // residual, widened, and the restriction -- which exchanges the ghost entries of the widened residual itself
   if (!(hip_restrictor && hip_restrictor->restrict_residual_f32(fine, it, b, *_b_coarse)))
   {
-    _op.residual(it, b, _res.data());
+    residual(it, b, _res.data());
     vec::widen(hd, n, _res.data(), _res64->get_values());
     restrictor->apply(*_res64, *_b_coarse);
   }
@@ -1286,6 +1402,9 @@ void HipFloatFineLevel::apply(float const *b, float *x) const
   smooth();
   if (it != x)
     MFMG_HIP_CHECK(hipMemcpyAsync(x, it, sizeof(float) * n, hipMemcpyDeviceToDevice, hd.stream));
+  if (_b_in_flight != nullptr)
+    hd.exchange_async_wait(); // (no sweep waited: the exchange must still be over before the caller touches b)
+  _b_of_cycle = _b_fresh = _b_in_flight = nullptr;
 }
 
 // ---- HipSolver -----------------------------------------------------------------

@@ -337,21 +337,39 @@ class Hierarchy;
 // "fine level precision" float: Hierarchy::apply of a two-level hierarchy (hierarchy.hpp:246-309) with the fine level in FP32.
 // Pre-smoother, residual and post-smoother run on float vectors through an FP32 instance of the matrix-free operator (the
 // polynomial of the FP64 smoother); the residual is widened, restricted, solved for and prolongated in FP64, and the
-// correction is subtracted from the float iterate.  One rank.
+// correction is subtracted from the float iterate.
+// Several ranks: the float vectors are the rank's local vectors.  The FP32 operator exchanges x as the FP64 one does (one plane
+// per application beside the interior tiles; once per sweep, as many planes deep as the sweep has terms; b one plane less, once
+// per cycle), widened to double on the wire (HipHandle::exchange_on); the coarse part exchanges for itself in FP64.
 class HipFloatFineLevel
 {
 public:
   HipFloatFineLevel(HipHandle &handle, mfmg_hip_mesh_desc const &mesh, Hierarchy<DVector> const &hierarchy);
   // one V-cycle on the FP32 vectors b, x of the fine DoFs
   void apply(float const *b, float *x) const;
+  // the FP32 operator of the level (owned entries; ghost entries of x are exchanged here): y = A x, res = A x - b,
+  // out = x + alpha (x - x_prev) - beta D^-1 (A x - b)
+  void vmult(float const *x, float *y) const;
+  void residual(float const *x, float const *b, float *res) const;
+  void smoother_step(float const *b, float const *x, float const *x_prev, float alpha, float beta, float *out) const;
+  int64_t n_dofs() const { return _op.n_dofs(); }
+  // terms the out-of-place smoother runs as one sweep (0: one launch per term)
+  int sweep_terms() const { return _schedule.out_of_place; }
 
 private:
+  void launch(MfMode mode, MfOperands<float> const &v) const;
+  void smoother_sweep(int n_terms, float const *alpha, float const *beta, float const *b, float const *x, float *out, float *out_prev) const;
+  void need_b_ghosts(float const *b, int width) const;
   void smooth_to(float const *b, float const *x_in, float *x_out) const;
 
   Hierarchy<DVector> const &_hierarchy;
   std::shared_ptr<HipSmoother const> _smoother;
   MatrixFreeLaplaceDevice<float> _op;
-  SweepSchedule _schedule; // of this operator's offer: out of place only
+  SweepSchedule _schedule; // of this operator's offer (several ranks: of what every rank's offers): out of place only
+  int _b_ghost_width = 0;  // several ranks: planes of ghost entries of b the sweeps read (0: none)
+  // the right-hand side of the cycle that is running: in flight on the exchange stream / fresh (HipHandle::rhs_*, for float)
+  mutable float const *_b_of_cycle = nullptr, *_b_in_flight = nullptr, *_b_fresh = nullptr;
+  mutable int _b_fresh_width = 0;
   mutable DeviceBuffer<float> _scratch_a, _scratch_b, _work, _res;
   mutable std::shared_ptr<DVector> _res64, _corr64, _b_coarse, _x_coarse;
 };

@@ -125,6 +125,21 @@ __global__ void regions_copy_kernel(double *v, int comps, int64_t nx, int64_t ny
   }
 }
 
+// the same regions of a FLOAT vector against the packed buffer of doubles: mode 0 buf = v widened, 1 v = buf narrowed (exact both
+// ways for what a float holds; the forward exchange only, so no region is added to)
+__global__ void regions_copy_f32_kernel(float *v, int comps, int64_t nx, int64_t ny, HaloRegions t, double *buf, int mode)
+{
+  const int64_t n = t.off[t.count];
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+  {
+    float *p = v + halo_region_entry(t, comps, nx, ny, i);
+    if (mode == 0)
+      buf[i] = (double)*p;
+    else
+      *p = (float)buf[i];
+  }
+}
+
 // the sub-box [b0, b0 + bn) of the lexicographic array of nodes `dims` (comps entries per node) against the contiguous buf
 // (mode 0: buf = v, 1: v = buf)
 __global__ void box_copy_kernel(double *v, int comps, int64_t nx, int64_t ny, int64_t bx0, int64_t by0, int64_t bz0, int64_t bnx,
@@ -153,6 +168,12 @@ __global__ void widen_kernel(int64_t n, float const *in, double *out)
 {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = (double)in[i];
+}
+
+__global__ void narrow_kernel(int64_t n, double const *in, float *out)
+{
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (float)in[i];
 }
 
 __global__ void subtract_narrowed_kernel(int64_t n, double const *c, float *x)
@@ -313,6 +334,14 @@ void widen(HipHandle &h, int64_t n, float const *in, double *out)
   MFMG_HIP_CHECK(hipGetLastError());
 }
 
+void narrow(HipHandle &h, int64_t n, double const *in, float *out)
+{
+  if (n <= 0)
+    return;
+  hipLaunchKernelGGL(narrow_kernel, dim3(stream_blocks(n)), dim3(block_size), 0, h.stream, n, in, out);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
 void subtract_narrowed(HipHandle &h, int64_t n, double const *correction, float *x)
 {
   if (n <= 0)
@@ -391,6 +420,24 @@ void halo_regions_copy(double *v, HaloSpace const &s, HaloRegions const &regions
     return;
   hipLaunchKernelGGL(vec::regions_copy_kernel, dim3(n_blocks_for(n, block_size, 4096)), dim3(block_size), 0, stream, v, s.comps, s.n_xy[0],
                      s.n_xy[1], regions, buf, mode);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void halo_regions_copy(float *v, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode, hipStream_t stream)
+{
+  s.check();
+  if (mode != 0 && mode != 1)
+    throw std::runtime_error("internal: float vectors are packed and unpacked, not added to");
+  const int64_t n = regions.count > 0 ? regions.off[regions.count] : 0;
+  if (n <= 0)
+    return;
+  // every region lies inside the local box: an entry outside it would be a write beyond the vector
+  for (int r = 0; r < regions.count; ++r)
+    for (int d = 0; d < 3; ++d)
+      if (regions.b[r][d] < 0 || regions.n[r][d] < 0 || regions.b[r][d] + regions.n[r][d] > s.dim(d))
+        throw std::runtime_error("internal: a halo region reaches beyond the local box (exchange wider than the ghost layers held)");
+  hipLaunchKernelGGL(vec::regions_copy_f32_kernel, dim3(n_blocks_for(n, block_size, 4096)), dim3(block_size), 0, stream, v, s.comps,
+                     s.n_xy[0], s.n_xy[1], regions, buf, mode);
   MFMG_HIP_CHECK(hipGetLastError());
 }
 

@@ -37,6 +37,8 @@ void select_rows(HipHandle &h, int const dims[3], int n_comp, int block, int con
 // fine level in FP32 around an FP64 coarse hierarchy: out = (double) in, and x -= (float) correction
 void widen(HipHandle &h, int64_t n, float const *in, double *out);
 void subtract_narrowed(HipHandle &h, int64_t n, double const *correction, float *x);
+// out = (float) in (the Krylov vector an FP32 preconditioner reads, on ranks: the whole local vector, ghost entries included)
+void narrow(HipHandle &h, int64_t n, double const *in, float *out);
 
 // Deterministic two-stage dot product; the result lands in device slot
 // `result_dev[slot]` (no host synchronisation).

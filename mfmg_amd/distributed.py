@@ -353,6 +353,16 @@ class HaloTransport:
         """One halo exchange of a vector of `space` (the cycle does this by itself; for tests)."""
         check(self._lib.mfmg_hip_context_exchange(self.ctx.handle, space, v.data_ptr(), 1 if reverse else 0))
 
+    def exchange_f32(self, space: int, v: torch.Tensor, width: int = 1):
+        """Context.exchange_f32: the forward exchange of a float32 vector of the fine DoF space, `width` planes deep."""
+        self.ctx.exchange_f32(space, v, width)
+
+    def box_messages(self, space: int, width: int = 1):
+        """The messages of one box exchange of `space`, `width` layers deep, as the library lays them out (host arithmetic only):
+        (peers, counts, send_entries, recv_entries) -- positions in the local vector, message after message."""
+        return box_messages(self.box(space), [self.part.coord[d] > 0 for d in range(3)],
+                            [self.part.coord[d] + 1 < self.part.grid[d] for d in range(3)], width, self.rank, self.part.grid)
+
     def reflect(self, delay_us: float = 0.0):
         """MEASUREMENT: from here on the messages of this rank are mirrored on the device (no partner is involved any more):
         its share of a distributed cycle with a wire that costs nothing -- or `delay_us` of stream time per grouped send/recv and
@@ -397,3 +407,19 @@ class HaloTransport:
 
     def owned_norm(self, x: torch.Tensor, space: int = 1) -> float:
         return self.owned_dot(x, x, space) ** 0.5
+
+
+def box_messages(box: dict, has_low, has_high, width: int, rank: int, grid):
+    """mfmg_hip_halo_box_messages for a space described as HaloTransport.box does (dims, own0, own_n, comps): numpy arrays
+    (peers, counts, send_entries, recv_entries).  No GPU, no context."""
+    import numpy as np
+    lib = _lib.load()
+    i64x3, i32x3 = C.c_int64 * 3, C.c_int32 * 3
+    n, peers, counts = C.c_int32(), (C.c_int32 * 26)(), (C.c_int64 * 26)()
+    args = (i64x3(*box["dims"]), i64x3(*box["own0"]), i64x3(*box["own_n"]), i32x3(*[int(bool(v)) for v in has_low]),
+            i32x3(*[int(bool(v)) for v in has_high]), int(box["comps"]), int(width), int(rank), i32x3(*grid))
+    check(lib.mfmg_hip_halo_box_messages(*args, C.byref(n), peers, counts, None, None, 0))
+    total = int(sum(counts[: n.value]))
+    send, recv = np.empty(total, dtype=np.int64), np.empty(total, dtype=np.int64)
+    check(lib.mfmg_hip_halo_box_messages(*args, C.byref(n), peers, counts, send.ctypes.data, recv.ctypes.data, total))
+    return np.array(peers[: n.value]), np.array(counts[: n.value]), send, recv

@@ -128,6 +128,9 @@ def load() -> C.CDLL:
         "mfmg_hip_context_transport_selftest": (C.c_int, [vp, i64, P(dbl)]),
         "mfmg_hip_context_exchange": (C.c_int, [vp, i32, vp, C.c_int]),
         "mfmg_hip_context_owned_dot": (C.c_int, [vp, i32, vp, vp, P(dbl)]),
+        "mfmg_hip_context_exchange_f32": (C.c_int, [vp, i32, vp, C.c_int]),
+        "mfmg_hip_halo_box_messages": (C.c_int, [P(i64), P(i64), P(i64), P(i32), P(i32), i32, i32, i32, P(i32), P(i32), P(i32), P(i64),
+                                                 vp, vp, i64]),
         "mfmg_hip_context_halo_space": (C.c_int, [vp, i32, vp]),
         "mfmg_hip_context_set_overlap_exchange": (C.c_int, [vp, C.c_int]),
         "mfmg_hip_context_set_cell_constant_layout": (C.c_int, [vp, C.c_int]),
@@ -213,6 +216,8 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_permute": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
         "mfmg_hip_hierarchy_apply": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_apply_f32": (C.c_int, [vp, vp, vp]),
+        "mfmg_hip_hierarchy_operator_f32": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_float, C.c_float, vp]),
+        "mfmg_hip_hierarchy_sweep_terms_f32": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_hierarchy_vmult": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_solve_cg": (C.c_int, [vp, vp, vp, C.c_double, C.c_int32, P(C.c_int32), P(C.c_double), P(C.c_double), C.c_int32]),
         "mfmg_hip_hierarchy_solve_fgmres": (C.c_int, [vp, vp, vp, dbl, i32, i32, i32, P(i32), P(dbl), P(dbl), i32]),
