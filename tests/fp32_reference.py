@@ -16,13 +16,20 @@ Bound, per entry, with u = 2^-24:  |got - ref| <= k u mag.
 
 The constants k: the longest chain of float roundings behind one output, each rounding at most u times a magnitude that the
 sums above majorise (the weights of the interpolations are positive and sum to one per direction, sum_modes lambda = max|K|).
+
+Either precision: the unit roundoff is a property of the Reference (u = 2^-24 by default, 2^-53 for the FP64 kernels:
+test_gpu_fp64_fine_level.py, test_fp64_bound_bites.py).  At 2^-53 the cell matrices and the diagonal are formed in long double
+as well (exact Gauss points, the factors from the double cell sizes), and the reference's own roundings are part of the bound:
+k u mag + K_REF 2^-64 mag = (k + k_ref) u mag with k_ref = K_REF 2^-11 (Reference.k_ref; zero at 2^-24, where nothing changes).
 """
 import numpy as np
 
 import mfmg_oracle as O
 
 U32 = 2.0 ** -24
+U64 = 2.0 ** -53
 LD = np.longdouble
+ULD = 2.0 ** -64     # unit roundoff of a 64-bit significand (x86 extended precision); checked where a Reference is built at 2^-53
 
 # One coefficient per cell, arithmetic of the one-term kernel (cell_apply_cc): corner difference 1; mass matrix over p: the
 # difference `dlt` and the rounded constant 2/3 act on |i0| + |i1| where the result weighs them 2/3 : 1/3, so they count twice:
@@ -44,24 +51,81 @@ K_OP_GENERAL = 32
 # rounded 1, three sums 3, kd rounded 1, product 1, division 1) 7, beta D^-1 1, fma 1, the final rounding of the result 1: 12.
 # The x term sees the final rounding alone, the alpha term alpha rounded, the difference, the fma and the final rounding (4).
 K_EPILOGUE = 12
+# FP64 instances: the same templates, the same constants.  What is "rounded to float" above (the coefficient, beta, alpha) is
+# exact in double, which takes one off every chain; the constants 2/3, the Gauss weights and the mass-matrix entries are rounded
+# as before.  What does not carry over unchanged is the set-up on the host, done in double for either precision: in float its
+# result is rounded once more (the "rounded factor", "lambda rounded" and "kd rounded" above) and its own roundings are 2^-29 of
+# that; in double they are roundings like any other.  Written out (mf_cell_factors): f_d = h0 h1 h2 / 8 / h_d^2 4 roundings where
+# float has 1 (one-term kernel, one coefficient per cell: 16 - 1 + 3 = 18; mode space, lambda_6 = (f0 + f1 + f2) / 18 7 where float
+# has 1: 13 - 1 + 6 = 18); kd = 2 m00 m00 (f0 + f1 + f2) with m00 = A^2 + B^2 from the rounded Gauss weights.  These worst cases lie
+# above the constants kept here; the FP64 tests hold the kernels to the float counts all the same (a tighter rule, never a wider
+# one), and what they observe on an MI355X is written next to k in test_gpu_fp64_fine_level.py.
+#
+# The reference's own error at 2^-53, in roundings of 2^-64 behind one entry (every one at most 2^-64 times a magnitude the sums
+# of the bound majorise): a cell-matrix entry -- gradients from the rounded Gauss points 3, the factor 4, three directions 5, eight
+# Gauss points with their coefficients 16 -- 28; einsum over the 8 corners 15; np.add.at over the 8 cells 8; the epilogue
+# (difference with b, D^-1 with its own 28 + 8 + 1, two products, momentum 3, two sums) 45 per term, and the recurrence of the
+# sweep propagates them as the bound propagates the kernel's.  96 per term: 96 2^-11 = 0.047 of one unit of k.
+K_REF = 96
+# diagonal_inverse() in FP64 (mf_diagonal_kernel: a table K[q][m] = sum_d f_d g_d^2 made on the host in double, then
+# sum += c_q K[q][m] over 8 cells x 8 Gauss points and 1 / sum, all terms positive): f_d 4; g_d a product of two rounded Gauss
+# weights (1 - xi rounded again) 5, squared 11; two products 2; three directions 3: 20 per table entry; 64 accumulations; the
+# division 1: 85.  (The float instance does the same in double and rounds once: the 2 u of test_gpu_fp32_fine_level.py.)
+K_DINV_F64 = 85
+
+
+def _cell_tables_long(mesh):
+    """(G[q][d][i], f[d]) in long double: the gradients at the exact Gauss points, the factors from the double cell sizes."""
+    g = 1 / np.sqrt(LD(3))
+    pts = [(1 - g) / 2, (1 + g) / 2]
+    assert abs(float(pts[0]) - O.GAUSS_PTS[0]) < 1e-15 and abs(float(pts[1]) - O.GAUSS_PTS[1]) < 1e-15
+    dim, nq = mesh.dim, 2 ** mesh.dim
+    G = np.zeros((nq, dim, nq), dtype=LD)
+    for q in range(nq):
+        xi = [pts[(q >> d) & 1] for d in range(dim)]
+        for i in range(nq):
+            for d in range(dim):
+                v = LD(1)
+                for e in range(dim):
+                    bit = (i >> e) & 1
+                    v = v * ((LD(1) if bit else LD(-1)) if e == d else (xi[e] if bit else 1 - xi[e]))
+                G[q, d, i] = v
+    h = [LD(v) for v in mesh.h]
+    vol = LD(1)
+    for v in h:
+        vol = vol * v
+    f = np.array([vol / nq / (v * v) for v in h], dtype=LD)
+    return G, f
 
 
 class Reference:
     """Operator, diagonal and bounds of one mesh and coefficient table (`coef`: float64 [cells][2^dim])."""
 
-    def __init__(self, n, coef, constrained=None):
+    def __init__(self, n, coef, constrained=None, u=U32):
+        assert u in (U32, U64)
+        self.u = u
+        self.long_tables = u == U64
+        if self.long_tables:
+            # 63 fraction bits: 2^-11 of the FP64 unit roundoff.  Anything less and this reference cannot judge a double.
+            assert np.finfo(LD).nmant >= 63, "np.longdouble has no 64-bit significand here: no reference for the FP64 kernels"
+        self.k_ref = K_REF * ULD / u if self.long_tables else 0.0
         self.mesh = O.StructuredMesh(n)
         self.coef = np.asarray(coef, dtype=np.float64)
         self.cd = self.mesh.cell_dofs().astype(np.int64)
         self.con = self.mesh.constrained_mask() if constrained is None else np.asarray(constrained, dtype=bool)
         self.n_dofs = self.mesh.n_dofs
         self.cell_constant = bool((self.coef == self.coef[:, :1]).all())
-        self.Ke = O.cell_matrices(self.mesh, self.coef).astype(LD)                      # [c][i][j]
+        if self.long_tables:
+            self.G, self.f = _cell_tables_long(self.mesh)
+            self.Ke = np.einsum("cq,qij->cij", self.coef.astype(LD), np.einsum("d,qdi,qdj->qij", self.f, self.G, self.G))
+        else:
+            self.G, self.f = O.reference_gradients(self.mesh.dim), O.geometry_factors(self.mesh)
+            self.Ke = O.cell_matrices(self.mesh, self.coef).astype(LD)                  # [c][i][j]
         if self.mesh.dim == 3:
             self.kmax = np.abs(self.Ke).max(axis=(1, 2))
         else:
             # (2-D kernel: sum_q c_q K_q[m][n] term by term, the terms of one entry may differ in sign)
-            G, f = O.reference_gradients(2), O.geometry_factors(self.mesh)
+            G, f = self.G, self.f
             Kq = np.abs(np.einsum("d,qdi,qdj->qij", f, G, G))
             self.kmax = np.einsum("cq,qij->cij", self.coef, Kq).max(axis=(1, 2)).astype(LD)
         self.k_op = K_OP_CC if (self.cell_constant and self.mesh.dim == 3) else K_OP_GENERAL
@@ -70,9 +134,8 @@ class Reference:
 
     def dinv_from(self, coef, cells=None):
         """1 / diagonal (constrained: 1) in long double; `cells`: a mask of the cells that take part."""
-        G, f = O.reference_gradients(self.mesh.dim), O.geometry_factors(self.mesh)
-        K = np.einsum("d,qdi,qdi->qi", f, G, G)
-        dloc = np.einsum("cq,qi->ci", np.asarray(coef, dtype=np.float64), K).astype(LD)
+        K = np.einsum("d,qdi,qdi->qi", self.f, self.G, self.G)
+        dloc = np.einsum("cq,qi->ci", np.asarray(coef, dtype=np.float64).astype(K.dtype), K).astype(LD)
         if cells is not None:
             dloc = dloc * cells[:, None]
         d = np.zeros(self.n_dofs, dtype=LD)
@@ -119,14 +182,14 @@ class Reference:
         return m
 
     def unit_vmult(self, x):
-        return U32 * self.mag(x)
+        return self.u * self.mag(x)
 
     def unit_residual(self, x, b):
-        return U32 * (self.mag(x) + np.abs(np.asarray(b).astype(LD)))
+        return self.u * (self.mag(x) + np.abs(np.asarray(b).astype(LD)))
 
     def unit_step(self, x, b, xp, alpha, beta):
         ax, axp = np.abs(np.asarray(x).astype(LD)), (np.abs(np.asarray(xp).astype(LD)) if xp is not None else 0)
-        return U32 * (ax + abs(alpha) * (ax + axp) + abs(beta) * self.dinv * (self.mag(x) + np.abs(np.asarray(b).astype(LD))))
+        return self.u * (ax + abs(alpha) * (ax + axp) + abs(beta) * self.dinv * (self.mag(x) + np.abs(np.asarray(b).astype(LD))))
 
     def unit_sweep(self, its, b, alphas, betas):
         """Propagated bounds of x_1 .. x_K in units of k_step (multiply by self.k_step)."""
@@ -141,6 +204,10 @@ class Reference:
 
 def f32(a):
     return np.asarray(a).astype(np.float32)
+
+
+def f64(a):
+    return np.asarray(a).astype(np.float64)
 
 
 def beyond(got, ref, bound):
