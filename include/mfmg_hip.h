@@ -42,6 +42,8 @@ extern "C" {
  *      mfmg_hip_host_sendrecv_fn (rank -+ 1); added mfmg_hip_context_set_communicator_box, mfmg_hip_context_halo_box,
  *      mfmg_hip_context_exchange_volume
  *      (later in round 3 added mfmg_hip_context_use_reflecting_transport: no change of the version)
+ *      (added mfmg_hip_hierarchy_coarse_amg_setup_info and which = 3 of mfmg_hip_hierarchy_coarse_amg_get: additions, no change
+ *      of the version)
  * mfmg_hip_abi_version() returns the value the loaded library was built with. */
 #define MFMG_HIP_ABI_VERSION 3
 
@@ -577,7 +579,8 @@ int mfmg_hip_hierarchy_get_coarse_operator(mfmg_hip_hierarchy_t h, mfmg_hip_csr_
 int mfmg_hip_hierarchy_get_fine_operator(mfmg_hip_hierarchy_t h, mfmg_hip_csr_t *a_borrowed);
 /* levels of the multilevel coarse solver (0 when the coarse solver is direct / pcg): operator A_l, prolongator P_l,
  * its transpose as stored for the restriction (which = 0 / 1 / 2; a borrowed handle, valid until the next call) and the
- * Chebyshev bounds of its smoother */
+ * Chebyshev bounds of its smoother.  which = 3: the smoothed prolongator of the cycle, P~ = (I - beta D^-1 A_l) P_l, of the
+ * levels that apply prolongation and post-smoothing as one operator; MFMG_HIP_ERROR_NOT_IMPLEMENTED ("not built") on the others */
 int mfmg_hip_hierarchy_coarse_amg_levels(mfmg_hip_hierarchy_t h, int32_t *n_levels);
 /* distributed runs: index of the first level of the multilevel coarse solver that is gathered and solved redundantly on
  * every rank (-1: one rank); the levels before it are coupled across the ranks by halo exchanges */
@@ -585,6 +588,17 @@ int mfmg_hip_hierarchy_coarse_amg_gather_level(mfmg_hip_hierarchy_t h, int32_t *
 int mfmg_hip_hierarchy_coarse_amg_get(mfmg_hip_hierarchy_t h, int32_t level, int32_t which, mfmg_hip_csr_t *borrowed);
 int mfmg_hip_hierarchy_coarse_amg_smoother(mfmg_hip_hierarchy_t h, int32_t level, int32_t *degree, double *lambda_min,
                                            double *lambda_max);
+/* what the setup of the aggregation hierarchy did on `level`, MFMG_HIP_AMG_SETUP_INFO_FIELDS values:
+ *   [0]      reach of the level's operator in nodes (0: a hierarchy without a node grid)
+ *   [1..3]   probe period per axis of the prolongator P_l            (0: not probed)
+ *   [4..6]   probe period per axis of the next operator P^T A P      (0: not probed)
+ *   [7..9]   probe period per axis of the smoothed prolongator P~    (0: not probed, or none)
+ *   [10]     how the next operator was formed: 0 probes, 1 CSR product on the device, 2 product on the host
+ *   [11]     1: the level belongs to the replicated tail (built by the host code of one rank)
+ *   [12]     1: the level has a smoothed prolongator (which = 3 of mfmg_hip_hierarchy_coarse_amg_get)
+ * (the last level forms nothing: its periods are 0) */
+#define MFMG_HIP_AMG_SETUP_INFO_FIELDS 13
+int mfmg_hip_hierarchy_coarse_amg_setup_info(mfmg_hip_hierarchy_t h, int32_t level, int32_t *values, int32_t n_values);
 /* smoother polynomial actually used (degree, lambda_min, lambda_max) */
 int mfmg_hip_hierarchy_smoother_info(mfmg_hip_hierarchy_t h, int32_t *degree, double *lambda_min, double *lambda_max);
 /* polynomial terms the fine-level smoother runs as ONE sweep over the mesh (mf_cheb_fused.hip): by Smoother::apply (in place: the last

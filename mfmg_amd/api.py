@@ -744,6 +744,38 @@ class Hierarchy:
             out.append((A, P, cheb))
         return out
 
+    def coarse_amg_smoothed_prolongators(self):
+        """[P~_l or None] per level of the multilevel coarse solver: the smoothed prolongator of the cycle, (I - beta D^-1 A_l) P_l,
+        where the setup built one (levels that apply prolongation and post-smoothing as one operator)."""
+        out = []
+        for info in self.coarse_amg_setup_info():
+            Pt = None
+            if info["smoothed"]:
+                h = C.c_void_p()
+                check(self._lib.mfmg_hip_hierarchy_coarse_amg_get(self.handle, info["level"], 3, C.byref(h)))
+                Pt = SparseMatrixDevice(self.ctx, _handle=h, _borrowed=True, _keepalive=self).to_scipy()
+            out.append(Pt)
+        return out
+
+    _AMG_PRODUCTS = ("probes", "device product", "host product")
+
+    def coarse_amg_setup_info(self):
+        """What the setup of the aggregation hierarchy did, one dict per level: reach of the level's operator in nodes, probe
+        periods per axis of P, A_c and P~ (None: not probed), how the next operator was formed ("probes", "device product",
+        "host product"; None on the last level), whether the level is part of the replicated tail and whether it has a
+        smoothed prolongator."""
+        n = C.c_int32()
+        check(self._lib.mfmg_hip_hierarchy_coarse_amg_levels(self.handle, C.byref(n)))
+        out = []
+        for l in range(n.value):
+            v = (C.c_int32 * _lib.AMG_SETUP_INFO_FIELDS)()
+            check(self._lib.mfmg_hip_hierarchy_coarse_amg_setup_info(self.handle, l, v, _lib.AMG_SETUP_INFO_FIELDS))
+            period = lambda q: tuple(v[q:q + 3]) if any(v[q:q + 3]) else None
+            out.append({"level": l, "reach": v[0], "period_p": period(1), "period_a": period(4), "period_t": period(7),
+                        "coarse_operator": self._AMG_PRODUCTS[v[10]] if l + 1 < n.value else None,
+                        "replicated": bool(v[11]), "smoothed": bool(v[12])})
+        return out
+
     def coarse_amg_kernels(self, regular_rows=None):
         """[(level, which, rows, kernel kind, stencil classes, listed rows)] of the matrices of the multilevel coarse
         solver (which: 0 A_l, 1 P_l, 2 its stored transpose); regular_rows True / False switches the table-driven paths

@@ -171,7 +171,7 @@ void HipSolver::setup_amg_on_device(std::shared_ptr<SparseMatrixDevice<double>> 
       // ---- gather this level; the rest of the hierarchy is replicated (host setup of one rank)
       A.n_rows = A.n_cols = g.n_rows();
       a_op->get_matrix()->download(A.row_ptr, A.col, A.val);
-      finish_amg_replicated(a_op, std::move(A), std::move(B), g.space, g.s, opts, smoother_params);
+      finish_amg_replicated(a_op, std::move(A), std::move(B), g.space, g.s, opts, smoother_params, g.reach);
       break;
     }
     const double t0 = wall_now();
@@ -316,6 +316,13 @@ void HipSolver::setup_amg_on_device(std::shared_ptr<SparseMatrixDevice<double>> 
     L.restrictor->set_spaces(0, 0);        // P^T has entries in owned fine rows only ...
     L.restrictor->set_reverse_range_space(c.space); // ... and returns the sums of ghost aggregates to their owners
     L.smoother = std::make_shared<HipSmoother>(L.a, smoother_params);
+    L.reach = g.reach;
+    L.coarse_product = by_product ? AmgLevel::by_device_product : AmgLevel::by_probes;
+    for (int d = 0; d < 3; ++d)
+    {
+      L.period_p[d] = period_p[d];
+      L.period_a[d] = by_product ? 0 : period_a[d];
+    }
     // ---- P~ = (I - beta D^-1 A) P for a level that runs V(0,1) with a damped-Jacobi post-smoother: the correction of such a
     //      level is x = P x_c followed by x' = x - beta D^-1 (A x - b) = P~ x_c + beta D^-1 b.  Probing with the columns of P
     //      themselves: the columns of coarse nodes floor((blk - 1 + 2 R) / blk) + 1 apart are disjoint, R = 2 reach the reach of
@@ -385,6 +392,8 @@ void HipSolver::setup_amg_on_device(std::shared_ptr<SparseMatrixDevice<double>> 
       L.smoothed_prolongator = std::make_shared<HipMatrixOperator>(pt_smoothed);
       L.smoothed_prolongator->set_spaces(c.space, 0);
       L.smoothed_beta = beta;
+      for (int d = 0; d < 3; ++d)
+        L.period_t[d] = period_t[d];
       if (verbose)
         std::fprintf(stderr, "[mfmg_hip] amg level %d: smoothed prolongator of the cycle, %d probes, %lld entries, %.2f s\n", level, n_col_t,
                      (long long)pt_smoothed->n_nonzero_elements(), wall_now() - t2);
@@ -405,7 +414,7 @@ void HipSolver::setup_amg_on_device(std::shared_ptr<SparseMatrixDevice<double>> 
 // The level `a_op` (owned rows in `A`, local numbering; `geom` its nodes) becomes the first replicated level: its operator and near-null
 // vector are gathered, the remaining hierarchy is built by the host code of one rank, identically on every rank.
 void HipSolver::finish_amg_replicated(std::shared_ptr<HipMatrixOperator> a_op, HostCsr A, std::vector<double> B, int space,
-                                      HaloSpace const &geom, AmgOptions const &opts, std::shared_ptr<ptree> smoother_params)
+                                      HaloSpace const &geom, AmgOptions const &opts, std::shared_ptr<ptree> smoother_params, int reach)
 {
   HipHandle &h = _handle;
   const bool distributed = h.comm.enabled() && space > 0;
@@ -555,6 +564,11 @@ void HipSolver::finish_amg_replicated(std::shared_ptr<HipMatrixOperator> a_op, H
   for (size_t l = 0; l < host_levels.size(); ++l)
   {
     AmgLevel &L = _amg[first + l];
+    // (the host products need no reach; it is recorded by the rule the probed levels follow)
+    L.reach = reach;
+    reach = (blk - 1 + 3 * reach) / blk;
+    L.replicated = true;
+    L.coarse_product = AmgLevel::by_host_product;
     if (l == 0 && !distributed)
       L.a = a_op; // the operator the caller handed in (local = global)
     else

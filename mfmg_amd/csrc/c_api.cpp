@@ -2248,12 +2248,35 @@ int mfmg_hip_hierarchy_coarse_amg_get(mfmg_hip_hierarchy_t h, int32_t level, int
     require(borrowed != nullptr, "null argument");
     auto const &lv = coarse_solver_of(h)->amg_levels();
     require(level >= 0 && level < (int)lv.size(), "level out of range");
-    require(which >= 0 && which <= 2, "which must be 0 (A), 1 (P) or 2 (P^T as stored for the restriction)");
-    auto op = which == 0 ? lv[level].a : which == 1 ? lv[level].prolongator : lv[level].restrictor;
+    require(which >= 0 && which <= 3, "which must be 0 (A), 1 (P), 2 (P^T as stored for the restriction) or 3 (the smoothed prolongator of the cycle)");
+    auto op = which == 0 ? lv[level].a : which == 1 ? lv[level].prolongator : which == 2 ? lv[level].restrictor : lv[level].smoothed_prolongator;
+    if (which == 3 && op == nullptr)
+      throw NotImplementedExc("the smoothed prolongator of this level is not built");
     require(op != nullptr, "the last level has no transfer operators");
     h->amg_view.op = op;
     h->amg_view.borrowed = true;
     *borrowed = &h->amg_view;
+  });
+}
+
+int mfmg_hip_hierarchy_coarse_amg_setup_info(mfmg_hip_hierarchy_t h, int32_t level, int32_t *values, int32_t n_values)
+{
+  return guarded([&] {
+    require(values != nullptr && n_values >= MFMG_HIP_AMG_SETUP_INFO_FIELDS, "the buffer must hold MFMG_HIP_AMG_SETUP_INFO_FIELDS values");
+    auto const &lv = coarse_solver_of(h)->amg_levels();
+    require(level >= 0 && level < (int)lv.size(), "level out of range");
+    auto const &L = lv[level];
+    int32_t *v = values;
+    *v++ = L.reach;
+    for (int d = 0; d < 3; ++d)
+      *v++ = L.period_p[d];
+    for (int d = 0; d < 3; ++d)
+      *v++ = L.period_a[d];
+    for (int d = 0; d < 3; ++d)
+      *v++ = L.period_t[d];
+    *v++ = L.coarse_product;
+    *v++ = L.replicated ? 1 : 0;
+    *v++ = L.smoothed_prolongator != nullptr ? 1 : 0;
   });
 }
 

@@ -1571,8 +1571,12 @@ HipSolver::HipSolver(HipHandle &handle, std::shared_ptr<Operator<DVector> const>
     matrix->download(A0.row_ptr, A0.col, A0.val);
     auto host_levels = build_aggregation_hierarchy(std::move(A0), std::move(b0), opts, local_grid.valid(n) ? &local_grid : nullptr);
     _amg.resize(host_levels.size());
+    int reach = local_grid.valid(n) ? local_grid.reach : 0; // (recorded only: 0 without a grid)
     for (size_t l = 0; l < host_levels.size(); ++l)
     {
+      _amg[l].reach = reach;
+      reach = reach > 0 ? (local_grid.block[0] - 1 + 3 * reach) / local_grid.block[0] : 0;
+      _amg[l].coarse_product = AmgLevel::by_host_product;
       if (l == 0)
         _amg[l].a = std::const_pointer_cast<HipMatrixOperator>(_matrix_operator);
       else

@@ -402,6 +402,14 @@ public:
     // -- in a distributed run -- one exchange instead of two of each, and A is not applied in the cycle at all
     std::shared_ptr<HipMatrixOperator> smoothed_prolongator;
     double smoothed_beta = 0.;
+    // what the setup did on this level, recorded for inspection (mfmg_hip_hierarchy_coarse_amg_setup_info): reach of the level's
+    // operator in nodes, the probe periods per axis of P, A_c and P~ (0: not probed), how the next operator was formed and
+    // whether the level belongs to the replicated tail (finish_amg_replicated)
+    enum CoarseProduct { by_probes = 0, by_device_product = 1, by_host_product = 2 };
+    int reach = 0;
+    int period_p[3] = {0, 0, 0}, period_a[3] = {0, 0, 0}, period_t[3] = {0, 0, 0};
+    int coarse_product = by_probes;
+    bool replicated = false;
     mutable std::shared_ptr<DVector> res, b_coarse, x_coarse, x_work;
   };
   std::vector<AmgLevel> const &amg_levels() const { return _amg; }
@@ -429,7 +437,7 @@ private:
                            AmgGridHint const &grid, AmgOptions const &opts, std::shared_ptr<ptree> smoother_params);
   // (`geom`: the level as a halo space -- local box, owned box, global box; on one rank all three coincide)
   void finish_amg_replicated(std::shared_ptr<HipMatrixOperator> a_op, HostCsr A, std::vector<double> B, int space,
-                             HaloSpace const &geom, AmgOptions const &opts, std::shared_ptr<ptree> smoother_params);
+                             HaloSpace const &geom, AmgOptions const &opts, std::shared_ptr<ptree> smoother_params, int reach);
   // Dense LU with partial pivoting, factored ONCE at setup (the reference re-factorises in every apply,
   // source/cuda/dealii_operator_device_helpers.cu:169-228).  Up to kTriangularInverseLimit rows the factors are
   // stored inverted as two dense triangular matrices and the solve is two SpMV launches over the whole chip
