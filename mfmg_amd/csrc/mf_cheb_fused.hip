@@ -248,8 +248,57 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     asm volatile("" : "+s"(p));
     return *reinterpret_cast<void *const __attribute__((address_space(4))) *>(p + off);
   };
-  auto k_alpha = [&](int s) { return karg_T(offsetof(MfFusedArgs<T>, alpha) + (size_t)s * sizeof(T)); };
-  auto k_beta = [&](int s) { return karg_T(offsetof(MfFusedArgs<T>, beta) + (size_t)s * sizeof(T)); };
+  // CARRY (the twelve-wavefront kernels): read ONCE per tile instead and held as uniform values in vector registers, which
+  // these kernels have to spare and the scalar file has not -- a scalar load per use is a round trip to the scalar cache that
+  // the wavefront waits for with lgkmcnt(0), its LDS reads drained along with it.  The same operands in the same expressions.
+  // How many of the six: all in the wide body of the mode-space kernels (161 VGPRs of 168); beta_1 .. beta_3 in the narrow body, which
+  // has room for three pairs (167) -- the others stay scalar there, as all do in the reference arithmetic (163 VGPRs without them)
+  constexpr int kHoldInVgpr = !MODES ? 0 : (NARROW ? 3 : 2 * K);
+  T held_alpha[K], held_beta[K], held_kd = T(0);
+  if constexpr (CARRY)
+  {
+    auto hold = [](T v, int rank) {
+      if (rank < kHoldInVgpr)
+        asm volatile("" : "+v"(v));
+      return v;
+    };
+#pragma unroll
+    for (int s = 0; s < K; ++s)
+    {
+      held_alpha[s] = s > 0 ? hold(a.alpha[s], K + s) : T(0);
+      held_beta[s] = hold(a.beta[s], s);
+    }
+    held_kd = hold(a.kd, K);
+  }
+  // CARRY: a wave-uniform number as the march sees it anew at a use.  A condition on a tile constant (this wavefront has a
+  // neighbour below, the row lies in the mesh, x_{K-1} is wanted) that the compiler can see through is formed before the march and
+  // held as a lane mask, two scalar registers each, most of them in spill lanes; formed where it is used it is one comparison.
+  auto fresh = [](int v) {
+    if constexpr (CARRY)
+    {
+      v = __builtin_amdgcn_readfirstlane(v);
+      asm volatile("" : "+s"(v));
+    }
+    return v;
+  };
+  auto k_alpha = [&](int s) {
+    if constexpr (CARRY)
+      return held_alpha[s];
+    else
+      return karg_T(offsetof(MfFusedArgs<T>, alpha) + (size_t)s * sizeof(T));
+  };
+  auto k_beta = [&](int s) {
+    if constexpr (CARRY)
+      return held_beta[s];
+    else
+      return karg_T(offsetof(MfFusedArgs<T>, beta) + (size_t)s * sizeof(T));
+  };
+  auto k_kd = [&]() {
+    if constexpr (CARRY)
+      return held_kd;
+    else
+      return karg_T(offsetof(MfFusedArgs<T>, kd));
+  };
 
   CellFactors<T> fac;
   fac.fx = fac.fy = fac.fz = T(0);
@@ -280,17 +329,83 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     if (r < TY && j >= own_y0 && j < own_y1 && j >= a.aff.ghost_lo[1] && j < a.Ny - a.aff.ghost_hi[1]) // (the node row two wavefronts share is stored by the upper one)
       rows_own |= 1u << r;
   }
+  // the lane x row part of "the DoF is free" / "this lane stores the DoF".  CARRY: formed once per tile, one lane mask per row,
+  // instead of recombined from the lane mask and the row bit at every use (each scalar factor is a mask of its own there)
+  bool row_free_lane[R], row_own_lane[R];
+  if constexpr (CARRY)
+  {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+    {
+      row_free_lane[r] = lane_free && ((rows_free >> r) & 1u);
+      row_own_lane[r] = col_owned && ((rows_own >> r) & 1u);
+    }
+  }
+  auto free_lane_row = [&](int r) -> bool {
+    if constexpr (CARRY)
+      return row_free_lane[r];
+    else
+      return lane_free && ((rows_free >> r) & 1u);
+  };
+  auto own_lane_row = [&](int r) -> bool {
+    if constexpr (CARRY)
+      return row_own_lane[r];
+    else
+      return col_owned && ((rows_own >> r) & 1u);
+  };
   // descriptors and uniform byte offsets: node row r / node layer n of a vector (clamped into the mesh), cell row q / layer n
   // of this chunk column's records
-  auto rs_vec = [&](size_t off) { return __builtin_amdgcn_make_buffer_rsrc(karg_ptr(off), 0, a.vec_bytes, 0x00020000); };
-  auto rs_rec_f = [&]() { return __builtin_amdgcn_make_buffer_rsrc(karg_ptr(offsetof(MfFusedArgs<T>, rec)), 0, a.rec_total_bytes, 0x00020000); };
-  const bool want_prev = a.out_prev != nullptr;
+  // (CARRY: from the pointers as the kernel received them -- a descriptor is a held pointer plus two constant words, no scalar
+  // load per request or store)
+  auto vec_ptr = [&](size_t off) -> void * {
+    if constexpr (CARRY)
+      return const_cast<T *>(off == offsetof(MfFusedArgs<T>, x) ? a.x : (off == offsetof(MfFusedArgs<T>, b) ? a.b : (off == offsetof(MfFusedArgs<T>, out) ? a.out : a.out_prev)));
+    else
+      return karg_ptr(off);
+  };
+  auto rec_ptr = [&]() -> void * {
+    if constexpr (CARRY)
+      return const_cast<unsigned char *>(a.rec);
+    else
+      return karg_ptr(offsetof(MfFusedArgs<T>, rec));
+  };
+  auto rs_vec = [&](size_t off) { return __builtin_amdgcn_make_buffer_rsrc(vec_ptr(off), 0, a.vec_bytes, 0x00020000); };
+  auto rs_rec_f = [&]() { return __builtin_amdgcn_make_buffer_rsrc(rec_ptr(), 0, a.rec_total_bytes, 0x00020000); };
+  const bool want_prev_tile = a.out_prev != nullptr;
+  int want_prev_i = 0;
+  if constexpr (CARRY)
+    want_prev_i = want_prev_tile ? 1 : 0;
+  auto want_prev_f = [&]() -> bool {
+    if constexpr (CARRY)
+      return fresh(want_prev_i) != 0;
+    else
+      return want_prev_tile;
+  };
   const unsigned int row_stride = (unsigned int)a.aff.s1 * (unsigned int)sizeof(T), layer_stride = (unsigned int)a.aff.s2 * (unsigned int)sizeof(T);
   const unsigned int rec_row = a.ncols * a.rec_bytes;
   const unsigned int rec_layer = (unsigned int)a.Ny * rec_row;
   const unsigned int rec_col = (unsigned int)tc * a.rec_bytes;
-  auto layer_free = [&](int n) { return n >= 0 && n < a.Nz && !(((a.aff.faces & 16) && n == 0) || ((a.aff.faces & 32) && n == a.Nz - 1)); };
-  auto layer_own = [&](int n) { return n >= Z0 && n < Z1 && n >= a.aff.ghost_lo[2] && n < a.Nz - a.aff.ghost_hi[2]; };
+  // (CARRY: the same sets of layers as two ranges formed once per tile)
+  int zfree0 = 0, zfree1 = 0, zown0 = 0, zown1 = 0;
+  if constexpr (CARRY)
+  {
+    zfree0 = (a.aff.faces & 16) ? 1 : 0;
+    zfree1 = (a.aff.faces & 32) ? a.Nz - 1 : a.Nz;
+    zown0 = max(Z0, a.aff.ghost_lo[2]);
+    zown1 = min(Z1, a.Nz - a.aff.ghost_hi[2]);
+  }
+  auto layer_free = [&](int n) {
+    if constexpr (CARRY)
+      return n >= zfree0 && n < zfree1;
+    else
+      return n >= 0 && n < a.Nz && !(((a.aff.faces & 16) && n == 0) || ((a.aff.faces & 32) && n == a.Nz - 1));
+  };
+  auto layer_own = [&](int n) {
+    if constexpr (CARRY)
+      return n >= zown0 && n < zown1;
+    else
+      return n >= Z0 && n < Z1 && n >= a.aff.ghost_lo[2] && n < a.Nz - a.aff.ghost_hi[2];
+  };
   // an address = per-lane part + wave-uniform part: the row belongs to the uniform part, except in a NARROW tile, whose halves
   // work on different rows
   struct Off
@@ -413,9 +528,18 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       if constexpr (S == 1)
       {
         // x_0 sits in the ring as it was read; Dirichlet and out-of-mesh values enter the cells as zero
-        const bool rf = (rows_free >> r) & 1u;
-        xl[r] = (lane_free && rf && lo_free) ? l : T(0);
-        xu[r] = (lane_free && rf && hi_free) ? u : T(0);
+        if constexpr (CARRY)
+        {
+          const bool lrf = free_lane_row(r);
+          xl[r] = (lrf && lo_free) ? l : T(0);
+          xu[r] = (lrf && hi_free) ? u : T(0);
+        }
+        else
+        {
+          const bool rf = (rows_free >> r) & 1u;
+          xl[r] = (lane_free && rf && lo_free) ? l : T(0);
+          xu[r] = (lane_free && rf && hi_free) ? u : T(0);
+        }
       }
       else
       {
@@ -534,8 +658,17 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     // one DoF (row r, layer c) of this stage is complete: yv = (A x_{S-1}) there
     auto finish = [&](auto rtag, T yv, T tcs) {
       constexpr int r = decltype(rtag)::value;
-      const bool fr = lane_free && ((rows_free >> r) & 1u) && lo_free;
-      const bool st = col_owned && ((rows_own >> r) & 1u) && l_own;
+      bool fr, st;
+      if constexpr (CARRY)
+      {
+        fr = free_lane_row(r) && lo_free;
+        st = own_lane_row(r) && l_own;
+      }
+      else
+      {
+        fr = lane_free && ((rows_free >> r) & 1u) && lo_free;
+        st = col_owned && ((rows_own >> r) & 1u) && l_own;
+      }
       if constexpr (S == 1)
       {
         T d;
@@ -544,7 +677,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
           // the eight cells of the DoF: two rows of this layer + the same of the layer below (carried)
           const T sum8 = tcs + pcs[r];
           pcs[r] = tcs;
-          d = DBG == 2 ? karg_T(offsetof(MfFusedArgs<T>, kd)) * sum8 : T(1) / (karg_T(offsetof(MfFusedArgs<T>, kd)) * sum8);
+          d = DBG == 2 ? k_kd() * sum8 : T(1) / (k_kd() * sum8);
           dq[0][r] = d;
         }
         else
@@ -560,7 +693,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         {
           *ring_at(1, sl(1, 0), r) = fr ? x1 : T(0);
           if constexpr (K == 2)
-            if (st && fr && want_prev)
+            if (st && fr && want_prev_f())
               st_vec(x1, rs_vec(offsetof(MfFusedArgs<T>, out_prev)), r, c);
         }
         // Dirichlet DoFs: identity rows with D^-1 = 1 (the stored diagonal says so too) -- the whole recurrence here
@@ -576,7 +709,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
             xb = xn;
           }
           st_vec(xb, rs_vec(offsetof(MfFusedArgs<T>, out)), r, c);
-          if (K > 1 && want_prev)
+          if (K > 1 && want_prev_f())
             st_vec(xa, rs_vec(offsetof(MfFusedArgs<T>, out_prev)), r, c);
         }
       }
@@ -589,13 +722,17 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
           xoo = xq[S - 2][r]; // (zero from a zero guess)
         else if constexpr (!(S == 2 && ZERO0))
           xoo = *ring_at(S - 2, sl(S - 2, 0), r);
-        const T xoo_m = (S == 2) ? ((lane_free && ((rows_free >> r) & 1u) && lo_free) ? xoo : T(0)) : xoo; // (x_0 sits in its ring unmasked)
+        T xoo_m; // (x_0 sits in its ring unmasked)
+        if constexpr (CARRY)
+          xoo_m = (S == 2) ? ((free_lane_row(r) && lo_free) ? xoo : T(0)) : xoo;
+        else
+          xoo_m = (S == 2) ? ((lane_free && ((rows_free >> r) & 1u) && lo_free) ? xoo : T(0)) : xoo;
         const T xs = fmadd<T>(-(k_beta(S - 1) * dq[S - 1][r]), yv - bq[S - 1][r], fmadd<T>(k_alpha(S - 1), xo - xoo_m, xo));
         if constexpr (S < K)
         {
           *ring_at(S, sl(S, 0), r) = fr ? xs : T(0);
           if constexpr (S == K - 1)
-            if (st && fr && want_prev)
+            if (st && fr && want_prev_f())
               st_vec(xs, rs_vec(offsetof(MfFusedArgs<T>, out_prev)), r, c);
         }
         else
@@ -626,15 +763,16 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
     // the rows shared with the neighbours: both wavefronts complete them, with the same operands in the same order
     {
       T lo0 = T(0), lo1 = T(0), hi0 = T(0), hi1 = T(0);
-      if (kExchange && wv > 0)
+      const int wvu = fresh(wv);
+      if (kExchange && wvu > 0)
       {
-        T const *ip = xport + (size_t)((ex & 1) * NW + wv - 1) * 4 * 64;
+        T const *ip = xport + (size_t)((ex & 1) * NW + wvu - 1) * 4 * 64;
         lo0 = ip[0];
         lo1 = ip[64];
       }
-      if (kExchange && wv + 1 < NW)
+      if (kExchange && wvu + 1 < NW)
       {
-        T const *ip = xport + (size_t)((ex & 1) * NW + wv + 1) * 4 * 64;
+        T const *ip = xport + (size_t)((ex & 1) * NW + wvu + 1) * 4 * 64;
         hi0 = ip[128];
         hi1 = ip[192];
       }
@@ -687,13 +825,16 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       pfhi = ld_coef(rs_rec, TY, c1 + 1);
     }
 
-    if (c1 <= stage_end(1))
+    // CARRY (three terms): the same conditions from Z0 and Nz alone -- c1 <= c_last = min(Z1 + 1, Nz + 1) in the march, which is
+    // the upper bound of stage 3 and the Z1 part of the other two
+    static_assert(!CARRY || K == 3, "the stage ranges of the twelve-wavefront kernels are those of three terms");
+    if (CARRY ? c1 < a.Nz : c1 <= stage_end(1))
       stage_pass(IntTag<1>{}, c1, [&](int s, int d) { return sl(s, d); });
     if constexpr (K >= 2)
-      if (c1 - 1 >= stage_start(2) && c1 - 1 <= stage_end(2))
+      if (CARRY ? (c1 >= max(Z0 - 1, 1) && c1 <= a.Nz) : (c1 - 1 >= stage_start(2) && c1 - 1 <= stage_end(2)))
         stage_pass(IntTag<2>{}, c1 - 1, [&](int s, int d) { return sl(s, d - 1); });
     if constexpr (K >= 3)
-      if (c1 - 2 >= stage_start(3) && c1 - 2 <= stage_end(3))
+      if (CARRY ? c1 >= max(Z0 + 1, 2) : (c1 - 2 >= stage_start(3) && c1 - 2 <= stage_end(3)))
         stage_pass(IntTag<3>{}, c1 - 2, [&](int s, int d) { return sl(s, d - 2); });
 
     // shift the carried state by one stage (a renaming: the trip of the march is K super-passes), land the requests
@@ -725,13 +866,18 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       if constexpr (!ZERO0)
         *ring_at(0, sl(0, 2), r) = pfx[r];
     }
+    int Ywu = Yw; // (a NARROW tile: per lane)
+    if constexpr (!NARROW)
+      Ywu = fresh(Yw);
+    else if constexpr (CARRY)
+      asm volatile("" : "+v"(Ywu)); // (one vector register and a comparison per use instead of a held lane mask per cell row)
 #pragma unroll
     for (int q = 0; q < TY; ++q)
-      cq[0][q] = (Yw + q >= 0) ? pfc[q] : T(0);
+      cq[0][q] = (Ywu + q >= 0) ? pfc[q] : T(0);
     if constexpr (!DREC)
     {
-      clo = (Yw - 1 >= 0) ? pflo : T(0);
-      chi = (Yw + TY >= 0) ? pfhi : T(0);
+      clo = (Ywu - 1 >= 0) ? pflo : T(0);
+      chi = (Ywu + TY >= 0) ? pfhi : T(0);
     }
   };
 
