@@ -567,6 +567,15 @@ int mfmg_hip_hierarchy_set_restrictor(mfmg_hip_hierarchy_t h, int64_t n_rows, in
  * one-pass form, 0 when the two-step form is in use. */
 int mfmg_hip_hierarchy_restrict_residual(mfmg_hip_hierarchy_t h, int32_t level, const double *x, const double *b, double *b_coarse);
 int mfmg_hip_hierarchy_residual_restriction_classes(mfmg_hip_hierarchy_t h, int32_t level, int32_t *n_classes);
+/* What a launch of the one-pass form consists of (tests: which path a case reaches).  fields[0..9], all 0 where the form is not built:
+ *   0 agglomerate classes, 1 runs of 62 agglomerates per row (row-wise part), 2 last agglomerate index i of a row in that part
+ *   3 agglomerates in the list (sixteen lanes each), 4 runs of the row-wise part whose agglomerates are in the list instead
+ *   5 kernel: 1 the tile form, 2 the row-wise kernel (MFMG_RR_KERNEL=rows)
+ *   6 agglomerate layers per tile (MFMG_RR_TILE_LAYERS when the tables were built, else chosen for the grid), 7 tiles along y,
+ *   8 tiles (6-8: 0 for the row-wise kernel), 9 workgroups of the row-wise part (a multiple of 8)
+ * Computed by the function the launch takes its grid from. */
+#define MFMG_HIP_RESIDUAL_RESTRICTION_FORM_FIELDS 10
+int mfmg_hip_hierarchy_residual_restriction_form(mfmg_hip_hierarchy_t h, int32_t level, int64_t *fields, int32_t n);
 /* The one-pass form on float x and b, as the FP32 fine level (mfmg_hip_hierarchy_apply_f32) runs it: x and b are widened as they
  * are loaded, all arithmetic and b_coarse are FP64.  There is no two-step form behind this entry (that one rounds the residual to
  * float): MFMG_HIP_ERROR_NOT_IMPLEMENTED where the one-pass form is not built (*_classes == 0) or the context has a communicator. */

@@ -815,6 +815,17 @@ class Hierarchy:
         check(self._lib.mfmg_hip_hierarchy_residual_restriction_classes(self.handle, level, C.byref(n)))
         return n.value
 
+    _RR_KERNELS = {0: None, 1: "tile", 2: "rows"}
+
+    def residual_restriction_form(self, level: int = 1) -> dict:
+        """What a launch of the one-pass residual restriction consists of: classes, runs per row (`segs`), last agglomerate of a
+        row in the row-wise part, agglomerates and runs left to the list, the kernel ("tile" or "rows") and the grid of the next
+        launch (`tile_layers`, `tiles_j`, `n_tiles`, `main_blocks`).  All zero and `kernel` None where the form is not built."""
+        f = (C.c_int64 * _lib.RESIDUAL_RESTRICTION_FORM_FIELDS)()
+        check(self._lib.mfmg_hip_hierarchy_residual_restriction_form(self.handle, level, f, _lib.RESIDUAL_RESTRICTION_FORM_FIELDS))
+        return {"classes": f[0], "segs": f[1], "main_last": f[2], "listed": f[3], "listed_runs": f[4],
+                "kernel": self._RR_KERNELS[f[5]], "tile_layers": f[6], "tiles_j": f[7], "n_tiles": f[8], "main_blocks": f[9]}
+
     def coarse_amg_gather_level(self) -> int:
         """Index of the first aggregation level that is gathered and solved redundantly on every rank (-1: one rank)."""
         n = C.c_int32()

@@ -2047,6 +2047,30 @@ int mfmg_hip_hierarchy_residual_restriction_classes(mfmg_hip_hierarchy_t h, int3
   });
 }
 
+int mfmg_hip_hierarchy_residual_restriction_form(mfmg_hip_hierarchy_t h, int32_t level, int64_t *fields, int32_t n)
+{
+  return guarded([&] {
+    require(h && fields, "null argument");
+    require(n >= MFMG_HIP_RESIDUAL_RESTRICTION_FORM_FIELDS, "residual_restriction_form needs MFMG_HIP_RESIDUAL_RESTRICTION_FORM_FIELDS fields");
+    require(level >= 1 && level < (int)h->hierarchy->levels().size(), "restrictors live on levels >= 1");
+    auto r = std::dynamic_pointer_cast<HipMatrixOperator const>(h->hierarchy->levels()[level].get_restrictor());
+    std::fill(fields, fields + n, 0);
+    if (!r || !r->has_residual_restriction() || r->structured() == nullptr)
+      return;
+    const auto f = r->structured()->residual_restriction_form();
+    fields[0] = f.classes;
+    fields[1] = f.segs;
+    fields[2] = f.main_last;
+    fields[3] = f.listed;
+    fields[4] = f.listed_runs;
+    fields[5] = f.kernel;
+    fields[6] = f.tile_layers;
+    fields[7] = f.tiles_j;
+    fields[8] = f.n_tiles;
+    fields[9] = (int64_t)f.main_blocks;
+  });
+}
+
 int mfmg_hip_hierarchy_restrict_residual(mfmg_hip_hierarchy_t h, int32_t level, const double *x, const double *b, double *b_coarse)
 {
   return guarded([&] {

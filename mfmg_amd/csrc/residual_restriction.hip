@@ -434,6 +434,9 @@ void StructuredRestrictorDevice::drop_residual_restriction()
   _rr_seg_class.release();
   _rr_listed.release();
   _rr_segs = _rr_classes = _rr_main_last = 0;
+  _rr_listed_runs = 0;
+  _rr_tile_layers = 0;
+  _rr_rows = false;
 }
 
 bool StructuredRestrictorDevice::build_residual_restriction(std::function<void(double const *, double *)> const &apply_a,
@@ -565,10 +568,76 @@ bool StructuredRestrictorDevice::build_residual_restriction(std::function<void(d
   _rr_segs = segs;
   _rr_main_last = main_last;
   _rr_classes = n_classes;
+  _rr_listed_runs = 0;
+  for (uint16_t c : seg_class)
+    _rr_listed_runs += c == 0xffff ? 1 : 0;
   // (read when the tables are built, as the switches of restrict / prolong are: two restrictors of one process can differ)
   char const *kernel = std::getenv("MFMG_RR_KERNEL");
   _rr_rows = kernel != nullptr && std::string(kernel) == "rows";
+  char const *layers = std::getenv("MFMG_RR_TILE_LAYERS");
+  _rr_tile_layers = layers != nullptr ? std::max(std::atoi(layers), 0) : 0;
   return true;
+}
+
+// Grid of the row-wise part.  Tile form: height of a tile in whole rounds of two workgroups per CU; a workgroup of ka agglomerate
+// layers passes 2 ka + 3 node layers.  Row-wise kernel (MFMG_RR_KERNEL=rows): four wavefronts = four runs per workgroup.
+StructuredRestrictorDevice::RrGrid StructuredRestrictorDevice::residual_restriction_grid() const
+{
+  RrGrid g;
+  const int64_t n_main_waves = (int64_t)_rr_segs * _na[1] * _na[2];
+  if (_rr_rows)
+  {
+    g.main_blocks = n_main_waves == 0 ? 0u : (unsigned int)(((n_main_waves + 3) / 4 + 7) / 8 * 8);
+    return g;
+  }
+  static const int n_cus = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      v = 256;
+    return v > 0 ? v : 256;
+  }();
+  g.tiles_j = (_na[1] + kTileRows - 1) / kTileRows;
+  int ka = _rr_tile_layers > 0 ? std::min(_rr_tile_layers, _na[2]) : 0;
+  if (ka == 0)
+  {
+    double best = 0.;
+    for (int nk = 1; nk <= _na[2]; ++nk)
+    {
+      const int t = (_na[2] + nk - 1) / nk;
+      if ((_na[2] + t - 1) / t != nk)
+        continue;
+      const int64_t tiles = (int64_t)_rr_segs * g.tiles_j * nk, slots = 2 * (int64_t)n_cus;
+      const double cost = double((tiles + slots - 1) / slots) * (2. * t + 3.);
+      if (ka == 0 || cost < best)
+      {
+        best = cost;
+        ka = t;
+      }
+    }
+  }
+  g.ka = std::max(ka, 1);
+  g.n_tiles = (int64_t)_rr_segs * g.tiles_j * ((_na[2] + g.ka - 1) / g.ka);
+  g.main_blocks = n_main_waves == 0 ? 0u : (unsigned int)((g.n_tiles + 7) / 8 * 8);
+  return g;
+}
+
+StructuredRestrictorDevice::ResidualRestrictionForm StructuredRestrictorDevice::residual_restriction_form() const
+{
+  ResidualRestrictionForm f;
+  if (!has_residual_restriction())
+    return f;
+  const RrGrid g = residual_restriction_grid();
+  f.classes = _rr_classes;
+  f.segs = _rr_segs;
+  f.main_last = _rr_main_last;
+  f.listed = (int64_t)_rr_listed.size();
+  f.listed_runs = _rr_listed_runs;
+  f.kernel = _rr_rows ? 2 : 1;
+  f.tile_layers = g.ka;
+  f.tiles_j = g.tiles_j;
+  f.n_tiles = g.n_tiles;
+  f.main_blocks = g.main_blocks;
+  return f;
 }
 
 template <typename TI>
@@ -585,9 +654,11 @@ void StructuredRestrictorDevice::restrict_residual_any(TI const *x, TI const *b,
   s.listed = _rr_listed.data();
   s.n_listed = (int64_t)_rr_listed.size();
   s.n_main_waves = (int64_t)_rr_segs * _na[1] * _na[2];
-  s.main_blocks = (unsigned int)(((s.n_main_waves + 3) / 4 + 7) / 8 * 8);
-  if (s.n_main_waves == 0)
-    s.main_blocks = 0;
+  const RrGrid grid_of = residual_restriction_grid();
+  s.main_blocks = grid_of.main_blocks;
+  s.tiles_j = grid_of.tiles_j;
+  s.ka = grid_of.ka;
+  s.n_tiles = grid_of.n_tiles;
   for (int d = 0; d < 3; ++d)
   {
     s.N[d] = _N[d];
@@ -600,36 +671,6 @@ void StructuredRestrictorDevice::restrict_residual_any(TI const *x, TI const *b,
   hipEvent_t stop = _handle.profiler.begin("residual_restriction", 2. * sizeof(TI) * double(_n_fine) + 8. * double(_n_coarse), _handle.stream);
   if (tile_form)
   {
-    // height of a tile: whole rounds of two workgroups per CU; a workgroup of ka agglomerate layers passes 2 ka + 3 node layers
-    static const int n_cus = [] {
-      int dev = 0, v = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        v = 256;
-      return v > 0 ? v : 256;
-    }();
-    static const int ka_env = std::getenv("MFMG_RR_TILE_LAYERS") ? std::atoi(std::getenv("MFMG_RR_TILE_LAYERS")) : 0;
-    s.tiles_j = (_na[1] + kTileRows - 1) / kTileRows;
-    int ka = ka_env > 0 ? std::min(ka_env, _na[2]) : 0;
-    if (ka == 0)
-    {
-      double best = 0.;
-      for (int nk = 1; nk <= _na[2]; ++nk)
-      {
-        const int t = (_na[2] + nk - 1) / nk;
-        if ((_na[2] + t - 1) / t != nk)
-          continue;
-        const int64_t tiles = (int64_t)_rr_segs * s.tiles_j * nk, slots = 2 * (int64_t)n_cus;
-        const double cost = double((tiles + slots - 1) / slots) * (2. * t + 3.);
-        if (ka == 0 || cost < best)
-        {
-          best = cost;
-          ka = t;
-        }
-      }
-    }
-    s.ka = std::max(ka, 1);
-    s.n_tiles = (int64_t)_rr_segs * s.tiles_j * ((_na[2] + s.ka - 1) / s.ka);
-    s.main_blocks = s.n_main_waves == 0 ? 0u : (unsigned int)((s.n_tiles + 7) / 8 * 8);
     s.listed_blocks = (unsigned int)((s.n_listed + 16 * kTileRows / 4 - 1) / (16 * kTileRows / 4)); // sixteen lanes per agglomerate
     static const int dbg = std::getenv("MFMG_RR_DEBUG") ? std::atoi(std::getenv("MFMG_RR_DEBUG")) : 0; // (timing experiments: 1 no list, 2 no tiles)
     static int calls = 0; // (the check of the setup against the two steps sees the whole kernel)

@@ -66,6 +66,17 @@ public:
   bool has_residual_restriction() const { return _rr_table.size() > 0; }
   void drop_residual_restriction();
   int residual_restriction_classes() const { return _rr_classes; }
+  // what the next launch of restrict_residual consists of (tests: which path a case reaches); all zero when nothing is built
+  struct ResidualRestrictionForm
+  {
+    int classes = 0, segs = 0, main_last = 0;
+    int64_t listed = 0, listed_runs = 0; // agglomerates in the list, runs of the row-wise part marked 0xffff in seg_class
+    int kernel = 0;                      // 1 the tile form, 2 the row-wise kernel (MFMG_RR_KERNEL=rows)
+    int tile_layers = 0, tiles_j = 0;    // tile form: agglomerate layers per tile, tiles along y
+    int64_t n_tiles = 0;
+    unsigned int main_blocks = 0;        // workgroups of the row-wise part (a multiple of 8)
+  };
+  ResidualRestrictionForm residual_restriction_form() const;
   void restrict_residual(double const *x, double const *b, double *y) const;
   // the same from FP32 vectors (the FP32 fine level of apply_f32): sums and result in FP64
   void restrict_residual(float const *x, float const *b, double *y) const;
@@ -129,5 +140,15 @@ private:
   DeviceBuffer<int32_t> _rr_listed;      // agglomerates left to the thread-per-agglomerate part
   int _rr_segs = 0, _rr_classes = 0, _rr_main_last = 0;
   bool _rr_rows = false; // MFMG_RR_KERNEL=rows when the tables were built
+  int _rr_tile_layers = 0; // MFMG_RR_TILE_LAYERS when the tables were built (0: chosen per launch grid)
+  int64_t _rr_listed_runs = 0;
+  // grid of the row-wise part: the launch and residual_restriction_form() both take it from here
+  struct RrGrid
+  {
+    int ka = 0, tiles_j = 0;
+    int64_t n_tiles = 0;
+    unsigned int main_blocks = 0;
+  };
+  RrGrid residual_restriction_grid() const;
 };
 } // namespace mfmg

@@ -21,6 +21,7 @@ NO_TRANS = 0
 TRANS = 1
 TRANS_SUBTRACT = 2   # restrictor_apply only: out -= R^T in
 RESTRICTOR_FORM_FIELDS = 12
+RESIDUAL_RESTRICTION_FORM_FIELDS = 10
 AMG_SETUP_INFO_FIELDS = 13   # MFMG_HIP_AMG_SETUP_INFO_FIELDS
 CSR_FORM_FIELDS = 22
 # modes of mfmg_hip_csr_launch
@@ -260,6 +261,7 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_restrict_residual": (C.c_int, [vp, i32, vp, vp, vp]),
         "mfmg_hip_hierarchy_restrict_residual_f32": (C.c_int, [vp, i32, vp, vp, vp]),
         "mfmg_hip_hierarchy_residual_restriction_classes": (C.c_int, [vp, i32, P(i32)]),
+        "mfmg_hip_hierarchy_residual_restriction_form": (C.c_int, [vp, i32, P(i64), i32]),
         "mfmg_hip_hierarchy_coarse_amg_get": (C.c_int, [vp, i32, i32, P(vp)]),
         "mfmg_hip_hierarchy_coarse_amg_smoother": (C.c_int, [vp, i32, P(i32), P(dbl), P(dbl)]),
         "mfmg_hip_hierarchy_coarse_amg_setup_info": (C.c_int, [vp, i32, P(i32), i32]),
