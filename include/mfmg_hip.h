@@ -550,6 +550,39 @@ int mfmg_hip_hierarchy_restrictor_apply(mfmg_hip_hierarchy_t h, int32_t level, c
  *  11 the block kernel in its marching form (0: a thread per agglomerate position, MFMG_SR_PROLONG=block) */
 #define MFMG_HIP_RESTRICTOR_FORM_FIELDS 12
 int mfmg_hip_hierarchy_restrictor_form(mfmg_hip_hierarchy_t h, int32_t level, int32_t *fields, int32_t n);
+/* What solved the agglomerate eigenproblems of the restrictor, parameter "restrictor.eigensolver" device (default) | host | lanczos:
+ *   device   dense cyclic Jacobi, one wavefront per agglomerate (amge_device.hip), for agglomerates of at most 64 nodes; larger
+ *            ones are solved by the same method on the host cores
+ *   host     dense cyclic Jacobi on the host cores
+ *   lanczos  batched matrix-free Lanczos with full reorthogonalisation on the device (amge_lanczos.hip), agglomerates of at most
+ *            729 nodes (8 x 8 x 8 cells; MFMG_HIP_ERROR_NOT_IMPLEMENTED beyond: an explicit request is not served by another
+ *            solver).  It honours eigensolver.tolerance (default 1e-14, taken as given), eigensolver.max_iterations (200) and
+ *            eigensolver.percent_overshoot (5) and returns the `krylov` selection; eigensolver.selection lapack with it is
+ *            MFMG_HIP_ERROR_RUNTIME.  An agglomerate that stops at max_iterations unconverged is counted, not an error.
+ * fields[0..6]:
+ *   0 solver that ran: 0 dense on the host cores, 1 dense on the device, 2 Lanczos
+ *   1 nodes of a full agglomerate, 2 agglomerates, 3 eigenproblems solved (identical agglomerates share one solve)
+ *   4 largest number of Lanczos steps of an agglomerate, 5 agglomerates whose run ended by breakdown (the Krylov space of the start
+ *     vector is invariant: harmless), 6 agglomerates unconverged at max_iterations   (4-6: 0 for the dense solvers)
+ * On several ranks every rank reports its own agglomerates: the solver hooks in per rank where the dense kernel does.
+ * *_seconds: wall time of the Lanczos kernel of that setup (0 for the dense solvers). */
+#define MFMG_HIP_EIGENSOLVER_INFO_FIELDS 7
+int mfmg_hip_hierarchy_restrictor_eigensolver_info(mfmg_hip_hierarchy_t h, int64_t *fields, int32_t n);
+int mfmg_hip_hierarchy_restrictor_eigensolver_seconds(mfmg_hip_hierarchy_t h, double *seconds);
+/* The agglomerate eigen-solves of the restrictor setup on their own, with the device solver that `params_info` names
+ * (restrictor.eigensolver device | lanczos; the agglomeration / eigensolver sections as mfmg_hip_hierarchy_create reads them;
+ * `matrix_free` picks the evaluator flavour, i.e. the default eigensolver.variant mf instead of device).
+ * Size query: with all five output arrays NULL only *n_agglomerates, *n_eigenvectors and *n_nodes (node stride of `weights`) are
+ * set.  Otherwise host arrays, agglomerates x fastest:
+ *   n_vec[a]                       vectors selected for agglomerate a
+ *   eigenvalues[a * n_eig + e]     eigenvalue of vector e (for eigensolver.variant host with the shift taken off)
+ *   weights[(a * n_eig + e) * n_nodes + l]   diag_loc[l] * vector e at local node l (x fastest inside the agglomerate), 0 on
+ *                                  nodes that are not part of the eigenproblem
+ *   iterations[a]                  Lanczos steps (0 for the dense solver)
+ *   flags[a]                       bit 0: converged, bit 1: ended by breakdown */
+int mfmg_hip_amge_eigen(mfmg_hip_context_t ctx, const mfmg_hip_mesh_desc *mesh, const char *params_info, int matrix_free,
+                        int64_t *n_agglomerates, int32_t *n_eigenvectors, int32_t *n_nodes, int32_t *n_vec, double *eigenvalues,
+                        double *weights, int32_t *iterations, int32_t *flags);
 /* out = (A R^T) in for the A R^T the coarse operator of `level` was formed from -- `fast_multiply_transpose()` when the
  * parameter `fast_ap` is true (include/mfmg/common/hierarchy.hpp:214-221), `a->multiply_transpose(restrictor)` otherwise.
  * Kept only by a hierarchy built with `keep_ap = true` (tests: the comparison of tests/test_hierarchy.cc:507-642). */

@@ -695,6 +695,20 @@ class Hierarchy:
                 "restrict": self._RESTRICT_KERNELS[f[9]], "prolong": self._PROLONG_KERNELS[f[10]],
                 "prolong_march": bool(f[11])}
 
+    _EIGENSOLVERS = {0: "host dense", 1: "device dense", 2: "lanczos"}
+
+    def restrictor_eigensolver_info(self) -> dict:
+        """What solved the agglomerate eigenproblems of the restrictor ("restrictor.eigensolver" device | host | lanczos) and its
+        bookkeeping: nodes of a full agglomerate, agglomerates, eigenproblems solved (identical agglomerates share one), and for
+        the Lanczos solver the largest step count, the agglomerates ended by breakdown and those unconverged at
+        eigensolver.max_iterations; kernel_seconds is the wall time of the Lanczos kernel."""
+        f = (C.c_int64 * _lib.EIGENSOLVER_INFO_FIELDS)()
+        check(self._lib.mfmg_hip_hierarchy_restrictor_eigensolver_info(self.handle, f, _lib.EIGENSOLVER_INFO_FIELDS))
+        t = C.c_double()
+        check(self._lib.mfmg_hip_hierarchy_restrictor_eigensolver_seconds(self.handle, C.byref(t)))
+        return {"solver": self._EIGENSOLVERS[f[0]], "nodes": f[1], "agglomerates": f[2], "solves": f[3], "max_iterations": f[4],
+                "breakdowns": f[5], "unconverged": f[6], "kernel_seconds": t.value}
+
     def ap_apply(self, level: int, vin, vout):
         """vout = (A R^T) vin for the A R^T of `level` (hierarchies built with keep_ap = true)."""
         nf, nc = self.level_size(level - 1), self.level_size(level)
@@ -922,6 +936,29 @@ class Hierarchy:
                 self.handle = None
         except Exception:
             pass
+
+
+def amge_eigen(ctx: Context, problem, params: dict | str, matrix_free: bool) -> dict:
+    """The agglomerate eigen-solves of the restrictor setup on their own, with the device solver `params` names
+    ("restrictor.eigensolver" device | lanczos).  Arrays per agglomerate (x fastest): n_vec [A], eigenvalues [A, n_eig],
+    weights [A, n_eig, nodes] (diag_loc * vector on the local nodes, x fastest), iterations [A], converged [A], breakdown [A]."""
+    lib = _lib.load()
+    desc = problem.mesh_desc()
+    info = (params if isinstance(params, str) else params_to_info(params)).encode()
+    mf = 1 if matrix_free else 0
+    na, ne, nn = C.c_int64(), C.c_int32(), C.c_int32()
+    check(lib.mfmg_hip_amge_eigen(ctx.handle, C.byref(desc), info, mf, C.byref(na), C.byref(ne), C.byref(nn), None, None, None, None,
+                                  None))
+    A, E, N = na.value, ne.value, nn.value
+    n_vec = np.zeros(A, dtype=np.int32)
+    ev = np.zeros((A, E), dtype=np.float64)
+    w = np.zeros((A, E, N), dtype=np.float64)
+    its = np.zeros(A, dtype=np.int32)
+    flags = np.zeros(A, dtype=np.int32)
+    check(lib.mfmg_hip_amge_eigen(ctx.handle, C.byref(desc), info, mf, C.byref(na), C.byref(ne), C.byref(nn), n_vec.ctypes.data,
+                                  ev.ctypes.data, w.ctypes.data, its.ctypes.data, flags.ctypes.data))
+    return {"n_vec": n_vec, "eigenvalues": ev, "weights": w, "iterations": its, "converged": (flags & 1) != 0,
+            "breakdown": (flags & 2) != 0}
 
 
 # ---- host-side setup pieces (no GPU) ------------------------------------------------------

@@ -27,25 +27,6 @@ namespace mfmg
 {
 namespace
 {
-struct AmgeArgs
-{
-  int dim, nc;
-  int n[3], N[3];   // cells, nodes of the mesh
-  int ag[3], cnt[3]; // cells per agglomerate, agglomerates per direction
-  int variant;       // 0 device, 1 host, 2 mf
-  int krylov;        // selection: 0 lapack, 1 krylov
-  int n_eig;
-  int use_coefficient;
-  int32_t const *node_dof;
-  uint8_t const *constrained;
-  double const *coefficient; // [cells][nc]
-  double const *Kq;          // [nc][nc][nc]
-  double *weights;           // [agglomerates][n_eig][NMAX]
-  int32_t *n_vec;            // [agglomerates]
-  int64_t n_agg;
-  int64_t const *list; // nullptr: every agglomerate; otherwise the n_agg agglomerates to solve (representatives)
-};
-
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
@@ -239,6 +220,8 @@ __global__ __launch_bounds__(256) void amge_agglomerate_kernel(AmgeArgs a)
           const bool active = (act_mask >> lane) & 1ull;
           out[(size_t)e * NMAX + lane] = active ? dl * V[col * na + pos_of(lane)] : 0.;
         }
+        if (a.eigenvalues && lane == 0)
+          a.eigenvalues[(size_t)agg * a.n_eig + e] = w[e];
       }
       n_sel = ne;
     }
@@ -310,6 +293,8 @@ __global__ __launch_bounds__(256) void amge_agglomerate_kernel(AmgeArgs a)
             const bool active = (act_mask >> lane) & 1ull;
             out[(size_t)n_sel * NMAX + lane] = active ? dl * (proj[pos_of(lane)] / pn) : 0.;
           }
+          if (a.eigenvalues && lane == 0)
+            a.eigenvalues[(size_t)agg * a.n_eig + n_sel] = w[i0];
           ++n_sel;
         }
         i0 = i1;
@@ -399,18 +384,12 @@ __global__ void amge_spread_kernel(int64_t n_agg, int per_agg, int64_t const *re
 }
 } // namespace
 
-void amge_device_eigen(HipHandle &handle, StructuredMesh const &mesh, RestrictorOptions const &opts, int const cnt[3],
-                       std::vector<double> &weights, std::vector<int32_t> &n_vec, int &nmax)
+AmgeArgs AmgeDeviceMesh::upload(HipHandle &handle, StructuredMesh const &mesh, RestrictorOptions const &opts, int const cnt[3])
 {
-  const int dim = mesh.dim, nc = mesh.nc();
-  int nloc = 1;
-  for (int d = 0; d < dim; ++d)
-    nloc *= opts.agglomerate[d] + 1;
-  ASSERT_THROW(nloc <= 64, "agglomerates of more than 64 nodes are solved on the host");
-  nmax = nloc <= 27 ? 27 : 64;
+  const int dim = mesh.dim;
   AmgeArgs a;
   a.dim = dim;
-  a.nc = nc;
+  a.nc = mesh.nc();
   for (int d = 0; d < 3; ++d)
   {
     a.n[d] = d < dim ? mesh.n[d] : 1;
@@ -423,29 +402,28 @@ void amge_device_eigen(HipHandle &handle, StructuredMesh const &mesh, Restrictor
   a.n_eig = opts.n_eigenvectors;
   a.use_coefficient = opts.use_coefficient ? 1 : 0;
   a.n_agg = (int64_t)cnt[0] * cnt[1] * cnt[2];
-  const auto Kq = reference_cell_tables(dim, mesh.h);
+  const auto tables = reference_cell_tables(dim, mesh.h);
   hipStream_t st = handle.stream;
-  DeviceBuffer<int32_t> d_node;
-  DeviceBuffer<uint8_t> d_con;
-  DeviceBuffer<double> d_coef, d_kq;
-  d_node.upload(mesh.node_dof.data(), mesh.node_dof.size(), st);
-  d_con.upload(mesh.constrained.data(), mesh.constrained.size(), st);
-  d_coef.upload(mesh.coefficient.data(), mesh.coefficient.size(), st);
-  d_kq.upload(Kq.data(), Kq.size(), st);
-  DeviceBuffer<double> d_w((size_t)a.n_agg * a.n_eig * nmax);
-  DeviceBuffer<int32_t> d_nv((size_t)a.n_agg);
-  MFMG_HIP_CHECK(hipMemsetAsync(d_w.data(), 0, d_w.size() * sizeof(double), st));
-  a.node_dof = d_node.data();
-  a.constrained = d_con.data();
-  a.coefficient = d_coef.data();
-  a.Kq = d_kq.data();
-  a.weights = d_w.data();
-  a.n_vec = d_nv.data();
+  node_dof.upload(mesh.node_dof.data(), mesh.node_dof.size(), st);
+  constrained.upload(mesh.constrained.data(), mesh.constrained.size(), st);
+  coefficient.upload(mesh.coefficient.data(), mesh.coefficient.size(), st);
+  Kq.upload(tables.data(), tables.size(), st);
+  a.node_dof = node_dof.data();
+  a.constrained = constrained.data();
+  a.coefficient = coefficient.data();
+  a.Kq = Kq.data();
+  a.weights = nullptr;
+  a.n_vec = nullptr;
   a.list = nullptr;
-  // identical agglomerates share one solve (the host path does the same with a table per thread)
-  const int64_t n_all = a.n_agg;
-  DeviceBuffer<int64_t> d_list, d_rep_of;
-  bool shared_solves = false;
+  a.eigenvalues = nullptr;
+  return a;
+}
+
+bool AmgeSharing::find(HipHandle &handle, AmgeArgs &a)
+{
+  hipStream_t st = handle.stream;
+  n_all = a.n_agg;
+  shared = false;
   if (!(std::getenv("MFMG_AMGE_MEMO") && std::string(std::getenv("MFMG_AMGE_MEMO")) == "0") && n_all >= 64)
   {
     DeviceBuffer<uint64_t> d_keys((size_t)2 * n_all);
@@ -457,11 +435,11 @@ void amge_device_eigen(HipHandle &handle, StructuredMesh const &mesh, Restrictor
       size_t operator()(std::pair<uint64_t, uint64_t> const &k) const { return (size_t)(k.first ^ (k.second * 0x9e3779b97f4a7c15ull)); }
     };
     std::unordered_map<std::pair<uint64_t, uint64_t>, int64_t, KeyHash> first_of;
-    std::vector<int64_t> rep_of((size_t)n_all), reps;
+    std::vector<int64_t> rep_of_host((size_t)n_all), reps;
     for (int64_t agg = 0; agg < n_all; ++agg)
     {
       auto ins = first_of.emplace(std::make_pair(keys[2 * agg], keys[2 * agg + 1]), agg);
-      rep_of[agg] = ins.first->second;
+      rep_of_host[agg] = ins.first->second;
       if (ins.second)
         reps.push_back(agg);
       if ((int64_t)reps.size() * 2 > n_all && agg * 2 < n_all)
@@ -469,13 +447,55 @@ void amge_device_eigen(HipHandle &handle, StructuredMesh const &mesh, Restrictor
     }
     if ((int64_t)reps.size() * 2 <= n_all)
     {
-      shared_solves = true;
-      d_list.upload(reps.data(), reps.size(), st);
-      d_rep_of.upload(rep_of.data(), rep_of.size(), st);
-      a.list = d_list.data();
+      shared = true;
+      list.upload(reps.data(), reps.size(), st);
+      rep_of.upload(rep_of_host.data(), rep_of_host.size(), st);
+      a.list = list.data();
       a.n_agg = (int64_t)reps.size();
     }
   }
+  return shared;
+}
+
+void AmgeSharing::spread(HipHandle &handle, int per_agg, double *values, int32_t *ints) const
+{
+  if (!shared)
+    return;
+  hipLaunchKernelGGL(amge_spread_kernel, dim3(n_blocks_for(n_all * per_agg, 256, 1 << 16)), dim3(256), 0, handle.stream, n_all,
+                     per_agg, rep_of.data(), values, ints);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void amge_device_eigen(HipHandle &handle, StructuredMesh const &mesh, RestrictorOptions const &opts, int const cnt[3],
+                       std::vector<double> &weights, std::vector<int32_t> &n_vec, int &nmax, std::vector<double> *eigenvalues,
+                       int64_t *n_solves)
+{
+  const int dim = mesh.dim;
+  int nloc = 1;
+  for (int d = 0; d < dim; ++d)
+    nloc *= opts.agglomerate[d] + 1;
+  ASSERT_THROW(nloc <= 64, "agglomerates of more than 64 nodes are solved on the host");
+  nmax = nloc <= 27 ? 27 : 64;
+  hipStream_t st = handle.stream;
+  AmgeDeviceMesh d_mesh;
+  AmgeArgs a = d_mesh.upload(handle, mesh, opts, cnt);
+  DeviceBuffer<double> d_w((size_t)a.n_agg * a.n_eig * nmax), d_ev;
+  DeviceBuffer<int32_t> d_nv((size_t)a.n_agg), d_unused;
+  MFMG_HIP_CHECK(hipMemsetAsync(d_w.data(), 0, d_w.size() * sizeof(double), st));
+  a.weights = d_w.data();
+  a.n_vec = d_nv.data();
+  if (eigenvalues)
+  {
+    d_ev.resize((size_t)a.n_agg * a.n_eig);
+    d_unused.resize((size_t)a.n_agg);
+    MFMG_HIP_CHECK(hipMemsetAsync(d_ev.data(), 0, d_ev.size() * sizeof(double), st));
+    a.eigenvalues = d_ev.data();
+  }
+  // identical agglomerates share one solve (the host path does the same with a table per thread)
+  AmgeSharing sharing;
+  sharing.find(handle, a);
+  if (n_solves)
+    *n_solves = a.n_agg;
   const int wpb = nmax == 27 ? 4 : 1;
   const size_t lds = (size_t)wpb * (2 * nmax * nmax + 5 * nmax) * sizeof(double);
   const unsigned int blocks = (unsigned int)std::min<int64_t>((a.n_agg + wpb - 1) / wpb, 256 * 16);
@@ -492,11 +512,11 @@ void amge_device_eigen(HipHandle &handle, StructuredMesh const &mesh, Restrictor
     hipLaunchKernelGGL(amge_agglomerate_kernel<64>, dim3(blocks), dim3(64 * wpb), lds, st, a);
   }
   MFMG_HIP_CHECK(hipGetLastError());
-  if (shared_solves)
+  sharing.spread(handle, a.n_eig * nmax, d_w.data(), d_nv.data());
+  if (eigenvalues)
   {
-    hipLaunchKernelGGL(amge_spread_kernel, dim3(n_blocks_for(n_all * a.n_eig * nmax, 256, 1 << 16)), dim3(256), 0, st, n_all,
-                       a.n_eig * nmax, d_rep_of.data(), d_w.data(), d_nv.data());
-    MFMG_HIP_CHECK(hipGetLastError());
+    sharing.spread(handle, a.n_eig, d_ev.data(), d_unused.data());
+    *eigenvalues = d_ev.download(st);
   }
   weights = d_w.download(st);
   n_vec = d_nv.download(st);

@@ -1,7 +1,9 @@
 #include "amge_structured.hpp"
 #include "amge_device.hpp"
+#include "amge_lanczos.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -541,7 +543,7 @@ struct AggKey
 
 HostCsr build_restrictor_structured(StructuredMesh const &mesh, std::vector<double> const &global_diag,
                                     RestrictorOptions const &opts, std::vector<int32_t> *row_agglomerate,
-                                    int *agglomerate_counts, HipHandle *device)
+                                    int *agglomerate_counts, HipHandle *device, AmgeEigensolverInfo *info)
 {
   const int dim = mesh.dim;
   const int nc = mesh.nc();
@@ -568,12 +570,41 @@ HostCsr build_restrictor_structured(StructuredMesh const &mesh, std::vector<doub
   std::vector<double> dev_weights;
   std::vector<int32_t> dev_n_vec;
   int dev_nmax = 0;
-  const bool on_device = device != nullptr && amge_device_supported(mesh, opts);
+  ASSERT_THROW(opts.solver == "dense" || opts.solver == "lanczos", "unknown agglomerate eigensolver \"" + opts.solver + "\"");
+  const bool lanczos = opts.solver == "lanczos";
+  if (lanczos)
+  {
+    ASSERT_THROW(device != nullptr, "the Lanczos eigensolver runs on the device");
+    ASSERT_THROW(opts.selection == "krylov", "eigensolver.selection lapack is not available with the Lanczos eigensolver: a "
+                                             "Krylov solver returns the krylov selection");
+  }
+  const bool on_device = lanczos || (device != nullptr && amge_device_supported(mesh, opts));
+  AmgeEigensolverInfo stats;
+  stats.solver = lanczos ? 2 : (on_device ? 1 : 0);
+  stats.agglomerates = n_agg;
+  stats.nodes_per_agglomerate = 1;
+  for (int d = 0; d < dim; ++d)
+    stats.nodes_per_agglomerate *= std::min(ag[d], mesh.n[d]) + 1;
+  std::atomic<int64_t> host_solves{0};
   const bool verbose_t = std::getenv("MFMG_HIP_VERBOSE") != nullptr;
   auto now_t = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double tt0 = now_t();
-  if (on_device)
-    amge_device_eigen(*device, mesh, opts, cnt, dev_weights, dev_n_vec, dev_nmax);
+  if (lanczos)
+  {
+    // an explicit request is not served by another solver: agglomerates beyond 729 nodes throw "not implemented" in there
+    std::vector<double> ev;
+    std::vector<int32_t> its, flags;
+    amge_lanczos_eigen(*device, mesh, opts, cnt, dev_weights, dev_n_vec, dev_nmax, ev, its, flags, &stats.solves,
+                       &stats.kernel_seconds);
+    for (int64_t a = 0; a < n_agg; ++a)
+    {
+      stats.max_iterations = std::max(stats.max_iterations, (int)its[a]);
+      stats.breakdowns += (flags[a] & kAmgeBreakdown) ? 1 : 0;
+      stats.unconverged += (flags[a] & kAmgeConverged) ? 0 : 1;
+    }
+  }
+  else if (on_device)
+    amge_device_eigen(*device, mesh, opts, cnt, dev_weights, dev_n_vec, dev_nmax, nullptr, &stats.solves);
   const double tt1 = now_t();
   // identical agglomerates (same shape, constraints and local matrix) share one eigen-solve;
   // the table is capped so that a spatially varying coefficient cannot blow up host memory
@@ -652,6 +683,7 @@ HostCsr build_restrictor_structured(StructuredMesh const &mesh, std::vector<doub
       }
       if (!found)
       {
+        host_solves.fetch_add(1, std::memory_order_relaxed);
         AggResult res;
         std::vector<double> diag_loc(nloc);
         // eliminate constrained rows / columns
@@ -785,6 +817,10 @@ HostCsr build_restrictor_structured(StructuredMesh const &mesh, std::vector<doub
   }
 
   const double tt2 = now_t();
+  if (!on_device)
+    stats.solves = host_solves.load();
+  if (info)
+    *info = stats;
   // assemble R (rows: agglomerates in x-fastest order, eigenvectors inside; columns sorted)
   HostCsr R;
   R.n_cols = mesh.n_dofs;

@@ -80,15 +80,38 @@ struct RestrictorOptions
   // (source/dealii/dealii_mesh_evaluator.cc:44-56) onto the eigenspace -- what ARPACK / Lanczos return.
   std::string selection = "lapack";
   bool use_coefficient = true; // tests/test_hierarchy_device.cu:239-244 ignores it on agglomerates
+  // 'dense': cyclic Jacobi on the formed matrix (host cores, or amge_device.hip up to 64 nodes)
+  // 'lanczos': matrix-free Lanczos on the device (amge_lanczos.hip, up to 729 nodes; selection 'krylov' only), with the keys
+  // eigensolver.tolerance / max_iterations / percent_overshoot of the reference's input file
+  // (include/mfmg/dealii/amge_host.templates.hpp:165-200); the tolerance is taken as given, not clamped to 1e-4
+  std::string solver = "dense";
+  double tolerance = 1e-14;
+  int max_iterations = 200;
+  int percent_overshoot = 5;
+};
+
+// What solved the agglomerate eigenproblems of a restrictor (mfmg_hip_hierarchy_restrictor_eigensolver_info)
+struct AmgeEigensolverInfo
+{
+  int solver = 0;               // 0 dense on the host cores, 1 dense on the device, 2 Lanczos on the device
+  int nodes_per_agglomerate = 0; // of a full agglomerate
+  int64_t agglomerates = 0;
+  int64_t solves = 0;           // eigenproblems solved: identical agglomerates share one
+  int max_iterations = 0;       // largest number of Lanczos steps (0 for the dense solvers)
+  int64_t breakdowns = 0;       // agglomerates whose Lanczos run ended by breakdown
+  int64_t unconverged = 0;      // agglomerates that stopped at max_iterations unconverged
+  double kernel_seconds = 0.;   // Lanczos: wall time of the kernel
 };
 
 // R as CSR (rows = coarse DoFs: agglomerates x-fastest, eigenvectors inside)
 // `row_agglomerate` (optional): agglomerate index (x fastest) of every row; `agglomerate_counts`: grid
 // `device` (optional): solve the agglomerate eigenproblems on the GPU of that handle (amge_device.hip) instead of
-// on the host cores; same rules, results equal to rounding
+// on the host cores; same rules, results equal to rounding.  opts.solver "lanczos" needs it (amge_lanczos.hip).
+// `info` (optional): which solver ran and its bookkeeping
 HostCsr build_restrictor_structured(StructuredMesh const &mesh, std::vector<double> const &global_diag,
                                     RestrictorOptions const &opts, std::vector<int32_t> *row_agglomerate = nullptr,
-                                    int *agglomerate_counts = nullptr, HipHandle *device = nullptr);
+                                    int *agglomerate_counts = nullptr, HipHandle *device = nullptr,
+                                    AmgeEigensolverInfo *info = nullptr);
 
 // A_c = R A R^T without storing A or A R^T: operator rows generated on the fly from the
 // coefficient table.  `Rt` must be the transpose of `R`.

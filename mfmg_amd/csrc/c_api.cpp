@@ -5,6 +5,7 @@
 #include <exception>
 #include <string>
 
+#include "amge_lanczos.hpp"
 #include "cell_contraction.hpp"
 #include "dof_permutation.hpp"
 #include "halo_transport.hpp"
@@ -155,6 +156,8 @@ struct mfmg_hip_hierarchy_s
   std::shared_ptr<TimerOutput> timer;
   std::unique_ptr<Hierarchy<DVector>> hierarchy;
   mfmg_hip_csr_s restrictor_view, coarse_view, amg_view, fine_view;
+  int64_t eigensolver_info[MFMG_HIP_EIGENSOLVER_INFO_FIELDS] = {0, 0, 0, 0, 0, 0, 0}; // what solved the agglomerate eigenproblems
+  double eigensolver_seconds = 0.;
   bool setup_values_float = false; // "setup value precision" of THIS hierarchy: on the handle only while one of its setups runs
   // "fine level precision" float: the matrix-free operator and its smoother in FP32 around the FP64 coarse levels
   std::unique_ptr<HipFloatFineLevel> fine_f32;
@@ -1348,6 +1351,9 @@ int mfmg_hip_hierarchy_create(mfmg_hip_context_t ctx, const char *evaluator_type
       // what the setup keys on a DoF id takes the caller's id of the node (HipSmoother::estimate_eigenvalues)
       ctx->handle->setup_caller_ids = h->perm ? h->perm->node_dof_host().data() : nullptr;
       h->hierarchy.reset(new Hierarchy<DVector>(nullptr, h->evaluator, params, h->timer));
+      std::copy(ctx->handle->restrictor_eigensolver_info, ctx->handle->restrictor_eigensolver_info + MFMG_HIP_EIGENSOLVER_INFO_FIELDS,
+                h->eigensolver_info);
+      h->eigensolver_seconds = ctx->handle->restrictor_eigensolver_seconds;
     }
     // "release setup matrices" true: once the hierarchy stands, the table-driven operators (A_c, the operators of the aggregation
     // levels) free their CSR arrays -- 12 B per entry that only the setup algebra and the exports (get_coarse_operator, the
@@ -2019,6 +2025,104 @@ int mfmg_hip_hierarchy_restrictor_form(mfmg_hip_hierarchy_t h, int32_t level, in
     fields[9] = s->restrict_kernel();
     fields[10] = s->prolong_kernel();
     fields[11] = s->prolong_march() ? 1 : 0;
+  });
+}
+
+int mfmg_hip_hierarchy_restrictor_eigensolver_info(mfmg_hip_hierarchy_t h, int64_t *fields, int32_t n)
+{
+  return guarded([&] {
+    require(h && fields, "null argument");
+    require(n >= MFMG_HIP_EIGENSOLVER_INFO_FIELDS, "restrictor_eigensolver_info needs MFMG_HIP_EIGENSOLVER_INFO_FIELDS fields");
+    std::fill(fields, fields + n, 0);
+    std::copy(h->eigensolver_info, h->eigensolver_info + MFMG_HIP_EIGENSOLVER_INFO_FIELDS, fields);
+  });
+}
+
+int mfmg_hip_hierarchy_restrictor_eigensolver_seconds(mfmg_hip_hierarchy_t h, double *seconds)
+{
+  return guarded([&] {
+    require(h && seconds, "null argument");
+    *seconds = h->eigensolver_seconds;
+  });
+}
+
+int mfmg_hip_amge_eigen(mfmg_hip_context_t ctx, const mfmg_hip_mesh_desc *mesh, const char *params_info, int matrix_free,
+                        int64_t *n_agglomerates, int32_t *n_eigenvectors, int32_t *n_nodes, int32_t *n_vec, double *eigenvalues,
+                        double *weights, int32_t *iterations, int32_t *flags)
+{
+  return guarded([&] {
+    require(ctx && mesh && n_agglomerates && n_eigenvectors && n_nodes, "null argument");
+    const bool query = !n_vec && !eigenvalues && !weights && !iterations && !flags;
+    require(query || (n_vec && eigenvalues && weights && iterations && flags), "pass all output arrays, or none for the size query");
+    ptree params = ptree::parse_info(params_info ? params_info : "");
+    HipHandle &handle = *ctx->handle;
+    StructuredMesh sm = StructuredMesh::from_desc(*mesh, handle.stream);
+    // the options as the evaluators read them (HipMeshEvaluator / HipMatrixFreeMeshEvaluator::agglomerate_options)
+    RestrictorOptions o;
+    o.agglomerate[0] = params.get("agglomeration.nx", 2);
+    o.agglomerate[1] = params.get("agglomeration.ny", 2);
+    o.agglomerate[2] = params.get("agglomeration.nz", 2);
+    o.n_eigenvectors = params.get("eigensolver.number of eigenvectors", 1);
+    o.variant = params.get("eigensolver.variant", matrix_free ? "mf" : "device");
+    o.selection = params.get("eigensolver.selection", "krylov");
+    o.use_coefficient = params.get("eigensolver.use_coefficient", true);
+    const std::string where = params.get("restrictor.eigensolver", "device");
+    require(where == "device" || where == "lanczos", "mfmg_hip_amge_eigen runs the device solvers: restrictor.eigensolver device or lanczos");
+    ASSERT_THROW(o.variant == "device" || o.variant == "host" || o.variant == "mf", "unknown AMGe variant \"" + o.variant + "\"");
+    ASSERT_THROW(o.selection == "lapack" || o.selection == "krylov", "unknown eigenvector selection \"" + o.selection + "\"");
+    ASSERT_THROW(o.n_eigenvectors >= 1, "number of eigenvectors must be positive");
+    int cnt[3] = {1, 1, 1};
+    for (int d = 0; d < sm.dim; ++d)
+    {
+      ASSERT_THROW(o.agglomerate[d] >= 1, "agglomerate dimensions must be positive");
+      cnt[d] = (sm.n[d] + o.agglomerate[d] - 1) / o.agglomerate[d];
+    }
+    const int64_t n_agg = (int64_t)cnt[0] * cnt[1] * cnt[2];
+    if (where == "lanczos")
+    {
+      o.solver = "lanczos";
+      o.tolerance = params.get("eigensolver.tolerance", 1e-14);
+      o.max_iterations = params.get("eigensolver.max_iterations", 200);
+      o.percent_overshoot = params.get("eigensolver.percent_overshoot", 5);
+      ASSERT_THROW(o.selection == "krylov", "eigensolver.selection lapack is not available with the Lanczos eigensolver: a Krylov "
+                                            "solver returns the krylov selection");
+      if (!amge_lanczos_supported(sm, o))
+        ASSERT_THROW_NOT_IMPLEMENTED("the Lanczos eigensolver takes agglomerates of at most 729 nodes");
+    }
+    else if (!amge_device_supported(sm, o))
+      ASSERT_THROW_NOT_IMPLEMENTED("the dense device eigensolver takes agglomerates of at most 64 nodes");
+    int nodes = 1;
+    if (where == "lanczos")
+      for (int d = 0; d < sm.dim; ++d)
+        nodes *= std::min(o.agglomerate[d], sm.n[d]) + 1;
+    else
+    {
+      for (int d = 0; d < sm.dim; ++d)
+        nodes *= o.agglomerate[d] + 1;
+      nodes = nodes <= 27 ? 27 : 64;
+    }
+    *n_agglomerates = n_agg;
+    *n_eigenvectors = o.n_eigenvectors;
+    *n_nodes = nodes;
+    if (query)
+      return;
+    std::vector<double> w, ev;
+    std::vector<int32_t> nv, its, fl;
+    int nmax = 0;
+    if (where == "lanczos")
+      amge_lanczos_eigen(handle, sm, o, cnt, w, nv, nmax, ev, its, fl);
+    else
+    {
+      amge_device_eigen(handle, sm, o, cnt, w, nv, nmax, &ev);
+      its.assign((size_t)n_agg, 0);
+      fl.assign((size_t)n_agg, kAmgeConverged);
+    }
+    require(nmax == nodes, "internal: node stride of the eigensolver output");
+    std::copy(nv.begin(), nv.end(), n_vec);
+    std::copy(ev.begin(), ev.end(), eigenvalues);
+    std::copy(w.begin(), w.end(), weights);
+    std::copy(its.begin(), its.end(), iterations);
+    std::copy(fl.begin(), fl.end(), flags);
   });
 }
 

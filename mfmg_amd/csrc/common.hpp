@@ -602,6 +602,11 @@ struct HipHandle
   // caller's DoF id of every lexicographic node (host array of the fine level's size) -- what is keyed on a DoF id, the start
   // vector of the Chebyshev eigenvalue estimate, takes the caller's id so that both modes estimate the same eigenvalues
   int32_t const *setup_caller_ids = nullptr;
+  // what solved the agglomerate eigenproblems of the restrictor built last from this handle (HipHierarchyHelpers::build_restrictor;
+  // the fields of mfmg_hip_hierarchy_restrictor_eigensolver_info, copied into the hierarchy when its setup ends) and the wall
+  // time of the Lanczos kernel
+  int64_t restrictor_eigensolver_info[7] = {0, 0, 0, 0, 0, 0, 0};
+  double restrictor_eigensolver_seconds = 0.;
   // kernel of the DoF permutation, MFMG_DOF_PERMUTATION = brick64 | brick16 | ids, read ONCE when the handle is built
   // (dof_permutation.hip: 0 lexicographic bricks of 64 x 8 x 4 nodes, 1 of 16 x 8 x 16, 2 blocks of consecutive caller ids: the
   // default, the fastest of the three on deal.II's numbering)

@@ -169,6 +169,15 @@ RestrictorOptions HipMeshEvaluator::agglomerate_options(ptree const &params) con
   // the reference device test poses the agglomerate problems without the coefficient
   // (tests/test_hierarchy_device.cu:239-244)
   o.use_coefficient = params.get("eigensolver.use_coefficient", true);
+  // "restrictor.eigensolver lanczos": the keys of the reference's input file (amge_host.templates.hpp:165-200), the tolerance as
+  // given (the reference clamps it to >= 1e-4 because its Lanczos does not reorthogonalise; this one does)
+  if (params.get("restrictor.eigensolver", "device") == std::string("lanczos"))
+  {
+    o.solver = "lanczos";
+    o.tolerance = params.get("eigensolver.tolerance", 1e-14);
+    o.max_iterations = params.get("eigensolver.max_iterations", 200);
+    o.percent_overshoot = params.get("eigensolver.percent_overshoot", 5);
+  }
   return o;
 }
 
@@ -1782,14 +1791,28 @@ HipHierarchyHelpers<VectorType>::build_restrictor(Communicator, std::shared_ptr<
   RestrictorOptions opts = hip_mesh_evaluator->agglomerate_options(*params);
   auto global_diag = hip_mesh_evaluator->get_locally_relevant_diag();
   _grid_hint = AmgGridHint();
-  // agglomerate eigenproblems: batched on the device (default) or on the host cores ("restrictor.eigensolver host")
+  // agglomerate eigenproblems: batched on the device (default: dense up to 64 nodes per agglomerate, beyond that on the host
+  // cores), on the host cores ("restrictor.eigensolver host"), or by the matrix-free Lanczos solver on the device up to 729
+  // nodes ("restrictor.eigensolver lanczos", amge_lanczos.hip)
   std::string const where = params->get("restrictor.eigensolver", "device");
-  ASSERT_THROW(where == "device" || where == "host", "restrictor.eigensolver must be device or host");
+  ASSERT_THROW(where == "device" || where == "host" || where == "lanczos", "restrictor.eigensolver must be device, host or lanczos");
   const bool verbose = std::getenv("MFMG_HIP_VERBOSE") != nullptr;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_r0 = now();
+  AmgeEigensolverInfo eig_info;
   HostCsr R = build_restrictor_structured(hip_mesh_evaluator->get_mesh(), global_diag, opts, &_grid_hint.node_of_row,
-                                          _grid_hint.dims, where == "device" ? &_handle : nullptr);
+                                          _grid_hint.dims, where != "host" ? &_handle : nullptr, &eig_info);
+  {
+    int64_t *f = _handle.restrictor_eigensolver_info;
+    f[0] = eig_info.solver;
+    f[1] = eig_info.nodes_per_agglomerate;
+    f[2] = eig_info.agglomerates;
+    f[3] = eig_info.solves;
+    f[4] = eig_info.max_iterations;
+    f[5] = eig_info.breakdowns;
+    f[6] = eig_info.unconverged;
+    _handle.restrictor_eigensolver_seconds = eig_info.kernel_seconds;
+  }
   // "setup value precision" float | double (default): round the matrices of the setup to float-representable values
   // (R here; R A R^T and the aggregation hierarchy where they are assembled: probe_assembly.hip).  The hierarchy is then
   // the exact FP64 cycle of the ROUNDED matrices -- what get_restrictor / get_coarse_operator hand out -- and the stored

@@ -21,6 +21,7 @@ NO_TRANS = 0
 TRANS = 1
 TRANS_SUBTRACT = 2   # restrictor_apply only: out -= R^T in
 RESTRICTOR_FORM_FIELDS = 12
+EIGENSOLVER_INFO_FIELDS = 7
 RESIDUAL_RESTRICTION_FORM_FIELDS = 10
 AMG_SETUP_INFO_FIELDS = 13   # MFMG_HIP_AMG_SETUP_INFO_FIELDS
 CSR_FORM_FIELDS = 22
@@ -232,6 +233,9 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_smoother_apply": (C.c_int, [vp, i32, vp, vp]),
         "mfmg_hip_hierarchy_restrictor_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
         "mfmg_hip_hierarchy_restrictor_form": (C.c_int, [vp, i32, P(i32), i32]),
+        "mfmg_hip_hierarchy_restrictor_eigensolver_info": (C.c_int, [vp, P(i64), i32]),
+        "mfmg_hip_hierarchy_restrictor_eigensolver_seconds": (C.c_int, [vp, P(dbl)]),
+        "mfmg_hip_amge_eigen": (C.c_int, [vp, P(MeshDesc), C.c_char_p, C.c_int, P(i64), P(i32), P(i32), vp, vp, vp, vp, vp]),
         "mfmg_hip_hierarchy_ap_apply": (C.c_int, [vp, i32, vp, vp]),
         "mfmg_hip_hierarchy_coarse_apply": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_set_restrictor": (C.c_int, [vp, i64, i64, i64, vp, vp, vp]),
