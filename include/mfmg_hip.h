@@ -392,6 +392,17 @@ int mfmg_hip_mf_laplace_set_sweep_reference(mfmg_hip_mf_laplace_t op, int on);
 /* tile of the sweep: n_waves (1 .. 8) wavefronts of tile_y cell rows (2, 3 or 4), tile_z owned layers; 0, 0, 0 = chosen from the mesh.
  * 12 wavefronts of 2 rows: the shape of the three-term FP64 sweep with D^-1 derived in the kernel (its default; 8, 3 is the shape
  * of before); a sweep that has no such kernel keeps its default tile when asked for it */
+/* Where the sweep of twelve wavefronts of two rows takes D^-1 from.  An FP64 operator that can run that sweep (one coefficient
+ * per cell, computed ids, three halo lanes, no D^-1 in the records) builds at construction a vector of n_dofs values
+ * 1 / (kd * sum of the coefficients of the eight cells of a DoF), bit for bit what the kernels derive on the fly, and the sweep
+ * reads it (stored = 1, the default there) instead of deriving it per DoF and launch (stored = 0: same results, bit for bit).
+ * The environment variable MFMG_MF_SWEEP_DINV=derived, read at construction, builds no vector: such an operator, and any that
+ * cannot run that sweep, reports 0, and asking it for 1 or for the vector is MFMG_HIP_ERROR_NOT_IMPLEMENTED.
+ * mfmg_hip_mf_laplace_sweep_diagonal_inverse copies the vector (device pointer, n_dofs doubles, the operator's numbering;
+ * entries of Dirichlet DoFs are finite and not read by any kernel).  (additions, no change of the ABI version) */
+int mfmg_hip_mf_laplace_set_sweep_diagonal(mfmg_hip_mf_laplace_t op, int stored);
+int mfmg_hip_mf_laplace_get_sweep_diagonal(mfmg_hip_mf_laplace_t op, int *stored);
+int mfmg_hip_mf_laplace_sweep_diagonal_inverse(mfmg_hip_mf_laplace_t op, double *dinv);
 int mfmg_hip_mf_laplace_set_sweep_tile(mfmg_hip_mf_laplace_t op, int n_waves, int tile_y, int tile_z);
 int mfmg_hip_mf_laplace_get_sweep_tile(mfmg_hip_mf_laplace_t op, int n_terms, int *n_waves, int *tile_y, int *tile_z);
 /* FP32 instance of the same operator (BASELINE.json configs[4]; the coefficient table is converted once,

@@ -460,6 +460,25 @@ class MatrixFreeLaplace:
         check(self._lib.mfmg_hip_mf_laplace_get_sweep_tile(self.handle, int(n_terms), C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def set_sweep_diagonal(self, source: str):
+        """D^-1 of the sweep of twelve wavefronts: "stored" (read from the vector built at construction, the default where
+        the operator has one) or "derived" (formed from the coefficient sums per DoF and launch); the same bits either way."""
+        if source not in ("stored", "derived"):
+            raise ValueError("source must be 'stored' or 'derived'")
+        check(self._lib.mfmg_hip_mf_laplace_set_sweep_diagonal(self.handle, int(source == "stored")))
+
+    def sweep_diagonal(self) -> str:
+        v = C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_get_sweep_diagonal(self.handle, C.byref(v)))
+        return "stored" if v.value else "derived"
+
+    def sweep_diagonal_inverse(self) -> torch.Tensor:
+        """A copy of the D^-1 vector of the sweep (raises where the operator has none)."""
+        out = torch.empty(self.n_dofs, dtype=torch.float64, device="cuda")
+        check(self._lib.mfmg_hip_mf_laplace_sweep_diagonal_inverse(self.handle, _dev_ptr(out)))
+        self.ctx.synchronize()
+        return out
+
     def diagonal_inverse(self) -> torch.Tensor:
         out = torch.empty(self.n_dofs, dtype=torch.float64, device="cuda")
         check(self._lib.mfmg_hip_mf_laplace_diagonal_inverse(self.handle, _dev_ptr(out)))

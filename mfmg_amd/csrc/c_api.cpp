@@ -1148,6 +1148,31 @@ int mfmg_hip_mf_laplace_f32_set_sweep_reference(mfmg_hip_mf_laplace_f32_t op, in
     op->op->set_fused_reference(on != 0);
   });
 }
+int mfmg_hip_mf_laplace_set_sweep_diagonal(mfmg_hip_mf_laplace_t op, int stored)
+{
+  return guarded([&] {
+    require(op != nullptr, "null operator");
+    if (stored != 0 && op->op->sweep_diagonal_inverse() == nullptr)
+      ASSERT_THROW_NOT_IMPLEMENTED("this operator holds no D^-1 vector of the sweep");
+    op->op->set_sweep_diagonal(stored != 0);
+  });
+}
+int mfmg_hip_mf_laplace_get_sweep_diagonal(mfmg_hip_mf_laplace_t op, int *stored)
+{
+  return guarded([&] {
+    require(op && stored, "null argument");
+    *stored = op->op->sweep_diagonal_stored() ? 1 : 0;
+  });
+}
+int mfmg_hip_mf_laplace_sweep_diagonal_inverse(mfmg_hip_mf_laplace_t op, double *dinv)
+{
+  return guarded([&] {
+    require(op && dinv, "null argument");
+    if (op->op->sweep_diagonal_inverse() == nullptr)
+      ASSERT_THROW_NOT_IMPLEMENTED("this operator holds no D^-1 vector of the sweep");
+    vec::copy<double>(op->op->handle(), op->op->n_dofs(), op->op->sweep_diagonal_inverse(), dinv);
+  });
+}
 int mfmg_hip_mf_laplace_set_sweep_tile(mfmg_hip_mf_laplace_t op, int n_waves, int tile_y, int tile_z)
 {
   return guarded([&] {

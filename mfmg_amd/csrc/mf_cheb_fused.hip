@@ -184,11 +184,18 @@ struct BufIO<float>
 // (xn at the stage that reads it, xq one super-pass later: a renaming like that of bq and dq) instead of in a third slot of
 // its ring.  The x_0 layer requested two ahead then lands over the slot of layer c1, which stage 1 has read by the end of the
 // super-pass.
-template <typename T, int K, int TY, bool DREC, bool MODES, int DBG = 0, bool NARROW = false, bool ZERO0 = false, int NWC = 0>
-__device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsigned int w)
+// DVEC: D^-1 is read from a vector of its own (dinv_vec: the operator's sweep_diagonal_inverse, by DoF id like b; an argument of
+// the kernel beside MfFusedArgs, whose layout the other kernels keep), requested like b one layer ahead, instead of derived from
+// the coefficient sums (!DREC) or read from the records (DREC): the bits of the derived form without its divisions, pair sums and
+// carried sums.  Dirichlet DoFs take D^-1 = 1 as the derived form does.
+template <typename T, int K, int TY, bool DREC, bool MODES, int DBG = 0, bool NARROW = false, bool ZERO0 = false, int NWC = 0, bool DVEC = false>
+__device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsigned int w, T const *dinv_vec = nullptr)
 {
 #pragma clang fp contract(off)
+  static_assert(!(DREC && DVEC), "one source of D^-1");
+  static_assert(!DVEC || NWC > 0, "the D^-1 vector is an argument of the twelve-wavefront kernels");
   constexpr int R = TY + 1; // node rows of a wavefront
+  constexpr bool DERIVE = !DREC && !DVEC; // D^-1 from the coefficient sums, formed by stage 1
   constexpr bool CARRY = NWC > 0;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63;
@@ -253,7 +260,8 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
   // the wavefront waits for with lgkmcnt(0), its LDS reads drained along with it.  The same operands in the same expressions.
   // How many of the six: all in the wide body of the mode-space kernels (161 VGPRs of 168); beta_1 .. beta_3 in the narrow body, which
   // has room for three pairs (167) -- the others stay scalar there, as all do in the reference arithmetic (163 VGPRs without them)
-  constexpr int kHoldInVgpr = !MODES ? 0 : (NARROW ? 3 : 2 * K);
+  // (D^-1 from its vector: ten VGPRs of carried sums are gone, kd is not used, and the narrow body holds the other five as well)
+  constexpr int kHoldInVgpr = !MODES ? 0 : ((NARROW && !DVEC) ? 3 : 2 * K);
   T held_alpha[K], held_beta[K], held_kd = T(0);
   if constexpr (CARRY)
   {
@@ -357,20 +365,62 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
   // of this chunk column's records
   // (CARRY: from the pointers as the kernel received them -- a descriptor is a held pointer plus two constant words, no scalar
   // load per request or store)
+  // DVEC: one of the five base addresses (0 .. 4: x, b, out, out_prev, the records) is held in a vector register pair and made
+  // uniform where a descriptor is built from it (two v_readfirstlane), like the address of the D^-1 vector below: the scalar
+  // file is what these kernels run out of, and with it their sgpr_spill_count stays at or under that of the kernels that derive
+  // D^-1.  Which one: the address used least -- x_{K-1}; from a zero guess that of the records, where out_prev left 29 spills
+  // against the 25 of the twin (profiles/r11_a_sweep_isa.txt has the counts of the choices tried).  One pair is what the
+  // vector registers have room for beside the twin's count.
+  constexpr int kHeldBase = !DVEC ? 0 : (ZERO0 ? 16 : 8);
+  unsigned long long hp[5] = {0, 0, 0, 0, 0};
+  if constexpr (DVEC)
+  {
+    const unsigned long long base[5] = {(unsigned long long)a.x, (unsigned long long)a.b, (unsigned long long)a.out, (unsigned long long)a.out_prev, (unsigned long long)a.rec};
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+      if ((kHeldBase >> i) & 1)
+      {
+        hp[i] = base[i];
+        asm volatile("" : "+v"(hp[i]));
+      }
+  }
+  auto hp_get = [&](int i) -> void * {
+    const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)hp[i]), hi = __builtin_amdgcn_readfirstlane((unsigned int)(hp[i] >> 32));
+    return reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
+  };
   auto vec_ptr = [&](size_t off) -> void * {
     if constexpr (CARRY)
+    {
+      const int i = off == offsetof(MfFusedArgs<T>, x) ? 0 : (off == offsetof(MfFusedArgs<T>, b) ? 1 : (off == offsetof(MfFusedArgs<T>, out) ? 2 : 3));
+      if ((kHeldBase >> i) & 1)
+        return hp_get(i);
       return const_cast<T *>(off == offsetof(MfFusedArgs<T>, x) ? a.x : (off == offsetof(MfFusedArgs<T>, b) ? a.b : (off == offsetof(MfFusedArgs<T>, out) ? a.out : a.out_prev)));
+    }
     else
       return karg_ptr(off);
   };
   auto rec_ptr = [&]() -> void * {
     if constexpr (CARRY)
+    {
+      if ((kHeldBase >> 4) & 1)
+        return hp_get(4);
       return const_cast<unsigned char *>(a.rec);
+    }
     else
       return karg_ptr(offsetof(MfFusedArgs<T>, rec));
   };
   auto rs_vec = [&](size_t off) { return __builtin_amdgcn_make_buffer_rsrc(vec_ptr(off), 0, a.vec_bytes, 0x00020000); };
   auto rs_rec_f = [&]() { return __builtin_amdgcn_make_buffer_rsrc(rec_ptr(), 0, a.rec_total_bytes, 0x00020000); };
+  // (the address of the D^-1 vector is held in a vector register pair and made uniform where its descriptor is built, once per
+  // super-pass: as a sixth pointer in scalar registers it pushed some twenty moves to and from spill lanes into the march of
+  // either body)
+  unsigned long long dinv_addr = (unsigned long long)dinv_vec;
+  if constexpr (DVEC)
+    asm volatile("" : "+v"(dinv_addr));
+  auto rs_dinv_f = [&]() {
+    const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)dinv_addr), hi = __builtin_amdgcn_readfirstlane((unsigned int)(dinv_addr >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo), 0, a.vec_bytes, 0x00020000);
+  };
   const bool want_prev_tile = a.out_prev != nullptr;
   int want_prev_i = 0;
   if constexpr (CARRY)
@@ -449,7 +499,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
 
   // ---- per-lane state carried from super-pass to super-pass (stage s + 1 uses entry s)
   T bq[K][R];  // b of the DoF (row r, layer of the stage)
-  T dq[K][R];  // D^-1 likewise (entry 0 written by stage 1 / loaded from the records)
+  T dq[K][R];  // D^-1 likewise (entry 0 written by stage 1 / loaded from the records or the D^-1 vector)
   T cq[K][TY]; // coefficient of the cell (row q, cell layer of the stage)
   T pt[K][R];  // z-carry of the partial sums
   T pcs[R];    // z-carry of the coefficient sums (D^-1 on the fly)
@@ -489,6 +539,8 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       bq[0][r] = ld_vec(rs_b, r, cb);
       if constexpr (DREC)
         dq[0][r] = ld_dinv(rs_rec, r, cb);
+      if constexpr (DVEC)
+        dq[0][r] = ld_vec(rs_dinv_f(), r, cb);
     }
 #pragma unroll
     for (int q = 0; q < TY; ++q)
@@ -496,7 +548,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       const T cv = ld_coef(rs_rec, q, cb);
       cq[0][q] = (Yw + q >= 0) ? cv : T(0);
     }
-    if constexpr (!DREC)
+    if constexpr (DERIVE)
     {
       const T l = ld_coef(rs_rec, -1, cb);
       const T h = ld_coef(rs_rec, TY, cb);
@@ -575,7 +627,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       for (int q = 0; q < TY; ++q)
       {
         lowA[q] = lowB[q] = upA[q] = upB[q] = sx[q] = T(0);
-        if constexpr (!DREC)
+        if constexpr (DERIVE)
         {
           const T cv = cq[0][q];
           sx[q] = cv + from_prev_lane(cv);
@@ -599,7 +651,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         const T cv = cq[S - 1][q];
         cell_row_modes<T>(Pl[q], Pl[q + 1], Ql[q], Ql[q + 1], Pu[q], Pu[q + 1], Qu[q], Qu[q + 1], cv, mf, lowA[q], lowB[q], upA[q], upB[q]);
         sx[q] = T(0);
-        if constexpr (S == 1 && !DREC)
+        if constexpr (S == 1 && DERIVE)
           sx[q] = cv + from_prev_lane(cv);
       }
     }
@@ -625,7 +677,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         lowB[q] = v[4] + from_prev_lane(v[5]);
         upB[q] = v[6] + from_prev_lane(v[7]);
         sx[q] = T(0);
-        if constexpr (S == 1 && !DREC)
+        if constexpr (S == 1 && DERIVE)
           sx[q] = cv + from_prev_lane(cv);
       }
     }
@@ -672,7 +724,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       if constexpr (S == 1)
       {
         T d;
-        if constexpr (!DREC)
+        if constexpr (DERIVE)
         {
           // the eight cells of the DoF: two rows of this layer + the same of the layer below (carried)
           const T sum8 = tcs + pcs[r];
@@ -781,7 +833,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         const T t1 = lowB[0] + lo1;
         const T yv = z_combine(t0, t1, pt[S - 1][0]);
         T tcs = T(0);
-        if constexpr (S == 1 && !DREC)
+        if constexpr (S == 1 && DERIVE)
           tcs = sx[0] + (clo + from_prev_lane(clo));
         finish(IntTag<0>{}, yv, tcs);
       }
@@ -790,7 +842,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         const T t1 = hi1 + upB[TY - 1];
         const T yv = z_combine(t0, t1, pt[S - 1][TY]);
         T tcs = T(0);
-        if constexpr (S == 1 && !DREC)
+        if constexpr (S == 1 && DERIVE)
           tcs = (chi + from_prev_lane(chi)) + sx[TY - 1];
         finish(IntTag<TY>{}, yv, tcs);
       }
@@ -815,11 +867,13 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
       pfd[r] = T(0);
       if constexpr (DREC)
         pfd[r] = ld_dinv(rs_rec, r, c1 + 1);
+      if constexpr (DVEC)
+        pfd[r] = ld_vec(rs_dinv_f(), r, c1 + 1);
     }
 #pragma unroll
     for (int q = 0; q < TY; ++q)
       pfc[q] = ld_coef(rs_rec, q, c1 + 1);
-    if constexpr (!DREC)
+    if constexpr (DERIVE)
     {
       pflo = ld_coef(rs_rec, -1, c1 + 1);
       pfhi = ld_coef(rs_rec, TY, c1 + 1);
@@ -861,7 +915,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
         for (int s = 0; s + 2 <= K; ++s)
           xq[s][r] = xn[s][r];
       }
-      if constexpr (DREC)
+      if constexpr (DREC || DVEC)
         dq[0][r] = pfd[r];
       if constexpr (!ZERO0)
         *ring_at(0, sl(0, 2), r) = pfx[r];
@@ -874,7 +928,7 @@ __device__ __forceinline__ void mf_cheb_fused_body(MfFusedArgs<T> const &a, unsi
 #pragma unroll
     for (int q = 0; q < TY; ++q)
       cq[0][q] = (Ywu + q >= 0) ? pfc[q] : T(0);
-    if constexpr (!DREC)
+    if constexpr (DERIVE)
     {
       clo = (Ywu - 1 >= 0) ? pflo : T(0);
       chi = (Ywu + TY >= 0) ? pfhi : T(0);
@@ -946,7 +1000,8 @@ __global__ __launch_bounds__(512, 2) void mf_cheb_fused_kernel(MfFusedArgs<T> a)
 }
 
 // Twelve wavefronts of TY = 2 rows, three per SIMD: the rows of eight of three (the same y-tiling, the same pairing of a narrow
-// last column) at three quarters of the per-row state each.  Three terms, FP64, D^-1 from the coefficient sums; at most 168
+// last column) at three quarters of the per-row state each.  Three terms, FP64, D^-1 from the coefficient sums (the kernels
+// below: from the operator's D^-1 vector, which the sweep launches where that vector exists); at most 168
 // VGPRs, and the rings two slots deep (mf_cheb_fused_body, NWC) so that 12 x (6 x 3) + 96 planes of 512 B = 156 KiB fit the LDS.
 constexpr int kWgWaves12 = 12, kWgRows12 = 2;
 constexpr bool kWg12ByDefault = true; // the tile of a sweep that can take it (choose_fused_tile)
@@ -972,6 +1027,33 @@ __global__ __launch_bounds__(64 * kWgWaves12, 3) void mf_cheb_fused_wg12_kernel(
     }
   }
   mf_cheb_fused_body<T, 3, kWgRows12, false, MODES, 0, false, ZERO0, kWgWaves12>(a, w);
+}
+
+// The same kernels with D^-1 read from the operator's vector (mf_cheb_fused_body, DVEC) instead of derived: per wavefront and
+// super-pass three divisions, the pair sums of four cell rows with their row and layer sums and two coefficient requests less,
+// three requests more (8 B/DoF); ten VGPRs of carried state go.  The sweep is bound by vector-ALU issue, not by memory.
+template <typename T, bool MODES, bool NARROW_TOO, bool ZERO0>
+__global__ __launch_bounds__(64 * kWgWaves12, 3) void mf_cheb_fused_wg12d_kernel(MfFusedArgs<T> a, T const *dinv)
+{
+  // (the tile order of mf_cheb_fused_kernel)
+  const unsigned int n_tiles = NARROW_TOO ? a.wide_tiles + a.ntiles_y2 * a.ntiles_z : a.wide_tiles;
+  unsigned int w = blockIdx.x;
+  if (n_tiles >= 64)
+  {
+    const unsigned int per_xcd = (n_tiles + 7) / 8;
+    w = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    if (w >= n_tiles)
+      return;
+  }
+  if constexpr (NARROW_TOO)
+  {
+    if (w >= a.wide_tiles)
+    {
+      mf_cheb_fused_body<T, 3, kWgRows12, false, MODES, 0, true, ZERO0, kWgWaves12, true>(a, w, dinv);
+      return;
+    }
+  }
+  mf_cheb_fused_body<T, 3, kWgRows12, false, MODES, 0, false, ZERO0, kWgWaves12, true>(a, w, dinv);
 }
 
 // The tiles of a narrow last chunk column alone, launched behind the wide-only kernel on the same stream (MFMG_MF_FUSED_NARROW=split;
@@ -1202,7 +1284,18 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
     if constexpr (std::is_same<T, double>::value)
       with_flag(narrow, [&](auto nt) {
         constexpr bool NT = decltype(nt)::value;
-        if (!modes)
+        // D^-1 from the operator's vector where it has one (sweep_diagonal_inverse) and set_sweep_diagonal has not said otherwise
+        if (_sweep_dinv_read)
+        {
+          auto go_d = [&](auto kernel) { mf_launch(kernel, MfGrid{n_blocks, nw, lds, st}, a, _sweep_dinv.data()); };
+          if (!modes)
+            go_d(mf_cheb_fused_wg12d_kernel<T, false, false, false>);
+          else if (zero_guess)
+            go_d(mf_cheb_fused_wg12d_kernel<T, true, NT, true>);
+          else
+            go_d(mf_cheb_fused_wg12d_kernel<T, true, NT, false>);
+        }
+        else if (!modes)
           go(mf_cheb_fused_wg12_kernel<T, false, false, false>, n_blocks);
         else if (zero_guess)
           go(mf_cheb_fused_wg12_kernel<T, true, NT, true>, n_blocks);

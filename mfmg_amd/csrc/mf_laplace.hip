@@ -654,6 +654,39 @@ __global__ void mf_fill_dinv_kernel(T const *dinv, int Nx, int ncols, int own, i
     reinterpret_cast<T *>(r + Rec<T, CC>::kDinvOff)[lane] = dinv[g];
   }
 }
+
+// D^-1 as the smoother kernels derive it with one coefficient per cell, once per DoF and by DoF id: 1 / (kd * sum8), sum8 from
+// the same operands in the same association as mf_laplace_body (make_dinv) and the stage 1 of mf_cheb_fused_body form it --
+// pair = the own cell + the cell of the lane to the left, layer sum = the pair of cell row j + that of row j - 1, sum8 = the layer
+// sum of cell layer k + that of layer k - 1; cell rows and layers below the mesh count zero, phantom cells and the columns
+// outside the mesh hold zero in the records.  The same bits, so a sweep that reads this vector equals one that derives it.
+// Dirichlet DoFs get the value too (the kernels take D^-1 = 1 there and do not read it).
+template <typename T>
+__global__ void mf_sweep_dinv_kernel(unsigned char const *rec, size_t rec_bytes, int Nx, int Ny, int Nz, int ncols, int own, int halo,
+                                     T kd, T *dinv)
+{
+#pragma clang fp contract(off)
+  const int64_t n = (int64_t)Nx * Ny * Nz;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+  {
+    const int i = t % Nx;
+    const int j = (t / Nx) % Ny;
+    const int k = t / ((int64_t)Nx * Ny);
+    int lane;
+    const size_t r = chunk_of(i, j, k, Ny, ncols, own, halo, lane); // (lane >= halo >= 1: the lane to the left is in the record)
+    const int id0 = reinterpret_cast<int const *>(rec + r * rec_bytes)[lane];
+    auto pair = [&](int jj, int kk) -> T {
+      if (jj < 0 || kk < 0)
+        return T(0);
+      T const *c = reinterpret_cast<T const *>(rec + (((size_t)kk * Ny + jj) * ncols + r % ncols) * rec_bytes + Rec<T, true>::kCoefOff);
+      return c[lane] + c[lane - 1];
+    };
+    const T upper = pair(j, k) + pair(j - 1, k);
+    const T lower = pair(j, k - 1) + pair(j - 1, k - 1);
+    const T sum8 = upper + lower;
+    dinv[(unsigned int)id0 & kIdMask] = T(1) / (kd * sum8);
+  }
+}
 } // namespace
 
 // ---- dim = 2 --------------------------------------------------------------------------------------------------
@@ -1020,6 +1053,25 @@ MatrixFreeLaplaceDevice<T>::MatrixFreeLaplaceDevice(HipHandle &handle, mfmg_hip_
                        _dinv.data(), _N[0], _ncols, _own, _halo, (int64_t)n_slots, _rec.data(), _rec_bytes);
   }
   MFMG_HIP_CHECK(hipGetLastError());
+  // D^-1 of the sweep of twelve wavefronts as a vector (sweep_diagonal_inverse): FP64 operators that can take that sweep.  It is
+  // bound by vector-ALU issue at a fifth of the HBM rate, and the vector is the same in every smoother application: 8 B/DoF to
+  // read instead of the coefficient sums and a division per DoF and launch.  MFMG_MF_SWEEP_DINV=derived builds none.
+  if constexpr (std::is_same<T, double>::value)
+  {
+    char const *env = std::getenv("MFMG_MF_SWEEP_DINV");
+    if (_compact && _affine_ids && _halo >= 3 && !_dinv_in_record && !sub_mesh && !(env && std::string(env) == "derived"))
+    {
+      MemoryKind dinv_kind("matrix-free operator: D^-1 vector of the sweep");
+      _sweep_dinv.resize(nd);
+      MfArgs<T> fa{};
+      double f3[3];
+      mf_cell_factors(fa, _h, f3); // (kd as the kernels get it)
+      hipLaunchKernelGGL(mf_sweep_dinv_kernel<T>, dim3(n_blocks_for(nd, 256, 1 << 16)), dim3(256), 0, st, _rec.data(), _rec_bytes, _N[0],
+                         _N[1], _N[2], _ncols, _own, _halo, fa.kd, _sweep_dinv.data());
+      MFMG_HIP_CHECK(hipGetLastError());
+      _sweep_dinv_read = true;
+    }
+  }
   MFMG_HIP_CHECK(hipStreamSynchronize(st));
 
   // ---- nearly empty last chunk: hand its columns to a rotated slab operator

@@ -186,6 +186,20 @@ public:
   T const *diagonal() const { return _diag.data(); }
   T const *diagonal_inverse() const { return _dinv.data(); }
 
+  // D^-1 of the twelve-wavefront sweep as a vector in the operator's numbering: 1 / (kd * sum of the coefficients of the
+  // eight cells of a DoF), the bits the sweep and the one-term kernel derive on the fly (mf_laplace.hip: mf_sweep_dinv_kernel;
+  // Dirichlet DoFs hold that value too, the kernels take 1 there).  Built once, at construction, for the FP64 operators that
+  // can take that sweep (one coefficient per cell, computed ids, three halo lanes, no D^-1 in the records) unless
+  // MFMG_MF_SWEEP_DINV=derived; nullptr where it does not exist.  The sweep reads it where it exists and set_sweep_diagonal
+  // has not said otherwise: 8 B/DoF more to read, a division and the coefficient sums less to compute per DoF and launch.
+  T const *sweep_diagonal_inverse() const { return _sweep_dinv.data(); }
+  bool sweep_diagonal_stored() const { return _sweep_dinv_read; }
+  void set_sweep_diagonal(bool stored)
+  {
+    ASSERT_THROW(!stored || _sweep_dinv.size() > 0, "this operator holds no D^-1 vector of the sweep");
+    _sweep_dinv_read = stored;
+  }
+
   // tile of one workgroup: n_waves wavefronts of ty cell rows each, tz layers (0 = chosen from the mesh size)
   void set_tile(int ty, int tz)
   {
@@ -275,6 +289,8 @@ private:
   std::unique_ptr<MatrixFreeLaplaceDevice<T>> _tail;
   DeviceBuffer<unsigned char> _rec;
   DeviceBuffer<T> _diag, _dinv;
+  DeviceBuffer<T> _sweep_dinv; // (see sweep_diagonal_inverse)
+  bool _sweep_dinv_read = false;
   int _tile_y = 0, _tile_z = 0, _tile_waves = 0;
   bool _compact = false;
   bool _dinv_in_record = true; // D^-1 is part of the chunk records (always for eight coefficients per cell)
