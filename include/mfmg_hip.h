@@ -439,6 +439,28 @@ int mfmg_hip_mf_laplace_cell_constant_layout(mfmg_hip_mf_laplace_t op, int *in_u
 /* the tile in use */
 int mfmg_hip_mf_laplace_get_tile(mfmg_hip_mf_laplace_t op, int *n_waves, int *tile_y, int *tile_z);
 
+/* ---- blocks of vectors: several right-hand sides against one operator (additions, no change of the ABI version) ----
+ * A block is n_vectors (1 .. 64) columns of doubles with a common leading dimension: column c starts at base + c * ld elements,
+ * ld >= n_dofs and even, the base aligned to 16 bytes.  All blocks of one call share ld.  FP64, one rank: a context with a
+ * communicator is refused (MFMG_HIP_ERROR_INVALID_ARGUMENT), as are n_vectors outside 1 .. 64, ld < n_dofs, an odd ld, a
+ * misaligned base, an out block that overlaps the x block and a null operand the mode reads.
+ * mfmg_hip_block_groups (host only): how a block is cut into launches -- groups of 4, then one of 2, then one single vector;
+ * `widths` receives up to MFMG_HIP_BLOCK_MAX_GROUPS entries.
+ * mfmg_hip_mf_laplace_block_launch: mode 0 out = A x, 1 out = A x - b, 2 out = x - beta dinv (A x - b), 3 out = x + alpha (x -
+ * x_prev) - beta dinv (A x - b), on every column; out may be x_prev.  Groups of 4 and 2 columns run mf_laplace_block_kernel (the
+ * chunk records are read once per group) where mfmg_hip_mf_laplace_block_available reports 1: eight coefficients per cell, 3-D;
+ * elsewhere, and for a single column, the one-vector kernel runs column by column.  Every column gets the bits of the one-vector
+ * entry point.  The block tile (n_waves 1 .. 8, tile_y 2 .. 4, tile_z; 0, 0, 0 = chosen from the mesh and the group's width) is a
+ * tuning knob; get_block_tile takes the width of the group (2 or 4). */
+#define MFMG_HIP_BLOCK_MAX_VECTORS 64
+#define MFMG_HIP_BLOCK_MAX_GROUPS 18
+int mfmg_hip_block_groups(int32_t n_vectors, int32_t *widths, int32_t *n_groups);
+int mfmg_hip_mf_laplace_block_launch(mfmg_hip_mf_laplace_t op, int mode, int32_t n_vectors, int64_t ld, const double *x, const double *b,
+                                     const double *x_prev, double alpha, double beta, double *out);
+int mfmg_hip_mf_laplace_block_available(mfmg_hip_mf_laplace_t op, int *available);
+int mfmg_hip_mf_laplace_set_block_tile(mfmg_hip_mf_laplace_t op, int n_waves, int tile_y, int tile_z);
+int mfmg_hip_mf_laplace_get_block_tile(mfmg_hip_mf_laplace_t op, int n_vectors, int *n_waves, int *tile_y, int *tile_z);
+
 /* ---- hierarchy: Hierarchy<VectorType> ---- */
 /* Evaluator tag strings accepted by the string switch (create_hierarchy_helpers,
  * include/mfmg/common/hierarchy.hpp:49-107):
@@ -702,6 +724,22 @@ int mfmg_hip_host_amg_destroy(mfmg_hip_host_amg_t amg);
 /* boost::property_tree INFO round trip of the parameter reader (tests/test_utils.cc:23-60 exercises ptree2plist) */
 int mfmg_hip_host_params_get(const char *params_info, const char *path, char *value_buf, size_t buf_size);
 
+
+/* ---- the cycle on a block of vectors (layout and checks as above) ----
+ * mfmg_hip_hierarchy_apply_block: x[c] = the result of mfmg_hip_hierarchy_apply(b[c], x[c]) for every column, bit for bit;
+ * _vmult_block the same with the argument order of _vmult; _smoother_apply_block that of _smoother_apply.  Where the fine level
+ * has the block kernel the block is taken in the groups of mfmg_hip_block_groups and pre-smoothing, residual and post-smoothing
+ * run as launches on the group; restriction, coarse cycle and prolongation run column by column.  Elsewhere the one-vector
+ * entry point runs per column.  With "internal numbering" lexicographic the columns are gathered into and scattered out of the
+ * library's block workspace (one group wide).
+ * mfmg_hip_hierarchy_block_info: fields[0] width of the widest group the fine level runs as one launch (1 = the loop over the
+ * columns), fields[1] launches of mf_laplace_block_kernel and fields[2] columns that went through the one-vector entry point in
+ * the last block call. */
+#define MFMG_HIP_BLOCK_INFO_FIELDS 3
+int mfmg_hip_hierarchy_apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x);
+int mfmg_hip_hierarchy_vmult_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, double *x, const double *b);
+int mfmg_hip_hierarchy_smoother_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld, const double *b, double *x);
+int mfmg_hip_hierarchy_block_info(mfmg_hip_hierarchy_t h, int64_t *fields);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,34 @@ def _dev_ptr(t: torch.Tensor, n: Optional[int] = None, dtype=torch.float64) -> i
     return t.data_ptr()
 
 
+def _block_ptr(t: torch.Tensor):
+    """(k, ld, device pointer) of a block of vectors: a 2-D float64 CUDA tensor of shape (k, m) whose rows are the vectors
+    (stride(1) == 1, ld = stride(0)).  What the library asks of k, ld and the alignment it checks itself."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("expected a torch tensor")
+    if t.device.type != "cuda":
+        raise ValueError("vectors must live on the GPU (the HIP path has no CPU fallback)")
+    if t.dtype != torch.float64 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("a block is a 2-D float64 tensor of shape (k, m) with stride(1) == 1")
+    return int(t.shape[0]), int(t.stride(0)), t.data_ptr()
+
+
+def _same_block(k, ld, t):
+    kk, ll, p = _block_ptr(t)
+    if (kk, ll) != (k, ld):
+        raise ValueError("the blocks of one call share the number of vectors and the leading dimension")
+    return p
+
+
+def block_groups(n_vectors: int):
+    """Widths of the launches a block of n_vectors (1 .. 64) is cut into: groups of 4, then one of 2, then one vector."""
+    lib = _lib.load()
+    w = (C.c_int32 * 18)()
+    n = C.c_int32()
+    check(lib.mfmg_hip_block_groups(int(n_vectors), w, C.byref(n)))
+    return [int(w[i]) for i in range(n.value)]
+
+
 def memory_inventory() -> str:
     """Live bytes of the library's device buffers per (setup section | kind of structure), as text."""
     lib = _lib.load()
@@ -518,6 +546,32 @@ class MatrixFreeLaplace:
         if waves is not None:
             check(self._lib.mfmg_hip_mf_laplace_set_tile_waves(self.handle, waves))
 
+    _BLOCK_MODES = {"apply": 0, "residual": 1, "first": 2, "next": 3}
+
+    def block_launch(self, mode: str, X, out, B=None, X_prev=None, alpha: float = 0.0, beta: float = 0.0):
+        """One operator launch on every vector of a block: mode "apply" out = A x, "residual" out = A x - b, "first" out = x -
+        beta D^-1 (A x - b), "next" out = x + alpha (x - x_prev) - beta D^-1 (A x - b).  The blocks are 2-D float64 tensors of
+        shape (k, m), stride(1) == 1, with one leading dimension ld = stride(0) >= n_dofs; out may be X_prev.  Every row gets
+        the bits of vmult / residual / smoother_step on that row."""
+        k, ld, px = _block_ptr(X)
+        check(self._lib.mfmg_hip_mf_laplace_block_launch(
+            self.handle, self._BLOCK_MODES[mode], k, ld, px, _same_block(k, ld, B) if B is not None else None,
+            _same_block(k, ld, X_prev) if X_prev is not None else None, alpha, beta, _same_block(k, ld, out)))
+
+    def block_available(self) -> bool:
+        """Groups of 4 and 2 vectors of a block run the block kernel (eight coefficients per cell, 3-D, no tail slab)."""
+        v = C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_block_available(self.handle, C.byref(v)))
+        return bool(v.value)
+
+    def set_block_tile(self, waves: int, ty: int, tz: int):
+        check(self._lib.mfmg_hip_mf_laplace_set_block_tile(self.handle, waves, ty, tz))
+
+    def get_block_tile(self, n_vectors: int):
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_get_block_tile(self.handle, int(n_vectors), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -693,6 +747,29 @@ class Hierarchy:
     def smoother_apply(self, level: int, b, x):
         n = self.level_size(level)
         check(self._lib.mfmg_hip_hierarchy_smoother_apply(self.handle, level, _dev_ptr(b, n), _dev_ptr(x, n)))
+
+    def apply_block(self, B: torch.Tensor, X: torch.Tensor):
+        """The cycle of apply() on every row of the blocks B and X: 2-D float64 tensors of shape (k, m), stride(1) == 1, with one
+        leading dimension ld = stride(0) >= n_dofs (even; the bases aligned to 16 bytes).  Row c of X gets the bits of
+        apply(B[c], X[c])."""
+        k, ld, pb = _block_ptr(B)
+        check(self._lib.mfmg_hip_hierarchy_apply_block(self.handle, k, ld, pb, _same_block(k, ld, X)))
+
+    def vmult_block(self, X: torch.Tensor, B: torch.Tensor):
+        k, ld, pb = _block_ptr(B)
+        check(self._lib.mfmg_hip_hierarchy_vmult_block(self.handle, k, ld, _same_block(k, ld, X), pb))
+
+    def smoother_apply_block(self, level: int, B: torch.Tensor, X: torch.Tensor):
+        k, ld, pb = _block_ptr(B)
+        check(self._lib.mfmg_hip_hierarchy_smoother_apply_block(self.handle, level, k, ld, pb, _same_block(k, ld, X)))
+
+    def block_info(self) -> dict:
+        """width: vectors of the widest group the fine level runs as one launch (1 = the loop over the vectors); block_launches /
+        column_launches: launches of the block kernel, and vectors that went through the one-vector entry point, in the last
+        block call."""
+        f = (C.c_int64 * 3)()
+        check(self._lib.mfmg_hip_hierarchy_block_info(self.handle, f))
+        return {"width": int(f[0]), "block_launches": int(f[1]), "column_launches": int(f[2])}
 
     def restrictor_apply(self, level: int, vin, vout, mode: int = _lib.NO_TRANS):
         """vout = R vin (NO_TRANS), vout = R^T vin (TRANS) or vout -= R^T vin (TRANS_SUBTRACT)."""

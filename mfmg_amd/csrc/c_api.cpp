@@ -169,6 +169,19 @@ struct mfmg_hip_hierarchy_s
   DeviceBuffer<double> work[2];
   DeviceBuffer<float> work_f32[2];
   KrylovWorkspace krylov;
+  // block entry points: the permuted columns of one group (b, x) and what the last block call did
+  DeviceBuffer<double> block_work[2];
+  int64_t block_info[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0};
+  double *block_workspace(int i, size_t n)
+  {
+    if (block_work[i].size() < n)
+    {
+      MemoryKind kind("hierarchy: block workspace (permuted columns of one group)");
+      block_work[i].resize(n);
+      MFMG_HIP_CHECK(hipMemsetAsync(block_work[i].data(), 0, n * sizeof(double), handle->stream));
+    }
+    return block_work[i].data();
+  }
   double *workspace(int i)
   {
     if (work[i].size() == 0)
@@ -1114,6 +1127,55 @@ int mfmg_hip_mf_laplace_smoother_step(mfmg_hip_mf_laplace_t op, const double *b,
   });
 }
 
+// ---- blocks of vectors ----
+int mfmg_hip_block_groups(int32_t n_vectors, int32_t *widths, int32_t *n_groups)
+{
+  return guarded([&] {
+    require(widths && n_groups, "null argument");
+    int w[kMfBlockMaxGroups];
+    const int n = mf_block_groups(n_vectors, w);
+    for (int g = 0; g < n; ++g)
+      widths[g] = w[g];
+    *n_groups = n;
+  });
+}
+
+int mfmg_hip_mf_laplace_block_launch(mfmg_hip_mf_laplace_t op, int mode, int32_t n_vectors, int64_t ld, const double *x, const double *b,
+                                     const double *x_prev, double alpha, double beta, double *out)
+{
+  return guarded([&] {
+    require(op != nullptr, "null argument");
+    require(mode >= 0 && mode <= 3, "mode: 0 out = A x, 1 out = A x - b, 2 / 3 a smoother term without / with x_prev");
+    op->op->launch_block(static_cast<MfMode>(mode), {x, b, x_prev, out, ld, n_vectors, alpha, beta});
+  });
+}
+
+int mfmg_hip_mf_laplace_block_available(mfmg_hip_mf_laplace_t op, int *available)
+{
+  return guarded([&] {
+    require(op && available, "null argument");
+    *available = op->op->block_kernel_available() ? 1 : 0;
+  });
+}
+
+int mfmg_hip_mf_laplace_set_block_tile(mfmg_hip_mf_laplace_t op, int n_waves, int tile_y, int tile_z)
+{
+  return guarded([&] {
+    require(op != nullptr, "null argument");
+    require((n_waves == 0 && tile_y == 0 && tile_z == 0) || (n_waves >= 1 && n_waves <= 8 && tile_y >= 2 && tile_y <= 4 && tile_z >= 1),
+            "block tile: 1..8 wavefronts of 2..4 cell rows, at least one layer (0, 0, 0: chosen from the mesh)");
+    op->op->set_block_tile(n_waves, tile_y, tile_z);
+  });
+}
+
+int mfmg_hip_mf_laplace_get_block_tile(mfmg_hip_mf_laplace_t op, int n_vectors, int *n_waves, int *tile_y, int *tile_z)
+{
+  return guarded([&] {
+    require(op && n_waves && tile_y && tile_z, "null argument");
+    op->op->get_block_tile(n_vectors, *n_waves, *tile_y, *tile_z);
+  });
+}
+
 int mfmg_hip_mf_laplace_sweep_available(mfmg_hip_mf_laplace_t op, int n_terms, int *available)
 {
   return guarded([&] {
@@ -1455,6 +1517,144 @@ int mfmg_hip_hierarchy_apply(mfmg_hip_hierarchy_t h, const double *b, double *x)
     const int64_t n = level_size(h, 0);
     DVector bv(*h->handle, n, const_cast<double *>(b)), xv(*h->handle, n, x);
     h->hierarchy->apply(bv, xv);
+  });
+}
+
+namespace
+{
+void check_block(mfmg_hip_hierarchy_t h, int level, int32_t n_vectors, int64_t ld, const double *b, const double *x)
+{
+  require(h && b && x, "null argument");
+  require(!h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+  require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
+  const int64_t n = level_size(h, level);
+  require(ld >= n, "the leading dimension of a block must be at least the vector size");
+  require(ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 16 bytes)");
+  require(reinterpret_cast<uintptr_t>(b) % 16 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, "the base of a block must be aligned to 16 bytes");
+  const int64_t extent = (int64_t)(n_vectors - 1) * ld + n;
+  require(b + extent <= x || x + extent <= b, "the blocks b and x overlap");
+}
+
+int64_t block_kernel_launches(mfmg_hip_hierarchy_t h)
+{
+  auto op = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(h->hierarchy->levels()[0].get_operator());
+  return op ? op->get_mesh_evaluator()->get_device_operator()->block_launches() : 0;
+}
+
+// The groups of a block, one after the other: `run` gets the columns of the group as views -- of the caller's vectors, or with
+// "internal numbering" lexicographic of the library's block workspace, gathered before and scattered after (x only)
+using BlockRun = std::function<void(std::vector<DVector const *> const &, std::vector<DVector *> const &)>;
+void for_block_groups(mfmg_hip_hierarchy_t h, int level, bool read_x, int32_t n_vectors, int64_t ld, const double *b, double *x, BlockRun const &run)
+{
+  const int64_t n = level_size(h, level);
+  const bool permute = h->perm && level == 0;
+  int widths[kMfBlockMaxGroups];
+  const int n_groups = mf_block_groups(n_vectors, widths);
+  const int64_t wld = permute ? n + (n & 1) : ld;
+  int64_t c0 = 0;
+  for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+  {
+    const int w = widths[g];
+    double const *gb = b + c0 * ld;
+    double *gx = x + c0 * ld;
+    if (permute)
+    {
+      double *wb = h->block_workspace(0, (size_t)w * wld), *wx = h->block_workspace(1, (size_t)w * wld);
+      for (int c = 0; c < w; ++c)
+      {
+        if (read_x)
+          h->perm->gather2(b + (c0 + c) * ld, static_cast<double const *>(x + (c0 + c) * ld), wb + c * wld, wx + c * wld);
+        else
+          h->perm->gather(b + (c0 + c) * ld, wb + c * wld);
+      }
+      gb = wb;
+      gx = wx;
+    }
+    std::vector<DVector> bv, xv;
+    bv.reserve(w);
+    xv.reserve(w);
+    std::vector<DVector const *> bp;
+    std::vector<DVector *> xp;
+    for (int c = 0; c < w; ++c)
+    {
+      bv.emplace_back(*h->handle, n, const_cast<double *>(gb) + c * wld);
+      xv.emplace_back(*h->handle, n, gx + c * wld);
+      bp.push_back(&bv.back());
+      xp.push_back(&xv.back());
+    }
+    run(bp, xp);
+    if (permute)
+      for (int c = 0; c < w; ++c)
+        h->perm->scatter(static_cast<double const *>(gx + c * wld), x + (c0 + c) * ld);
+  }
+}
+
+void apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x)
+{
+  check_block(h, 0, n_vectors, ld, b, x);
+  const int64_t launches = block_kernel_launches(h);
+  int64_t looped = 0;
+  for_block_groups(h, 0, !h->hierarchy->is_preconditioner(), n_vectors, ld, b, x, [&](std::vector<DVector const *> const &bp, std::vector<DVector *> const &xp) {
+    h->hierarchy->apply_block(bp, xp);
+    looped += h->hierarchy->block_columns_looped();
+  });
+  h->block_info[0] = h->hierarchy->block_width();
+  h->block_info[1] = block_kernel_launches(h) - launches;
+  h->block_info[2] = looped;
+}
+} // namespace
+
+int mfmg_hip_hierarchy_apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x)
+{
+  return guarded([&] { apply_block(h, n_vectors, ld, b, x); });
+}
+
+int mfmg_hip_hierarchy_vmult_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, double *x, const double *b)
+{
+  return guarded([&] {
+    require(h != nullptr, "null argument");
+    timer_enter_subsection(h->timer, "Apply");
+    try
+    {
+      apply_block(h, n_vectors, ld, b, x);
+    }
+    catch (...)
+    {
+      timer_leave_subsection(h->timer);
+      throw;
+    }
+    timer_leave_subsection(h->timer);
+  });
+}
+
+int mfmg_hip_hierarchy_smoother_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld, const double *b, double *x)
+{
+  return guarded([&] {
+    require(h != nullptr, "null argument");
+    require(level >= 0 && level < (int)h->hierarchy->levels().size(), "level out of range");
+    check_block(h, level, n_vectors, ld, b, x);
+    auto smoother = h->hierarchy->levels()[level].get_smoother();
+    require(smoother != nullptr, "this level has no smoother");
+    const int64_t launches = block_kernel_launches(h);
+    int64_t looped = 0;
+    for_block_groups(h, level, true, n_vectors, ld, b, x, [&](std::vector<DVector const *> const &bp, std::vector<DVector *> const &xp) {
+      smoother->apply_block(bp, xp);
+      if (smoother->block_width() == 1 || bp.size() == 1)
+        looped += (int64_t)bp.size();
+    });
+    h->block_info[0] = level == 0 ? smoother->block_width() : 1;
+    h->block_info[1] = block_kernel_launches(h) - launches;
+    h->block_info[2] = looped;
+  });
+}
+
+int mfmg_hip_hierarchy_block_info(mfmg_hip_hierarchy_t h, int64_t *fields)
+{
+  return guarded([&] {
+    require(h && fields, "null argument");
+    h->block_info[0] = h->hierarchy->block_width();
+    for (int i = 0; i < MFMG_HIP_BLOCK_INFO_FIELDS; ++i)
+      fields[i] = h->block_info[i];
   });
 }
 

@@ -827,6 +827,67 @@ void HipMatrixFreeOperator::smoother_step(DVector const &b, DVector const &x, DV
   apply_mode(mf_smoother_mode(xp, alpha), {x.get_values(), b.get_values(), xp, alpha, beta, out.get_values()});
 }
 
+// ---- blocks of vectors ----
+int64_t block_leading_dimension(std::vector<DVector const *> const &columns)
+{
+  if (columns.empty())
+    return 0;
+  const int64_t n = columns[0]->size();
+  if (columns.size() == 1)
+    return n;
+  const int64_t ld = columns[1]->get_values() - columns[0]->get_values();
+  if (ld < n)
+    return 0;
+  for (size_t c = 0; c < columns.size(); ++c)
+    if (columns[c]->size() != n || columns[c]->get_values() != columns[0]->get_values() + (int64_t)c * ld)
+      return 0;
+  return ld;
+}
+
+namespace
+{
+std::vector<DVector const *> as_const(std::vector<DVector *> const &v) { return std::vector<DVector const *>(v.begin(), v.end()); }
+// what launch_block asks of a block beyond equal distances: an even leading dimension, a base aligned to 16 bytes
+bool block_kernel_layout(std::vector<DVector const *> const &columns, int64_t ld)
+{
+  return block_leading_dimension(columns) == ld && ld % 2 == 0 && reinterpret_cast<uintptr_t>(columns[0]->get_values()) % 16 == 0;
+}
+} // namespace
+
+int HipMatrixFreeOperator::block_width() const
+{
+  return (!get_hip_handle().comm.enabled() && _mesh_evaluator->get_device_operator()->block_kernel_available()) ? 4 : 1;
+}
+
+void HipMatrixFreeOperator::apply_mode_block(MfMode mode, MfBlockOperands<double> const &v) const
+{
+  _mesh_evaluator->get_device_operator()->launch_block(mode, v);
+}
+
+void HipMatrixFreeOperator::residual_block(std::vector<DVector const *> const &x, std::vector<DVector const *> const &b,
+                                           std::vector<DVector *> const &res) const
+{
+  ASSERT_THROW(x.size() == b.size() && x.size() == res.size() && !x.empty(), "the blocks of a residual need the same number of columns");
+  const int64_t ld = block_leading_dimension(x);
+  if (block_width() == 1 || x.size() == 1 || x.size() > (size_t)kMfBlockMaxVectors || ld == 0 || !block_kernel_layout(x, ld) ||
+      !block_kernel_layout(b, ld) || !block_kernel_layout(as_const(res), ld))
+    return Operator<DVector>::residual_block(x, b, res);
+  apply_mode_block(MfMode::residual, {x[0]->get_values(), b[0]->get_values(), nullptr, res[0]->get_values(), ld, (int)x.size(), 0., 0.});
+}
+
+std::vector<std::shared_ptr<DVector>> HipMatrixFreeOperator::build_domain_block(int width, int64_t ld) const
+{
+  const int64_t n = (int64_t)grid_complexity();
+  ASSERT_THROW(width >= 1 && ld >= n, "a block needs a leading dimension of at least the vector size");
+  HipHandle &handle = get_hip_handle();
+  auto storage = std::make_shared<DeviceBuffer<double>>((size_t)width * ld); // (hipMalloc: aligned to 256 bytes)
+  vec::set<double>(handle, (int64_t)width * ld, 0., storage->data());
+  std::vector<std::shared_ptr<DVector>> columns;
+  for (int c = 0; c < width; ++c)
+    columns.emplace_back(new DVector(handle, n, storage->data() + (int64_t)c * ld), [storage](DVector *v) { delete v; });
+  return columns;
+}
+
 bool HipMatrixFreeOperator::sweep_available(int n_terms) const
 {
   return _mesh_evaluator->get_device_operator()->fused_sweep_available(n_terms);
@@ -1195,6 +1256,65 @@ void HipSmoother::apply(DVector const &b, DVector &x) const
     return;
   }
   run(_schedule.in_place, b, x, x);
+}
+
+int HipSmoother::block_width() const
+{
+  // (a schedule with a multi-term sweep belongs to the cell-constant layout, which has no block kernel)
+  auto mf = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator);
+  return (mf && _schedule.in_place == 0) ? mf->block_width() : 1;
+}
+
+void HipSmoother::apply_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const
+{
+  ASSERT_THROW(b.size() == x.size() && !x.empty(), "a block needs as many right-hand sides as iterates");
+  auto mf = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator);
+  const int64_t ld = block_leading_dimension(as_const(x));
+  if (block_width() == 1 || x.size() == 1 || x.size() > (size_t)kMfBlockMaxVectors || ld == 0 || !block_kernel_layout(as_const(x), ld) ||
+      !block_kernel_layout(b, ld))
+    return Smoother<DVector>::apply_block(b, x);
+  // groups of the block: every group runs the polynomial of apply(), its terms as launches on the group
+  int widths[kMfBlockMaxGroups];
+  const int n_groups = mf_block_groups((int)x.size(), widths);
+  HipHandle &handle = _hip_operator->get_hip_handle();
+  const int64_t n = x[0]->size();
+  size_t c0 = 0;
+  for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+  {
+    const int w = widths[g];
+    if (w == 1)
+    {
+      apply(*b[c0], *x[c0]);
+      continue;
+    }
+    for (auto &s : _block_scratch)
+      if (s.size() < (size_t)w * ld)
+      {
+        MemoryKind kind("smoother: block scratch vectors (one group of right-hand sides)");
+        s.resize((size_t)w * ld);
+        vec::set<double>(handle, (int64_t)w * ld, 0., s.data());
+      }
+    struct Block
+    {
+      double *p;
+    };
+    Block xb{x[c0]->get_values()}, sa{_block_scratch[0].data()}, sb{_block_scratch[1].data()};
+    double const *bp = b[c0]->get_values();
+    auto step = [&](Block const *cur, Block const *prev, double alpha, double beta, Block *out) {
+      double const *xp = prev ? prev->p : nullptr;
+      mf->apply_mode_block(mf_smoother_mode(xp, alpha), {cur->p, bp, xp, out->p, ld, w, alpha, beta});
+    };
+    if (_coefficients.size() == 1)
+    {
+      step(&xb, nullptr, 0., _coefficients[0].second, &sa);
+      for (int c = 0; c < w; ++c)
+        vec::copy<double>(handle, n, sa.p + (int64_t)c * ld, xb.p + (int64_t)c * ld);
+      continue;
+    }
+    run_polynomial<double>(
+        _coefficients, 0, static_cast<Block const *>(&xb), &xb, [&](int i) { return i == 0 ? &sa : &sb; }, step,
+        [&](int, double const *, double const *, Block const *, Block *, Block *) { ASSERT_THROW(false, "internal: no sweep on a block"); });
+  }
 }
 
 void HipSmoother::apply_zero_guess(DVector const &b, DVector &x) const

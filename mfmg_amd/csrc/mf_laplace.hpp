@@ -50,6 +50,23 @@ struct MfOperands
   T *out;
 };
 
+// The same for a block of n_vectors vectors: the columns of x, b, x_prev and out share the leading dimension ld (column c of x
+// starts at x + c * ld elements; ld >= n_dofs, even; the bases aligned to 16 bytes).  out may be x_prev, column for column.
+template <typename T>
+struct MfBlockOperands
+{
+  T const *x, *b, *x_prev;
+  T *out;
+  int64_t ld;
+  int n_vectors;
+  T alpha, beta;
+};
+
+// How a block of n_vectors (1 .. kMfBlockMaxVectors) is cut into launches: groups of 4, then one of 2, then one single vector.
+// Returns the number of groups, their widths in `widths`; InvalidArgumentExc outside the range.  (mf_laplace_block.hip)
+constexpr int kMfBlockMaxVectors = 64, kMfBlockMaxGroups = 18;
+int mf_block_groups(int n_vectors, int widths[kMfBlockMaxGroups]);
+
 // A smoother term without momentum (no x_prev, or alpha = 0) is a `first` term: it reads no x_prev.
 template <typename T>
 inline MfMode mf_smoother_mode(T const *x_prev, T alpha)
@@ -217,6 +234,25 @@ public:
   }
   HipHandle &handle() const { return _handle; }
 
+  // The operations of `launch` on a block of vectors (mf_laplace_block.hip, FP64): the block is cut by mf_block_groups, groups of
+  // 4 and 2 columns run mf_laplace_block_kernel -- one read of the chunk records for all columns of the group --, a single
+  // column runs the one-vector kernel.  Every column gets the bits of the one-vector launch.  Operators without the block
+  // kernel (block_kernel_available: the cell-constant layout, whose sweep has no record bytes worth sharing; dim = 2; a tail
+  // slab) run column by column.  InvalidArgumentExc: n_vectors outside 1 .. 64, ld < n_dofs or odd, a base not aligned to 16
+  // bytes, the out block overlapping the x block, a null operand the mode reads, a context with a communicator.
+  void launch_block(MfMode mode, MfBlockOperands<T> const &v) const;
+  bool block_kernel_available() const;
+  // tile of the block kernel (0, 0, 0: chosen from the mesh and the width of the group); ty = 2, 3 or 4
+  void set_block_tile(int nw, int ty, int tz)
+  {
+    _block_tile[0] = nw;
+    _block_tile[1] = ty;
+    _block_tile[2] = tz;
+  }
+  void get_block_tile(int nv, int &nw, int &ty, int &tz) const;
+  // launches of mf_laplace_block_kernel so far
+  int64_t block_launches() const { return _block_launches; }
+
   // Bytes of one operator application y = A x.
   // survey: the indexed form of SURVEY.md 8(d) -- x, y, 8 index ints, 8 coefficients (112 B/DoF in FP64; one
   //         coefficient per cell: 56);
@@ -269,6 +305,10 @@ private:
   DeviceBuffer<uint8_t> _cn2;
   double _k2[64] = {};
   MfTile choose_tile() const;
+  MfTile choose_block_tile(int nv) const;
+  void run_block(MfMode mode, MfBlockOperands<T> const &v, int nv) const;
+  int _block_tile[3] = {0, 0, 0};
+  mutable int64_t _block_launches = 0;
   void choose_fused_tile(int n_terms, int &nw, int &ty, int &tz) const;
   bool fused_wg12_capable(int n_terms) const; // the sweep has the kernel of twelve wavefronts of two rows
   int _fused_tile[3] = {0, 0, 0};

@@ -234,6 +234,87 @@ public:
     }
   }
 
+  // The cycle of apply() on the columns of a block of vectors (several right-hand sides): x[c] gets the bits of apply(b[c], x[c]).
+  // Where the fine level offers no block kernel (Smoother / Operator::block_width() == 1) that is what runs.  Otherwise the
+  // block is taken in the groups of mf_block_groups (at most four columns) and the whole cycle runs per group: pre-smoothing and
+  // residual on the block -- the operator's data read once for the group --, then restriction, coarse cycle and prolongation
+  // column by column with the kernels of apply(), then post-smoothing on the block.  The workspace is one group wide whatever
+  // the number of columns; it is built at the first block call.  The columns of b and of x must share one leading dimension.
+  void apply_block(std::vector<VectorType const *> const &b, std::vector<VectorType *> const &x) const
+  {
+    ASSERT_THROW(b.size() == x.size() && !b.empty(), "a block needs as many right-hand sides as iterates");
+    _block_columns_looped = 0;
+    auto &level_fine = _levels[0];
+    auto a = level_fine.get_operator();
+    auto smoother = level_fine.get_smoother();
+    const bool block = _levels.size() > 1 && smoother && !smoother->prefers_out_of_place() && smoother->block_width() > 1 && a->block_width() > 1;
+    int widths[kMfBlockMaxGroups];
+    const int n_groups = mf_block_groups((int)b.size(), widths);
+    size_t c0 = 0;
+    for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+    {
+      const size_t w = (size_t)widths[g];
+      if (!block || w == 1)
+      {
+        for (size_t c = c0; c < c0 + w; ++c)
+          apply(*b[c], *x[c]);
+        _block_columns_looped += (int64_t)w;
+        continue;
+      }
+      timer_enter_subsection(_timer, "Apply: fine levels");
+      const std::vector<VectorType const *> bg(b.begin() + c0, b.begin() + c0 + w);
+      const std::vector<VectorType *> xg(x.begin() + c0, x.begin() + c0 + w);
+      auto &level_coarse = _levels[1];
+      auto restrictor = level_coarse.get_restrictor();
+      if (_is_preconditioner)
+        for (auto *xc : xg)
+          *xc = 0.;
+      for (unsigned int i = 0; i < _n_smoothing_steps; ++i)
+        smoother->apply_block(bg, xg);
+      // the residual of the group in one launch, unless the restrictor forms R (A x - b) in one pass as apply() then does
+      auto b_coarse = level_coarse.workspace_vector(1);
+      auto x_coarse = level_coarse.workspace_vector(2);
+      const bool one_pass = restrictor->restrict_residual(*a, *xg[0], *bg[0], *b_coarse);
+      std::vector<VectorType *> res;
+      if (!one_pass)
+      {
+        const int64_t ld = w > 1 ? (int64_t)(xg[1]->get_values() - xg[0]->get_values()) : xg[0]->size();
+        if (_block_workspace.size() < w || _block_workspace_ld != ld)
+        {
+          MemoryKind kind("hierarchy: block workspace (residual of one group of right-hand sides)");
+          _block_workspace.clear(); // (before the wider one is built)
+          _block_workspace = a->build_domain_block((int)w, ld);
+          _block_workspace_ld = ld;
+        }
+        for (size_t c = 0; c < w; ++c)
+          res.push_back(_block_workspace[c].get());
+        a->residual_block(std::vector<VectorType const *>(xg.begin(), xg.end()), bg, res);
+      }
+      for (size_t c = 0; c < w; ++c)
+      {
+        if (!one_pass)
+          restrictor->apply(*res[c], *b_coarse);
+        else if (c > 0)
+          ASSERT_THROW(restrictor->restrict_residual(*a, *xg[c], *bg[c], *b_coarse), "internal: the one-pass residual restriction was refused");
+        apply(*b_coarse, *x_coarse, 1);
+        restrictor->apply_subtract(*x_coarse, *xg[c], OperatorMode::TRANS);
+      }
+      for (unsigned int i = 0; i < _n_smoothing_steps; ++i)
+        smoother->apply_block(bg, xg);
+      timer_leave_subsection(_timer);
+    }
+  }
+  // columns of the last apply_block that went through apply() one by one
+  int64_t block_columns_looped() const { return _block_columns_looped; }
+  // width of the widest group apply_block runs as one launch on the fine level (1: the loop over the columns)
+  int block_width() const
+  {
+    auto smoother = _levels[0].get_smoother();
+    const bool block = _levels.size() > 1 && smoother && !smoother->prefers_out_of_place() && smoother->block_width() > 1 &&
+                       _levels[0].get_operator()->block_width() > 1;
+    return block ? std::min(smoother->block_width(), _levels[0].get_operator()->block_width()) : 1;
+  }
+
   // Replace R on level 1 and re-derive A_c and the coarse solver (same sequence as
   // the constructor, hierarchy.hpp:209-233,193-196): lets CPU and GPU runs share one R.
   void set_restrictor(std::shared_ptr<Operator<VectorType>> restrictor)
@@ -267,5 +348,8 @@ private:
   std::vector<std::shared_ptr<Operator<VectorType>>> _ap_operators; // only with "keep_ap"
   bool _is_preconditioner = true;
   unsigned int _n_smoothing_steps;
+  mutable std::vector<std::shared_ptr<VectorType>> _block_workspace; // apply_block: the residuals of one group
+  mutable int64_t _block_workspace_ld = 0;
+  mutable int64_t _block_columns_looped = 0;
 };
 } // namespace mfmg

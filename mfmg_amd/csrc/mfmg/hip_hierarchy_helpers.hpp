@@ -215,6 +215,11 @@ public:
   HipHandle &get_hip_handle() const override { return _mesh_evaluator->get_hip_handle(); }
   std::shared_ptr<HipMatrixFreeMeshEvaluator> get_mesh_evaluator() const { return _mesh_evaluator; }
   void apply_mode(MfMode mode, MfOperands<double> const &v) const;
+  // blocks of vectors (mf_laplace_block.hip): one launch per group of 4 or 2 columns where the device operator has the kernel
+  int block_width() const override;
+  void residual_block(std::vector<DVector const *> const &x, std::vector<DVector const *> const &b, std::vector<DVector *> const &res) const override;
+  std::vector<std::shared_ptr<DVector>> build_domain_block(int width, int64_t ld) const override;
+  void apply_mode_block(MfMode mode, MfBlockOperands<double> const &v) const;
   int domain_space() const override { return 1; }
   int range_space() const override { return 1; }
   void apply_local(DVector const &x, DVector &y) const override;
@@ -296,6 +301,10 @@ public:
   void apply_to(DVector const &b, DVector const &x_in, DVector &x_out) const override;
   bool apply_from_zero(DVector const &b, DVector &x_out) const override;
   bool prefers_out_of_place() const override { return _schedule.out_of_place > 0; }
+  // the polynomial of apply() on the columns of a block, term by term in place with block scratch vectors: one launch of the
+  // block kernel per term and group of 4 or 2 columns (the matrix-free operator with eight coefficients per cell)
+  int block_width() const override;
+  void apply_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const override;
   int fused_terms() const { return _fused_terms; }
   // smoother.sweep_arithmetic "reference": the sweep computes with the one-term kernel's arithmetic, bit for bit
   bool sweep_reference() const { return _sweep_reference; }
@@ -329,7 +338,12 @@ private:
   bool _sweep_reference = false;
   SweepSchedule _schedule;
   mutable std::shared_ptr<DVector> _scratch_a, _scratch_b;
+  mutable DeviceBuffer<double> _block_scratch[2]; // apply_block: one group of columns each
 };
+
+// The columns as ONE block the block kernel can take: `width` vectors of equal size at equal distances.  Returns their leading
+// dimension (elements between two columns; the size of the only column), 0 where they do not form such a block.
+int64_t block_leading_dimension(std::vector<DVector const *> const &columns);
 
 template <typename VectorType>
 class Hierarchy;

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <memory>
+#include <vector>
 
 #include "../common.hpp"
 
@@ -45,6 +46,25 @@ public:
   {
     apply(x, res);
     res.add(-1., b);
+  }
+  // Extension: blocks of vectors (several right-hand sides against one operator).  res[c] = A x[c] - b[c] for every column c: an
+  // operator with a kernel that reads its data once for several vectors overrides this, the default loops over the columns.
+  // block_width(): columns the widest such launch takes (1: only the loop exists).  build_domain_block: `width` domain vectors
+  // as the columns of one block with the leading dimension ld where the operator can lay them out so (what its block kernel
+  // takes), separate vectors otherwise.
+  virtual int block_width() const { return 1; }
+  virtual void residual_block(std::vector<vector_type const *> const &x, std::vector<vector_type const *> const &b,
+                              std::vector<vector_type *> const &res) const
+  {
+    for (size_t c = 0; c < x.size(); ++c)
+      residual(*x[c], *b[c], *res[c]);
+  }
+  virtual std::vector<std::shared_ptr<vector_type>> build_domain_block(int width, int64_t /*ld*/) const
+  {
+    std::vector<std::shared_ptr<vector_type>> columns;
+    for (int c = 0; c < width; ++c)
+      columns.push_back(build_domain_vector());
+    return columns;
   }
   // Called on a RESTRICTOR: b_coarse = R (A x - b), the residual and its restriction (hierarchy.hpp:281-290) in one
   // pass where the restrictor knows the rows of R A (structured_restrictor.hpp).  false: not available, nothing done.

@@ -34,6 +34,16 @@ public:
   // hierarchy.hpp:253-259).  False (nothing done): the caller zeroes x and applies as usual.
   virtual bool apply_from_zero(vector_type const & /*b*/, vector_type & /*x_out*/) const { return false; }
 
+  // Extension: the update of apply() on every column of a block of vectors, with the bits of apply() column by column.  A
+  // smoother whose operator reads its data once for several vectors overrides this; block_width(): columns its widest launch
+  // takes (1: only the loop exists).
+  virtual int block_width() const { return 1; }
+  virtual void apply_block(std::vector<vector_type const *> const &b, std::vector<vector_type *> const &x) const
+  {
+    for (size_t c = 0; c < x.size(); ++c)
+      apply(*b[c], *x[c]);
+  }
+
 protected:
   std::shared_ptr<operator_type const> _operator;
   std::shared_ptr<ptree const> _params;

@@ -216,6 +216,15 @@ def load() -> C.CDLL:
         "mfmg_hip_mf_laplace_f32_diagonal_inverse": (C.c_int, [vp, vp]),
         "mfmg_hip_mf_laplace_f32_residual": (C.c_int, [vp, vp, vp, vp]),
         "mfmg_hip_mf_laplace_f32_smoother_step": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_float, vp]),
+        "mfmg_hip_block_groups": (C.c_int, [i32, P(i32), P(i32)]),
+        "mfmg_hip_mf_laplace_block_launch": (C.c_int, [vp, C.c_int, i32, i64, vp, vp, vp, dbl, dbl, vp]),
+        "mfmg_hip_mf_laplace_block_available": (C.c_int, [vp, P(C.c_int)]),
+        "mfmg_hip_mf_laplace_set_block_tile": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "mfmg_hip_mf_laplace_get_block_tile": (C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]),
+        "mfmg_hip_hierarchy_apply_block": (C.c_int, [vp, i32, i64, vp, vp]),
+        "mfmg_hip_hierarchy_vmult_block": (C.c_int, [vp, i32, i64, vp, vp]),
+        "mfmg_hip_hierarchy_smoother_apply_block": (C.c_int, [vp, i32, i32, i64, vp, vp]),
+        "mfmg_hip_hierarchy_block_info": (C.c_int, [vp, P(i64)]),
         "mfmg_hip_hierarchy_create": (C.c_int, [vp, C.c_char_p, P(MeshDesc), C.c_char_p, P(vp)]),
         "mfmg_hip_hierarchy_destroy": (C.c_int, [vp]),
         "mfmg_hip_hierarchy_internal_numbering": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
@@ -276,7 +285,10 @@ def load() -> C.CDLL:
     # entry points added without a change of the ABI version: an older build of the library named by MFMG_HIP_LIBRARY (a
     # measurement against the commit before) lacks them and is loaded without; calling one there fails loudly
     added_later = {"mfmg_hip_mf_laplace_set_sweep_diagonal", "mfmg_hip_mf_laplace_get_sweep_diagonal",
-                   "mfmg_hip_mf_laplace_sweep_diagonal_inverse"}
+                   "mfmg_hip_mf_laplace_sweep_diagonal_inverse", "mfmg_hip_block_groups", "mfmg_hip_mf_laplace_block_launch",
+                   "mfmg_hip_mf_laplace_block_available", "mfmg_hip_mf_laplace_set_block_tile", "mfmg_hip_mf_laplace_get_block_tile",
+                   "mfmg_hip_hierarchy_apply_block", "mfmg_hip_hierarchy_vmult_block", "mfmg_hip_hierarchy_smoother_apply_block",
+                   "mfmg_hip_hierarchy_block_info"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
