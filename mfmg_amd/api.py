@@ -1037,7 +1037,11 @@ class Hierarchy:
 def amge_eigen(ctx: Context, problem, params: dict | str, matrix_free: bool) -> dict:
     """The agglomerate eigen-solves of the restrictor setup on their own, with the device solver `params` names
     ("restrictor.eigensolver" device | lanczos).  Arrays per agglomerate (x fastest): n_vec [A], eigenvalues [A, n_eig],
-    weights [A, n_eig, nodes] (diag_loc * vector on the local nodes, x fastest), iterations [A], converged [A], breakdown [A]."""
+    weights [A, n_eig, nodes] (diag_loc * vector on the local nodes, x fastest), iterations [A], converged [A], breakdown [A].
+    The eigenvalues are those of the unshifted problem with either solver: under eigensolver.variant host, where the matrix that is
+    solved carries the mean local diagonal as a shift, the shift is taken off.  A krylov group reports one of its members (the dense
+    kernel its first).  Slots >= n_vec, nodes beyond the clipped agglomerate up to the stride and nodes that are not part of the
+    eigenproblem (constrained ones under variant mf) are exactly 0."""
     lib = _lib.load()
     desc = problem.mesh_desc()
     info = (params if isinstance(params, str) else params_to_info(params)).encode()

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void amge_agglomerate_kernel(AmgeArgs a)
           out[(size_t)e * NMAX + lane] = active ? dl * V[col * na + pos_of(lane)] : 0.;
         }
         if (a.eigenvalues && lane == 0)
-          a.eigenvalues[(size_t)agg * a.n_eig + e] = w[e];
+          a.eigenvalues[(size_t)agg * a.n_eig + e] = w[e] - avg; // of the unshifted problem, as Lanczos reports it
       }
       n_sel = ne;
     }
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void amge_agglomerate_kernel(AmgeArgs a)
             out[(size_t)n_sel * NMAX + lane] = active ? dl * (proj[pos_of(lane)] / pn) : 0.;
           }
           if (a.eigenvalues && lane == 0)
-            a.eigenvalues[(size_t)agg * a.n_eig + n_sel] = w[i0];
+            a.eigenvalues[(size_t)agg * a.n_eig + n_sel] = w[i0] - avg;
           ++n_sel;
         }
         i0 = i1;

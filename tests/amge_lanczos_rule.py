@@ -44,17 +44,18 @@ def case_id(c):
     return "x".join(map(str, c[0])) + "-" + "x".join(map(str, c[1])) + "-" + c[2]
 
 
-def agglomerate_problems(n, agg, material, variant):
+def agglomerate_problems(n, agg, material, variant, subset=None):
     """Per agglomerate (x fastest) of the oracle's mesh: dict with the global DoFs `gl`, the matrix `M` of `variant` on the active
     DoFs, their mask `act`, the start vector `v0` on them, `diag_loc` on all local DoFs and the `shift` of variant host --
-    the pieces of oracle.build_restrictor, which this restates line by line up to the eigen-solve."""
+    the pieces of oracle.build_restrictor, which this restates line by line up to the eigen-solve.
+    subset: the indices of the agglomerates to build, in the order given (the others are not walked); None for all."""
     mesh = O.StructuredMesh(n)
     coef = O.coefficient_table(mesh, material)
     con = mesh.constrained_mask()
     Ae = O.cell_matrices(mesh, coef)
     aggs, _ = O.block_agglomerates(mesh, agg[:mesh.dim])
     out = []
-    for lo, hi in aggs:
+    for lo, hi in (aggs if subset is None else [aggs[a] for a in subset]):
         gl, lcd, cid, lN = O.agglomerate_local(mesh, lo, hi)
         nloc = len(gl)
         A = np.zeros((nloc, nloc))
