@@ -324,7 +324,7 @@ int mfmg_hip_csr_residual(mfmg_hip_csr_t a, const double *x, const double *b, do
 int mfmg_hip_csr_launch(mfmg_hip_csr_t a, int mode, const double *x, const double *b, const double *dinv, const double *x_prev,
                         double alpha, double beta, double *out);
 /* Which kernels an application of the matrix launches as it stands (tests: which kernel a case reaches).  Filled from the
- * record the launch itself branches on.  fields[0..21]:
+ * record the launch itself branches on.  fields[0..26]:
  *   0 storage variant as mfmg_hip_csr_get_kernel reports it
  *   1 CSR kernel: 0 none, 1 lanes per row, 2 a workgroup per row, 3 LDS-cached; 2 lanes per row of the instance
  *   3 unknowns per node, 4 stored block diagonals, 5 offsets of the full stencil (tables)
@@ -337,9 +337,24 @@ int mfmg_hip_csr_launch(mfmg_hip_csr_t a, int mode, const double *x, const doubl
  *  15 launch of the classes: 0 none, 1 one thread per node, 4 / 16 split
  *  16 stored-plane kernel: 0 none, 1 rows, 2 rows of a symmetric half, 3 symmetric half split over four wavefronts
  *  17 row-base slots, 18 / 19 unknowns per node and offsets of the node classes of a rectangular matrix
- *  20 whether the last launch found every vector 16-byte aligned (-1: no launch yet), 21 1 = CSR arrays released */
-#define MFMG_HIP_CSR_FORM_FIELDS 22
+ *  20 whether the last launch found every vector 16-byte aligned (-1: no launch yet), 21 1 = CSR arrays released
+ *  22 1 = twin nodes (mfmg_hip_csr_enable_node_twins): one launch of bdia_twin_node_kernel, two row nodes per lane
+ *  23 slots of the twin lists (padded to wavefronts, two nodes each), 24 twin classes (ordered pairs of node classes)
+ *  25 slots left to the classed nodes without a twin (with twins: also what field 11 reports)
+ *  26 whether the last twin launch took the 32-byte epilogue: b, dinv, x_prev and out 32-byte aligned, x 16-byte (-1: no twin
+ *     launch yet, 0: the halves of the one-node kernel)
+ * (22-26 were appended: n >= 22 is accepted and the fields up to n are filled, so a caller built against 22 fields still
+ * works and a caller that passes 27 to an older library reads zeros there: no change of the ABI version) */
+#define MFMG_HIP_CSR_FORM_FIELDS 27
 int mfmg_hip_csr_form(mfmg_hip_csr_t a, int64_t *fields, int32_t n);
+/* Twin nodes for a rectangular matrix in node classes (FP64, 1 or 2 unknowns per node, fewer than 48 offsets): the row nodes
+ * (n, n + 1), n even, in classes and with one base become one lane.  *taken = 0 and the matrix as it was where fewer than
+ * 90 % of the classed nodes are twins, where the layout does not apply, and under MFMG_NODE_TWINS=0 (read by this call).
+ * The aggregation setup calls it on the smoothed prolongators it builds. */
+int mfmg_hip_csr_enable_node_twins(mfmg_hip_csr_t a, int *taken);
+/* Free the CSR arrays of a matrix whose kernels read tables, as "release setup matrices" does inside a hierarchy (the
+ * listed rows are kept as a compact CSR of their own).  *released = 0 for a matrix whose kernels read the arrays. */
+int mfmg_hip_csr_release_csr(mfmg_hip_csr_t a, int *released);
 
 /* ---- matrix-free Q1 Laplace operator on a logically structured hex mesh ---- */
 /* What the deal.II driver hands over (tests/laplace_matrix_free.hpp:243-313):

@@ -354,6 +354,20 @@ class SparseMatrixDevice:
     def set_regular_rows(self, enable: bool):
         check(self._lib.mfmg_hip_csr_set_regular_rows(self.handle, int(bool(enable))))
 
+    def enable_node_twins(self) -> bool:
+        """Two row nodes (n, n + 1) per lane for a node-class matrix whose neighbouring nodes share their base (what the
+        aggregation setup does to its smoothed prolongators); False where the matrix declined (`MFMG_NODE_TWINS=0`, fewer
+        than 90 % twins, not FP64 with 1 or 2 unknowns per node)."""
+        v = C.c_int()
+        check(self._lib.mfmg_hip_csr_enable_node_twins(self.handle, C.byref(v)))
+        return bool(v.value)
+
+    def release_csr(self) -> bool:
+        """Free the CSR arrays of a table-driven matrix ("release setup matrices"); False where the kernels read them."""
+        v = C.c_int()
+        check(self._lib.mfmg_hip_csr_release_csr(self.handle, C.byref(v)))
+        return bool(v.value)
+
     def get_kernel(self):
         a, b = C.c_int(), C.c_int()
         check(self._lib.mfmg_hip_csr_get_kernel(self.handle, C.byref(a), C.byref(b)))
@@ -401,7 +415,8 @@ class SparseMatrixDevice:
 
     _FORM_FIELDS = ("kind", "csr_kernel", "lanes", "c", "stored_d", "full_d", "symmetric_half", "float_planes", "regular",
                     "all_in_classes", "classes", "class_slots", "listed", "listed_route", "regular_kernel", "class_kernel",
-                    "stored_kernel", "row_base_slots", "node_class_c", "node_class_d", "pairs", "csr_released")
+                    "stored_kernel", "row_base_slots", "node_class_c", "node_class_d", "pairs", "csr_released",
+                    "twin_kernel", "twin_slots", "twin_classes", "single_slots", "twin_wide")
     _CSR_KERNELS = {0: None, 1: "lanes", 2: "row_block", 3: "lds"}
     _LISTED_ROUTES = {0: None, 1: "class_tail", 2: "split_tail", 3: "own_launch", 4: "stored_planes"}
     _STORED_KERNELS = {0: None, 1: "rows", 2: "sym_rows", 3: "sym_split"}
@@ -865,6 +880,19 @@ class Hierarchy:
                 check(self._lib.mfmg_hip_hierarchy_coarse_amg_get(self.handle, info["level"], 3, C.byref(h)))
                 Pt = SparseMatrixDevice(self.ctx, _handle=h, _borrowed=True, _keepalive=self).to_scipy()
             out.append(Pt)
+        return out
+
+    def coarse_amg_smoothed_prolongator_forms(self):
+        """[form() of P~_l or None] per level of the multilevel coarse solver: which kernels the smoothed prolongator of the
+        cycle launches (also after "release setup matrices", when the matrix itself can no longer be exported)."""
+        out = []
+        for info in self.coarse_amg_setup_info():
+            f = None
+            if info["smoothed"]:
+                h = C.c_void_p()
+                check(self._lib.mfmg_hip_hierarchy_coarse_amg_get(self.handle, info["level"], 3, C.byref(h)))
+                f = SparseMatrixDevice(self.ctx, _handle=h, _borrowed=True, _keepalive=self).form()
+            out.append(f)
         return out
 
     _AMG_PRODUCTS = ("probes", "device product", "host product")

@@ -391,6 +391,8 @@ void HipSolver::setup_amg_on_device(std::shared_ptr<SparseMatrixDevice<double>> 
       Zt.release();
       L.smoothed_prolongator = std::make_shared<HipMatrixOperator>(pt_smoothed);
       L.smoothed_prolongator->set_spaces(c.space, 0);
+      // the two fine nodes of an aggregate along x couple to the same coarse nodes: one lane for both (bdia_twin_node_kernel)
+      pt_smoothed->enable_node_twins();
       L.smoothed_beta = beta;
       for (int d = 0; d < 3; ++d)
         L.period_t[d] = period_t[d];
@@ -631,6 +633,7 @@ void HipSolver::finish_amg_replicated(std::shared_ptr<HipMatrixOperator> a_op, H
             }
         }
         L.smoothed_prolongator = std::make_shared<HipMatrixOperator>(upload_csr(h, std::move(pt), false));
+        L.smoothed_prolongator->get_matrix()->enable_node_twins(); // (declines without node classes: these levels are small)
         L.smoothed_beta = beta;
       }
     }

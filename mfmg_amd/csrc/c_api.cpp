@@ -1026,7 +1026,7 @@ int mfmg_hip_csr_form(mfmg_hip_csr_t a, int64_t *fields, int32_t n)
 {
   return guarded([&] {
     require(a && fields, "null argument");
-    require(n >= MFMG_HIP_CSR_FORM_FIELDS, "csr_form needs MFMG_HIP_CSR_FORM_FIELDS fields");
+    require(n >= 22, "csr_form needs 22 fields at least (MFMG_HIP_CSR_FORM_FIELDS for all of them)");
     std::fill(fields, fields + n, (int64_t)0);
     const CsrForm f = a->op->get_matrix()->form();
     fields[0] = f.kind;
@@ -1051,6 +1051,30 @@ int mfmg_hip_csr_form(mfmg_hip_csr_t a, int64_t *fields, int32_t n)
     fields[19] = f.node_class_d;
     fields[20] = f.pairs;
     fields[21] = f.csr_released;
+    if (n >= MFMG_HIP_CSR_FORM_FIELDS)
+    {
+      fields[22] = f.twin_kernel;
+      fields[23] = f.twin_slots;
+      fields[24] = f.twin_classes;
+      fields[25] = f.single_slots;
+      fields[26] = f.twin_wide;
+    }
+  });
+}
+
+int mfmg_hip_csr_enable_node_twins(mfmg_hip_csr_t a, int *taken)
+{
+  return guarded([&] {
+    require(a && taken, "null argument");
+    *taken = a->op->get_matrix()->enable_node_twins() ? 1 : 0;
+  });
+}
+
+int mfmg_hip_csr_release_csr(mfmg_hip_csr_t a, int *released)
+{
+  return guarded([&] {
+    require(a && released, "null argument");
+    *released = a->op->get_matrix()->release_csr() ? 1 : 0;
   });
 }
 

@@ -436,19 +436,12 @@ __device__ __forceinline__ void listed_row_wave(CsrArgs<T> const &a, int32_t con
 // wavefronts (node -1): the class of a wavefront is uniform, its stencil constants are scalar loads like the
 // regular ones, and only the node list and x are read.  Neighbours outside the matrix carry the constant 0 and
 // are read at a clamped position.
+// slot t of the class lists: one thread, one node (the body of bdia_class_node_kernel and of the single nodes of
+// bdia_twin_node_kernel)
 template <typename T, int C>
-__global__ __launch_bounds__(256) void bdia_class_node_kernel(CsrArgs<T> a, BdiaRegular<T> g, int32_t const *nodes,
-                                                              int32_t const *class_of_wave, T const *class_table,
-                                                              int64_t n_slots, int32_t const *listed, int64_t n_listed)
+__device__ __forceinline__ void class_node_slot(CsrArgs<T> const &a, BdiaRegular<T> const &g, int32_t const *nodes,
+                                                int32_t const *class_of_wave, T const *class_table, int64_t n_slots, int64_t t)
 {
-  // the workgroups behind the class lists take the listed rows (a launch of their own would cost more than they do)
-  const int64_t class_blocks = (n_slots + 255) / 256;
-  if ((int64_t)blockIdx.x >= class_blocks)
-  {
-    listed_row_wave(a, listed, n_listed, ((int64_t)blockIdx.x - class_blocks) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
-    return;
-  }
-  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (t >= n_slots)
     return;
   const int cls = __builtin_amdgcn_readfirstlane(class_of_wave[t >> 6]);
@@ -488,6 +481,155 @@ __global__ __launch_bounds__(256) void bdia_class_node_kernel(CsrArgs<T> a, Bdia
         sum[rc] += tab[((size_t)rc * g.Df + d) * C + cc] * xv[cc];
   }
   store_node<T, C>(a, node, sum);
+}
+
+template <typename T, int C>
+__global__ __launch_bounds__(256) void bdia_class_node_kernel(CsrArgs<T> a, BdiaRegular<T> g, int32_t const *nodes,
+                                                              int32_t const *class_of_wave, T const *class_table,
+                                                              int64_t n_slots, int32_t const *listed, int64_t n_listed)
+{
+  // the workgroups behind the class lists take the listed rows (a launch of their own would cost more than they do)
+  const int64_t class_blocks = (n_slots + 255) / 256;
+  if ((int64_t)blockIdx.x >= class_blocks)
+  {
+    listed_row_wave(a, listed, n_listed, ((int64_t)blockIdx.x - class_blocks) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    return;
+  }
+  class_node_slot<T, C>(a, g, nodes, class_of_wave, class_table, n_slots, blockIdx.x * (int64_t)blockDim.x + threadIdx.x);
+}
+
+// Twin nodes (SparseMatrixDevice::enable_node_twins): the row nodes n and n + 1, n even, of a rectangular node-class matrix
+// that share their base -- the two fine nodes of an aggregate along x under a smoothed prolongator -- are one lane.  Sorted
+// by class a wavefront holds the nodes 2 k, 2 k + 2, .. of a row: half of every 32 bytes of b, D^-1 and out, the other half
+// left to a wavefront of another class in another workgroup, and both gather the same neighbours.  Here a neighbour is
+// loaded once and feeds the sums of both nodes (the expression and the order of d and cc per row as in class_node_slot: the
+// same bits), and the epilogue of the 2 C rows is contiguous per lane.
+struct TwinLists
+{
+  int32_t const *nodes;           // first node of the twin of a slot, -1: padding
+  int32_t const *base;            // ... and its base (that of both nodes), by slot
+  int32_t const *classes_of_wave; // [wavefront][2]: the classes of the first and of the second nodes
+  int64_t n_slots;
+  int wide; // b, D^-1, x_prev and out are 32-byte aligned and x 16-byte: the rows of a twin are whole 16-byte accesses at node * C (n even)
+};
+
+// The epilogue of the 2 C rows of a twin, every operand of both nodes requested before the first store (see store_node);
+// without the alignment, the two nodes one after the other.
+template <typename T, int C>
+__device__ __forceinline__ void store_twin(CsrArgs<T> const &a, int wide, int64_t node, T const (&s0)[C], T const (&s1)[C])
+{
+  if constexpr ((C == 1 || C == 2) && sizeof(T) == 8)
+  {
+    if (wide)
+    {
+      constexpr int R = 2 * C;
+      const int64_t row0 = node * C;
+      T sum[R], xr[R], br[R], dr[R], pr[R], orr[R];
+#pragma unroll
+      for (int rc = 0; rc < C; ++rc)
+      {
+        sum[rc] = s0[rc];
+        sum[C + rc] = s1[rc];
+      }
+      const CsrMode mode = static_cast<CsrMode>(a.mode);
+      // (operands_of(mode), written in place: see there)
+      const bool need_x = mode == CsrMode::first || mode == CsrMode::next,
+                 need_b = (mode >= CsrMode::residual && mode <= CsrMode::next) || mode == CsrMode::plus_scaled,
+                 need_d = need_x || mode == CsrMode::plus_scaled, need_p = mode == CsrMode::next,
+                 need_o = mode == CsrMode::subtract || mode == CsrMode::add;
+      auto ld = [&](T const *v, T(&t)[R]) {
+#pragma unroll
+        for (int q = 0; q < R; q += 2)
+        {
+          const double2 w = *reinterpret_cast<double2 const *>(v + row0 + q);
+          t[q] = w.x;
+          t[q + 1] = w.y;
+        }
+      };
+      if (need_x)
+        ld(a.x, xr);
+      if (need_b)
+        ld(a.b, br);
+      if (need_d)
+        ld(a.dinv, dr);
+      if (need_p)
+        ld(a.xprev, pr);
+      if (need_o)
+        ld(a.out, orr);
+      T o[R];
+#pragma unroll
+      for (int rc = 0; rc < R; ++rc)
+        o[rc] = epilogue(mode, sum + rc, xr, br, dr, pr, orr, rc, a.alpha, a.beta);
+#pragma unroll
+      for (int q = 0; q < R; q += 2)
+        *reinterpret_cast<double2 *>(a.out + row0 + q) = make_double2(o[q], o[q + 1]);
+      return;
+    }
+  }
+  store_node<T, C>(a, node, s0);
+  store_node<T, C>(a, node + 1, s1);
+}
+
+// One launch, three ranges of workgroups: the twins, the classed nodes without a twin (class_node_slot), the listed rows.
+template <typename T, int C>
+__global__ __launch_bounds__(256) void bdia_twin_node_kernel(CsrArgs<T> a, BdiaRegular<T> g, TwinLists tw, int32_t const *nodes,
+                                                             int32_t const *class_of_wave, T const *class_table, int64_t n_slots,
+                                                             int32_t const *listed, int64_t n_listed)
+{
+  const int64_t twin_blocks = (tw.n_slots + 255) / 256, class_blocks = (n_slots + 255) / 256;
+  if ((int64_t)blockIdx.x >= twin_blocks + class_blocks)
+  {
+    listed_row_wave(a, listed, n_listed, ((int64_t)blockIdx.x - twin_blocks - class_blocks) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    return;
+  }
+  if ((int64_t)blockIdx.x >= twin_blocks)
+  {
+    class_node_slot<T, C>(a, g, nodes, class_of_wave, class_table, n_slots, ((int64_t)blockIdx.x - twin_blocks) * 256 + threadIdx.x);
+    return;
+  }
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= tw.n_slots)
+    return;
+  const int cls0 = __builtin_amdgcn_readfirstlane(tw.classes_of_wave[2 * (t >> 6)]);
+  const int cls1 = __builtin_amdgcn_readfirstlane(tw.classes_of_wave[2 * (t >> 6) + 1]);
+  const int64_t node = tw.nodes[t];
+  if (node < 0)
+    return;
+  const int first = tw.base[t], last = (int)(g.n_col_nodes - 1);
+  const_as<T> *tab0 = as_constant(class_table + (size_t)cls0 * (size_t)(C * g.Df * C));
+  const_as<T> *tab1 = as_constant(class_table + (size_t)cls1 * (size_t)(C * g.Df * C));
+  const_as<int32_t> *offs = as_constant(g.offs);
+  T sum0[C], sum1[C];
+#pragma unroll
+  for (int rc = 0; rc < C; ++rc)
+    sum0[rc] = sum1[rc] = T(0);
+#pragma unroll 4
+  for (int d = 0; d < g.Df; ++d)
+  {
+    const int64_t nb = max(0, min(first + offs[d], last));
+    T xv[C];
+    if constexpr (C == 2 && sizeof(T) == 8)
+    {
+      const double2 v = reinterpret_cast<double2 const *>(a.x)[nb];
+      xv[0] = v.x;
+      xv[1] = v.y;
+    }
+    else
+    {
+#pragma unroll
+      for (int cc = 0; cc < C; ++cc)
+        xv[cc] = a.x[nb * C + cc];
+    }
+#pragma unroll
+    for (int rc = 0; rc < C; ++rc)
+#pragma unroll
+      for (int cc = 0; cc < C; ++cc)
+      {
+        sum0[rc] += tab0[((size_t)rc * g.Df + d) * C + cc] * xv[cc];
+        sum1[rc] += tab1[((size_t)rc * g.Df + d) * C + cc] * xv[cc];
+      }
+  }
+  store_twin<T, C>(a, tw.wide, node, sum0, sum1);
 }
 
 // The same two node kernels for wide stencils (the second level of the aggregation hierarchy couples 125 nodes):
@@ -1944,6 +2086,137 @@ void SparseMatrixDevice<T>::build_node_classes()
   _use_nodecls = true;
 }
 
+// Twin nodes (see bdia_twin_node_kernel), from the lists of build_node_classes: a twin is (n, n + 1) with n even, both nodes
+// in a class and base[n] == base[n + 1] -- both then walk offs[] against the same clamped neighbours.  (The plain
+// prolongator, whose bases differ by a node from one aggregate to the next, has none: such nodes stay single.)  A twin class is
+// the ordered pair of the two node classes; twins are sorted by (tile of 4096 twins, twin class, n), every run padded to
+// whole wavefronts, first node and base per slot in two arrays read side by side (no base[nodes[t]] gather).  The classed
+// nodes without a twin keep their slots in the class lists, in their order; the listed rows keep their tail.
+template <typename T>
+bool SparseMatrixDevice<T>::enable_node_twins()
+{
+  if (_tw_nodes.size() > 0)
+    return true;
+  if (!std::is_same_v<T, double> || !_use_nodecls || (_nc_c != 1 && _nc_c != 2) || _nc_d >= kSplitStencil)
+    return false;
+  char const *env = std::getenv("MFMG_NODE_TWINS");
+  const bool verbose = std::getenv("MFMG_HIP_VERBOSE") != nullptr;
+  if (env != nullptr && std::string(env) == "0")
+  {
+    if (verbose)
+      std::fprintf(stderr, "[mfmg_hip] matrix %lld x %lld: MFMG_NODE_TWINS=0, one node per lane kept\n", (long long)_n_rows, (long long)_n_cols);
+    return false;
+  }
+  MemoryKind kind("derived layouts (planes, tables, node lists)");
+  hipStream_t st = _handle.stream;
+  const int64_t n_nodes = _n_rows / _nc_c;
+  const std::vector<int32_t> nodes = _nc_nodes.download(st), class_of_wave = _nc_class_of_wave.download(st), base = _nc_base.download(st);
+  std::vector<int32_t> cls_of_node((size_t)n_nodes, -1);
+  int64_t n_classed = 0;
+  for (size_t t = 0; t < nodes.size(); ++t)
+    if (nodes[t] >= 0)
+    {
+      cls_of_node[nodes[t]] = class_of_wave[t >> 6];
+      ++n_classed;
+    }
+  auto is_twin = [&](int64_t n) {
+    return n % 2 == 0 && n + 1 < n_nodes && cls_of_node[n] >= 0 && cls_of_node[n + 1] >= 0 && base[n] == base[n + 1];
+  };
+  int64_t n_twins = 0;
+  for (int64_t n = 0; n + 1 < n_nodes; n += 2)
+    n_twins += is_twin(n) ? 1 : 0;
+  if (n_twins == 0 || 2 * n_twins * 10 < n_classed * 9)
+  {
+    if (verbose)
+      std::fprintf(stderr, "[mfmg_hip] matrix %lld x %lld: %lld of %lld classed nodes are twins (< 90 %%), one node per lane kept\n",
+                   (long long)_n_rows, (long long)_n_cols, (long long)(2 * n_twins), (long long)n_classed);
+    return false;
+  }
+  // twin classes, numbered in the order of (first class, second class)
+  std::vector<std::pair<int32_t, int32_t>> pairs_met;
+  for (int64_t n = 0; n + 1 < n_nodes; n += 2)
+    if (is_twin(n))
+      pairs_met.emplace_back(cls_of_node[n], cls_of_node[n + 1]);
+  std::sort(pairs_met.begin(), pairs_met.end());
+  pairs_met.erase(std::unique(pairs_met.begin(), pairs_met.end()), pairs_met.end());
+  // (tile, twin class, n) order like the class lists: larger tiles where small ones would mostly hold padding
+  constexpr int64_t kTwinTile = 4096;
+  std::vector<int32_t> tw_nodes, tw_base, tw_classes;
+  std::vector<std::pair<int32_t, int32_t>> in_tile; // (twin class, first node)
+  bool done = false;
+  for (int64_t tile : {2 * kTwinTile, 16 * kTwinTile, n_nodes}) // (in nodes)
+  {
+    if (done)
+      break;
+    tw_nodes.clear();
+    tw_classes.clear();
+    for (int64_t t0 = 0; t0 < n_nodes; t0 += tile)
+    {
+      in_tile.clear();
+      for (int64_t n = t0; n < std::min(n_nodes, t0 + tile); n += 2)
+        if (is_twin(n))
+        {
+          const auto key = std::make_pair(cls_of_node[n], cls_of_node[n + 1]);
+          in_tile.emplace_back((int32_t)(std::lower_bound(pairs_met.begin(), pairs_met.end(), key) - pairs_met.begin()), (int32_t)n);
+        }
+      std::sort(in_tile.begin(), in_tile.end());
+      for (size_t q = 0; q < in_tile.size(); ++q)
+      {
+        if (q > 0 && in_tile[q].first != in_tile[q - 1].first)
+          while (tw_nodes.size() % 64 != 0)
+            tw_nodes.push_back(-1);
+        if (tw_nodes.size() % 64 == 0)
+        {
+          tw_classes.push_back(pairs_met[in_tile[q].first].first);
+          tw_classes.push_back(pairs_met[in_tile[q].first].second);
+        }
+        tw_nodes.push_back(in_tile[q].second);
+      }
+      while (tw_nodes.size() % 64 != 0)
+        tw_nodes.push_back(-1);
+    }
+    done = (double)tw_nodes.size() <= 1.25 * (double)n_twins || tile >= n_nodes;
+  }
+  tw_base.resize(tw_nodes.size());
+  for (size_t t = 0; t < tw_nodes.size(); ++t)
+    tw_base[t] = tw_nodes[t] >= 0 ? base[tw_nodes[t]] : 0;
+  // the classed nodes without a twin, in the order they had: a run ends where the class of the wavefront changes
+  std::vector<int32_t> single_nodes, single_class_of_wave;
+  for (size_t t = 0; t < nodes.size(); ++t)
+  {
+    if (t % 64 == 0 && t > 0 && class_of_wave[t >> 6] != class_of_wave[(t >> 6) - 1])
+      while (single_nodes.size() % 64 != 0)
+        single_nodes.push_back(-1);
+    const int32_t n = nodes[t];
+    if (n < 0 || is_twin(n - n % 2))
+      continue;
+    if (single_nodes.size() % 64 == 0)
+      single_class_of_wave.push_back(class_of_wave[t >> 6]);
+    single_nodes.push_back(n);
+  }
+  while (single_nodes.size() % 64 != 0)
+    single_nodes.push_back(-1);
+  _tw_nodes.upload(tw_nodes.data(), tw_nodes.size(), st);
+  _tw_base.upload(tw_base.data(), tw_base.size(), st);
+  _tw_classes_of_wave.upload(tw_classes.data(), tw_classes.size(), st);
+  _tw_classes = (int)pairs_met.size();
+  // the lists the twins replace are freed (the base by node only where no single node is left to read it)
+  _nc_nodes.release();
+  _nc_class_of_wave.release();
+  if (single_nodes.empty())
+    _nc_base.release();
+  else
+  {
+    _nc_nodes.upload(single_nodes.data(), single_nodes.size(), st);
+    _nc_class_of_wave.upload(single_class_of_wave.data(), single_class_of_wave.size(), st);
+  }
+  MFMG_HIP_CHECK(hipStreamSynchronize(st));
+  if (verbose)
+    std::fprintf(stderr, "[mfmg_hip] matrix %lld x %lld: %lld twins of %d twin classes in %lld slots, %lld slots of single nodes\n",
+                 (long long)_n_rows, (long long)_n_cols, (long long)n_twins, _tw_classes, (long long)tw_nodes.size(), (long long)single_nodes.size());
+  return true;
+}
+
 template <typename T>
 void SparseMatrixDevice<T>::build_row_base(std::vector<int32_t> const &row_ptr, std::vector<int32_t> const &col,
                                            std::vector<T> const &val)
@@ -2041,6 +2314,15 @@ CsrForm SparseMatrixDevice<T>::form() const
     f.listed = (int64_t)_nc_listed.size();
     f.class_kernel = parts_of(_nc_d, _n_rows / _nc_c);
     f.listed_route = f.listed == 0 ? CsrForm::listed_none : f.class_kernel == 1 ? CsrForm::listed_class_tail : CsrForm::listed_split_tail;
+    if (_tw_nodes.size() > 0)
+    {
+      // (enable_node_twins: only where class_kernel is 1; the singles and the listed rows ride in the twin launch)
+      f.twin_kernel = 1;
+      f.twin_slots = (int64_t)_tw_nodes.size();
+      f.twin_classes = _tw_classes;
+      f.single_slots = (int64_t)_nc_nodes.size();
+      f.twin_wide = _last_twin_wide.load(std::memory_order_relaxed);
+    }
     return f;
   }
   if (_use_rowbase)
@@ -2182,10 +2464,34 @@ void SparseMatrixDevice<T>::launch(CsrMode mode, T const *x, T const *b, T const
     g.Df = _nc_d;
     g.base = _nc_base.data();
     g.n_col_nodes = _n_cols / _nc_c;
-    with_node_width(_nc_c, [&](auto cc) {
-      launch_classes(cc, g, _nc_nodes.data(), _nc_class_of_wave.data(), _nc_table.data(), (int64_t)_nc_nodes.size(),
-                     _nc_listed.data(), (int64_t)_nc_listed.size());
-    });
+    if (f.twin_kernel)
+    {
+      auto aligned32 = [](void const *p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 32 == 0; };
+      TwinLists tw;
+      tw.nodes = _tw_nodes.data();
+      tw.base = _tw_base.data();
+      tw.classes_of_wave = _tw_classes_of_wave.data();
+      tw.n_slots = f.twin_slots;
+      // (a.pairs: x too is 16-byte aligned -- the smoother modes of a square matrix read it at the rows of the twin, 16 bytes
+      // at node * C with n even)
+      tw.wide = (a.pairs && aligned32(b) && aligned32(dinv) && aligned32(x_prev) && aligned32(out)) ? 1 : 0;
+      _last_twin_wide.store(tw.wide, std::memory_order_relaxed);
+      const unsigned int grid = (unsigned int)((f.twin_slots + 255) / 256 + (f.single_slots + 255) / 256 + (f.listed + 3) / 4);
+      if constexpr (std::is_same_v<T, double>)
+      {
+        if (_nc_c == 1)
+          hipLaunchKernelGGL((bdia_twin_node_kernel<T, 1>), dim3(grid), dim3(256), 0, st, a, g, tw, _nc_nodes.data(),
+                             _nc_class_of_wave.data(), _nc_table.data(), f.single_slots, _nc_listed.data(), f.listed);
+        else
+          hipLaunchKernelGGL((bdia_twin_node_kernel<T, 2>), dim3(grid), dim3(256), 0, st, a, g, tw, _nc_nodes.data(),
+                             _nc_class_of_wave.data(), _nc_table.data(), f.single_slots, _nc_listed.data(), f.listed);
+      }
+    }
+    else
+      with_node_width(_nc_c, [&](auto cc) {
+        launch_classes(cc, g, _nc_nodes.data(), _nc_class_of_wave.data(), _nc_table.data(), (int64_t)_nc_nodes.size(),
+                       _nc_listed.data(), (int64_t)_nc_listed.size());
+      });
   }
   else if (f.kind == 4)
     hipLaunchKernelGGL(rowbase_spmv_kernel<T>, dim3((unsigned int)((_n_rows + 255) / 256)), dim3(256), 0, st, a,

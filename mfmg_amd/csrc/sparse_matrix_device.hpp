@@ -71,6 +71,12 @@ struct CsrForm
   int node_class_c = 0, node_class_d = 0;
   int pairs = -1;          // a.pairs of the last launch (-1: none yet)
   int csr_released = 0;
+  // twin nodes (enable_node_twins): two row nodes (n, n + 1) per lane of bdia_twin_node_kernel, which then is the one launch
+  int twin_kernel = 0;
+  int64_t twin_slots = 0;   // slots of the twin lists (padded to wavefronts), two nodes each
+  int twin_classes = 0;     // ordered pairs of node classes met
+  int64_t single_slots = 0; // slots of the class lists left to the classed nodes without a twin
+  int twin_wide = -1;       // whether the last twin launch took the 32-byte epilogue (-1: none yet; 0: the store_node halves)
 };
 
 template <typename T>
@@ -174,6 +180,12 @@ public:
   // Afterwards download / transpose / mmult / the diagonal kernels and a change of kernel throw.
   bool release_csr();
   bool csr_released() const { return _csr_released; }
+  // Twin nodes on top of the node classes (FP64, 1 or 2 unknowns per node, the one-thread-per-node class kernel): the row
+  // nodes (n, n + 1), n even, both in a class and with one base, become one lane of bdia_twin_node_kernel.  Taken when at
+  // least 90 % of the classed nodes are twins; false (the matrix stays as it was) otherwise and under MFMG_NODE_TWINS=0,
+  // which is read here.  The aggregation setup calls it on the smoothed prolongators it builds.
+  bool enable_node_twins();
+  bool node_twins() const { return _tw_nodes.size() > 0; }
   // the CSR arrays on the device (a no-op unless the upload was deferred)
   void ensure_device_csr() const;
   bool device_csr_deferred() const { return _device_csr_deferred; }
@@ -194,7 +206,7 @@ public:
     {
       _use_bdia = (use_lds == 2 || use_lds == 3) && (_bdia_val.size() > 0 || _bdia_val_f32.size() > 0);
       _use_rowbase = (use_lds == 4) && _rb_val.size() > 0;
-      _use_nodecls = (use_lds == 5) && _nc_nodes.size() > 0;
+      _use_nodecls = (use_lds == 5) && (_nc_nodes.size() > 0 || _tw_nodes.size() > 0);
       _use_lds = (use_lds == 1) && _lcol.size() > 0;
     }
   }
@@ -235,6 +247,7 @@ private:
 
   // a.pairs of the last launch, for form() only (atomic: launches from several host threads stay free of a data race)
   mutable std::atomic<int> _last_pairs{-1};
+  mutable std::atomic<int> _last_twin_wide{-1}; // tw.wide of the last twin launch, likewise
   HipHandle &_handle;
   int64_t _n_rows, _n_cols, _nnz;
   int _lanes_per_row;
@@ -264,6 +277,10 @@ private:
   int _nc_c = 0, _nc_d = 0, _nc_classes = 0;
   DeviceBuffer<int32_t> _nc_base, _nc_offs, _nc_nodes, _nc_class_of_wave, _nc_listed;
   DeviceBuffer<T> _nc_table;
+  // twin nodes (enable_node_twins): first node and base per slot, the two classes per wavefront; _nc_nodes / _nc_class_of_wave
+  // then hold the classed nodes without a twin only
+  DeviceBuffer<int32_t> _tw_nodes, _tw_base, _tw_classes_of_wave;
+  int _tw_classes = 0;
   bool _use_bdia = false;
   bool _bdia_sym = false;
   // regular rows of a translation-invariant operator: stencil table instead of stored values (see the .hip file)

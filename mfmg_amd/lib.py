@@ -24,7 +24,7 @@ RESTRICTOR_FORM_FIELDS = 12
 EIGENSOLVER_INFO_FIELDS = 7
 RESIDUAL_RESTRICTION_FORM_FIELDS = 10
 AMG_SETUP_INFO_FIELDS = 13   # MFMG_HIP_AMG_SETUP_INFO_FIELDS
-CSR_FORM_FIELDS = 22
+CSR_FORM_FIELDS = 27   # MFMG_HIP_CSR_FORM_FIELDS
 # modes of mfmg_hip_csr_launch
 CSR_APPLY, CSR_RESIDUAL, CSR_FIRST, CSR_NEXT, CSR_SUBTRACT, CSR_ADD, CSR_PLUS_SCALED = range(7)
 
@@ -192,6 +192,8 @@ def load() -> C.CDLL:
         "mfmg_hip_csr_residual": (C.c_int, [vp, vp, vp, vp]),
         "mfmg_hip_csr_launch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, dbl, dbl, vp]),
         "mfmg_hip_csr_form": (C.c_int, [vp, P(i64), i32]),
+        "mfmg_hip_csr_enable_node_twins": (C.c_int, [vp, P(C.c_int)]),
+        "mfmg_hip_csr_release_csr": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_mf_laplace_create": (C.c_int, [vp, P(MeshDesc), P(vp)]),
         "mfmg_hip_mf_laplace_destroy": (C.c_int, [vp]),
         "mfmg_hip_mf_laplace_size": (C.c_int, [vp, P(i64)]),
@@ -288,7 +290,7 @@ def load() -> C.CDLL:
                    "mfmg_hip_mf_laplace_sweep_diagonal_inverse", "mfmg_hip_block_groups", "mfmg_hip_mf_laplace_block_launch",
                    "mfmg_hip_mf_laplace_block_available", "mfmg_hip_mf_laplace_set_block_tile", "mfmg_hip_mf_laplace_get_block_tile",
                    "mfmg_hip_hierarchy_apply_block", "mfmg_hip_hierarchy_vmult_block", "mfmg_hip_hierarchy_smoother_apply_block",
-                   "mfmg_hip_hierarchy_block_info"}
+                   "mfmg_hip_hierarchy_block_info", "mfmg_hip_csr_enable_node_twins", "mfmg_hip_csr_release_csr"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
