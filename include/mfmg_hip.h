@@ -756,6 +756,52 @@ int mfmg_hip_hierarchy_vmult_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, in
 int mfmg_hip_hierarchy_smoother_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld, const double *b, double *x);
 int mfmg_hip_hierarchy_block_info(mfmg_hip_hierarchy_t h, int64_t *fields);
 
+/* ---- preconditioned CG on a block of right-hand sides (additions, no change of the ABI version) ----
+ * mfmg_hip_hierarchy_solve_cg_block: mfmg_hip_hierarchy_solve_cg for every column of the blocks b and x (layout and checks of
+ * the block entry points above: 1 .. 64 vectors, an even ld >= n_dofs, bases aligned to 16 bytes, no overlap, no communicator;
+ * MFMG_HIP_ERROR_INVALID_ARGUMENT otherwise, as for a negative tolerance or max_iterations).  Per column the semantics are exactly
+ * those of the one-vector driver, and so are the BITS of x, the iteration count, the final residual and the history: x holds the
+ * initial guess; ||r_0|| <= tolerances[c] gives 0 iterations with x[c] unchanged; residual_history (may be NULL) receives
+ * ||r_0||, ||r_1||, ... of column c at residual_history[c * history_ld + i] as far as history_ld reaches; tolerances,
+ * n_iterations, final_residuals (n_vectors entries each) are host arrays, the tolerances absolute l2 norms.  Returns
+ * MFMG_HIP_ERROR_RUNTIME when any column is unconverged at max_iterations, with all outputs filled.
+ * A column that converged (or started converged) takes no further preconditioner or operator application and no vector pass:
+ * the columns still iterating are kept in the first slots of the library-owned working blocks r, z, p, A p -- when a slot retires
+ * the last active slot's r and p are copied into it (mfmg_hip_block_cg_retire is that plan) -- so the groups of
+ * mfmg_hip_block_groups apply to what is left.  Per iteration: the cycle on the active slots as mfmg_hip_hierarchy_vmult_block runs
+ * it, one reduction for all (r, z), the direction, the operator on the block, one reduction for all (p, A p), the update with the
+ * partial sums of (r, r) folded into the same pass, ONE device-to-host copy and ONE stream synchronisation.  The working blocks
+ * (4 n_vectors fine vectors; 6 with "internal numbering" lexicographic, where b and x are gathered once and x is scattered once:
+ * 2 n_vectors launches of "dof_permutation" per solve) are owned by the hierarchy and kept for the next solve; an allocation that
+ * fails returns an error and leaves nothing behind.
+ *   work (may be NULL): [0] column-applications of the preconditioner, [1] of the operator -- both the sum of n_iterations --,
+ *   [2] launches of mf_laplace_block_kernel, [3] slot moves (at most n_vectors).
+ * Not in this driver: a block FGMRES, the FP32 preconditioner, ranks.
+ * mfmg_hip_block_cg_retire (host only): of n_active (0 .. 64) slots those with retire_flags[s] != 0 retire.  Retired slots are
+ * filled in ascending order, each from the last slot that survives behind it: moves[2 i], moves[2 i + 1] = from, to (capacity
+ * n_active pairs), slot_col[to] = slot_col[from]; afterwards the first n_active_out slots are the survivors.  n_moves is at most the
+ * number retired.
+ * mfmg_hip_hierarchy_operator_apply_block: y[c] = A x[c] on `level` for every column, with the bits of
+ * mfmg_hip_hierarchy_operator_apply (one launch of the block kernel per group where the level has it).
+ * The kernels of the driver on their own (tests; a context without a communicator; X, Y, Z, P, AP, R: device blocks of k slots with
+ * leading dimension ld >= n; the scalars -- k doubles each -- and slot_col are device arrays):
+ *   block_dots          out[s] = (X_s, Y_s), per slot the reduction of the one-vector dot product, bit for bit
+ *   block_cg_direction  P_s = Z_s + (rz_new[s] / rz_old[s]) P_s, a zero divisor gives beta = 0; rz_old NULL: P_s = Z_s
+ *   block_cg_update     alpha_s = rz[s] / pap[s] (zero divisor: 0); X_{slot_col[s]} += alpha_s P_s in the block X with leading
+ *                       dimension ldx; R_s -= alpha_s AP_s; rr_out[s] = (R_s, R_s) of the new R with the bits of block_dots */
+int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                      const double *tolerances, int32_t max_iterations, int32_t *n_iterations,
+                                      double *final_residuals, double *residual_history, int32_t history_ld, int64_t *work);
+int mfmg_hip_block_cg_retire(int32_t n_active, const int32_t *retire_flags, int32_t *slot_col, int32_t *moves, int32_t *n_moves,
+                             int32_t *n_active_out);
+int mfmg_hip_hierarchy_operator_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld, const double *x,
+                                            double *y);
+int mfmg_hip_block_dots(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *X, const double *Y, double *out);
+int mfmg_hip_block_cg_direction(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *Z, double *P,
+                                const double *rz_new, const double *rz_old);
+int mfmg_hip_block_cg_update(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *P, const double *AP, double *R,
+                             int64_t ldx, double *X, const int32_t *slot_col, const double *rz, const double *pap, double *rr_out);
+
 #ifdef __cplusplus
 }
 #endif

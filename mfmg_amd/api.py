@@ -133,6 +133,21 @@ def block_groups(n_vectors: int):
     return [int(w[i]) for i in range(n.value)]
 
 
+def block_cg_retire(retire_flags, slot_col):
+    """The slot moves of solve_cg_block when the slots flagged in retire_flags (one per active slot) retire: returns
+    (moves, slot_col, n_active) -- moves a list of (from, to) pairs, slot_col the updated slot -> column map (its first n_active
+    entries are the survivors').  Host only."""
+    lib = _lib.load()
+    n = len(retire_flags)
+    if len(slot_col) != n:
+        raise ValueError("one slot_col entry per active slot")
+    arr = C.c_int32 * max(n, 1)
+    flags, cols, moves = arr(*[int(bool(f)) for f in retire_flags]), arr(*[int(c) for c in slot_col]), (C.c_int32 * (2 * max(n, 1)))()
+    n_moves, n_out = C.c_int32(), C.c_int32()
+    check(lib.mfmg_hip_block_cg_retire(n, flags, cols, moves, C.byref(n_moves), C.byref(n_out)))
+    return [(int(moves[2 * i]), int(moves[2 * i + 1])) for i in range(n_moves.value)], [int(cols[i]) for i in range(n)], n_out.value
+
+
 def memory_inventory() -> str:
     """Live bytes of the library's device buffers per (setup section | kind of structure), as text."""
     lib = _lib.load()
@@ -256,6 +271,36 @@ class Context:
         check(self._lib.mfmg_hip_krylov_orthogonalize(self.handle, n, ld, n_columns - 1, _dev_ptr(V), _dev_ptr(w), _dev_ptr(h),
                                                       _dev_ptr(norm), passes))
         return h, norm
+
+    # The vector kernels of Hierarchy.solve_cg_block on their own (tests).  Blocks are 2-D float64 CUDA tensors of shape (k, ld)
+    # with stride(1) == 1; n entries of every row are used; scalars are float64 device tensors of k entries.
+    def block_dots(self, n: int, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+        """out[s] = (X[s, :n], Y[s, :n]) with the reduction of dot(), bit for bit; a device tensor."""
+        k, ld, px = _block_ptr(X)
+        out = torch.empty(k, dtype=torch.float64, device=X.device)
+        check(self._lib.mfmg_hip_block_dots(self.handle, int(n), k, ld, px, _same_block(k, ld, Y), _dev_ptr(out)))
+        return out
+
+    def block_cg_direction(self, n: int, Z: torch.Tensor, P: torch.Tensor, rz_new=None, rz_old=None):
+        """P[s] = Z[s] + (rz_new[s] / rz_old[s]) P[s] (a zero divisor: beta = 0); rz_old None: P[s] = Z[s]."""
+        k, ld, pz = _block_ptr(Z)
+        s = lambda t: None if t is None else _dev_ptr(t, k)
+        check(self._lib.mfmg_hip_block_cg_direction(self.handle, int(n), k, ld, pz, _same_block(k, ld, P), s(rz_new), s(rz_old)))
+
+    def block_cg_update(self, n: int, P: torch.Tensor, AP: torch.Tensor, R: torch.Tensor, X: torch.Tensor, slot_col: torch.Tensor,
+                        rz: torch.Tensor, pap: torch.Tensor) -> torch.Tensor:
+        """alpha = rz[s] / pap[s] (zero divisor: 0); X[slot_col[s]] += alpha P[s]; R[s] -= alpha AP[s]; returns (R[s], R[s]) of the
+        new R with the bits of block_dots.  X is a block of its own shape and leading dimension; slot_col an int32 device tensor
+        naming every column of X at most once."""
+        k, ld, pp = _block_ptr(P)
+        kx, ldx, px = _block_ptr(X)
+        cols = slot_col.cpu().tolist()
+        if len(cols) != k or len(set(cols)) != k or min(cols) < 0 or max(cols) >= kx or ldx < n:
+            raise ValueError("slot_col names k different columns of X")
+        out = torch.empty(k, dtype=torch.float64, device=P.device)
+        check(self._lib.mfmg_hip_block_cg_update(self.handle, int(n), k, ld, pp, _same_block(k, ld, AP), _same_block(k, ld, R), ldx, px,
+                                                 _dev_ptr(slot_col, k, torch.int32), _dev_ptr(rz, k), _dev_ptr(pap, k), _dev_ptr(out)))
+        return out
 
     def krylov_combine(self, Z: torch.Tensor, y: torch.Tensor, x: torch.Tensor):
         """x += sum_i y[i] Z[i] in one pass (Z: [columns, ld] contiguous, ld >= len(x); y on the device)."""
@@ -1014,6 +1059,36 @@ class Hierarchy:
                                                     C.byref(it), C.byref(res), hist.ctypes.data_as(C.POINTER(C.c_double)),
                                                     len(hist)))
         return it.value, hist[: it.value + 1]
+
+    def solve_cg_block(self, B: torch.Tensor, X: torch.Tensor, tolerances, max_iterations: int = 1000):
+        """solve_cg for every row of the blocks B and X (2-D float64 tensors of shape (k, m), stride(1) == 1, one even leading
+        dimension ld = stride(0) >= n_dofs) in one call: row c of X, its iteration count and its history are those of
+        solve_cg(B[c], X[c], tolerances[c], max_iterations), bit for bit.  A column that converged costs nothing further.
+        Returns (iterations, histories, work): k ints, k arrays, and a dict with the column-applications of the preconditioner
+        and of the operator (each the sum of the iterations), the launches of the block kernel and the slot moves.  Raises the
+        error of solve_cg when a column is unconverged at max_iterations; X and `last_block_solve` (the same triple) are filled."""
+        k, ld, pb = _block_ptr(B)
+        px = _same_block(k, ld, X)
+        tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tolerances, dtype=np.float64), (k,)))
+        its = np.zeros(k, dtype=np.int32)
+        res = np.zeros(k)
+        hist = np.zeros((k, max(max_iterations, 0) + 1))
+        work = np.zeros(4, dtype=np.int64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        status = self._lib.mfmg_hip_hierarchy_solve_cg_block(self.handle, k, ld, pb, px, dp(tol), max_iterations,
+                                                             its.ctypes.data_as(C.POINTER(C.c_int32)), dp(res), dp(hist), hist.shape[1],
+                                                             work.ctypes.data_as(C.POINTER(C.c_int64)))
+        out = ([int(i) for i in its], [hist[c, : its[c] + 1].copy() for c in range(k)],
+               {"preconditioner_columns": int(work[0]), "operator_columns": int(work[1]), "block_launches": int(work[2]),
+                "slot_moves": int(work[3])})
+        self.last_block_solve = out
+        check(status)
+        return out
+
+    def operator_apply_block(self, level: int, X: torch.Tensor, Y: torch.Tensor):
+        """Y[c] = A X[c] on `level` for every row of the blocks, with the bits of operator_apply."""
+        k, ld, px = _block_ptr(X)
+        check(self._lib.mfmg_hip_hierarchy_operator_apply_block(self.handle, level, k, ld, px, _same_block(k, ld, Y)))
 
     def solve_fgmres(self, b, x, tolerance: float = 1e-6, max_iterations: int = 1000, restart: int = 30,
                      preconditioner: str = "double"):

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "amge_lanczos.hpp"
+#include "block_krylov.hpp"
 #include "cell_contraction.hpp"
 #include "dof_permutation.hpp"
 #include "halo_transport.hpp"
@@ -149,6 +150,63 @@ struct KrylovWorkspace
   ~KrylovWorkspace() { release_host(); }
 };
 
+// What mfmg_hip_hierarchy_solve_cg_block keeps between solves: the working blocks r, z, p, A p [ld x columns], with "internal
+// numbering" lexicographic the gathered b and x, the partials of the block reductions [columns x 1024], the per-slot scalars
+// ((r, z) of this / the previous iteration, (p, A p), (r, r): four rows of `columns`), the slot -> column map and the pinned host
+// mirror of the (r, r) and the map.  Grown on demand, never shrunk; a failed allocation leaves the workspace EMPTY.
+struct BlockCgWorkspace
+{
+  int64_t ld = 0;
+  int columns = 0;
+  bool permuted = false;
+  DeviceBuffer<double> R, Z, P, AP, B, X, partials, scalars;
+  DeviceBuffer<int32_t> slot_col;
+  double *host = nullptr;        // pinned: `columns` doubles ...
+  int32_t *host_col = nullptr;   // ... and behind them `columns` slot -> column entries
+  void reserve(int64_t want_ld, int k, bool permute, hipStream_t stream)
+  {
+    if (want_ld == ld && k <= columns && (!permute || permuted))
+      return;
+    MemoryKind kind("block CG working set");
+    const int want = std::max(k, want_ld == ld ? columns : 0);
+    release(); // (before the larger one is allocated)
+    const size_t block = (size_t)want_ld * want;
+    DeviceBuffer<double> *blocks[6] = {&R, &Z, &P, &AP, &B, &X};
+    for (int i = 0; i < (permute ? 6 : 4); ++i)
+    {
+      blocks[i]->resize(block);
+      // (zeros: the tails between the columns are never written, and a preconditioner that reads its start vector finds numbers)
+      MFMG_HIP_CHECK(hipMemsetAsync(blocks[i]->data(), 0, block * sizeof(double), stream));
+    }
+    partials.resize((size_t)want * block_krylov::kReduceBlocks);
+    scalars.resize((size_t)4 * want);
+    slot_col.resize((size_t)want);
+    MFMG_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&host), (size_t)want * (sizeof(double) + sizeof(int32_t))));
+    host_col = reinterpret_cast<int32_t *>(host + want);
+    ld = want_ld; // only now: everything above stands
+    columns = want;
+    permuted = permute;
+  }
+  void release()
+  {
+    ld = 0;
+    columns = 0;
+    permuted = false;
+    release_host();
+    for (DeviceBuffer<double> *b : {&R, &Z, &P, &AP, &B, &X, &partials, &scalars})
+      b->release();
+    slot_col.release();
+  }
+  void release_host()
+  {
+    if (host)
+      (void)hipHostFree(host);
+    host = nullptr;
+    host_col = nullptr;
+  }
+  ~BlockCgWorkspace() { release_host(); }
+};
+
 struct mfmg_hip_hierarchy_s
 {
   HipHandle *handle = nullptr;
@@ -169,6 +227,7 @@ struct mfmg_hip_hierarchy_s
   DeviceBuffer<double> work[2];
   DeviceBuffer<float> work_f32[2];
   KrylovWorkspace krylov;
+  BlockCgWorkspace block_cg;
   // block entry points: the permuted columns of one group (b, x) and what the last block call did
   DeviceBuffer<double> block_work[2];
   int64_t block_info[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0};
@@ -1878,6 +1937,276 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
       h->perm->scatter(static_cast<double const *>(x_run), x);
     if (!converged)
       throw std::runtime_error("CG did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
+  });
+}
+
+namespace
+{
+// the first `count` columns of a block as vectors (views)
+struct BlockViews
+{
+  std::vector<DVector> store;
+  std::vector<DVector *> ptr;
+  std::vector<DVector const *> cptr;
+  BlockViews(HipHandle &handle, int64_t n, int64_t ld, int count, double *base)
+  {
+    store.reserve(count);
+    for (int c = 0; c < count; ++c)
+    {
+      store.emplace_back(handle, n, base + (int64_t)c * ld);
+      ptr.push_back(&store.back());
+      cptr.push_back(&store.back());
+    }
+  }
+};
+} // namespace
+
+// mfmg_hip_hierarchy_solve_cg on a block of right-hand sides.  All columns iterate in lockstep, so "the first iteration" is the
+// same for every slot; a column that converged leaves the working blocks (block_krylov::plan_retire keeps the active slots
+// contiguous) and costs nothing further.  Per iteration: the cycle on the active slots (Hierarchy::apply_block), (r, z) of all of
+// them in one reduction, the direction, the operator on the block, (p, A p), the update with the partials of (r, r) folded in,
+// ONE device-to-host copy of the active slots' (r, r) and ONE synchronisation.  Every kernel gives a slot the bits the one-vector
+// driver gives its vector, so x, the iteration count and the history of a column are those of mfmg_hip_hierarchy_solve_cg.
+int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                      const double *tolerances, int32_t max_iterations, int32_t *n_iterations, double *final_residuals,
+                                      double *residual_history, int32_t history_ld, int64_t *work)
+{
+  return guarded([&] {
+    check_block(h, 0, n_vectors, ld, b, x);
+    require(tolerances != nullptr, "null argument");
+    require(max_iterations >= 0, "bad stopping criterion");
+    for (int c = 0; c < n_vectors; ++c)
+      require(tolerances[c] >= 0., "bad stopping criterion");
+    require(residual_history == nullptr || history_ld >= 0, "bad history length");
+    HipHandle &handle = *h->handle;
+    const int k = n_vectors;
+    const int64_t n = level_size(h, 0);
+    auto op = h->hierarchy->levels()[0].get_operator();
+    // "internal numbering" lexicographic: b and x are gathered once into library blocks, the whole iteration runs in the internal
+    // numbering, x is scattered once: 2 k launches of the permutation per solve.  Otherwise the working blocks take the caller's
+    // leading dimension, so that the operator runs from the caller's x into r on one block layout.
+    const bool permute = (bool)h->perm;
+    const int64_t wld = permute ? n + (n & 1) : ld;
+    BlockCgWorkspace &ws = h->block_cg;
+    try
+    {
+      ws.reserve(wld, k, permute, handle.stream);
+    }
+    catch (...)
+    {
+      ws.release();
+      (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
+      throw;
+    }
+    double const *b_run = b;
+    double *x_run = x;
+    if (permute)
+    {
+      for (int c = 0; c < k; ++c)
+        h->perm->gather2(b + c * ld, static_cast<double const *>(x + c * ld), ws.B.data() + c * wld, ws.X.data() + c * wld);
+      b_run = ws.B.data();
+      x_run = ws.X.data();
+    }
+    double *const R = ws.R.data(), *const Z = ws.Z.data(), *const P = ws.P.data(), *const AP = ws.AP.data();
+    double *const partials = ws.partials.data();
+    double *const rz[2] = {ws.scalars.data(), ws.scalars.data() + ws.columns}; // (r, z) of this / the previous iteration, alternating
+    double *const pap = ws.scalars.data() + 2 * ws.columns, *const rr = ws.scalars.data() + 3 * ws.columns;
+    const bool z_is_read = !h->hierarchy->is_preconditioner(); // the cycle then starts from what z holds: the one-vector driver's zero / last z
+    if (z_is_read)
+      MFMG_HIP_CHECK(hipMemsetAsync(Z, 0, sizeof(double) * (size_t)wld * k, handle.stream));
+    const int64_t launches_before = block_kernel_launches(h);
+    int64_t preconditioner_columns = 0, operator_columns = 0, slot_moves = 0;
+    auto fetch = [&](int count) { // (r, r) of the first `count` slots: the one round trip of an iteration
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, rr, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+    };
+    auto record = [&](int c, int it, double v) {
+      if (residual_history && it < history_ld)
+        residual_history[(int64_t)c * history_ld + it] = v;
+    };
+    // r = b - A x, as the one-vector driver forms it: the operator, then r = -r + b per column
+    {
+      BlockViews xv(handle, n, wld, k, x_run), rv(handle, n, wld, k, R);
+      op->apply_block(xv.cptr, rv.ptr);
+      for (int c = 0; c < k; ++c)
+        vec::sadd<double>(handle, n, -1., 1., b_run + c * wld, R + c * wld);
+    }
+    block_krylov::dots(handle, n, k, wld, R, R, partials, rr);
+    fetch(k);
+    std::vector<double> res(k);
+    std::vector<int32_t> iterations(k, 0), flags(k), moves(2 * (size_t)k);
+    int n_active = k;
+    bool any = false;
+    for (int c = 0; c < k; ++c)
+    {
+      res[c] = std::sqrt(ws.host[c]);
+      record(c, 0, res[c]);
+      flags[c] = res[c] <= tolerances[c];
+      any = any || flags[c];
+      ws.host_col[c] = c;
+    }
+    int it = 0, cur = 0;
+    // the slots named by `flags` retire; r, p (and what else the next iteration reads of a slot) of the slots that move follow.
+    // (host_col is written only after the synchronisation that follows the upload before: the copy never reads a changing array)
+    auto retire = [&](bool upload_always) {
+      int n_left = n_active, n_moves = 0;
+      if (any)
+        n_moves = block_krylov::plan_retire(n_active, flags.data(), ws.host_col, moves.data(), &n_left);
+      n_active = n_left;
+      if (n_active == 0 || it >= max_iterations || !(any || upload_always))
+        return;
+      for (int m = 0; m < n_moves; ++m)
+      {
+        const int64_t from = moves[2 * m], to = moves[2 * m + 1];
+        vec::copy<double>(handle, n, R + from * wld, R + to * wld);
+        if (it > 0)
+        {
+          vec::copy<double>(handle, n, P + from * wld, P + to * wld);
+          if (z_is_read)
+            vec::copy<double>(handle, n, Z + from * wld, Z + to * wld);
+          MFMG_HIP_CHECK(hipMemcpyAsync(rz[1 - cur] + to, rz[1 - cur] + from, sizeof(double), hipMemcpyDeviceToDevice, handle.stream));
+        }
+      }
+      slot_moves += n_moves;
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.slot_col.data(), ws.host_col, sizeof(int32_t) * n_active, hipMemcpyHostToDevice, handle.stream));
+    };
+    retire(true);
+    while (n_active > 0 && it < max_iterations)
+    {
+      {
+        BlockViews rv(handle, n, wld, n_active, R), zv(handle, n, wld, n_active, Z);
+        timer_enter_subsection(h->timer, "Apply");
+        try
+        {
+          h->hierarchy->apply_block(rv.cptr, zv.ptr);
+        }
+        catch (...)
+        {
+          timer_leave_subsection(h->timer);
+          throw;
+        }
+        timer_leave_subsection(h->timer);
+      }
+      preconditioner_columns += n_active;
+      block_krylov::dots(handle, n, n_active, wld, R, Z, partials, rz[cur]);
+      block_krylov::cg_direction(handle, n, n_active, wld, Z, P, rz[cur], rz[1 - cur], it == 0); // p = z + beta p
+      {
+        BlockViews pv(handle, n, wld, n_active, P), apv(handle, n, wld, n_active, AP);
+        op->apply_block(pv.cptr, apv.ptr);
+      }
+      operator_columns += n_active;
+      block_krylov::dots(handle, n, n_active, wld, P, AP, partials, pap);
+      block_krylov::cg_update(handle, n, n_active, wld, P, AP, R, wld, x_run, ws.slot_col.data(), rz[cur], pap, partials, rr);
+      fetch(n_active);
+      cur = 1 - cur; // rz[1 - cur] is now the (r, z) of the iteration that just ended
+      ++it;
+      any = false;
+      for (int s = 0; s < n_active; ++s)
+      {
+        const int c = ws.host_col[s];
+        res[c] = std::sqrt(ws.host[s]);
+        iterations[c] = it;
+        record(c, it, res[c]);
+        flags[s] = res[c] <= tolerances[c];
+        any = any || flags[s];
+      }
+      retire(false);
+    }
+    for (int c = 0; c < k; ++c)
+    {
+      if (n_iterations)
+        n_iterations[c] = iterations[c];
+      if (final_residuals)
+        final_residuals[c] = res[c];
+    }
+    if (permute)
+      for (int c = 0; c < k; ++c)
+        h->perm->scatter(static_cast<double const *>(x_run + c * wld), x + c * ld);
+    if (work)
+    {
+      work[0] = preconditioner_columns;
+      work[1] = operator_columns;
+      work[2] = block_kernel_launches(h) - launches_before;
+      work[3] = slot_moves;
+    }
+    if (n_active > 0)
+      throw std::runtime_error("CG did not reach the tolerance within max_iterations on every column of the block (SolverControl::NoConvergence)");
+  });
+}
+
+int mfmg_hip_block_cg_retire(int32_t n_active, const int32_t *retire_flags, int32_t *slot_col, int32_t *moves, int32_t *n_moves,
+                             int32_t *n_active_out)
+{
+  return guarded([&] {
+    require(retire_flags && slot_col && moves && n_moves && n_active_out, "null argument");
+    require(n_active >= 0 && n_active <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds at most 64 slots");
+    int left = 0;
+    *n_moves = block_krylov::plan_retire(n_active, retire_flags, slot_col, moves, &left);
+    *n_active_out = left;
+  });
+}
+
+namespace
+{
+void check_kernel_block(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld)
+{
+  require(ctx != nullptr, "null argument");
+  require(!ctx->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+  require(n >= 1 && k >= 1 && k <= MFMG_HIP_BLOCK_MAX_VECTORS && ld >= n, "bad shape");
+}
+} // namespace
+
+int mfmg_hip_block_dots(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *X, const double *Y, double *out)
+{
+  return guarded([&] {
+    check_kernel_block(ctx, n, k, ld);
+    require(X && Y && out, "null argument");
+    HipHandle &handle = *ctx->handle;
+    DeviceBuffer<double> partials((size_t)k * block_krylov::kReduceBlocks);
+    block_krylov::dots(handle, n, k, ld, X, Y, partials.data(), out);
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the partials go away)
+  });
+}
+
+int mfmg_hip_block_cg_direction(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *Z, double *P, const double *rz_new,
+                                const double *rz_old)
+{
+  return guarded([&] {
+    check_kernel_block(ctx, n, k, ld);
+    require(Z && P && (rz_new || !rz_old), "null argument");
+    block_krylov::cg_direction(*ctx->handle, n, k, ld, Z, P, rz_new, rz_old, rz_old == nullptr);
+  });
+}
+
+int mfmg_hip_block_cg_update(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *P, const double *AP, double *R,
+                             int64_t ldx, double *X, const int32_t *slot_col, const double *rz, const double *pap, double *rr_out)
+{
+  return guarded([&] {
+    check_kernel_block(ctx, n, k, ld);
+    require(P && AP && R && X && slot_col && rz && pap && rr_out, "null argument");
+    require(ldx >= n, "bad shape");
+    HipHandle &handle = *ctx->handle;
+    // (slot_col lives on the device: that its entries are columns of X, each named once, is the caller's contract)
+    DeviceBuffer<double> partials((size_t)k * block_krylov::kReduceBlocks);
+    block_krylov::cg_update(handle, n, k, ld, P, AP, R, ldx, X, slot_col, rz, pap, partials.data(), rr_out);
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the partials go away)
+  });
+}
+
+int mfmg_hip_hierarchy_operator_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld, const double *x, double *y)
+{
+  return guarded([&] {
+    require(h != nullptr, "null argument");
+    require(level >= 0 && level < (int)h->hierarchy->levels().size(), "level out of range");
+    check_block(h, level, n_vectors, ld, x, y);
+    auto op = h->hierarchy->levels()[level].get_operator();
+    const int64_t launches = block_kernel_launches(h);
+    for_block_groups(h, level, false, n_vectors, ld, x, y, [&](std::vector<DVector const *> const &xp, std::vector<DVector *> const &yp) {
+      op->apply_block(xp, yp);
+    });
+    h->block_info[0] = h->hierarchy->block_width();
+    h->block_info[1] = block_kernel_launches(h) - launches;
+    h->block_info[2] = 0;
   });
 }
 

@@ -875,6 +875,17 @@ void HipMatrixFreeOperator::residual_block(std::vector<DVector const *> const &x
   apply_mode_block(MfMode::residual, {x[0]->get_values(), b[0]->get_values(), nullptr, res[0]->get_values(), ld, (int)x.size(), 0., 0.});
 }
 
+void HipMatrixFreeOperator::apply_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y) const
+{
+  ASSERT_THROW(x.size() == y.size() && !x.empty(), "the blocks of an operator application need the same number of columns");
+  const int64_t ld = block_leading_dimension(x);
+  if (block_width() == 1 || x.size() == 1 || x.size() > (size_t)kMfBlockMaxVectors || ld == 0 || !block_kernel_layout(x, ld) ||
+      !block_kernel_layout(as_const(y), ld))
+    return Operator<DVector>::apply_block(x, y);
+  // (launch_block cuts the columns into the groups of mf_block_groups)
+  apply_mode_block(MfMode::apply, {x[0]->get_values(), nullptr, nullptr, y[0]->get_values(), ld, (int)x.size(), 0., 0.});
+}
+
 std::vector<std::shared_ptr<DVector>> HipMatrixFreeOperator::build_domain_block(int width, int64_t ld) const
 {
   const int64_t n = (int64_t)grid_complexity();

@@ -218,6 +218,7 @@ public:
   // blocks of vectors (mf_laplace_block.hip): one launch per group of 4 or 2 columns where the device operator has the kernel
   int block_width() const override;
   void residual_block(std::vector<DVector const *> const &x, std::vector<DVector const *> const &b, std::vector<DVector *> const &res) const override;
+  void apply_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y) const override;
   std::vector<std::shared_ptr<DVector>> build_domain_block(int width, int64_t ld) const override;
   void apply_mode_block(MfMode mode, MfBlockOperands<double> const &v) const;
   int domain_space() const override { return 1; }

@@ -59,6 +59,12 @@ public:
     for (size_t c = 0; c < x.size(); ++c)
       residual(*x[c], *b[c], *res[c]);
   }
+  // y[c] = A x[c] for every column c, each with the bits of apply (the operator term of a Krylov iteration on a block)
+  virtual void apply_block(std::vector<vector_type const *> const &x, std::vector<vector_type *> const &y) const
+  {
+    for (size_t c = 0; c < x.size(); ++c)
+      apply(*x[c], *y[c]);
+  }
   virtual std::vector<std::shared_ptr<vector_type>> build_domain_block(int width, int64_t /*ld*/) const
   {
     std::vector<std::shared_ptr<vector_type>> columns;

@@ -227,6 +227,12 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_vmult_block": (C.c_int, [vp, i32, i64, vp, vp]),
         "mfmg_hip_hierarchy_smoother_apply_block": (C.c_int, [vp, i32, i32, i64, vp, vp]),
         "mfmg_hip_hierarchy_block_info": (C.c_int, [vp, P(i64)]),
+        "mfmg_hip_hierarchy_solve_cg_block": (C.c_int, [vp, i32, i64, vp, vp, P(dbl), i32, P(i32), P(dbl), P(dbl), i32, P(i64)]),
+        "mfmg_hip_block_cg_retire": (C.c_int, [i32, P(i32), P(i32), P(i32), P(i32), P(i32)]),
+        "mfmg_hip_hierarchy_operator_apply_block": (C.c_int, [vp, i32, i32, i64, vp, vp]),
+        "mfmg_hip_block_dots": (C.c_int, [vp, i64, i32, i64, vp, vp, vp]),
+        "mfmg_hip_block_cg_direction": (C.c_int, [vp, i64, i32, i64, vp, vp, vp, vp]),
+        "mfmg_hip_block_cg_update": (C.c_int, [vp, i64, i32, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
         "mfmg_hip_hierarchy_create": (C.c_int, [vp, C.c_char_p, P(MeshDesc), C.c_char_p, P(vp)]),
         "mfmg_hip_hierarchy_destroy": (C.c_int, [vp]),
         "mfmg_hip_hierarchy_internal_numbering": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
@@ -290,7 +296,9 @@ def load() -> C.CDLL:
                    "mfmg_hip_mf_laplace_sweep_diagonal_inverse", "mfmg_hip_block_groups", "mfmg_hip_mf_laplace_block_launch",
                    "mfmg_hip_mf_laplace_block_available", "mfmg_hip_mf_laplace_set_block_tile", "mfmg_hip_mf_laplace_get_block_tile",
                    "mfmg_hip_hierarchy_apply_block", "mfmg_hip_hierarchy_vmult_block", "mfmg_hip_hierarchy_smoother_apply_block",
-                   "mfmg_hip_hierarchy_block_info", "mfmg_hip_csr_enable_node_twins", "mfmg_hip_csr_release_csr"}
+                   "mfmg_hip_hierarchy_block_info", "mfmg_hip_csr_enable_node_twins", "mfmg_hip_csr_release_csr",
+                   "mfmg_hip_hierarchy_solve_cg_block", "mfmg_hip_block_cg_retire", "mfmg_hip_hierarchy_operator_apply_block",
+                   "mfmg_hip_block_dots", "mfmg_hip_block_cg_direction", "mfmg_hip_block_cg_update"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
