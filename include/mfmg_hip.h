@@ -776,7 +776,7 @@ int mfmg_hip_hierarchy_block_info(mfmg_hip_hierarchy_t h, int64_t *fields);
  * fails returns an error and leaves nothing behind.
  *   work (may be NULL): [0] column-applications of the preconditioner, [1] of the operator -- both the sum of n_iterations --,
  *   [2] launches of mf_laplace_block_kernel, [3] slot moves (at most n_vectors).
- * Not in this driver: a block FGMRES, the FP32 preconditioner, ranks.
+ * Not in this driver: non-symmetric cycles and the FP32 preconditioner (mfmg_hip_hierarchy_solve_fgmres_block below), ranks.
  * mfmg_hip_block_cg_retire (host only): of n_active (0 .. 64) slots those with retire_flags[s] != 0 retire.  Retired slots are
  * filled in ascending order, each from the last slot that survives behind it: moves[2 i], moves[2 i + 1] = from, to (capacity
  * n_active pairs), slot_col[to] = slot_col[from]; afterwards the first n_active_out slots are the survivors.  n_moves is at most the
@@ -801,6 +801,59 @@ int mfmg_hip_block_cg_direction(mfmg_hip_context_t ctx, int64_t n, int32_t k, in
                                 const double *rz_new, const double *rz_old);
 int mfmg_hip_block_cg_update(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *P, const double *AP, double *R,
                              int64_t ldx, double *X, const int32_t *slot_col, const double *rz, const double *pap, double *rr_out);
+
+/* ---- flexible GMRES on a block of right-hand sides (additions, no change of the ABI version) ----
+ * mfmg_hip_hierarchy_solve_fgmres_block: mfmg_hip_hierarchy_solve_fgmres for every column of the blocks b and x (layout and checks
+ * of the block entry points above; restart >= 1, tolerances >= 0, preconditioner_fp32 0 or 1 -- 1 needs "fine level precision"
+ * float --, MFMG_HIP_ERROR_INVALID_ARGUMENT otherwise).  Column c of x, n_iterations[c], final_residuals[c] and the history
+ * residual_history[c * history_ld + i] are those of mfmg_hip_hierarchy_solve_fgmres(b_c, x_c, tolerances[c], max_iterations,
+ * restart, preconditioner_fp32), bit for bit, the entry recorded after a breakdown included.  Returns MFMG_HIP_ERROR_RUNTIME when
+ * any column is unconverged at max_iterations, with all outputs filled.
+ * Every column owns a SLOT of the library-owned bases: basis vector j of slot s at V + (j k + s) ld, Z likewise (k = n_vectors,
+ * ld the caller's, or n_dofs rounded up to even with "internal numbering" lexicographic, where b and x are gathered once and x is
+ * scattered once).  All live columns share the iteration count and the basis length.  Per iteration: the cycle and the operator
+ * on every maximal run of consecutive live slots (as mfmg_hip_hierarchy_vmult_block / _operator_apply_block run a block; with
+ * preconditioner_fp32 the FP32 fine level column by column), both Gram-Schmidt passes and the normalisation with one launch each
+ * for all live slots, ONE device-to-host copy and ONE stream synchronisation.  A column that converges gets x += Z y at once and
+ * leaves the live list; nothing is copied to close the gap, and the next restart cycle packs the surviving columns into the
+ * first slots by changing the slot -> column map alone (mfmg_hip_block_fgmres_plan is that plan).  A column that breaks down
+ * (h_{j+1,j} = 0) gets its update and is finished by the one-vector driver from its x and the shared iteration count.
+ * Working set, owned by the hierarchy, kept for the next solve, grown on demand: with m = max(1, min(restart, max_iterations))
+ * (2 m + 1) k ld doubles for V and Z; with preconditioner_fp32 2 k ld floats; with a permutation 2 k ld doubles for b and x;
+ * k (m + 1) 1024 + k 1024 doubles of partial sums, k (3 m + 2) doubles of coefficients, k (2 m + 1) pinned host doubles.  An
+ * allocation that fails returns MFMG_HIP_ERROR_DEVICE and leaves nothing behind.
+ *   work (may be NULL): [0] column-applications of the preconditioner, [1] of the operator inside Arnoldi steps -- both the sum
+ *   of n_iterations --, [2] launches of mf_laplace_block_kernel, [3] cycle-start residuals b - A x (one per column and cycle
+ *   start, the first included).
+ * mfmg_hip_block_fgmres_plan (host only): of n_slots (0 .. 64) slots those with live[s] != 0 work on, slot_col[s] is the column of
+ * slot s.  run_start / run_width / run_groups [n_runs]: the maximal runs of consecutive live slots in ascending order and the
+ * number of launches each is cut into; group_width [n_groups]: the widths of those launches, run after run (mfmg_hip_block_groups
+ * of each run's width); packed_col [n_packed]: the columns of the live slots in slot order -- the map of the next cycle, whose live
+ * slots are the first n_packed.  Every output array holds n_slots entries.
+ * The kernels of the driver on their own (tests; a context without a communicator).  V, Z: device blocks in the layout above with
+ * an even ld >= n and a base aligned to 16 bytes; live_slots: n_live slots of 0 .. k - 1 in ascending order (host array); slots
+ * that are not named are neither read nor written:
+ *   block_krylov_orthogonalize  w_s = vector j + 1 of slot s: twice { c = V_s^T w_s; w_s -= V_s c } against the vectors 0 .. j
+ *                       of the slot, in place; h_out[s (j + 1) + i] = the summed coefficients, norm_out[s] = ||w_s|| (device
+ *                       arrays of k (j + 1) and k doubles); v_next (may be NULL; a block of k slots, ld apart, aligned to 16
+ *                       bytes) receives w_s / ||w_s||, zeros for a zero norm, and v_next_f32 (may be NULL) its float copy.  Per
+ *                       slot the bits of mfmg_hip_krylov_orthogonalize with passes = 2.
+ *   block_krylov_combine  x_{slot_col[s]} += sum_{i <= j} y[s (j + 1) + i] Z_i of slot s for the live slots; x: a block of
+ *                       n_x_columns columns with leading dimension ldx >= n, aligned to 8 bytes; slot_col: k entries (host
+ *                       array), the live ones different columns of x.  Per slot the bits of mfmg_hip_krylov_combine. */
+int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                          const double *tolerances, int32_t max_iterations, int32_t restart,
+                                          int32_t preconditioner_fp32, int32_t *n_iterations, double *final_residuals,
+                                          double *residual_history, int32_t history_ld, int64_t *work);
+int mfmg_hip_block_fgmres_plan(int32_t n_slots, const int32_t *live, const int32_t *slot_col, int32_t *run_start, int32_t *run_width,
+                               int32_t *run_groups, int32_t *n_runs, int32_t *group_width, int32_t *n_groups, int32_t *packed_col,
+                               int32_t *n_packed);
+int mfmg_hip_block_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, int32_t j, int32_t n_live,
+                                        const int32_t *live_slots, double *V, double *v_next, float *v_next_f32, double *h_out,
+                                        double *norm_out);
+int mfmg_hip_block_krylov_combine(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, int32_t j, int32_t n_live,
+                                  const int32_t *live_slots, const int32_t *slot_col, const double *Z, const double *y,
+                                  int32_t n_x_columns, int64_t ldx, double *x);
 
 #ifdef __cplusplus
 }

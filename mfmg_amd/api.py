@@ -148,6 +148,28 @@ def block_cg_retire(retire_flags, slot_col):
     return [(int(moves[2 * i]), int(moves[2 * i + 1])) for i in range(n_moves.value)], [int(cols[i]) for i in range(n)], n_out.value
 
 
+def block_fgmres_plan(live, slot_col):
+    """The plan of one step of solve_fgmres_block for slots with the flags `live` and the slot -> column map `slot_col`: returns
+    (runs, packed) -- runs a list of (start, width, group widths) for every maximal run of consecutive live slots, packed the
+    columns of the live slots in slot order (the map of the next restart cycle).  Host only."""
+    lib = _lib.load()
+    n = len(live)
+    if len(slot_col) != n:
+        raise ValueError("one slot_col entry per slot")
+    arr = C.c_int32 * max(n, 1)
+    flags, cols = arr(*[int(bool(f)) for f in live]), arr(*[int(c) for c in slot_col])
+    start, width, groups, gw, packed = arr(), arr(), arr(), arr(), arr()
+    n_runs, n_groups, n_packed = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.mfmg_hip_block_fgmres_plan(n, flags, cols, start, width, groups, C.byref(n_runs), gw, C.byref(n_groups), packed,
+                                         C.byref(n_packed)))
+    runs, g0 = [], 0
+    for r in range(n_runs.value):
+        runs.append((int(start[r]), int(width[r]), [int(gw[g0 + g]) for g in range(groups[r])]))
+        g0 += groups[r]
+    assert g0 == n_groups.value
+    return runs, [int(packed[i]) for i in range(n_packed.value)]
+
+
 def memory_inventory() -> str:
     """Live bytes of the library's device buffers per (setup section | kind of structure), as text."""
     lib = _lib.load()
@@ -307,6 +329,46 @@ class Context:
         n, ld = x.numel(), Z.shape[1]
         assert 1 <= y.numel() <= Z.shape[0] and ld >= n
         check(self._lib.mfmg_hip_krylov_combine(self.handle, n, ld, y.numel() - 1, _dev_ptr(Z), _dev_ptr(y), _dev_ptr(x)))
+
+    # The basis kernels of Hierarchy.solve_fgmres_block on their own (tests).  A basis block is a contiguous 3-D float64 CUDA tensor
+    # of shape (vectors, k, ld): vector i of slot s is V[i, s, :n]; ld even, the base aligned to 16 bytes.  `live` names the slots
+    # the launches work on, in ascending order; the others are neither read nor written.
+    @staticmethod
+    def _basis_block(V: torch.Tensor):
+        if not isinstance(V, torch.Tensor) or V.device.type != "cuda" or V.dtype != torch.float64 or V.dim() != 3 or not V.is_contiguous():
+            raise ValueError("a basis block is a contiguous 3-D float64 CUDA tensor of shape (vectors, k, ld)")
+        return int(V.shape[0]), int(V.shape[1]), int(V.shape[2]), V.data_ptr()
+
+    def block_krylov_orthogonalize(self, n: int, V: torch.Tensor, j: int, live, v_next=None, v_next_f32=None):
+        """w_s = V[j + 1, s] is orthogonalised in place against V[0 .. j, s] for every live slot s (classical Gram-Schmidt twice,
+        one launch per pass for all of them).  Returns (h, norm): device tensors (k, j + 1) and (k,) with the summed coefficients
+        and ||w_s||, NaN where a slot is not live.  v_next (k, ld) float64 receives w_s / ||w_s|| (zeros for a zero norm),
+        v_next_f32 (k, ld) float32 its narrowed copy.  Per slot the bits of krylov_orthogonalize."""
+        nv, k, ld, pv = self._basis_block(V)
+        if not 0 <= j < nv - 1:
+            raise ValueError("the block holds no vector j + 1")
+        for t, dt in ((v_next, torch.float64), (v_next_f32, torch.float32)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (k, ld) or not t.is_contiguous() or t.device != V.device):
+                raise ValueError("v_next and v_next_f32 are contiguous (k, ld) tensors on the device of V")
+        h = torch.full((k, j + 1), float("nan"), dtype=torch.float64, device=V.device)
+        norm = torch.full((k,), float("nan"), dtype=torch.float64, device=V.device)
+        slots = (C.c_int32 * max(len(live), 1))(*[int(s) for s in live])
+        ptr = lambda t: None if t is None else t.data_ptr()
+        check(self._lib.mfmg_hip_block_krylov_orthogonalize(self.handle, int(n), k, ld, int(j), len(live), slots, pv, ptr(v_next),
+                                                            ptr(v_next_f32), h.data_ptr(), norm.data_ptr()))
+        return h, norm
+
+    def block_krylov_combine(self, n: int, Z: torch.Tensor, y: torch.Tensor, live, slot_col, X: torch.Tensor):
+        """X[slot_col[s], :n] += sum_i y[s, i] Z[i, s, :n] for every live slot s in one launch (y: (k, columns) float64 on the
+        device; X a block of its own shape and leading dimension, aligned to 8 bytes).  Per slot the bits of krylov_combine."""
+        nv, k, ld, pz = self._basis_block(Z)
+        kx, ldx, px = _block_ptr(X)
+        if y.dim() != 2 or y.shape[0] != k or not 1 <= y.shape[1] <= nv or len(slot_col) != k:
+            raise ValueError("y holds one row of at most as many coefficients as Z has vectors per slot, slot_col one entry per slot")
+        slots = (C.c_int32 * max(len(live), 1))(*[int(s) for s in live])
+        cols = (C.c_int32 * k)(*[int(c) for c in slot_col])
+        check(self._lib.mfmg_hip_block_krylov_combine(self.handle, int(n), k, ld, int(y.shape[1]) - 1, len(live), slots, cols, pz,
+                                                      _dev_ptr(y, k * int(y.shape[1])), kx, ldx, px))
 
     def cell_contraction(self, u: torch.Tensor, c: torch.Tensor, v: torch.Tensor, cell_size, variant: str = "mfma"):
         """v[m, cell] = c[cell] * sum_k K_ref[m, k] u[k, cell] (BASELINE.json configs[4]); u, v: [8, n] contiguous CUDA
@@ -1106,6 +1168,37 @@ class Hierarchy:
                                                         restart, 1 if preconditioner == "float" else 0, C.byref(it), C.byref(res),
                                                         hist.ctypes.data_as(C.POINTER(C.c_double)), len(hist)))
         return it.value, hist[: it.value + 1]
+
+    def solve_fgmres_block(self, B: torch.Tensor, X: torch.Tensor, tolerances, max_iterations: int = 1000, restart: int = 30,
+                           preconditioner: str = "double"):
+        """solve_fgmres for every row of the blocks B and X (2-D float64 tensors of shape (k, m), stride(1) == 1, one even leading
+        dimension ld = stride(0) >= n_dofs) in one call: row c of X, its iteration count and its history are those of
+        solve_fgmres(B[c], X[c], tolerances[c], max_iterations, restart, preconditioner), bit for bit -- with the non-symmetric
+        cycles and the FP32 fine level solve_cg_block cannot take.  A column that converged costs nothing further.
+        Returns (iterations, histories, work): k ints, k arrays, and a dict with the column-applications of the preconditioner
+        and of the operator inside Arnoldi steps (each the sum of the iterations), the launches of the block kernel and the
+        cycle-start residuals formed.  Raises the error of solve_fgmres when a column is unconverged at max_iterations; X and
+        `last_block_solve` (the same triple, with the final residuals as `residuals` in the dict) are filled."""
+        if preconditioner not in ("double", "float"):
+            raise _lib.MfmgInvalidArgument('preconditioner must be "double" or "float"')
+        k, ld, pb = _block_ptr(B)
+        px = _same_block(k, ld, X)
+        tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tolerances, dtype=np.float64), (k,)))
+        its = np.zeros(k, dtype=np.int32)
+        res = np.zeros(k)
+        hist = np.zeros((k, max(max_iterations, 0) + 1))
+        work = np.zeros(4, dtype=np.int64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        status = self._lib.mfmg_hip_hierarchy_solve_fgmres_block(self.handle, k, ld, pb, px, dp(tol), max_iterations, restart,
+                                                                 1 if preconditioner == "float" else 0,
+                                                                 its.ctypes.data_as(C.POINTER(C.c_int32)), dp(res), dp(hist),
+                                                                 hist.shape[1], work.ctypes.data_as(C.POINTER(C.c_int64)))
+        out = ([int(i) for i in its], [hist[c, : its[c] + 1].copy() for c in range(k)],
+               {"preconditioner_columns": int(work[0]), "operator_columns": int(work[1]), "block_launches": int(work[2]),
+                "cycle_starts": int(work[3]), "residuals": [float(r) for r in res]})
+        self.last_block_solve = out
+        check(status)
+        return out
 
     def operator_tile(self):
         a, b, c = C.c_int(), C.c_int(), C.c_int()

@@ -7,6 +7,7 @@
 
 #include "amge_lanczos.hpp"
 #include "block_krylov.hpp"
+#include "block_krylov_basis.hpp"
 #include "cell_contraction.hpp"
 #include "dof_permutation.hpp"
 #include "halo_transport.hpp"
@@ -207,6 +208,138 @@ struct BlockCgWorkspace
   ~BlockCgWorkspace() { release_host(); }
 };
 
+// The host arithmetic of flexible GMRES for ONE right-hand side, used by the one-vector and the block driver alike: the
+// triangular factor of the Hessenberg matrix (column-major with m + 1 rows), the Givens rotations, the rotated right-hand side g,
+// the breakdown flag and the back-substitution for y.
+struct FgmresColumn
+{
+  int m;
+  std::vector<double> R, cs, sn, g;
+  int k = 0; // columns of this cycle
+  bool breakdown = false;
+  explicit FgmresColumn(int m) : m(m), R((size_t)(m + 1) * m), cs(m), sn(m), g(m + 1) {}
+  void begin_cycle(double residual)
+  {
+    std::fill(g.begin(), g.end(), 0.);
+    g[0] = residual;
+    k = 0;
+    breakdown = false;
+  }
+  // where the caller puts h_0 .. h_j, ||w|| of step j
+  double *column(int j) { return &R[(size_t)j * (m + 1)]; }
+  // the column of step k goes through the rotations; returns |g_{k+1}|, the residual norm of the least-squares problem
+  double rotate()
+  {
+    const int j = k;
+    double *const c = column(j);
+    for (int i = 0; i < j; ++i)
+    {
+      const double t = cs[i] * c[i] + sn[i] * c[i + 1];
+      c[i + 1] = -sn[i] * c[i] + cs[i] * c[i + 1];
+      c[i] = t;
+    }
+    // h_{j+1,j} = 0: the Krylov space is exhausted -- v_{j+1} is zero (basis_scale_store), the cycle ends with the update
+    breakdown = c[j + 1] == 0.;
+    const double d = std::hypot(c[j], c[j + 1]);
+    cs[j] = d > 0. ? c[j] / d : 1.;
+    sn[j] = d > 0. ? c[j + 1] / d : 0.;
+    c[j] = d;
+    c[j + 1] = 0.;
+    g[j + 1] = -sn[j] * g[j];
+    g[j] = cs[j] * g[j];
+    ++k;
+    return std::abs(g[j + 1]);
+  }
+  // R y = g over the k columns of this cycle (a zero pivot -- a singular Hessenberg matrix -- contributes nothing: no division by zero)
+  void solve(double *y) const
+  {
+    for (int i = k - 1; i >= 0; --i)
+    {
+      double s = g[i];
+      for (int l = i + 1; l < k; ++l)
+        s -= R[(size_t)l * (m + 1) + i] * y[l];
+      const double pivot = R[(size_t)i * (m + 1) + i];
+      y[i] = pivot != 0. ? s / pivot : 0.;
+    }
+  }
+};
+
+// What mfmg_hip_hierarchy_solve_fgmres_block keeps between solves, for `slots` columns and restart cycles of `columns` vectors:
+// the bases V [(columns + 1) x slots x ld] and Z [columns x slots x ld] (block_krylov_basis.hpp), the float vectors around an FP32
+// preconditioner [slots x ld] twice, with "internal numbering" lexicographic the gathered b and x, the scratch of the launches,
+// per slot the Hessenberg column (columns + 1 doubles) and y (columns doubles) on the device and their pinned host mirror.
+// Grown on demand, never shrunk; a failed allocation leaves the workspace EMPTY.
+struct BlockFgmresWorkspace
+{
+  int64_t ld = 0;
+  int slots = 0, columns = 0;
+  bool permuted = false, fp32 = false;
+  DeviceBuffer<double> V, Z, B, X, coefficients, y;
+  DeviceBuffer<float> v_f32, z_f32;
+  std::unique_ptr<block_krylov_basis::Scratch> scratch;
+  double *host = nullptr; // pinned: slots x (columns + 1) coefficients, then slots x columns entries of y
+  double *host_y() const { return host + (size_t)slots * (columns + 1); }
+  void reserve(int64_t want_ld, int k, int m, bool permute, bool with_fp32, hipStream_t stream)
+  {
+    if (want_ld == ld && k <= slots && m <= columns && (!permute || permuted) && (!with_fp32 || fp32))
+      return;
+    MemoryKind kind("block FGMRES working set");
+    const bool same = want_ld == ld;
+    const int want_slots = std::max(k, same ? slots : 0), want_columns = std::max(m, same ? columns : 0);
+    permute = permute || (same && permuted);
+    with_fp32 = with_fp32 || (same && fp32);
+    release(); // (before the larger one is allocated)
+    const size_t block = (size_t)want_ld * want_slots;
+    // (zeros: the tails between the columns are never written, and a cycle that reads its start vector finds numbers)
+    auto zeros = [&](DeviceBuffer<double> &b, size_t count) {
+      b.resize(count);
+      MFMG_HIP_CHECK(hipMemsetAsync(b.data(), 0, count * sizeof(double), stream));
+    };
+    zeros(V, block * ((size_t)want_columns + 1));
+    zeros(Z, block * (size_t)want_columns);
+    if (permute)
+    {
+      zeros(B, block);
+      zeros(X, block);
+    }
+    if (with_fp32)
+    {
+      v_f32.resize(block);
+      z_f32.resize(block);
+      MFMG_HIP_CHECK(hipMemsetAsync(v_f32.data(), 0, block * sizeof(float), stream));
+      MFMG_HIP_CHECK(hipMemsetAsync(z_f32.data(), 0, block * sizeof(float), stream));
+    }
+    scratch.reset(new block_krylov_basis::Scratch(want_slots, want_columns + 1));
+    coefficients.resize((size_t)want_slots * (want_columns + 1));
+    y.resize((size_t)want_slots * want_columns);
+    MFMG_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&host), (size_t)want_slots * (2 * (size_t)want_columns + 1) * sizeof(double)));
+    ld = want_ld; // only now: everything above stands
+    slots = want_slots;
+    columns = want_columns;
+    permuted = permute;
+    fp32 = with_fp32;
+  }
+  void release()
+  {
+    ld = 0;
+    slots = columns = 0;
+    permuted = fp32 = false;
+    release_host();
+    for (DeviceBuffer<double> *b : {&V, &Z, &B, &X, &coefficients, &y})
+      b->release();
+    v_f32.release();
+    z_f32.release();
+    scratch.reset();
+  }
+  void release_host()
+  {
+    if (host)
+      (void)hipHostFree(host);
+    host = nullptr;
+  }
+  ~BlockFgmresWorkspace() { release_host(); }
+};
+
 struct mfmg_hip_hierarchy_s
 {
   HipHandle *handle = nullptr;
@@ -228,6 +361,7 @@ struct mfmg_hip_hierarchy_s
   DeviceBuffer<float> work_f32[2];
   KrylovWorkspace krylov;
   BlockCgWorkspace block_cg;
+  BlockFgmresWorkspace block_fgmres;
   // block entry points: the permuted columns of one group (b, x) and what the last block call did
   DeviceBuffer<double> block_work[2];
   int64_t block_info[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0};
@@ -2221,6 +2355,191 @@ int mfmg_hip_hierarchy_operator_apply_block(mfmg_hip_hierarchy_t h, int32_t leve
 // then on the host already.  EVERY control decision below -- convergence, breakdown, restart, the end of the iteration -- is
 // taken from all-reduced values alone (`res`, the column, the iteration count), so all ranks take the same branch: a rank that
 // left the loop by itself would leave the others waiting in the next exchange.
+namespace
+{
+struct FgmresOutcome
+{
+  int iterations = 0;
+  double residual = 0.;
+  bool converged = false;
+  int64_t cycle_starts = 0; // residuals b - A x formed: the first one and one per restart / breakdown
+};
+
+// The iteration of mfmg_hip_hierarchy_solve_fgmres on vectors in the numbering the hierarchy runs in (`b_run`, `x_run`), with
+// restart cycles of m columns, from the iteration count `it_start`: the state at the start of a cycle is x and the count alone, so
+// a solve that is taken up at a cycle start (the block driver hands over a column that broke down) goes on with the bits of the
+// solve that was never interrupted.  history[it] receives the residual of iteration it (it < history_len), history[it_start]
+// that of the cycle start.
+extern "C++" FgmresOutcome fgmres_run(mfmg_hip_hierarchy_t h, const double *b_run, double *x_run, double tolerance, int max_iterations,
+                                      int m, bool fp32, int it_start, double *residual_history, int history_len)
+{
+  HipHandle &handle = *h->handle;
+  const int64_t n = level_size(h, 0);
+  KrylovWorkspace &ws = h->krylov;
+  try
+  {
+    ws.reserve(n, m, fp32);
+  }
+  catch (...)
+  {
+    ws.release();
+    (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
+    throw;
+  }
+  const int64_t ld = ws.ld;
+  krylov::Scratch &scratch = *ws.scratch;
+  double *const V = ws.V.data(), *const Z = ws.Z.data(), *const hcol = ws.coefficients.data(), *const y_dev = hcol + ws.columns + 1;
+  double *const y_host = ws.host + ws.columns + 1;
+  float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
+  auto op = h->hierarchy->levels()[0].get_operator();
+  const bool distributed = handle.comm.enabled();
+  krylov::OwnedBox box;
+  if (distributed)
+  {
+    auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
+    const int space = hop ? hop->domain_space() : 0;
+    if (space <= 0 || !handle.comm.spaces[space].configured())
+      throw std::runtime_error("the fine operator of a distributed run has no halo space");
+    if (!handle.comm.transport)
+      throw std::runtime_error("no halo transport was registered with the context");
+    box = krylov::OwnedBox(handle.comm.spaces[space]);
+    if (box.n_local() != n)
+      throw std::runtime_error("internal: the fine halo space does not describe the fine vectors");
+  }
+  // `count` doubles at `dev` summed over the ranks: to the host (ws.host), one all-reduce, back to `dev`; the sums stay in ws.host
+  auto allreduce = [&](double *dev, int count) {
+    MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+    handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
+    MFMG_HIP_CHECK(hipMemcpyAsync(dev, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
+  };
+  // ||w||^2 over the owned entries of all ranks from this rank's s.norm_partials: on the device (scratch.norm_squared) and returned
+  auto norm_squared_of_all = [&] {
+    krylov::basis_norm_finish(handle, scratch, box);
+    allreduce(scratch.norm_squared.data(), 1);
+    return ws.host[0];
+  };
+  DVector bv(handle, n, const_cast<double *>(b_run)), xv(handle, n, x_run);
+  auto fetch = [&](int count) { // the first `count` device coefficients: the one round trip of an iteration
+    MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, hcol, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+  };
+  // v_0 = r / ||r|| with r = b - A x (and its float copy); returns ||r||
+  auto start_cycle = [&] {
+    DVector r(handle, n, V);
+    op->apply(xv, r);
+    r.sadd(-1., 1., bv);
+    if (distributed)
+    {
+      krylov::basis_norm_partials(handle, scratch, box, V);
+      const double norm = std::sqrt(norm_squared_of_all());
+      krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), V, V, nullptr);
+      // (the whole local vector: what its ghost entries hold is exchanged over by the FP32 level where it reads them)
+      if (fp32)
+        vec::narrow(handle, n, V, v_f32);
+      return norm;
+    }
+    krylov::basis_norm_partials(handle, scratch, n, V);
+    krylov::basis_scale_store(handle, scratch, n, V, V, v_f32, hcol);
+    fetch(1);
+    return ws.host[0];
+  };
+  auto precondition = [&](int j) { // z_j = M^-1 v_j, from a zero start whatever "is preconditioner" says
+    const bool zero_first = !h->hierarchy->is_preconditioner();
+    if (fp32)
+    {
+      if (zero_first)
+        MFMG_HIP_CHECK(hipMemsetAsync(ws.z_f32.data(), 0, sizeof(float) * n, handle.stream));
+      h->fine_f32->apply(v_f32, ws.z_f32.data());
+      vec::widen(handle, n, ws.z_f32.data(), Z + j * ld);
+      return;
+    }
+    DVector vj(handle, n, V + j * ld), zj(handle, n, Z + j * ld);
+    if (zero_first)
+      zj = 0.;
+    h->hierarchy->vmult(zj, vj);
+  };
+  auto record = [&](int k, double v) {
+    if (residual_history && k < history_len)
+      residual_history[k] = v;
+  };
+  FgmresOutcome out;
+  double res = start_cycle();
+  ++out.cycle_starts;
+  int it = it_start;
+  record(it, res);
+  bool converged = res <= tolerance;
+  FgmresColumn col(m);
+  while (!converged && it < max_iterations)
+  {
+    col.begin_cycle(res);
+    while (col.k < m && it < max_iterations && !converged && !col.breakdown)
+    {
+      const int j = col.k;
+      precondition(j);
+      double *const w = V + (int64_t)(j + 1) * ld;
+      {
+        DVector zj(handle, n, Z + j * ld), wv(handle, n, w);
+        op->apply(zj, wv);
+      }
+      double *const c = col.column(j);
+      if (distributed)
+      {
+        // the column h_0 .. h_j, ||w|| is summed over the ranks on its way: no fetch
+        double *const pc = scratch.pass_coefficients.data();
+        for (int pass = 0; pass < 2; ++pass)
+        {
+          krylov::basis_dots(handle, scratch, box, ld, j + 1, V, w, pc, pc, false);
+          allreduce(pc, j + 1);
+          for (int i = 0; i <= j; ++i)
+            c[i] = pass == 0 ? ws.host[i] : c[i] + ws.host[i];
+          krylov::basis_update(handle, scratch, box, ld, j + 1, V, pc, w, pass == 1);
+        }
+        c[j + 1] = std::sqrt(norm_squared_of_all());
+        krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), w, w, nullptr);
+        if (fp32)
+          vec::narrow(handle, n, w, v_f32);
+      }
+      else
+      {
+        for (int pass = 0; pass < 2; ++pass)
+        {
+          krylov::basis_dots(handle, scratch, n, ld, j + 1, V, w, scratch.pass_coefficients.data(), hcol, pass == 1);
+          krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass == 1);
+        }
+        krylov::basis_scale_store(handle, scratch, n, w, w, v_f32, hcol + j + 1);
+        fetch(j + 2);
+        std::copy(ws.host, ws.host + j + 2, c);
+      }
+      res = col.rotate();
+      ++it;
+      // a breakdown is not taken at its word (a singular Hessenberg matrix also gives |g_{j+1}| = 0): the cycle ends, and the
+      // residual recomputed below is what is recorded and tested
+      if (!col.breakdown)
+        record(it, res);
+      converged = !col.breakdown && res <= tolerance;
+    }
+    col.solve(y_host);
+    MFMG_HIP_CHECK(hipMemcpyAsync(y_dev, y_host, sizeof(double) * col.k, hipMemcpyHostToDevice, handle.stream));
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (y_host is written again by the next cycle / the next solve)
+    krylov::basis_combine(handle, n, ld, col.k, Z, y_dev, x_run);
+    // after a restart and after a breakdown the residual is the true one, recomputed
+    if (!converged && (it < max_iterations || col.breakdown))
+    {
+      res = start_cycle();
+      ++out.cycle_starts;
+      converged = res <= tolerance;
+      if (col.breakdown)
+        record(it, res);
+    }
+  }
+  out.iterations = it;
+  out.residual = res;
+  out.converged = converged;
+  return out;
+}
+} // namespace
+
 int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance, int32_t max_iterations,
                                     int32_t restart, int32_t preconditioner_fp32, int32_t *n_iterations, double *final_residual,
                                     double *residual_history, int32_t history_len)
@@ -2230,55 +2549,9 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
     require(tolerance >= 0. && max_iterations >= 0, "bad stopping criterion");
     require(restart >= 1, "the restart length must be at least 1");
     require(preconditioner_fp32 == 0 || preconditioner_fp32 == 1, "preconditioner_fp32 must be 0 or 1");
-    HipHandle &handle = *h->handle;
     const bool fp32 = preconditioner_fp32 != 0;
     require(!fp32 || h->fine_f32 != nullptr, "preconditioner_fp32 needs a hierarchy built with \"fine level precision\" float");
-    const int64_t n = level_size(h, 0);
     const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
-    KrylovWorkspace &ws = h->krylov;
-    try
-    {
-      ws.reserve(n, m, fp32);
-    }
-    catch (...)
-    {
-      ws.release();
-      (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
-      throw;
-    }
-    const int64_t ld = ws.ld;
-    krylov::Scratch &scratch = *ws.scratch;
-    double *const V = ws.V.data(), *const Z = ws.Z.data(), *const hcol = ws.coefficients.data(), *const y_dev = hcol + ws.columns + 1;
-    double *const y_host = ws.host + ws.columns + 1;
-    float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
-    auto op = h->hierarchy->levels()[0].get_operator();
-    const bool distributed = handle.comm.enabled();
-    krylov::OwnedBox box;
-    if (distributed)
-    {
-      auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
-      const int space = hop ? hop->domain_space() : 0;
-      if (space <= 0 || !handle.comm.spaces[space].configured())
-        throw std::runtime_error("the fine operator of a distributed run has no halo space");
-      if (!handle.comm.transport)
-        throw std::runtime_error("no halo transport was registered with the context");
-      box = krylov::OwnedBox(handle.comm.spaces[space]);
-      if (box.n_local() != n)
-        throw std::runtime_error("internal: the fine halo space does not describe the fine vectors");
-    }
-    // `count` doubles at `dev` summed over the ranks: to the host (ws.host), one all-reduce, back to `dev`; the sums stay in ws.host
-    auto allreduce = [&](double *dev, int count) {
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-      handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
-      MFMG_HIP_CHECK(hipMemcpyAsync(dev, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
-    };
-    // ||w||^2 over the owned entries of all ranks from this rank's s.norm_partials: on the device (scratch.norm_squared) and returned
-    auto norm_squared_of_all = [&] {
-      krylov::basis_norm_finish(handle, scratch, box);
-      allreduce(scratch.norm_squared.data(), 1);
-      return ws.host[0];
-    };
     // "internal numbering" lexicographic: as in mfmg_hip_hierarchy_solve_cg -- b and x are gathered once, the basis, the operator
     // and the preconditioner live in the internal numbering, x is scattered once: two launches of the permutation per solve
     double const *b_run = b;
@@ -2289,153 +2562,391 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
       b_run = h->workspace(0);
       x_run = h->workspace(1);
     }
-    DVector bv(handle, n, const_cast<double *>(b_run)), xv(handle, n, x_run);
-    auto fetch = [&](int count) { // the first `count` device coefficients: the one round trip of an iteration
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, hcol, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-    };
-    // v_0 = r / ||r|| with r = b - A x (and its float copy); returns ||r||
-    auto start_cycle = [&] {
-      DVector r(handle, n, V);
-      op->apply(xv, r);
-      r.sadd(-1., 1., bv);
-      if (distributed)
-      {
-        krylov::basis_norm_partials(handle, scratch, box, V);
-        const double norm = std::sqrt(norm_squared_of_all());
-        krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), V, V, nullptr);
-        // (the whole local vector: what its ghost entries hold is exchanged over by the FP32 level where it reads them)
-        if (fp32)
-          vec::narrow(handle, n, V, v_f32);
-        return norm;
-      }
-      krylov::basis_norm_partials(handle, scratch, n, V);
-      krylov::basis_scale_store(handle, scratch, n, V, V, v_f32, hcol);
-      fetch(1);
-      return ws.host[0];
-    };
-    auto precondition = [&](int j) { // z_j = M^-1 v_j, from a zero start whatever "is preconditioner" says
-      const bool zero_first = !h->hierarchy->is_preconditioner();
-      if (fp32)
-      {
-        if (zero_first)
-          MFMG_HIP_CHECK(hipMemsetAsync(ws.z_f32.data(), 0, sizeof(float) * n, handle.stream));
-        h->fine_f32->apply(v_f32, ws.z_f32.data());
-        vec::widen(handle, n, ws.z_f32.data(), Z + j * ld);
-        return;
-      }
-      DVector vj(handle, n, V + j * ld), zj(handle, n, Z + j * ld);
-      if (zero_first)
-        zj = 0.;
-      h->hierarchy->vmult(zj, vj);
-    };
-    auto record = [&](int k, double v) {
-      if (residual_history && k < history_len)
-        residual_history[k] = v;
-    };
-    double res = start_cycle();
-    int it = 0;
-    record(0, res);
-    bool converged = res <= tolerance;
-    // the triangular factor of the Hessenberg matrix, column-major with m + 1 rows, the rotations and the rotated right-hand side
-    std::vector<double> R((size_t)(m + 1) * m), cs(m), sn(m), g(m + 1);
-    while (!converged && it < max_iterations)
-    {
-      std::fill(g.begin(), g.end(), 0.);
-      g[0] = res;
-      int k = 0; // columns of this cycle
-      bool breakdown = false;
-      while (k < m && it < max_iterations && !converged && !breakdown)
-      {
-        const int j = k;
-        precondition(j);
-        double *const w = V + (int64_t)(j + 1) * ld;
-        {
-          DVector zj(handle, n, Z + j * ld), wv(handle, n, w);
-          op->apply(zj, wv);
-        }
-        double *const c = &R[(size_t)j * (m + 1)];
-        if (distributed)
-        {
-          // the column h_0 .. h_j, ||w|| is summed over the ranks on its way: no fetch
-          double *const pc = scratch.pass_coefficients.data();
-          for (int pass = 0; pass < 2; ++pass)
-          {
-            krylov::basis_dots(handle, scratch, box, ld, j + 1, V, w, pc, pc, false);
-            allreduce(pc, j + 1);
-            for (int i = 0; i <= j; ++i)
-              c[i] = pass == 0 ? ws.host[i] : c[i] + ws.host[i];
-            krylov::basis_update(handle, scratch, box, ld, j + 1, V, pc, w, pass == 1);
-          }
-          c[j + 1] = std::sqrt(norm_squared_of_all());
-          krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), w, w, nullptr);
-          if (fp32)
-            vec::narrow(handle, n, w, v_f32);
-        }
-        else
-        {
-          for (int pass = 0; pass < 2; ++pass)
-          {
-            krylov::basis_dots(handle, scratch, n, ld, j + 1, V, w, scratch.pass_coefficients.data(), hcol, pass == 1);
-            krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass == 1);
-          }
-          krylov::basis_scale_store(handle, scratch, n, w, w, v_f32, hcol + j + 1);
-          fetch(j + 2);
-          std::copy(ws.host, ws.host + j + 2, c);
-        }
-        for (int i = 0; i < j; ++i)
-        {
-          const double t = cs[i] * c[i] + sn[i] * c[i + 1];
-          c[i + 1] = -sn[i] * c[i] + cs[i] * c[i + 1];
-          c[i] = t;
-        }
-        // h_{j+1,j} = 0: the Krylov space is exhausted -- v_{j+1} is zero (basis_scale_store), the cycle ends with the update
-        breakdown = c[j + 1] == 0.;
-        const double d = std::hypot(c[j], c[j + 1]);
-        cs[j] = d > 0. ? c[j] / d : 1.;
-        sn[j] = d > 0. ? c[j + 1] / d : 0.;
-        c[j] = d;
-        c[j + 1] = 0.;
-        g[j + 1] = -sn[j] * g[j];
-        g[j] = cs[j] * g[j];
-        res = std::abs(g[j + 1]);
-        ++k;
-        ++it;
-        // a breakdown is not taken at its word (a singular Hessenberg matrix also gives |g_{j+1}| = 0): the cycle ends, and the
-        // residual recomputed below is what is recorded and tested
-        if (!breakdown)
-          record(it, res);
-        converged = !breakdown && res <= tolerance;
-      }
-      // x += Z y with R y = g (a zero pivot -- a singular Hessenberg matrix -- contributes nothing: no division by zero)
-      for (int i = k - 1; i >= 0; --i)
-      {
-        double s = g[i];
-        for (int l = i + 1; l < k; ++l)
-          s -= R[(size_t)l * (m + 1) + i] * y_host[l];
-        const double pivot = R[(size_t)i * (m + 1) + i];
-        y_host[i] = pivot != 0. ? s / pivot : 0.;
-      }
-      MFMG_HIP_CHECK(hipMemcpyAsync(y_dev, y_host, sizeof(double) * k, hipMemcpyHostToDevice, handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (y_host is written again by the next cycle / the next solve)
-      krylov::basis_combine(handle, n, ld, k, Z, y_dev, x_run);
-      // after a restart and after a breakdown the residual is the true one, recomputed
-      if (!converged && (it < max_iterations || breakdown))
-      {
-        res = start_cycle();
-        converged = res <= tolerance;
-        if (breakdown)
-          record(it, res);
-      }
-    }
+    const FgmresOutcome out = fgmres_run(h, b_run, x_run, tolerance, max_iterations, m, fp32, 0, residual_history, history_len);
     if (n_iterations)
-      *n_iterations = it;
+      *n_iterations = out.iterations;
     if (final_residual)
-      *final_residual = res;
+      *final_residual = out.residual;
     if (h->perm)
       h->perm->scatter(static_cast<double const *>(x_run), x);
-    if (!converged)
+    if (!out.converged)
       throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
+  });
+}
+
+// mfmg_hip_hierarchy_solve_fgmres on a block of right-hand sides.  Every column owns a slot of the bases (block_krylov_basis.hpp);
+// all live columns share the iteration count and, inside a restart cycle, the basis length j.  Per iteration: the cycle and the
+// operator on every maximal run of consecutive live slots (Hierarchy::apply_block, Operator::apply_block), classical Gram-Schmidt
+// twice and scale_store with one launch each for all live slots, ONE device-to-host copy of their j + 2 coefficients and ONE
+// synchronisation, then the rotations per column on the host (FgmresColumn).  A column that converges inside a cycle gets its
+// x += Z y at once and leaves the live list; no basis vector is ever copied -- the slots left behind stay where they are until
+// the cycle ends, and the next cycle packs the surviving columns into the first slots by changing the slot -> column map alone
+// (block_krylov_basis::plan).  A column that breaks down ends its cycle by itself and would be out of step: it gets its update,
+// and fgmres_run finishes it from (x, it) -- all a cycle start knows.  Every kernel gives a slot the bits the one-vector driver
+// gives its vector, so x, the count, the final residual and the history of a column are those of mfmg_hip_hierarchy_solve_fgmres.
+int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                          const double *tolerances, int32_t max_iterations, int32_t restart, int32_t preconditioner_fp32,
+                                          int32_t *n_iterations, double *final_residuals, double *residual_history, int32_t history_ld,
+                                          int64_t *work)
+{
+  namespace bkb = block_krylov_basis;
+  return guarded([&] {
+    check_block(h, 0, n_vectors, ld, b, x);
+    require(tolerances != nullptr, "null argument");
+    require(max_iterations >= 0, "bad stopping criterion");
+    for (int c = 0; c < n_vectors; ++c)
+      require(tolerances[c] >= 0., "bad stopping criterion");
+    require(restart >= 1, "the restart length must be at least 1");
+    require(preconditioner_fp32 == 0 || preconditioner_fp32 == 1, "preconditioner_fp32 must be 0 or 1");
+    require(residual_history == nullptr || history_ld >= 0, "bad history length");
+    const bool fp32 = preconditioner_fp32 != 0;
+    require(!fp32 || h->fine_f32 != nullptr, "preconditioner_fp32 needs a hierarchy built with \"fine level precision\" float");
+    HipHandle &handle = *h->handle;
+    const int k = n_vectors;
+    const int64_t n = level_size(h, 0);
+    const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
+    auto op = h->hierarchy->levels()[0].get_operator();
+    // "internal numbering" lexicographic: b and x are gathered once into library blocks and x is scattered once, as in
+    // mfmg_hip_hierarchy_solve_cg_block.  Otherwise the bases take the caller's leading dimension, so that the operator runs from
+    // the caller's x into the basis on one block layout.
+    const bool permute = (bool)h->perm;
+    const int64_t wld = permute ? n + (n & 1) : ld;
+    BlockFgmresWorkspace &ws = h->block_fgmres;
+    try
+    {
+      ws.reserve(wld, k, m, permute, fp32, handle.stream);
+    }
+    catch (...)
+    {
+      ws.release();
+      (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
+      throw;
+    }
+    double const *b_run = b;
+    double *x_run = x;
+    if (permute)
+    {
+      for (int c = 0; c < k; ++c)
+        h->perm->gather2(b + c * ld, static_cast<double const *>(x + c * ld), ws.B.data() + c * wld, ws.X.data() + c * wld);
+      b_run = ws.B.data();
+      x_run = ws.X.data();
+    }
+    bkb::Scratch &scratch = *ws.scratch;
+    const bkb::Basis V{n, wld, (int64_t)k * wld, ws.V.data()}, Z{n, wld, (int64_t)k * wld, ws.Z.data()};
+    const int64_t cstride = ws.columns + 1, ystride = ws.columns;
+    double *const coef = ws.coefficients.data();
+    float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
+    const bool zero_first = !h->hierarchy->is_preconditioner(); // the cycle then starts from what z holds: from zero, as in fgmres_run
+    const int64_t launches_before = block_kernel_launches(h);
+    int64_t preconditioner_columns = 0, operator_columns = 0, cycle_starts = 0;
+
+    std::vector<int32_t> live(k, 1), slot_col(k), run_start(k), run_width(k), run_groups(k), group_width(k), packed(k);
+    for (int s = 0; s < k; ++s)
+      slot_col[s] = s;
+    int n_live = k;
+    std::vector<double> res(k, 0.);
+    std::vector<int32_t> iterations(k, 0);
+    std::vector<char> converged(k, 0);
+    std::vector<FgmresColumn> columns(k, FgmresColumn(m));
+
+    auto record = [&](int c, int it, double v) {
+      if (residual_history && it < history_ld)
+        residual_history[(int64_t)c * history_ld + it] = v;
+    };
+    auto live_list = [&] {
+      bkb::SlotList l;
+      for (int s = 0; s < k; ++s)
+        if (live[s])
+        {
+          l.id[l.count] = s;
+          l.col[l.count++] = slot_col[s];
+        }
+      return l;
+    };
+    // the first `count` coefficients of every slot in `l`: the one round trip of an iteration.  One copy from the first to the
+    // last of the slots; the coefficients of slot s are then at fetched(l, s)
+    auto fetch = [&](bkb::SlotList const &l, int count) {
+      const int first = l.id[0], last = l.id[l.count - 1];
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, coef + first * cstride, sizeof(double) * ((last - first) * cstride + count), hipMemcpyDeviceToHost,
+                                    handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+    };
+    auto fetched = [&](bkb::SlotList const &l, int s) { return ws.host + (s - l.id[0]) * cstride; };
+    // `run(start, width)` for every maximal run of consecutive live slots (with `by_column`: whose columns follow each other too)
+    auto for_runs = [&](bool by_column, std::function<void(int, int)> const &run) {
+      int32_t n_groups = 0, n_packed = 0;
+      const int n_runs = bkb::plan(k, live.data(), slot_col.data(), run_start.data(), run_width.data(), run_groups.data(), group_width.data(),
+                                   &n_groups, packed.data(), &n_packed);
+      for (int r = 0; r < n_runs; ++r)
+      {
+        int s0 = run_start[r];
+        const int end = s0 + run_width[r];
+        for (int s = s0 + 1; s <= end; ++s)
+          if (s == end || (by_column && slot_col[s] != slot_col[s - 1] + 1))
+          {
+            run(s0, s - s0);
+            s0 = s;
+          }
+      }
+    };
+    // v_0 = r / ||r|| with r = b - A x for every live slot (and its float copy); res[column] = ||r||
+    auto start_cycle = [&] {
+      const bkb::SlotList l = live_list();
+      for_runs(true, [&](int s0, int width) {
+        BlockViews xv(handle, n, wld, width, x_run + slot_col[s0] * wld), rv(handle, n, wld, width, V.vector(0, s0));
+        op->apply_block(xv.cptr, rv.ptr);
+      });
+      for (int i = 0; i < l.count; ++i)
+        vec::sadd<double>(handle, n, -1., 1., b_run + l.col[i] * wld, V.vector(0, l.id[i]));
+      bkb::norm_partials(handle, scratch, l, n, wld, V.vector(0));
+      bkb::scale_store(handle, scratch, l, n, wld, V.vector(0), V.vector(0), v_f32, coef, cstride);
+      fetch(l, 1);
+      for (int i = 0; i < l.count; ++i)
+        res[l.col[i]] = fetched(l, l.id[i])[0];
+      cycle_starts += l.count;
+    };
+    // z_j = M^-1 v_j on the live slots, from a zero start whatever "is preconditioner" says
+    auto precondition = [&](int j) {
+      if (fp32)
+      {
+        // (no FP32 block kernel: column by column, on the float copy scale_store left)
+        for (int s = 0; s < k; ++s)
+          if (live[s])
+          {
+            float *const zf = ws.z_f32.data() + s * wld;
+            if (zero_first)
+              MFMG_HIP_CHECK(hipMemsetAsync(zf, 0, sizeof(float) * n, handle.stream));
+            h->fine_f32->apply(v_f32 + s * wld, zf);
+            vec::widen(handle, n, zf, Z.vector(j, s));
+          }
+        return;
+      }
+      for_runs(false, [&](int s0, int width) {
+        if (zero_first)
+          MFMG_HIP_CHECK(hipMemsetAsync(Z.vector(j, s0), 0, sizeof(double) * (size_t)wld * width, handle.stream));
+        BlockViews vv(handle, n, wld, width, V.vector(j, s0)), zv(handle, n, wld, width, Z.vector(j, s0));
+        timer_enter_subsection(h->timer, "Apply");
+        try
+        {
+          h->hierarchy->apply_block(vv.cptr, zv.ptr);
+        }
+        catch (...)
+        {
+          timer_leave_subsection(h->timer);
+          throw;
+        }
+        timer_leave_subsection(h->timer);
+      });
+    };
+    // x_col += Z y over the j columns of this cycle for the slots of `l`, each with its own y
+    auto combine = [&](bkb::SlotList const &l, int j) {
+      const int first = l.id[0], last = l.id[l.count - 1];
+      double *const y_host = ws.host_y();
+      for (int i = 0; i < l.count; ++i)
+        columns[l.col[i]].solve(y_host + l.id[i] * ystride);
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.y.data() + first * ystride, y_host + first * ystride, sizeof(double) * ((last - first) * ystride + j),
+                                    hipMemcpyHostToDevice, handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the host copy of y is written again by the next retirement)
+      bkb::combine(handle, l, Z, j, ws.y.data(), ystride, x_run, wld);
+    };
+    auto retire_converged_at_start = [&] {
+      for (int s = 0; s < k; ++s)
+        if (live[s] && res[slot_col[s]] <= tolerances[slot_col[s]])
+        {
+          converged[slot_col[s]] = 1;
+          live[s] = 0;
+          --n_live;
+        }
+    };
+
+    start_cycle();
+    for (int c = 0; c < k; ++c)
+      record(c, 0, res[c]);
+    retire_converged_at_start();
+    int it = 0;
+    while (n_live > 0 && it < max_iterations)
+    {
+      for (int s = 0; s < k; ++s)
+        if (live[s])
+          columns[slot_col[s]].begin_cycle(res[slot_col[s]]);
+      int j = 0;
+      for (; j < m && it < max_iterations && n_live > 0; ++j)
+      {
+        const bkb::SlotList l = live_list();
+        precondition(j);
+        preconditioner_columns += l.count;
+        for_runs(false, [&](int s0, int width) {
+          BlockViews zv(handle, n, wld, width, Z.vector(j, s0)), wv(handle, n, wld, width, V.vector(j + 1, s0));
+          op->apply_block(zv.cptr, wv.ptr);
+        });
+        operator_columns += l.count;
+        double *const w = V.vector(j + 1);
+        for (int pass = 0; pass < 2; ++pass)
+        {
+          bkb::dots(handle, scratch, l, V, j + 1, w, coef, cstride, pass == 1);
+          bkb::update(handle, scratch, l, V, j + 1, w, pass == 1);
+        }
+        bkb::scale_store(handle, scratch, l, n, wld, w, w, v_f32, coef + j + 1, cstride);
+        fetch(l, j + 2);
+        ++it;
+        bkb::SlotList leaving, broken;
+        for (int i = 0; i < l.count; ++i)
+        {
+          const int s = l.id[i], c = l.col[i];
+          FgmresColumn &col = columns[c];
+          std::copy(fetched(l, s), fetched(l, s) + j + 2, col.column(j));
+          const double r = col.rotate();
+          iterations[c] = it;
+          // a breakdown is not taken at its word: the column gets its update, and the residual fgmres_run recomputes is what is
+          // recorded and tested
+          if (!col.breakdown)
+          {
+            res[c] = r;
+            record(c, it, r);
+            converged[c] = r <= tolerances[c];
+          }
+          if (col.breakdown || converged[c])
+          {
+            leaving.id[leaving.count] = s;
+            leaving.col[leaving.count++] = c;
+            live[s] = 0;
+            --n_live;
+          }
+          if (col.breakdown)
+            broken.col[broken.count++] = c;
+        }
+        if (leaving.count > 0)
+          combine(leaving, j + 1);
+        for (int i = 0; i < broken.count; ++i)
+        {
+          // (the one-vector loop from this column's x and the shared count: the cycle start is the whole state)
+          const int c = broken.col[i];
+          const FgmresOutcome out = fgmres_run(h, b_run + c * wld, x_run + c * wld, tolerances[c], max_iterations, m, fp32, it,
+                                               residual_history ? residual_history + (int64_t)c * history_ld : nullptr, history_ld);
+          iterations[c] = out.iterations;
+          res[c] = out.residual;
+          converged[c] = out.converged;
+          cycle_starts += out.cycle_starts;
+          preconditioner_columns += out.iterations - it;
+          operator_columns += out.iterations - it;
+        }
+      }
+      if (n_live > 0)
+        combine(live_list(), j);
+      if (n_live == 0 || it >= max_iterations)
+        break;
+      // restart: the survivors move to the first slots (the map alone changes), the residual is the true one, recomputed
+      {
+        int32_t n_groups = 0, n_packed = 0;
+        bkb::plan(k, live.data(), slot_col.data(), run_start.data(), run_width.data(), run_groups.data(), group_width.data(), &n_groups,
+                  packed.data(), &n_packed);
+        for (int s = 0; s < k; ++s)
+        {
+          live[s] = s < n_packed;
+          if (s < n_packed)
+            slot_col[s] = packed[s];
+        }
+      }
+      start_cycle();
+      retire_converged_at_start();
+    }
+    bool all = true;
+    for (int c = 0; c < k; ++c)
+    {
+      if (n_iterations)
+        n_iterations[c] = iterations[c];
+      if (final_residuals)
+        final_residuals[c] = res[c];
+      all = all && converged[c];
+    }
+    if (permute)
+      for (int c = 0; c < k; ++c)
+        h->perm->scatter(static_cast<double const *>(x_run + c * wld), x + c * ld);
+    if (work)
+    {
+      work[0] = preconditioner_columns;
+      work[1] = operator_columns;
+      work[2] = block_kernel_launches(h) - launches_before;
+      work[3] = cycle_starts;
+    }
+    if (!all)
+      throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations on every column of the block (SolverControl::NoConvergence)");
+  });
+}
+
+int mfmg_hip_block_fgmres_plan(int32_t n_slots, const int32_t *live, const int32_t *slot_col, int32_t *run_start, int32_t *run_width,
+                               int32_t *run_groups, int32_t *n_runs, int32_t *group_width, int32_t *n_groups, int32_t *packed_col,
+                               int32_t *n_packed)
+{
+  return guarded([&] {
+    require(live && slot_col && run_start && run_width && run_groups && n_runs && group_width && n_groups && packed_col && n_packed,
+            "null argument");
+    require(n_slots >= 0 && n_slots <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds at most 64 slots");
+    *n_runs = block_krylov_basis::plan(n_slots, live, slot_col, run_start, run_width, run_groups, group_width, n_groups, packed_col, n_packed);
+  });
+}
+
+namespace
+{
+// the list of the test entry points: n_live different slots of a block of k, in ascending order
+extern "C++" block_krylov_basis::SlotList checked_slot_list(int32_t k, int32_t n_live, const int32_t *slots, const int32_t *cols, int32_t n_cols)
+{
+  require(slots != nullptr, "null argument");
+  require(k >= 1 && k <= MFMG_HIP_BLOCK_MAX_VECTORS && n_live >= 1 && n_live <= k, "a block holds 1 to 64 slots, of which 1 to all are live");
+  block_krylov_basis::SlotList l;
+  for (int i = 0; i < n_live; ++i)
+  {
+    require(slots[i] >= 0 && slots[i] < k && (i == 0 || slots[i] > slots[i - 1]), "the live slots are named once, in ascending order");
+    l.id[i] = slots[i];
+    l.col[i] = cols ? cols[slots[i]] : slots[i];
+    require(l.col[i] >= 0 && l.col[i] < n_cols, "a slot's column lies outside x");
+    for (int q = 0; q < i; ++q)
+      require(l.col[q] != l.col[i], "two live slots name one column of x");
+  }
+  l.count = n_live;
+  return l;
+}
+} // namespace
+
+int mfmg_hip_block_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, int32_t j, int32_t n_live,
+                                        const int32_t *live_slots, double *V, double *v_next, float *v_next_f32, double *h_out,
+                                        double *norm_out)
+{
+  namespace bkb = block_krylov_basis;
+  return guarded([&] {
+    require(ctx && V && h_out && norm_out, "null argument");
+    require(!ctx->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+    require(n >= 1 && ld >= n && j >= 0, "bad shape");
+    require(ld % 2 == 0 && reinterpret_cast<uintptr_t>(V) % 16 == 0 && reinterpret_cast<uintptr_t>(v_next) % 16 == 0 &&
+                reinterpret_cast<uintptr_t>(v_next_f32) % 8 == 0,
+            "the basis block needs an even leading dimension and a base aligned to 16 bytes");
+    const bkb::SlotList l = checked_slot_list(k, n_live, live_slots, nullptr, k);
+    HipHandle &handle = *ctx->handle;
+    bkb::Scratch scratch(k, j + 1);
+    const bkb::Basis B{n, ld, (int64_t)k * ld, V};
+    double *const w = B.vector(j + 1);
+    for (int pass = 0; pass < 2; ++pass)
+    {
+      bkb::dots(handle, scratch, l, B, j + 1, w, h_out, j + 1, pass == 1);
+      bkb::update(handle, scratch, l, B, j + 1, w, pass == 1);
+    }
+    bkb::scale_store(handle, scratch, l, n, ld, w, v_next, v_next_f32, norm_out, 1);
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the scratch goes away)
+  });
+}
+
+int mfmg_hip_block_krylov_combine(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, int32_t j, int32_t n_live,
+                                  const int32_t *live_slots, const int32_t *slot_col, const double *Z, const double *y, int32_t n_x_columns,
+                                  int64_t ldx, double *x)
+{
+  namespace bkb = block_krylov_basis;
+  return guarded([&] {
+    require(ctx && Z && y && x && slot_col, "null argument");
+    require(!ctx->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+    require(n >= 1 && ld >= n && ldx >= n && j >= 0 && n_x_columns >= 1, "bad shape");
+    require(ld % 2 == 0 && reinterpret_cast<uintptr_t>(Z) % 16 == 0, "the basis block needs an even leading dimension and a base aligned to 16 bytes");
+    const bkb::SlotList l = checked_slot_list(k, n_live, live_slots, slot_col, n_x_columns);
+    bkb::combine(*ctx->handle, l, bkb::Basis{n, ld, (int64_t)k * ld, const_cast<double *>(Z)}, j + 1, y, j + 1, x, ldx);
   });
 }
 

@@ -244,6 +244,11 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_vmult": (C.c_int, [vp, vp, vp]),
         "mfmg_hip_hierarchy_solve_cg": (C.c_int, [vp, vp, vp, C.c_double, C.c_int32, P(C.c_int32), P(C.c_double), P(C.c_double), C.c_int32]),
         "mfmg_hip_hierarchy_solve_fgmres": (C.c_int, [vp, vp, vp, dbl, i32, i32, i32, P(i32), P(dbl), P(dbl), i32]),
+        "mfmg_hip_hierarchy_solve_fgmres_block": (C.c_int, [vp, i32, i64, vp, vp, P(dbl), i32, i32, i32, P(i32), P(dbl), P(dbl), i32,
+                                                            P(i64)]),
+        "mfmg_hip_block_fgmres_plan": (C.c_int, [i32, P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32)]),
+        "mfmg_hip_block_krylov_orthogonalize": (C.c_int, [vp, i64, i32, i64, i32, i32, P(i32), vp, vp, vp, vp, vp]),
+        "mfmg_hip_block_krylov_combine": (C.c_int, [vp, i64, i32, i64, i32, i32, P(i32), P(i32), vp, vp, i32, i64, vp]),
         "mfmg_hip_krylov_orthogonalize": (C.c_int, [vp, i64, i64, i32, vp, vp, vp, vp, i32]),
         "mfmg_hip_krylov_combine": (C.c_int, [vp, i64, i64, i32, vp, vp, vp]),
         "mfmg_hip_krylov_orthogonalize_box": (C.c_int, [vp, P(i64), P(i64), P(i64), i32, i64, i32, vp, vp, vp, vp, i32]),
@@ -298,7 +303,9 @@ def load() -> C.CDLL:
                    "mfmg_hip_hierarchy_apply_block", "mfmg_hip_hierarchy_vmult_block", "mfmg_hip_hierarchy_smoother_apply_block",
                    "mfmg_hip_hierarchy_block_info", "mfmg_hip_csr_enable_node_twins", "mfmg_hip_csr_release_csr",
                    "mfmg_hip_hierarchy_solve_cg_block", "mfmg_hip_block_cg_retire", "mfmg_hip_hierarchy_operator_apply_block",
-                   "mfmg_hip_block_dots", "mfmg_hip_block_cg_direction", "mfmg_hip_block_cg_update"}
+                   "mfmg_hip_block_dots", "mfmg_hip_block_cg_direction", "mfmg_hip_block_cg_update",
+                   "mfmg_hip_hierarchy_solve_fgmres_block", "mfmg_hip_block_fgmres_plan", "mfmg_hip_block_krylov_orthogonalize",
+                   "mfmg_hip_block_krylov_combine"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
