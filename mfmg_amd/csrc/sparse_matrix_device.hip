@@ -172,6 +172,93 @@ __device__ __forceinline__ void store_node(CsrArgs<T> const &a, int64_t node, T 
     a.out[row0 + rc] = epilogue(mode, sum + rc, xr, br, dr, pr, orr, rc, a.alpha, a.beta);
 }
 
+// Entries of a row that a lane keeps in flight (the batch of lane_row_sum and of the staging of csr_spmv_lds_kernel).
+constexpr int kRowBatch = 4;
+
+// The partial sum of one lane over a row: the entries p, p + S, p + 2 S, .. below e (S lanes share the row), x taken at
+// idx[] -- the global x by column, or the LDS copy of csr_spmv_lds_kernel by local column.  Entry by entry a lane waits for
+// (val, idx), then for x, with nothing of the next entry requested: two dependent round trips per entry in kernels bound
+// by their latency.  Here B entries are one batch: all of its index and value loads, then all of its x reads, then the
+// multiply-adds in ascending entry order, each through the one `sum += val * x` -- the chain of a lane is what it was,
+// only the requests are earlier.  In the last, short batch of a row nothing is read past e, and an entry that is not
+// there is SKIPPED, never added as a product with zero (the x it reads instead may be Inf or NaN, and a sum of -0 stays
+// -0).
+template <int S, int B, typename T, typename I, typename X>
+__device__ __forceinline__ T lane_row_sum(T const *val, I const *idx, X const *x, int p, int e)
+{
+  T sum = T(0);
+  I c[B];
+  T v[B], xv[B];
+  // (e - p, not p + (B - 1) S: no overflow at the end of 2^31 entries)
+  for (; e - p > (B - 1) * S; p += B * S)
+  {
+#pragma unroll
+    for (int k = 0; k < B; ++k)
+    {
+      c[k] = idx[p + k * S];
+      v[k] = val[p + k * S];
+    }
+#pragma unroll
+    for (int k = 0; k < B; ++k)
+      xv[k] = x[c[k]];
+#pragma unroll
+    for (int k = 0; k < B; ++k)
+      sum += v[k] * xv[k];
+  }
+  if (p < e)
+  {
+    // B - 1 entries at most, the first of them is there: an entry that is not reads at the first one's position instead
+    // (under a branch of its own every load would be waited for with all requests before it: one after the other again)
+#pragma unroll
+    for (int k = 0; k < B - 1; ++k)
+    {
+      const int q = e - p > k * S ? p + k * S : p;
+      c[k] = idx[q];
+      v[k] = val[q];
+    }
+#pragma unroll
+    for (int k = 0; k < B - 1; ++k)
+      xv[k] = x[c[k]];
+#pragma unroll
+    for (int k = 0; k < B - 1; ++k)
+      if (e - p > k * S)
+        sum += v[k] * xv[k];
+  }
+  return sum;
+}
+
+// The operands of the epilogue at one row, requested ahead of the row loop by the lane that will store (store_row alone
+// asks for them after the reduction: one more dependent round trip).  out as an operand (subtract, add) is read before
+// the gathers of x, which is the same value only because launch() rejects out == x.
+template <typename T>
+struct RowOperands
+{
+  T x, b, dinv, xprev, out;
+};
+template <typename T>
+__device__ __forceinline__ RowOperands<T> row_operands(CsrArgs<T> const &a, int64_t row)
+{
+  const CsrOperands need = operands_of(static_cast<CsrMode>(a.mode));
+  RowOperands<T> o{};
+  if (need.x)
+    o.x = a.x[row];
+  if (need.b)
+    o.b = a.b[row];
+  if (need.dinv)
+    o.dinv = a.dinv[row];
+  if (need.xprev)
+    o.xprev = a.xprev[row];
+  if (need.out)
+    o.out = a.out[row];
+  return o;
+}
+// the epilogue of one row from operands requested before (the one epilogue(): same expression, same bits)
+template <typename T>
+__device__ __forceinline__ void store_row(CsrArgs<T> const &a, int64_t row, T sum, RowOperands<T> const &o)
+{
+  a.out[row] = epilogue(static_cast<CsrMode>(a.mode), &sum, &o.x, &o.b, &o.dinv, &o.xprev, &o.out, int64_t(0), a.alpha, a.beta);
+}
+
 template <typename T, int LPR>
 __global__ void csr_spmv_kernel(CsrArgs<T> a)
 {
@@ -180,11 +267,7 @@ __global__ void csr_spmv_kernel(CsrArgs<T> a)
   const int sub = threadIdx.x % LPR;
   T sum = T(0);
   if (row < a.n_rows)
-  {
-    const int s = a.row_ptr[row], e = a.row_ptr[row + 1];
-    for (int p = s + sub; p < e; p += LPR)
-      sum += a.val[p] * a.x[a.col[p]];
-  }
+    sum = lane_row_sum<LPR, kRowBatch>(a.val, a.col, a.x, a.row_ptr[row] + sub, a.row_ptr[row + 1]);
 #pragma unroll
   for (int off = LPR / 2; off > 0; off >>= 1)
     sum += __shfl_xor(sum, off);
@@ -200,9 +283,10 @@ __global__ __launch_bounds__(256) void csr_spmv_row_block_kernel(CsrArgs<T> a)
 {
   __shared__ T part[4];
   const int64_t row = blockIdx.x;
-  T sum = T(0);
-  for (int p = a.row_ptr[row] + (int)threadIdx.x, e = a.row_ptr[row + 1]; p < e; p += 256)
-    sum += a.val[p] * a.x[a.col[p]];
+  // (the row is uniform: scalar loads, requested beside row_ptr by every wavefront rather than under a branch of thread 0,
+  // behind which they would be waited for before the row loop starts)
+  const RowOperands<T> ops = row_operands(a, row);
+  T sum = lane_row_sum<256, kRowBatch>(a.val, a.col, a.x, a.row_ptr[row] + (int)threadIdx.x, a.row_ptr[row + 1]);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
     sum += __shfl_xor(sum, off);
@@ -210,7 +294,7 @@ __global__ __launch_bounds__(256) void csr_spmv_row_block_kernel(CsrArgs<T> a)
     part[threadIdx.x >> 6] = sum;
   __syncthreads();
   if (threadIdx.x == 0)
-    store_row(a, row, ((part[0] + part[1]) + part[2]) + part[3]);
+    store_row(a, row, ((part[0] + part[1]) + part[2]) + part[3], ops);
 }
 
 // LDS-cached SpMV: the x entries a block of rows touches are gathered once (coalesced through the sorted
@@ -227,10 +311,51 @@ __global__ void csr_spmv_lds_kernel(CsrArgs<T> a, int32_t const *blk_ptr, int32_
   const int64_t row0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t row1 = min(row0 + rows_per_block, a.n_rows);
   const int l0 = blk_ptr[blockIdx.x], l1 = blk_ptr[blockIdx.x + 1];
-  for (int i = threadIdx.x; i <= (int)(row1 - row0); i += blockDim.x)
-    rp[i] = a.row_ptr[row0 + i];
-  for (int i = threadIdx.x; i < l1 - l0; i += blockDim.x)
-    xs[i] = a.x[l2g[l0 + i]];
+  // Staging of rp[] and xs[].  Element by element x waits for l2g, the LDS write for x and the next l2g for the LDS write.
+  // Here a thread requests its row_ptr first and writes it last, and takes all of its elements of xs[] as one batch: their
+  // l2g loads, then their x loads, then the LDS writes.  The batch is the uniform number of elements per thread, rounded up
+  // to 1, 2, 4 or 8 (8 x 1024 threads hold the longest list the LDS form accepts); an element past the end of the list
+  // reads at the thread's first one instead (as in lane_row_sum) and is not written.
+  {
+    const int n_rp = (int)(row1 - row0) + 1, n_x = l1 - l0, nt = blockDim.x, t = threadIdx.x;
+    int r = 0;
+    if (t < n_rp)
+      r = a.row_ptr[row0 + t];
+    auto stage = [&](auto kk) {
+      constexpr int K = decltype(kk)::value;
+      if (t >= n_x)
+        return;
+      int g[K];
+      T xv[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        g[k] = l2g[l0 + (n_x - t > k * nt ? t + k * nt : t)];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        xv[k] = a.x[g[k]];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (n_x - t > k * nt)
+          xs[t + k * nt] = xv[k];
+    };
+    if (n_x <= nt)
+      stage(std::integral_constant<int, 1>());
+    else if (n_x <= 2 * nt)
+      stage(std::integral_constant<int, 2>());
+    else if (n_x <= 4 * nt)
+      stage(std::integral_constant<int, 4>());
+    else
+      stage(std::integral_constant<int, 8>());
+    if (t < n_rp)
+      rp[t] = r;
+    // (a workgroup of fewer threads than an eighth of the list, or than rows + 1)
+#pragma unroll 1
+    for (int i = t + 8 * nt; i < n_x; i += nt)
+      xs[i] = a.x[l2g[l0 + i]];
+#pragma unroll 1
+    for (int i = t + nt; i < n_rp; i += nt)
+      rp[i] = a.row_ptr[row0 + i];
+  }
   __syncthreads();
   const int group = threadIdx.x / LPR, sub = threadIdx.x % LPR, n_groups = blockDim.x / LPR;
   // every lane runs the same number of passes so that the shuffles are wave-uniform
@@ -239,11 +364,7 @@ __global__ void csr_spmv_lds_kernel(CsrArgs<T> a, int32_t const *blk_ptr, int32_
     const int64_t row = base + group;
     T sum = T(0);
     if (row < row1)
-    {
-      const int s = rp[row - row0], e = rp[row - row0 + 1];
-      for (int p = s + sub; p < e; p += LPR)
-        sum += a.val[p] * xs[lcol[p]];
-    }
+      sum = lane_row_sum<LPR, kRowBatch>(a.val, lcol, xs, rp[row - row0] + sub, rp[row - row0 + 1]);
 #pragma unroll
     for (int off = LPR / 2; off > 0; off >>= 1)
       sum += __shfl_xor(sum, off);
@@ -420,15 +541,16 @@ __device__ __forceinline__ void listed_row_wave(CsrArgs<T> const &a, int32_t con
   if (w >= n_listed)
     return;
   const int64_t row = rows[w];
-  T sum = T(0);
+  RowOperands<T> ops{};
+  if (lane == 0)
+    ops = row_operands(a, row);
   const int p0 = a.kept_ptr ? a.kept_ptr[w] : a.row_ptr[row], e = a.kept_ptr ? a.kept_ptr[w + 1] : a.row_ptr[row + 1];
-  for (int p = p0 + lane; p < e; p += 64)
-    sum += a.val[p] * a.x[a.col[p]];
+  T sum = lane_row_sum<64, kRowBatch>(a.val, a.col, a.x, p0 + lane, e);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
     sum += __shfl_xor(sum, off);
   if (lane == 0)
-    store_row(a, row, sum);
+    store_row(a, row, sum, ops);
 }
 
 // Non-regular nodes that repeat one stencil among themselves (the nodes at the same distance from the faces of a

@@ -18,7 +18,13 @@ for r in tail:
     k = name(r); a = acc.setdefault(k, [0, 0]); a[0] += 1; a[1] += int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
 for k, (c, t) in sorted(acc.items(), key=lambda kv: -kv[1][1]):
     print(f"{t/ncyc/1e3:9.1f} us/cycle {c/ncyc:5.1f} x {t/c/1e3:8.1f} us  {k[:110]}")
-if len(sys.argv) > 2:   # sequence of one cycle
+if len(sys.argv) > 2 and sys.argv[2] == "spread":   # every launch of the cycle over the 10 cycles: mean, min .. max
+    n = len(tail) // ncyc
+    for j in range(n):
+        d = [(int(tail[c * n + j]["End_Timestamp"]) - int(tail[c * n + j]["Start_Timestamp"])) / 1e3 for c in range(ncyc)]
+        r = tail[j]
+        print(f"{j:3d} {sum(d)/ncyc:8.1f} {min(d):8.1f} ..{max(d):7.1f}  {name(r)[:90]}  grid {r.get('Grid_Size_X','')}")
+elif len(sys.argv) > 2:   # sequence of one cycle
     n = len(tail) // ncyc
     for r in tail[-n:]:
         print(f"{(int(r['Start_Timestamp'])-int(tail[-n]['Start_Timestamp']))/1e3:9.1f} {(int(r['End_Timestamp'])-int(r['Start_Timestamp']))/1e3:8.1f}  {name(r)[:90]}  grid {r.get('Grid_Size_X','')}")
