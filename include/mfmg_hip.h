@@ -813,7 +813,7 @@ int mfmg_hip_block_cg_update(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64
  * ld the caller's, or n_dofs rounded up to even with "internal numbering" lexicographic, where b and x are gathered once and x is
  * scattered once).  All live columns share the iteration count and the basis length.  Per iteration: the cycle and the operator
  * on every maximal run of consecutive live slots (as mfmg_hip_hierarchy_vmult_block / _operator_apply_block run a block; with
- * preconditioner_fp32 the FP32 fine level column by column), both Gram-Schmidt passes and the normalisation with one launch each
+ * preconditioner_fp32 the FP32 cycle on the float copies of the run, as mfmg_hip_hierarchy_apply_f32_block runs a block), both Gram-Schmidt passes and the normalisation with one launch each
  * for all live slots, ONE device-to-host copy and ONE stream synchronisation.  A column that converges gets x += Z y at once and
  * leaves the live list; nothing is copied to close the gap, and the next restart cycle packs the surviving columns into the
  * first slots by changing the slot -> column map alone (mfmg_hip_block_fgmres_plan is that plan).  A column that breaks down
@@ -854,6 +854,30 @@ int mfmg_hip_block_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int32
 int mfmg_hip_block_krylov_combine(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, int32_t j, int32_t n_live,
                                   const int32_t *live_slots, const int32_t *slot_col, const double *Z, const double *y,
                                   int32_t n_x_columns, int64_t ldx, double *x);
+
+/* ---- the FP32 fine level on blocks of float vectors (additions, no change of the ABI version) ----
+ * A float block: n_vectors (1 .. 64) columns of floats with a common leading dimension, column c at base + c * ld elements, ld >=
+ * n_dofs and even, the base aligned to 8 bytes (a lane reads one element at a time); one rank.  The refusals are those of the FP64
+ * block entry points.
+ * mfmg_hip_mf_laplace_f32_block_launch / _block_available / _set_block_tile / _get_block_tile: as the entry points without _f32
+ * above, on the FP32 operator.  Groups of 4 and 2 columns run mf_laplace_block_f32_kernel (the chunk records are read once per
+ * group), a single column the one-vector kernel; every column gets the bits of the one-vector FP32 entry point, for every tile.
+ * mfmg_hip_hierarchy_apply_f32_block: x[c] = the result of mfmg_hip_hierarchy_apply_f32(b[c], x[c]) for every column, bit for bit
+ * (needs "fine level precision" float).  Per group of mfmg_hip_block_groups: pre-smoothing, residual and post-smoothing as block
+ * launches, restriction, coarse cycle and prolongation column by column; a group of one, and every group where the FP32 operator
+ * has no block kernel (cell-constant layout: the multi-term sweep), runs the one-vector cycle.  With "internal numbering"
+ * lexicographic on a renumbered mesh the columns are gathered into and scattered from a library block one by one.
+ * mfmg_hip_hierarchy_block_info_f32: fields[0] width of the widest group the FP32 fine level runs as one launch, fields[1] launches
+ * of mf_laplace_block_f32_kernel and fields[2] columns that went through the one-vector cycle in the last FP32 block call: the last
+ * mfmg_hip_hierarchy_apply_f32_block, or the preconditioner applications of the last mfmg_hip_hierarchy_solve_fgmres_block with
+ * preconditioner_fp32 = 1. */
+int mfmg_hip_mf_laplace_f32_block_launch(mfmg_hip_mf_laplace_f32_t op, int mode, int32_t n_vectors, int64_t ld, const float *x,
+                                         const float *b, const float *x_prev, float alpha, float beta, float *out);
+int mfmg_hip_mf_laplace_f32_block_available(mfmg_hip_mf_laplace_f32_t op, int *available);
+int mfmg_hip_mf_laplace_f32_set_block_tile(mfmg_hip_mf_laplace_f32_t op, int n_waves, int tile_y, int tile_z);
+int mfmg_hip_mf_laplace_f32_get_block_tile(mfmg_hip_mf_laplace_f32_t op, int n_vectors, int *n_waves, int *tile_y, int *tile_z);
+int mfmg_hip_hierarchy_apply_f32_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const float *b, float *x);
+int mfmg_hip_hierarchy_block_info_f32(mfmg_hip_hierarchy_t h, int64_t *fields);
 
 #ifdef __cplusplus
 }

@@ -105,20 +105,21 @@ def _dev_ptr(t: torch.Tensor, n: Optional[int] = None, dtype=torch.float64) -> i
     return t.data_ptr()
 
 
-def _block_ptr(t: torch.Tensor):
-    """(k, ld, device pointer) of a block of vectors: a 2-D float64 CUDA tensor of shape (k, m) whose rows are the vectors
-    (stride(1) == 1, ld = stride(0)).  What the library asks of k, ld and the alignment it checks itself."""
+def _block_ptr(t: torch.Tensor, dtype=torch.float64):
+    """(k, ld, device pointer) of a block of vectors: a 2-D float64 (or, for the FP32 entry points, float32) CUDA tensor of shape
+    (k, m) whose rows are the vectors (stride(1) == 1, ld = stride(0)).  What the library asks of k, ld and the alignment it
+    checks itself."""
     if not isinstance(t, torch.Tensor):
         raise TypeError("expected a torch tensor")
     if t.device.type != "cuda":
         raise ValueError("vectors must live on the GPU (the HIP path has no CPU fallback)")
-    if t.dtype != torch.float64 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError("a block is a 2-D float64 tensor of shape (k, m) with stride(1) == 1")
+    if t.dtype != dtype or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"a block is a 2-D {str(dtype).split('.')[-1]} tensor of shape (k, m) with stride(1) == 1")
     return int(t.shape[0]), int(t.stride(0)), t.data_ptr()
 
 
-def _same_block(k, ld, t):
-    kk, ll, p = _block_ptr(t)
+def _same_block(k, ld, t, dtype=torch.float64):
+    kk, ll, p = _block_ptr(t, dtype)
     if (kk, ll) != (k, ld):
         raise ValueError("the blocks of one call share the number of vectors and the leading dimension")
     return p
@@ -764,6 +765,32 @@ class MatrixFreeLaplaceF32:
         if waves is not None:
             check(self._lib.mfmg_hip_mf_laplace_f32_set_tile_waves(self.handle, waves))
 
+    _BLOCK_MODES = MatrixFreeLaplace._BLOCK_MODES
+
+    def block_launch(self, mode: str, X, out, B=None, X_prev=None, alpha: float = 0.0, beta: float = 0.0):
+        """MatrixFreeLaplace.block_launch on float32 blocks: 2-D float32 tensors of shape (k, m), stride(1) == 1, with one even
+        leading dimension ld = stride(0) >= n_dofs and bases aligned to 8 bytes; out may be X_prev.  Every row gets the bits of
+        vmult / residual / smoother_step of this operator on that row."""
+        f32 = torch.float32
+        k, ld, px = _block_ptr(X, f32)
+        check(self._lib.mfmg_hip_mf_laplace_f32_block_launch(
+            self.handle, self._BLOCK_MODES[mode], k, ld, px, _same_block(k, ld, B, f32) if B is not None else None,
+            _same_block(k, ld, X_prev, f32) if X_prev is not None else None, alpha, beta, _same_block(k, ld, out, f32)))
+
+    def block_available(self) -> bool:
+        """Groups of 4 and 2 vectors of a block run mf_laplace_block_f32_kernel (eight coefficients per cell, 3-D, no tail slab)."""
+        v = C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_f32_block_available(self.handle, C.byref(v)))
+        return bool(v.value)
+
+    def set_block_tile(self, waves: int, ty: int, tz: int):
+        check(self._lib.mfmg_hip_mf_laplace_f32_set_block_tile(self.handle, waves, ty, tz))
+
+    def get_block_tile(self, n_vectors: int):
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_f32_get_block_tile(self.handle, int(n_vectors), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def diagonal_in_record(self) -> bool:
         v = C.c_int()
         check(self._lib.mfmg_hip_mf_laplace_f32_diagonal_in_record(self.handle, C.byref(v)))
@@ -843,6 +870,20 @@ class Hierarchy:
         context with a HaloTransport b and x are the rank's local float vectors (ghost entries are don't-care on entry)."""
         n = self.level_size(0)
         check(self._lib.mfmg_hip_hierarchy_apply_f32(self.handle, _dev_ptr(b, n, torch.float32), _dev_ptr(x, n, torch.float32)))
+
+    def apply_f32_block(self, B: torch.Tensor, X: torch.Tensor):
+        """The cycle of apply_f32() on every row of the float32 blocks B and X (shape (k, m), stride(1) == 1, one even leading
+        dimension ld = stride(0) >= n_dofs, bases aligned to 8 bytes).  Row c of X gets the bits of apply_f32(B[c], X[c])."""
+        k, ld, pb = _block_ptr(B, torch.float32)
+        check(self._lib.mfmg_hip_hierarchy_apply_f32_block(self.handle, k, ld, pb, _same_block(k, ld, X, torch.float32)))
+
+    def block_info_f32(self) -> dict:
+        """block_info() of the FP32 fine level: width; block_launches / column_launches of mf_laplace_block_f32_kernel and of the
+        one-vector cycle in the last FP32 block call -- apply_f32_block, or the preconditioner applications of the last
+        solve_fgmres_block(preconditioner="float")."""
+        f = (C.c_int64 * 3)()
+        check(self._lib.mfmg_hip_hierarchy_block_info_f32(self.handle, f))
+        return {"width": int(f[0]), "block_launches": int(f[1]), "column_launches": int(f[2])}
 
     def operator_f32(self, mode: str, x: torch.Tensor, out: torch.Tensor, b=None, x_prev=None, alpha: float = 0.0, beta: float = 0.0):
         """The FP32 operator of the fine level on its own (tests): mode "vmult" out = A x, "residual" out = A x - b, "step"

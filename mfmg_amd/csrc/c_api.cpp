@@ -365,6 +365,19 @@ struct mfmg_hip_hierarchy_s
   // block entry points: the permuted columns of one group (b, x) and what the last block call did
   DeviceBuffer<double> block_work[2];
   int64_t block_info[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0};
+  int64_t block_info_f32[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0}; // ... and the last FP32 block call
+  DeviceBuffer<float> block_work_f32[2];
+  float *block_workspace_f32(int i, size_t n)
+  {
+    if (block_work_f32[i].size() < n)
+    {
+      MemoryKind kind("hierarchy: FP32 block workspace (permuted columns)");
+      block_work_f32[i].release();
+      block_work_f32[i].resize(n);
+      MFMG_HIP_CHECK(hipMemsetAsync(block_work_f32[i].data(), 0, n * sizeof(float), handle->stream));
+    }
+    return block_work_f32[i].data();
+  }
   double *block_workspace(int i, size_t n)
   {
     if (block_work[i].size() < n)
@@ -1579,6 +1592,43 @@ int mfmg_hip_mf_laplace_f32_diagonal_in_record(mfmg_hip_mf_laplace_f32_t op, int
   });
 }
 
+// ---- blocks of float vectors ----
+int mfmg_hip_mf_laplace_f32_block_launch(mfmg_hip_mf_laplace_f32_t op, int mode, int32_t n_vectors, int64_t ld, const float *x, const float *b,
+                                         const float *x_prev, float alpha, float beta, float *out)
+{
+  return guarded([&] {
+    require(op != nullptr, "null argument");
+    require(mode >= 0 && mode <= 3, "mode: 0 out = A x, 1 out = A x - b, 2 / 3 a smoother term without / with x_prev");
+    op->op->launch_block(static_cast<MfMode>(mode), {x, b, x_prev, out, ld, n_vectors, alpha, beta});
+  });
+}
+
+int mfmg_hip_mf_laplace_f32_block_available(mfmg_hip_mf_laplace_f32_t op, int *available)
+{
+  return guarded([&] {
+    require(op && available, "null argument");
+    *available = op->op->block_kernel_available() ? 1 : 0;
+  });
+}
+
+int mfmg_hip_mf_laplace_f32_set_block_tile(mfmg_hip_mf_laplace_f32_t op, int n_waves, int tile_y, int tile_z)
+{
+  return guarded([&] {
+    require(op != nullptr, "null argument");
+    require((n_waves == 0 && tile_y == 0 && tile_z == 0) || (n_waves >= 1 && n_waves <= 8 && tile_y >= 2 && tile_y <= 4 && tile_z >= 1),
+            "block tile: 1..8 wavefronts of 2..4 cell rows, at least one layer (0, 0, 0: chosen from the mesh)");
+    op->op->set_block_tile(n_waves, tile_y, tile_z);
+  });
+}
+
+int mfmg_hip_mf_laplace_f32_get_block_tile(mfmg_hip_mf_laplace_f32_t op, int n_vectors, int *n_waves, int *tile_y, int *tile_z)
+{
+  return guarded([&] {
+    require(op && n_waves && tile_y && tile_z, "null argument");
+    op->op->get_block_tile(n_vectors, *n_waves, *tile_y, *tile_z);
+  });
+}
+
 int mfmg_hip_mf_laplace_get_tile(mfmg_hip_mf_laplace_t op, int *n_waves, int *tile_y, int *tile_z)
 {
   return guarded([&] {
@@ -1929,6 +1979,57 @@ int mfmg_hip_hierarchy_apply_f32(mfmg_hip_hierarchy_t h, const float *b, float *
       return;
     }
     h->fine_f32->apply(b, x);
+  });
+}
+
+// ... on the columns of a float block (HipFloatFineLevel::apply_block).  "internal numbering" lexicographic: the columns are gathered
+// into a library block and scattered back one by one, as mfmg_hip_hierarchy_apply_f32 does with its vector.
+int mfmg_hip_hierarchy_apply_f32_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const float *b, float *x)
+{
+  return guarded([&] {
+    require(h != nullptr, "null argument");
+    require(h->fine_f32 != nullptr, "the hierarchy was not built with \"fine level precision\" float");
+    require(!h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+    require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
+    require(b && x, "null argument");
+    const int64_t n = level_size(h, 0);
+    require(ld >= n, "the leading dimension of a block must be at least the vector size");
+    require(ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 8 bytes)");
+    require(reinterpret_cast<uintptr_t>(b) % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 8 == 0, "the base of a block must be aligned to 8 bytes");
+    const int64_t extent = (int64_t)(n_vectors - 1) * ld + n;
+    require(b + extent <= x || x + extent <= b, "the blocks b and x overlap");
+    const int64_t launches = h->fine_f32->block_launches();
+    if (h->perm)
+    {
+      const int64_t wld = n + (n & 1);
+      float *wb = h->block_workspace_f32(0, (size_t)n_vectors * wld), *wx = h->block_workspace_f32(1, (size_t)n_vectors * wld);
+      for (int c = 0; c < n_vectors; ++c)
+      {
+        if (h->hierarchy->is_preconditioner())
+          h->perm->gather(b + c * ld, wb + c * wld);
+        else
+          h->perm->gather2(b + c * ld, static_cast<float const *>(x + c * ld), wb + c * wld, wx + c * wld);
+      }
+      h->fine_f32->apply_block(n_vectors, wld, wb, wx);
+      for (int c = 0; c < n_vectors; ++c)
+        h->perm->scatter(static_cast<float const *>(wx + c * wld), x + c * ld);
+    }
+    else
+      h->fine_f32->apply_block(n_vectors, ld, b, x);
+    h->block_info_f32[0] = h->fine_f32->block_width();
+    h->block_info_f32[1] = h->fine_f32->block_launches() - launches;
+    h->block_info_f32[2] = h->fine_f32->block_columns_looped();
+  });
+}
+
+int mfmg_hip_hierarchy_block_info_f32(mfmg_hip_hierarchy_t h, int64_t *fields)
+{
+  return guarded([&] {
+    require(h && fields, "null argument");
+    require(h->fine_f32 != nullptr, "the hierarchy was not built with \"fine level precision\" float");
+    h->block_info_f32[0] = h->fine_f32->block_width();
+    for (int i = 0; i < MFMG_HIP_BLOCK_INFO_FIELDS; ++i)
+      fields[i] = h->block_info_f32[i];
   });
 }
 
@@ -2639,6 +2740,8 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
     const bool zero_first = !h->hierarchy->is_preconditioner(); // the cycle then starts from what z holds: from zero, as in fgmres_run
     const int64_t launches_before = block_kernel_launches(h);
     int64_t preconditioner_columns = 0, operator_columns = 0, cycle_starts = 0;
+    const int64_t fp32_launches_before = fp32 ? h->fine_f32->block_launches() : 0;
+    int64_t fp32_columns_looped = 0;
 
     std::vector<int32_t> live(k, 1), slot_col(k), run_start(k), run_width(k), run_groups(k), group_width(k), packed(k);
     for (int s = 0; s < k; ++s)
@@ -2709,16 +2812,17 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
     auto precondition = [&](int j) {
       if (fp32)
       {
-        // (no FP32 block kernel: column by column, on the float copy scale_store left)
-        for (int s = 0; s < k; ++s)
-          if (live[s])
-          {
-            float *const zf = ws.z_f32.data() + s * wld;
-            if (zero_first)
-              MFMG_HIP_CHECK(hipMemsetAsync(zf, 0, sizeof(float) * n, handle.stream));
-            h->fine_f32->apply(v_f32 + s * wld, zf);
-            vec::widen(handle, n, zf, Z.vector(j, s));
-          }
+        // the FP32 cycle on every run of live slots, on the float copies scale_store left
+        for_runs(false, [&](int s0, int width) {
+          float *const zf = ws.z_f32.data() + s0 * wld;
+          if (zero_first)
+            for (int c = 0; c < width; ++c)
+              MFMG_HIP_CHECK(hipMemsetAsync(zf + c * wld, 0, sizeof(float) * n, handle.stream));
+          h->fine_f32->apply_block(width, wld, v_f32 + s0 * wld, zf);
+          fp32_columns_looped += h->fine_f32->block_columns_looped();
+          for (int c = 0; c < width; ++c)
+            vec::widen(handle, n, zf + c * wld, Z.vector(j, s0 + c));
+        });
         return;
       }
       for_runs(false, [&](int s0, int width) {
@@ -2868,6 +2972,13 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
       work[1] = operator_columns;
       work[2] = block_kernel_launches(h) - launches_before;
       work[3] = cycle_starts;
+    }
+    if (fp32)
+    {
+      // (mfmg_hip_hierarchy_block_info_f32: the preconditioner applications of this solve)
+      h->block_info_f32[0] = h->fine_f32->block_width();
+      h->block_info_f32[1] = h->fine_f32->block_launches() - fp32_launches_before;
+      h->block_info_f32[2] = fp32_columns_looped;
     }
     if (!all)
       throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations on every column of the block (SolverControl::NoConvergence)");

@@ -1478,6 +1478,9 @@ void HipFloatFineLevel::apply(float const *b, float *x) const
       // (ghost entries beyond what an exchange refreshes are read by no kernel's result, but they are read: no NaN there)
       for (DeviceBuffer<float> *buf : {&_scratch_a, &_scratch_b, &_res, &_work})
         MFMG_HIP_CHECK(hipMemsetAsync(buf->data(), 0, sizeof(float) * n, hd.stream));
+  }
+  if (!_res64) // (a block call may have built them)
+  {
     _res64 = fine.build_range_vector();
     _corr64 = fine.build_range_vector();
   }
@@ -1545,6 +1548,116 @@ void HipFloatFineLevel::apply(float const *b, float *x) const
   if (_b_in_flight != nullptr)
     hd.exchange_async_wait(); // (no sweep waited: the exchange must still be over before the caller touches b)
   _b_of_cycle = _b_fresh = _b_in_flight = nullptr;
+}
+
+void HipFloatFineLevel::apply_block(int k, int64_t ld, float const *b, float *x) const
+{
+  HipHandle &hd = _op.handle();
+  const int64_t n = _op.n_dofs();
+  auto require = [](bool cond, char const *what) {
+    if (!cond)
+      throw InvalidArgumentExc(what);
+  };
+  require(!hd.comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+  require(k >= 1 && k <= kMfBlockMaxVectors, "a block holds 1 to 64 vectors");
+  require(b != nullptr && x != nullptr, "null vector");
+  require(ld >= n, "the leading dimension of a block must be at least n_dofs");
+  require(ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 8 bytes)");
+  require(reinterpret_cast<uintptr_t>(b) % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 8 == 0, "the base of a block must be aligned to 8 bytes");
+  const int64_t extent = (int64_t)(k - 1) * ld + n;
+  require(b + extent <= x || x + extent <= b, "the blocks b and x overlap");
+  _block_columns_looped = 0;
+  auto const &levels = _hierarchy.levels();
+  auto const &fine = *levels[0].get_operator();
+  const bool block = block_width() > 1;
+  int widths[kMfBlockMaxGroups];
+  const int n_groups = mf_block_groups(k, widths);
+  int64_t c0 = 0;
+  for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+  {
+    const int w = widths[g];
+    float const *gb = b + c0 * ld;
+    float *gx = x + c0 * ld;
+    if (!block || w == 1)
+    {
+      for (int c = 0; c < w; ++c)
+        apply(gb + c * ld, gx + c * ld);
+      _block_columns_looped += w;
+      continue;
+    }
+    static char const *const kinds[4] = {"FP32 fine level: block scratch vectors a (one group of right-hand sides)",
+                                         "FP32 fine level: block scratch vectors b (one group of right-hand sides)",
+                                         "FP32 fine level: block residual (one group of right-hand sides)",
+                                         "FP32 fine level: block work vectors (one group of right-hand sides)"};
+    for (int i = 0; i < 4; ++i)
+      if (_block_buffers[i].size() < (size_t)w * ld)
+      {
+        MemoryKind kind(kinds[i]);
+        _block_buffers[i].release(); // (before the wider one is built)
+        _block_buffers[i].resize((size_t)w * ld);
+        MFMG_HIP_CHECK(hipMemsetAsync(_block_buffers[i].data(), 0, sizeof(float) * (size_t)w * ld, hd.stream));
+      }
+    if (!_res64)
+    {
+      _res64 = fine.build_range_vector();
+      _corr64 = fine.build_range_vector();
+    }
+    auto const &coarse = *levels[1].get_operator();
+    if (!_b_coarse || _b_coarse->size() != (int64_t)coarse.grid_complexity())
+    {
+      _b_coarse = coarse.build_range_vector();
+      _x_coarse = coarse.build_range_vector();
+    }
+    struct Block
+    {
+      float *p;
+    };
+    Block sa{_block_buffers[0].data()}, sb{_block_buffers[1].data()};
+    float *const res = _block_buffers[2].data();
+    // the iterate of the group alternates between its x columns and the work block, as the iterate of apply() does
+    Block it{gx}, other{_block_buffers[3].data()};
+    auto smooth = [&] {
+      for (unsigned int i = 0; i < _hierarchy.n_smoothing_steps(); ++i)
+      {
+        run_polynomial<float>(
+            _smoother->coefficients(), 0, static_cast<Block const *>(&it), &other, [&](int i) { return i == 0 ? &sa : &sb; },
+            [&](Block const *cur, Block const *prev, float alpha, float beta, Block *out) {
+              float const *xp = prev ? prev->p : nullptr;
+              _op.launch_block(mf_smoother_mode(xp, alpha), {cur->p, gb, xp, out->p, ld, w, alpha, beta});
+            },
+            [&](int, float const *, float const *, Block const *, Block *, Block *) { ASSERT_THROW(false, "internal: no sweep on a block"); });
+        std::swap(it, other);
+      }
+    };
+    if (_hierarchy.is_preconditioner())
+      for (int c = 0; c < w; ++c)
+        MFMG_HIP_CHECK(hipMemsetAsync(gx + c * ld, 0, sizeof(float) * n, hd.stream));
+    smooth();
+    auto restrictor = levels[1].get_restrictor();
+    auto hip_restrictor = std::dynamic_pointer_cast<HipMatrixOperator const>(restrictor);
+    // b_c = R (A x - b) in one pass per column where apply() forms it so; otherwise the residual of the group in one launch
+    const bool one_pass = hip_restrictor && hip_restrictor->restrict_residual_f32(fine, it.p, gb, *_b_coarse);
+    if (!one_pass)
+      _op.launch_block(MfMode::residual, {it.p, gb, nullptr, res, ld, w, 0.f, 0.f});
+    for (int c = 0; c < w; ++c)
+    {
+      if (!one_pass)
+      {
+        vec::widen(hd, n, res + c * ld, _res64->get_values());
+        restrictor->apply(*_res64, *_b_coarse);
+      }
+      else if (c > 0)
+        ASSERT_THROW(hip_restrictor->restrict_residual_f32(fine, it.p + c * ld, gb + c * ld, *_b_coarse),
+                     "internal: the one-pass residual restriction was refused");
+      _hierarchy.apply(*_b_coarse, *_x_coarse, 1);
+      restrictor->apply(*_x_coarse, *_corr64, OperatorMode::TRANS);
+      vec::subtract_narrowed(hd, n, _corr64->get_values(), it.p + c * ld);
+    }
+    smooth();
+    if (it.p != gx)
+      for (int c = 0; c < w; ++c)
+        MFMG_HIP_CHECK(hipMemcpyAsync(gx + c * ld, it.p + c * ld, sizeof(float) * n, hipMemcpyDeviceToDevice, hd.stream));
+  }
 }
 
 // ---- HipSolver -----------------------------------------------------------------

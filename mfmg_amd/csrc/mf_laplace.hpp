@@ -51,7 +51,7 @@ struct MfOperands
 };
 
 // The same for a block of n_vectors vectors: the columns of x, b, x_prev and out share the leading dimension ld (column c of x
-// starts at x + c * ld elements; ld >= n_dofs, even; the bases aligned to 16 bytes).  out may be x_prev, column for column.
+// starts at x + c * ld elements; ld >= n_dofs, even; the bases aligned to two elements: 16 bytes in FP64, 8 in FP32).  out may be x_prev, column for column.
 template <typename T>
 struct MfBlockOperands
 {
@@ -234,12 +234,12 @@ public:
   }
   HipHandle &handle() const { return _handle; }
 
-  // The operations of `launch` on a block of vectors (mf_laplace_block.hip, FP64): the block is cut by mf_block_groups, groups of
-  // 4 and 2 columns run mf_laplace_block_kernel -- one read of the chunk records for all columns of the group --, a single
-  // column runs the one-vector kernel.  Every column gets the bits of the one-vector launch.  Operators without the block
+  // The operations of `launch` on a block of vectors (mf_laplace_block.hip): the block is cut by mf_block_groups, groups of
+  // 4 and 2 columns run mf_laplace_block_kernel (FP64) or mf_laplace_block_f32_kernel (FP32) -- one read of the chunk records for
+  // all columns of the group --, a single column runs the one-vector kernel.  Every column gets the bits of the one-vector launch.  Operators without the block
   // kernel (block_kernel_available: the cell-constant layout, whose sweep has no record bytes worth sharing; dim = 2; a tail
   // slab) run column by column.  InvalidArgumentExc: n_vectors outside 1 .. 64, ld < n_dofs or odd, a base not aligned to 16
-  // bytes, the out block overlapping the x block, a null operand the mode reads, a context with a communicator.
+  // bytes (FP32: 8), the out block overlapping the x block, a null operand the mode reads, a context with a communicator.
   void launch_block(MfMode mode, MfBlockOperands<T> const &v) const;
   bool block_kernel_available() const;
   // tile of the block kernel (0, 0, 0: chosen from the mesh and the width of the group); ty = 2, 3 or 4
@@ -250,7 +250,7 @@ public:
     _block_tile[2] = tz;
   }
   void get_block_tile(int nv, int &nw, int &ty, int &tz) const;
-  // launches of mf_laplace_block_kernel so far
+  // launches of the block kernel so far
   int64_t block_launches() const { return _block_launches; }
 
   // Bytes of one operator application y = A x.

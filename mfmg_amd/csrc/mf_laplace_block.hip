@@ -28,20 +28,19 @@ namespace
 {
 // LDS of a workgroup of nw wavefronts of ty cell rows at nv vectors: per wavefront pt[nv][ty] and xz[nv][ty + 1] (columns of
 // 64 doubles), the hand-over slots [2][nw][nv][2], per wavefront the id column idz[ty + 1] (held once for all vectors)
-constexpr size_t mf_block_lds(int nv, int nw, int ty)
+constexpr size_t mf_block_lds(int nv, int nw, int ty, size_t elem)
 {
-  return ((size_t)nw * nv * (2 * ty + 1) + (size_t)2 * nw * nv * 2) * 64 * sizeof(double) + (size_t)nw * (ty + 1) * 64 * sizeof(int);
+  return ((size_t)nw * nv * (2 * ty + 1) + (size_t)2 * nw * nv * 2) * 64 * elem + (size_t)nw * (ty + 1) * 64 * sizeof(int);
 }
 
 // The tile body (see mf_laplace_body for the march, the data conventions and the memory pipeline).  TY rows per wavefront at
 // compile time, one request batch per cell row: the NV x requests of the row, its coefficients (16 VGPRs, shared), the epilogue
 // operands of the row it completes -- all issued before the first cell of the row is computed.  The ids of the next pass are
 // prefetched across the barrier.
-template <int NV, int TY, bool AFF>
-__device__ __forceinline__ void mf_laplace_block_body(MfArgs<double> const &a, size_t ldim, unsigned int bid)
+template <typename T, int NV, int TY, bool AFF>
+__device__ __forceinline__ void mf_laplace_block_body(MfArgs<T> const &a, size_t ldim, unsigned int bid)
 {
 #pragma clang fp contract(off)
-  using T = double;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform, keep it scalar
@@ -367,7 +366,14 @@ __device__ __forceinline__ void mf_laplace_block_body(MfArgs<double> const &a, s
 template <int NV, int TY, bool AFF>
 __global__ __launch_bounds__(512) void mf_laplace_block_kernel(MfArgs<double> a, size_t ldim)
 {
-  mf_laplace_block_body<NV, TY, AFF>(a, ldim, blockIdx.x);
+  mf_laplace_block_body<double, NV, TY, AFF>(a, ldim, blockIdx.x);
+}
+
+// the float instances: a kernel of their own name (the profiler and the resource tests tell the two apart)
+template <int NV, int TY, bool AFF>
+__global__ __launch_bounds__(512) void mf_laplace_block_f32_kernel(MfArgs<float> a, size_t ldim)
+{
+  mf_laplace_block_body<float, NV, TY, AFF>(a, ldim, blockIdx.x);
 }
 
 template <int NV>
@@ -382,6 +388,21 @@ void block_kernel_launch(MfArgs<double> const &a, size_t ldim, MfGrid const &gri
       go(mf_laplace_block_kernel<NV, 3, AFF>);
     else
       go(mf_laplace_block_kernel<NV, 4, AFF>);
+  });
+}
+
+template <int NV>
+void block_kernel_launch(MfArgs<float> const &a, size_t ldim, MfGrid const &grid, int ty, bool affine)
+{
+  auto go = [&](auto kernel) { mf_launch(kernel, grid, a, ldim); };
+  with_flag(affine, [&](auto aff) {
+    constexpr bool AFF = decltype(aff)::value;
+    if (ty == 2)
+      go(mf_laplace_block_f32_kernel<NV, 2, AFF>);
+    else if (ty == 3)
+      go(mf_laplace_block_f32_kernel<NV, 3, AFF>);
+    else
+      go(mf_laplace_block_f32_kernel<NV, 4, AFF>);
   });
 }
 } // namespace
@@ -404,7 +425,7 @@ int mf_block_groups(int n_vectors, int widths[kMfBlockMaxGroups])
 template <typename T>
 bool MatrixFreeLaplaceDevice<T>::block_kernel_available() const
 {
-  return std::is_same<T, double>::value && _dim == 3 && !_compact && !_tail && _halo == 1 && _dinv_in_record;
+  return _dim == 3 && !_compact && !_tail && _halo == 1 && _dinv_in_record;
 }
 
 // Tiles of the block kernel.  Its wavefronts hold NV times the requests in flight of a one-vector wavefront and NV times its LDS
@@ -413,16 +434,36 @@ bool MatrixFreeLaplaceDevice<T>::block_kernel_available() const
 // share a compute unit.  Two rows at NV = 2 as well: that instance allocates 156 VGPRs (three wavefronts per SIMD), those of three
 // and four rows 166 - 173 (two).  As for the one-vector kernel the largest tile that still gives every compute unit two rounds
 // is taken.
+// FP32: half the LDS (39 KiB at NV = 4 and four wavefronts of two rows, 22 KiB at NV = 2) and fewer VGPRs of vector state; see
+// kBlockTilesF32 below for the register counts of the twelve instances and the list chosen by timing.
+namespace
+{
+struct BlockTilePrefs
+{
+  int tile[5][3];
+  int waves_per_simd; // the occupancy the list plans (512 VGPRs / waves per SIMD bound the instance)
+};
+// FP64 (see above)
+constexpr BlockTilePrefs kBlockTilesF64[2] = {{{{4, 2, 16}, {4, 2, 8}, {2, 2, 8}, {2, 2, 4}, {1, 2, 4}}, 3},  // NV = 2
+                                              {{{4, 2, 16}, {4, 2, 8}, {2, 2, 8}, {2, 2, 4}, {1, 2, 4}}, 2}}; // NV = 4
+// FP32.  VGPRs of the instances <NV, TY> (AFF false / true), from the code object metadata, no spill, no scratch:
+//   <2, 2>  98 / 101    <2, 3> 121 / 118    <2, 4> 125 / 120     -- all within 128: four wavefronts per SIMD
+//   <4, 2> 141 / 141    <4, 3> 153 / 150    <4, 4> 157 / 152     -- all within 168: three wavefronts per SIMD
+// (FP64: 156 - 173 at NV = 2, 220 - 245 at NV = 4.)  The lists plan that occupancy; their order was chosen by timing at 257^3
+// DoFs.
+constexpr BlockTilePrefs kBlockTilesF32[2] = {{{{4, 2, 16}, {4, 2, 8}, {2, 2, 8}, {2, 2, 4}, {1, 2, 4}}, 4},  // NV = 2
+                                              {{{4, 2, 16}, {4, 2, 8}, {2, 2, 8}, {2, 2, 4}, {1, 2, 4}}, 3}}; // NV = 4
+} // namespace
+
 template <typename T>
 MfTile MatrixFreeLaplaceDevice<T>::choose_block_tile(int nv) const
 {
   if (_block_tile[0] > 0 && _block_tile[1] > 0 && _block_tile[2] > 0)
     return {_block_tile[0], _block_tile[1], _block_tile[2]};
-  static const int pref4[][3] = {{4, 2, 16}, {4, 2, 8}, {2, 2, 8}, {2, 2, 4}, {1, 2, 4}};
-  static const int pref2[][3] = {{4, 2, 16}, {4, 2, 8}, {2, 2, 8}, {2, 2, 4}, {1, 2, 4}};
-  const int(*pref)[3] = nv >= 4 ? pref4 : pref2;
+  BlockTilePrefs const &p = (std::is_same<T, double>::value ? kBlockTilesF64 : kBlockTilesF32)[nv >= 4 ? 1 : 0];
+  const int(*pref)[3] = p.tile;
   constexpr int n_pref = 5;
-  const int64_t waves_wanted = (int64_t)2 * (nv >= 4 ? 8 : 12) * mf_n_cus(); // two rounds of 2 resp. 3 wavefronts per SIMD
+  const int64_t waves_wanted = (int64_t)2 * 4 * p.waves_per_simd * mf_n_cus(); // two rounds at the planned occupancy
   int pick = n_pref - 1;
   for (int c = 0; c < n_pref; ++c)
   {
@@ -452,13 +493,12 @@ void MatrixFreeLaplaceDevice<T>::get_block_tile(int nv, int &nw, int &ty, int &t
 template <typename T>
 void MatrixFreeLaplaceDevice<T>::run_block(MfMode mode, MfBlockOperands<T> const &v, int nv) const
 {
-  if constexpr (std::is_same<T, double>::value)
   {
     const MfTile tile = choose_block_tile(nv);
     const int nw = tile.nw, ty = tile.ty, tz = tile.tz;
     ASSERT_THROW(nw >= 1 && nw <= 8, "1..8 wavefronts per workgroup");
     ASSERT_THROW(ty >= 2 && ty <= 4 && tz >= 1, "the block kernel runs 2, 3 or 4 cell rows per wavefront");
-    const size_t lds = mf_block_lds(nv, nw, ty);
+    const size_t lds = mf_block_lds(nv, nw, ty, sizeof(T));
     ASSERT_THROW(lds <= kMfMaxLds, "operator tile too large for the LDS");
     static const bool graded_env = !(std::getenv("MFMG_MF_GRADED_TILES") && std::string(std::getenv("MFMG_MF_GRADED_TILES")) == "0");
     int all_z = 0;
@@ -472,7 +512,8 @@ void MatrixFreeLaplaceDevice<T>::run_block(MfMode mode, MfBlockOperands<T> const
     const double vec = sizeof(T) * double(_n_dofs);
     const double record = required_bytes_apply() - 2. * vec + (mode >= MfMode::first ? vec : 0.);
     const double vectors = 2. * vec + (mode == MfMode::apply ? 0. : vec) + (mode == MfMode::next ? vec : 0.);
-    hipEvent_t stop = _handle.profiler.begin("mf_laplace_block_kernel", record + nv * vectors, _handle.stream);
+    hipEvent_t stop = _handle.profiler.begin(std::is_same<T, double>::value ? "mf_laplace_block_kernel" : "mf_laplace_block_f32_kernel",
+                                             record + nv * vectors, _handle.stream);
     if (nv == 4)
       block_kernel_launch<4>(a, (size_t)v.ld, grid, ty, _affine_ids);
     else
@@ -481,8 +522,6 @@ void MatrixFreeLaplaceDevice<T>::run_block(MfMode mode, MfBlockOperands<T> const
     KernelProfiler::end(stop, _handle.stream);
     ++_block_launches;
   }
-  else
-    ASSERT_THROW_NOT_IMPLEMENTED("the block kernel is FP64 only");
 }
 
 template <typename T>
@@ -495,14 +534,17 @@ void MatrixFreeLaplaceDevice<T>::launch_block(MfMode mode, MfBlockOperands<T> co
   require(!_handle.comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
   require(v.n_vectors >= 1 && v.n_vectors <= kMfBlockMaxVectors, "a block holds 1 to 64 vectors");
   require(v.ld >= _n_dofs, "the leading dimension of a block must be at least n_dofs");
-  require(v.ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 16 bytes)");
+  // (a lane reads one element at a time: a column need only be aligned to two elements, 16 bytes in FP64 and 8 in FP32)
+  constexpr uintptr_t kAlign = 2 * sizeof(T);
+  require(v.ld % 2 == 0, sizeof(T) == 8 ? "the leading dimension of a block must be even (columns aligned to 16 bytes)"
+                                        : "the leading dimension of a block must be even (columns aligned to 8 bytes)");
   require(v.x != nullptr && v.out != nullptr, "null vector");
   if (mode == MfMode::next)
     mode = mf_smoother_mode(v.x_prev, v.alpha);
   require(mode == MfMode::apply || v.b != nullptr, "null right-hand side");
-  auto aligned = [](void const *p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  auto aligned = [](void const *p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % kAlign == 0; };
   require(aligned(v.x) && aligned(v.out) && (mode == MfMode::apply || aligned(v.b)) && (mode != MfMode::next || aligned(v.x_prev)),
-          "the base of a block must be aligned to 16 bytes");
+          sizeof(T) == 8 ? "the base of a block must be aligned to 16 bytes" : "the base of a block must be aligned to 8 bytes");
   // (the blocks as address ranges: the last column ends n_dofs after its start)
   const int64_t extent = (int64_t)(v.n_vectors - 1) * v.ld + _n_dofs;
   require(v.out + extent <= v.x || v.x + extent <= v.out, "the operator kernel cannot run in place (the out block overlaps the x block)");
@@ -537,4 +579,9 @@ template MfTile MatrixFreeLaplaceDevice<double>::choose_block_tile(int) const;
 template void MatrixFreeLaplaceDevice<double>::get_block_tile(int, int &, int &, int &) const;
 template void MatrixFreeLaplaceDevice<double>::run_block(MfMode, MfBlockOperands<double> const &, int) const;
 template void MatrixFreeLaplaceDevice<double>::launch_block(MfMode, MfBlockOperands<double> const &) const;
+template bool MatrixFreeLaplaceDevice<float>::block_kernel_available() const;
+template MfTile MatrixFreeLaplaceDevice<float>::choose_block_tile(int) const;
+template void MatrixFreeLaplaceDevice<float>::get_block_tile(int, int &, int &, int &) const;
+template void MatrixFreeLaplaceDevice<float>::run_block(MfMode, MfBlockOperands<float> const &, int) const;
+template void MatrixFreeLaplaceDevice<float>::launch_block(MfMode, MfBlockOperands<float> const &) const;
 } // namespace mfmg

@@ -362,6 +362,18 @@ public:
   HipFloatFineLevel(HipHandle &handle, mfmg_hip_mesh_desc const &mesh, Hierarchy<DVector> const &hierarchy);
   // one V-cycle on the FP32 vectors b, x of the fine DoFs
   void apply(float const *b, float *x) const;
+  // The cycle of apply() on the k columns of a float block (column c of b at b + c * ld; 1 to 64 columns, ld >= n_dofs and even,
+  // the bases aligned to 8 bytes, one rank): every column of x gets the bits of apply().  The block is taken in the groups of
+  // mf_block_groups and the cycle runs per group, in the shape of Hierarchy::apply_block: the smoother terms and the residual as
+  // launches of mf_laplace_block_f32_kernel on the group, the restriction, the coarse cycle and the prolongation column by
+  // column.  A group of one runs apply(); so does every group where the float operator has no block kernel or the schedule has a
+  // multi-term sweep (cell-constant layout).  The workspace is one group wide whatever k is, built at the first block call.
+  void apply_block(int k, int64_t ld, float const *b, float *x) const;
+  // widest group apply_block runs as one launch (1: the loop over the columns)
+  int block_width() const { return (_op.block_kernel_available() && _schedule.out_of_place == 0) ? 4 : 1; }
+  // launches of mf_laplace_block_f32_kernel so far; columns of the last apply_block that went through apply()
+  int64_t block_launches() const { return _op.block_launches(); }
+  int64_t block_columns_looped() const { return _block_columns_looped; }
   // the FP32 operator of the level (owned entries; ghost entries of x are exchanged here): y = A x, res = A x - b,
   // out = x + alpha (x - x_prev) - beta D^-1 (A x - b)
   void vmult(float const *x, float *y) const;
@@ -387,6 +399,9 @@ private:
   mutable int _b_fresh_width = 0;
   mutable DeviceBuffer<float> _scratch_a, _scratch_b, _work, _res;
   mutable std::shared_ptr<DVector> _res64, _corr64, _b_coarse, _x_coarse;
+  // apply_block: scratch a and b, residual, work -- one group of columns each, with the leading dimension of the caller's block
+  mutable DeviceBuffer<float> _block_buffers[4];
+  mutable int64_t _block_columns_looped = 0;
 };
 
 // ---- coarse solver -------------------------------------------------------------

@@ -249,6 +249,12 @@ def load() -> C.CDLL:
         "mfmg_hip_block_fgmres_plan": (C.c_int, [i32, P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32)]),
         "mfmg_hip_block_krylov_orthogonalize": (C.c_int, [vp, i64, i32, i64, i32, i32, P(i32), vp, vp, vp, vp, vp]),
         "mfmg_hip_block_krylov_combine": (C.c_int, [vp, i64, i32, i64, i32, i32, P(i32), P(i32), vp, vp, i32, i64, vp]),
+        "mfmg_hip_mf_laplace_f32_block_launch": (C.c_int, [vp, C.c_int, i32, i64, vp, vp, vp, C.c_float, C.c_float, vp]),
+        "mfmg_hip_mf_laplace_f32_block_available": (C.c_int, [vp, P(C.c_int)]),
+        "mfmg_hip_mf_laplace_f32_set_block_tile": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "mfmg_hip_mf_laplace_f32_get_block_tile": (C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]),
+        "mfmg_hip_hierarchy_apply_f32_block": (C.c_int, [vp, i32, i64, vp, vp]),
+        "mfmg_hip_hierarchy_block_info_f32": (C.c_int, [vp, P(i64)]),
         "mfmg_hip_krylov_orthogonalize": (C.c_int, [vp, i64, i64, i32, vp, vp, vp, vp, i32]),
         "mfmg_hip_krylov_combine": (C.c_int, [vp, i64, i64, i32, vp, vp, vp]),
         "mfmg_hip_krylov_orthogonalize_box": (C.c_int, [vp, P(i64), P(i64), P(i64), i32, i64, i32, vp, vp, vp, vp, i32]),
@@ -305,7 +311,9 @@ def load() -> C.CDLL:
                    "mfmg_hip_hierarchy_solve_cg_block", "mfmg_hip_block_cg_retire", "mfmg_hip_hierarchy_operator_apply_block",
                    "mfmg_hip_block_dots", "mfmg_hip_block_cg_direction", "mfmg_hip_block_cg_update",
                    "mfmg_hip_hierarchy_solve_fgmres_block", "mfmg_hip_block_fgmres_plan", "mfmg_hip_block_krylov_orthogonalize",
-                   "mfmg_hip_block_krylov_combine"}
+                   "mfmg_hip_block_krylov_combine", "mfmg_hip_mf_laplace_f32_block_launch", "mfmg_hip_mf_laplace_f32_block_available",
+                   "mfmg_hip_mf_laplace_f32_set_block_tile", "mfmg_hip_mf_laplace_f32_get_block_tile",
+                   "mfmg_hip_hierarchy_apply_f32_block", "mfmg_hip_hierarchy_block_info_f32"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
