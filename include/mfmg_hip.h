@@ -451,6 +451,12 @@ int mfmg_hip_mf_laplace_set_tile(mfmg_hip_mf_laplace_t op, int tile_y, int tile_
 int mfmg_hip_mf_laplace_set_tile_waves(mfmg_hip_mf_laplace_t op, int n_waves);
 /* 1 when the operator keeps one coefficient per cell (see mfmg_hip_context_set_cell_constant_layout) */
 int mfmg_hip_mf_laplace_cell_constant_layout(mfmg_hip_mf_laplace_t op, int *in_use);
+/* uniform = 1 when the operator holds ONE coefficient for the whole mesh: the cell-constant layout with computed ids, all six
+ * faces Dirichlet, one rank, no D^-1 in the records, every stored cell coefficient of the same bits (decided on the device at
+ * construction).  The three-term FP64 sweep then applies the operator as three 1-D stencils, on every tile shape
+ * (MFMG_MF_UNIFORM_SWEEP=0: the mode-space kernels as before); sweeps = how many sweeps of this operator took that kernel so
+ * far (may be NULL).  (addition, no change of the ABI version) */
+int mfmg_hip_mf_laplace_uniform_coefficient(mfmg_hip_mf_laplace_t op, int *uniform, int64_t *sweeps);
 /* the tile in use */
 int mfmg_hip_mf_laplace_get_tile(mfmg_hip_mf_laplace_t op, int *n_waves, int *tile_y, int *tile_z);
 

@@ -647,6 +647,19 @@ class MatrixFreeLaplace:
         check(self._lib.mfmg_hip_mf_laplace_cell_constant_layout(self.handle, C.byref(v)))
         return bool(v.value)
 
+    def uniform_coefficient(self) -> bool:
+        """One coefficient for the whole mesh, all six faces Dirichlet, one rank: the three-term FP64 sweep applies the
+        operator as three 1-D stencils (MFMG_MF_UNIFORM_SWEEP=0 keeps the mode-space kernels)."""
+        v = C.c_int()
+        check(self._lib.mfmg_hip_mf_laplace_uniform_coefficient(self.handle, C.byref(v), None))
+        return bool(v.value)
+
+    def uniform_sweep_launches(self) -> int:
+        """Sweeps of this operator that took the stencil kernel of a uniform coefficient so far."""
+        v, n = C.c_int(), C.c_int64()
+        check(self._lib.mfmg_hip_mf_laplace_uniform_coefficient(self.handle, C.byref(v), C.byref(n)))
+        return int(n.value)
+
     def diagonal_in_record(self) -> bool:
         v = C.c_int()
         check(self._lib.mfmg_hip_mf_laplace_diagonal_in_record(self.handle, C.byref(v)))

@@ -832,6 +832,16 @@ int mfmg_hip_mf_laplace_cell_constant_layout(mfmg_hip_mf_laplace_t op, int *in_u
   });
 }
 
+int mfmg_hip_mf_laplace_uniform_coefficient(mfmg_hip_mf_laplace_t op, int *uniform, int64_t *sweeps)
+{
+  return guarded([&] {
+    require(op && uniform, "null argument");
+    *uniform = op->op->uniform_coefficient() ? 1 : 0;
+    if (sweeps)
+      *sweeps = op->op->uniform_sweep_launches();
+  });
+}
+
 int mfmg_hip_mf_laplace_f32_cell_constant_layout(mfmg_hip_mf_laplace_f32_t op, int *in_use)
 {
   return guarded([&] {

@@ -1073,6 +1073,430 @@ __global__ __launch_bounds__(512, 2) void mf_cheb_fused_narrow_kernel(MfFusedArg
   }
   mf_cheb_fused_body<T, K, TY, DREC, MODES, 0, true, ZERO0>(a, a.wide_tiles + w);
 }
+
+// ---- one coefficient for the whole mesh, all six faces Dirichlet (MatrixFreeLaplaceDevice::uniform_coefficient) ------------
+// On the free DoFs the operator is then ONE 27-point stencil and D^-1 one number, and the stencil is separable:
+//   A = c (K (x) M (x) M + M (x) K (x) M + M (x) M (x) K),   K = 2 f_d (2, -1), M = (4/3, 1/3) per direction
+// (the assembled 1-D stiffness and mass stencils of the cell matrix of cell_row_modes).  Applied direction by direction on the
+// node layer n, with the factors 1/3 and 2 f c folded into the constants q[] and z[] (host, in double):
+//   x:  s = u[i-1] + u[i+1];            mx = 4 u + s,  kx = 2 u - s                              per node
+//   y:  sM = mx[j-1] + mx[j+1], sK likewise;  P = 4 mx + sM,  Q = q0 mx + q1 sM + q2 kx + q3 sK       per node
+//   z:  Z1 = z1p P + z1q Q,  Z0 = z0p P + z0q Q;  (A u) of layer n = Z1(n-1) + Z0(n) + Z1(n+1)
+// About 20 FP64 operations per node and term against 43 per cell and 2 per node in mode space; no coefficient and no D^-1 is
+// loaded or carried.
+//
+// The structure is that of mf_cheb_fused_body with NWC = 12 (tiles and their order, the march in trips of three, the rings two
+// slots deep with the neighbour columns read from them, the carried momentum operand, the descriptors, owner computes, Dirichlet
+// DoFs finished by stage 1).  What differs:
+//  - A stage pass "on the cell layer c" forms the products of the node layer c + 1 alone and completes the DoF layer c from them
+//    and two carries per DoF (cA = Z1(c-1) + Z0(c), cB = Z1(c)).  A stage therefore starts one pass earlier than in the cell form:
+//    its first pass primes the carries with layer start + 1, the second completes them, the third is right -- unless the start is
+//    the bottom of the mesh, whose layer 0 is Dirichlet and contributes zero.
+//  - The exchange: a wavefront exports the x-transformed values (mx, kx) of the node rows next to the two it shares -- with two
+//    cell rows that is its middle row, the only row its neighbours do not hold; both neighbours complete the row they share from the
+//    same operands in the same order (row below + row above).  Two values per wavefront and stage pass (four with three or four
+//    cell rows), one barrier.
+template <typename T>
+struct MfUniformArgs
+{
+  T const *x; // x_0
+  T const *b;
+  T *out;      // x_3
+  T *out_prev; // x_2 (nullptr: not wanted)
+  int Nx, Ny, Nz;
+  unsigned int ncols, ntiles_y, ntiles_z;
+  int own, halo;
+  int TZ;
+  T q[4], z[4];     // the stencil constants above: z = {z0p, z0q, z1p, z1q}
+  T alpha[3], beta[3];
+  T bd[3];          // beta_s D^-1 of the free DoFs
+  AffineIds aff;
+  unsigned int vec_bytes;
+  unsigned int wide_tiles, ntiles_y2; // (MfFusedArgs)
+};
+
+// TY, NWC: cell rows per wavefront; the number of wavefronts where the kernel fixes it (0: that of the launch).  Every shape
+// evaluates a DoF through the same expressions, so the results do not depend on the shape either.
+// XV: values a wavefront exports per stage pass -- (mx, kx) of its node row TY - 1 for the neighbour above and of its node row 1
+// for the neighbour below; with two cell rows these are one row.
+template <typename T, int TY, bool NARROW, bool ZERO0, int NWC>
+__device__ __forceinline__ void mf_cheb_uniform_body(MfUniformArgs<T> const &a, unsigned int w)
+{
+#pragma clang fp contract(off)
+  constexpr int K = 3, R = TY + 1, XV = TY == 2 ? 2 : 4;
+  const int NW = NWC > 0 ? NWC : (int)(blockDim.x >> 6);
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // LDS: per wavefront the rings x_0 .. x_2 ([6 planes][R rows][64 lanes]); then the exports [2][NW][XV][64]
+  T *ring = reinterpret_cast<T *>(smem_raw) + (size_t)wv * (2 * K * R * 64) + lane;
+  // the same planes as the next / the previous lane sees them (the last / first lane: its own, a halo lane)
+  T const *ring_next = ring + (lane == 63 ? 0 : 1);
+  T const *ring_prev = ring - (lane == 0 ? 0 : 1);
+  T *xport = reinterpret_cast<T *>(smem_raw) + (size_t)NW * (2 * K * R * 64) + lane;
+
+  const int wcols = a.ntiles_y2 > 0 ? (int)a.ncols - 1 : (int)a.ncols;
+  int tc, tyi, tzi, lx = lane;
+  if constexpr (NARROW)
+  {
+    const unsigned int v = w - a.wide_tiles;
+    tc = (int)a.ncols - 1;
+    tyi = 2 * (int)(v % a.ntiles_y2) + (lane >> 5); // (per lane)
+    tzi = (int)(v / a.ntiles_y2);
+    lx = lane & 31;
+  }
+  else
+  {
+    tc = (int)(w % (unsigned int)wcols);
+    tyi = (int)((w / (unsigned int)wcols) % a.ntiles_y);
+    tzi = (int)(w / ((unsigned int)wcols * a.ntiles_y));
+  }
+  const bool tile_live = !NARROW || tyi < (int)a.ntiles_y;
+
+  // (all six faces are Dirichlet, no ghost layers)
+  const int ci = tc * a.own - a.halo + lx;
+  const bool lane_free = ci >= 1 && ci < a.Nx - 1;
+  const bool col_owned = tile_live && lx >= a.halo && lx < a.halo + a.own && ci < a.Nx;
+  const int RY = NW * TY - 2 * K + 1;
+  const int Yw = tyi * RY - K + wv * TY;
+  const int own_y0 = tyi * RY, own_y1 = min(own_y0 + RY, a.Ny);
+  const int Z0 = tzi * a.TZ, Z1 = min(Z0 + a.TZ, a.Nz);
+  const unsigned int off_lane = (unsigned int)(a.aff.base + min(max(ci, 0), a.Nx - 1) * a.aff.s0) * (unsigned int)sizeof(T);
+
+  // the constants as uniform values in vector registers (mf_cheb_fused_body, CARRY)
+  auto hold = [](T v) {
+    asm volatile("" : "+v"(v));
+    return v;
+  };
+  const T q0 = hold(a.q[0]), q1 = hold(a.q[1]), q2 = hold(a.q[2]), q3 = hold(a.q[3]);
+  const T z0p = hold(a.z[0]), z0q = hold(a.z[1]), z1p = hold(a.z[2]), z1q = hold(a.z[3]);
+  T held_alpha[K], held_bd[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s)
+  {
+    held_alpha[s] = s > 0 ? hold(a.alpha[s]) : T(0);
+    held_bd[s] = hold(a.bd[s]);
+  }
+  auto fresh = [](int v) {
+    v = __builtin_amdgcn_readfirstlane(v);
+    asm volatile("" : "+s"(v));
+    return v;
+  };
+
+  bool row_free_lane[R], row_own_lane[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+  {
+    const int j = Yw + r;
+    row_free_lane[r] = lane_free && j >= 1 && j < a.Ny - 1;
+    row_own_lane[r] = col_owned && r < TY && j >= own_y0 && j < own_y1; // (the node row two wavefronts share is stored by the upper one)
+  }
+  auto rs_vec = [&](T const *p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(p), 0, a.vec_bytes, 0x00020000); };
+  const int want_prev_i = a.out_prev != nullptr ? 1 : 0;
+  auto want_prev_f = [&]() -> bool { return fresh(want_prev_i) != 0; };
+  const unsigned int row_stride = (unsigned int)a.aff.s1 * (unsigned int)sizeof(T), layer_stride = (unsigned int)a.aff.s2 * (unsigned int)sizeof(T);
+  const int zown0 = Z0, zown1 = Z1;
+  auto layer_free = [&](int n) { return n >= 1 && n < a.Nz - 1; };
+  auto layer_own = [&](int n) { return n >= zown0 && n < zown1; };
+  struct Off
+  {
+    unsigned int v, s;
+  };
+  auto vec_off = [&](int r, int n) -> Off {
+    const unsigned int rowb = (unsigned int)min(max(Yw + r, 0), a.Ny - 1) * row_stride, layb = (unsigned int)min(max(n, 0), a.Nz - 1) * layer_stride;
+    if constexpr (NARROW)
+      return Off{off_lane + rowb, layb};
+    else
+      return Off{off_lane, rowb + layb};
+  };
+  auto ld_vec = [&](__amdgpu_buffer_rsrc_t rs, int r, int n) -> T {
+    const Off o = vec_off(r, n);
+    return BufIO<T>::ld(rs, o.v, o.s);
+  };
+  auto st_vec = [&](T v, __amdgpu_buffer_rsrc_t rs, int r, int n) {
+    const Off o = vec_off(r, n);
+    BufIO<T>::st(v, rs, o.v, o.s);
+  };
+  auto ring_at = [&](int s, int sl, int r) -> T * { return ring + ((2 * s + sl) * R + r) * 64; };
+  auto ring_next_at = [&](int s, int sl, int r) -> T const * { return ring_next + ((2 * s + sl) * R + r) * 64; };
+  auto ring_prev_at = [&](int s, int sl, int r) -> T const * { return ring_prev + ((2 * s + sl) * R + r) * 64; };
+
+  // ---- per-lane state carried from super-pass to super-pass (stage s + 1 uses entry s)
+  T bq[K][R];         // b of the DoF (row r, layer of the stage)
+  T pa[K][R], pb[K][R]; // the z-carries cA and cB
+  T xn[K][R], xq[K][R]; // the momentum operand (mf_cheb_fused_body, CARRY)
+#pragma unroll
+  for (int s = 0; s < K; ++s)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      bq[s][r] = pa[s][r] = pb[s][r] = xn[s][r] = xq[s][r] = T(0);
+
+  // stage s starts on the cell layer max(Z0 - K + (s - 1) - 1, 0): one layer below the start of the cell form (the priming pass)
+  const int cb = max(Z0 - K - 1, 0);
+
+  // ---- prologue: the two x_0 layers and b of the first super-pass
+  {
+    const __amdgpu_buffer_rsrc_t rs_x = rs_vec(a.x), rs_b = rs_vec(a.b);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+    {
+      if constexpr (!ZERO0)
+      {
+        *ring_at(0, 0, r) = ld_vec(rs_x, r, cb);
+        *ring_at(0, 1, r) = ld_vec(rs_x, r, cb + 1);
+      }
+      bq[0][r] = ld_vec(rs_b, r, cb);
+    }
+  }
+
+  unsigned int ex = 0; // stage passes so far (parity of the export buffers)
+
+  // ---- one stage pass: stage S (1-based) on the cell layer c; sl(s, d) = the slot of node layer c + d in ring s
+  auto stage_pass = [&](auto tag, int c, auto sl) {
+    constexpr int S = decltype(tag)::value;
+    constexpr bool kApply = !(S == 1 && ZERO0); // (A 0 = 0: no arithmetic, no exchange, no barrier)
+    const bool lo_free = layer_free(c), hi_free = layer_free(c + 1);
+    const bool l_own = layer_own(c);
+    T xown[R], mx[R], kx[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+    {
+      xown[r] = mx[r] = kx[r] = T(0);
+      if constexpr (kApply)
+      {
+        const T l = *ring_at(S - 1, sl(S - 1, 0), r), u = *ring_at(S - 1, sl(S - 1, 1), r);
+        xown[r] = l;
+        if constexpr (S < K)
+          xn[S - 1][r] = l;
+        T um, sm;
+        if constexpr (S == 1)
+        {
+          // x_0 sits in the ring as it was read; Dirichlet and out-of-mesh values enter the stencil as zero
+          um = (row_free_lane[r] && hi_free) ? u : T(0);
+          sm = from_prev_lane(um) + from_next_lane(um);
+        }
+        else
+        {
+          um = u;
+          sm = *ring_prev_at(S - 1, sl(S - 1, 1), r) + *ring_next_at(S - 1, sl(S - 1, 1), r);
+        }
+        mx[r] = fmadd<T>(T(4), um, sm);
+        kx[r] = fmadd<T>(T(2), um, -sm);
+      }
+    }
+    if constexpr (kApply)
+    {
+      T *xp = xport + (size_t)((ex & 1) * NW + wv) * XV * 64;
+      xp[0] = mx[TY - 1];
+      xp[64] = kx[TY - 1];
+      if constexpr (XV == 4)
+      {
+        xp[128] = mx[1];
+        xp[192] = kx[1];
+      }
+    }
+    // the y-stencil of a node row from the rows below (b), its own and above (a); then the z-stencil with the carries
+    auto apply_yz = [&](T mb, T kb, T m, T k, T ma, T ka, T &cA, T &cB) -> T {
+      const T sM = mb + ma, sK = kb + ka;
+      const T P = fmadd<T>(T(4), m, sM);
+      const T Q = fmadd<T>(q3, sK, fmadd<T>(q2, k, fmadd<T>(q1, sM, q0 * m)));
+      const T Zn = fmadd<T>(z1q, Q, z1p * P), Zd = fmadd<T>(z0q, Q, z0p * P);
+      const T yv = cA + Zn;
+      cA = cB + Zd;
+      cB = Zn;
+      return yv;
+    };
+    // one DoF (row r, layer c) of this stage is complete: yv = (A x_{S-1}) there
+    auto finish = [&](auto rtag, T yv) {
+      constexpr int r = decltype(rtag)::value;
+      const bool fr = row_free_lane[r] && lo_free;
+      const bool st = row_own_lane[r] && l_own;
+      if constexpr (S == 1)
+      {
+        const T x0 = xown[r], lb = bq[0][r];
+        const T x1 = fmadd<T>(-held_bd[0], yv - lb, x0);
+        *ring_at(1, sl(1, 0), r) = fr ? x1 : T(0);
+        // Dirichlet DoFs: identity rows with D^-1 = 1 -- the whole recurrence here
+        if (st && !fr)
+        {
+          T xa = x0, xb = fmadd<T>(-a.beta[0], x0 - lb, x0); // x_{s-1}, x_s
+#pragma unroll
+          for (int s = 1; s < K; ++s)
+          {
+            const T xc = fmadd<T>(-a.beta[s], xb - lb, fmadd<T>(a.alpha[s], xb - xa, xb));
+            xa = xb;
+            xb = xc;
+          }
+          st_vec(xb, rs_vec(a.out), r, c);
+          if (want_prev_f())
+            st_vec(xa, rs_vec(a.out_prev), r, c);
+        }
+      }
+      else
+      {
+        const T xo = xown[r];
+        const T xoo = xq[S - 2][r]; // (zero from a zero guess)
+        const T xoo_m = (S == 2) ? (fr ? xoo : T(0)) : xoo; // (x_0 sits in its ring unmasked)
+        const T xs = fmadd<T>(-held_bd[S - 1], yv - bq[S - 1][r], fmadd<T>(held_alpha[S - 1], xo - xoo_m, xo));
+        if constexpr (S < K)
+        {
+          *ring_at(S, sl(S, 0), r) = fr ? xs : T(0);
+          if constexpr (S == K - 1)
+            if (st && fr && want_prev_f())
+              st_vec(xs, rs_vec(a.out_prev), r, c);
+        }
+        else
+        {
+          if (st && fr)
+            st_vec(xs, rs_vec(a.out), r, c);
+        }
+      }
+    };
+    // the rows between the wavefront's own cells: their neighbour rows are the wavefront's own
+    auto inner = [&](auto rtag) {
+      constexpr int r = decltype(rtag)::value;
+      T yv = T(0);
+      if constexpr (kApply)
+        yv = apply_yz(mx[r - 1], kx[r - 1], mx[r], kx[r], mx[r + 1], kx[r + 1], pa[S - 1][r], pb[S - 1][r]);
+      finish(rtag, yv);
+    };
+    inner(IntTag<1>{});
+    if constexpr (TY >= 3)
+      inner(IntTag<2>{});
+    if constexpr (TY >= 4)
+      inner(IntTag<3>{});
+    // (LDS only: the requests of the next super-pass stay in flight across the barrier)
+    if constexpr (kApply)
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // the rows shared with the neighbours: both wavefronts complete them, with the same operands in the same order
+    {
+      T lom = T(0), lok = T(0), him = T(0), hik = T(0);
+      const int wvu = fresh(wv);
+      if (kApply && wvu > 0)
+      {
+        T const *ip = xport + (size_t)((ex & 1) * NW + wvu - 1) * XV * 64;
+        lom = ip[0];
+        lok = ip[64];
+      }
+      if (kApply && wvu + 1 < NW)
+      {
+        T const *ip = xport + (size_t)((ex & 1) * NW + wvu + 1) * XV * 64;
+        him = ip[XV == 4 ? 128 : 0];
+        hik = ip[XV == 4 ? 192 : 64];
+      }
+      {
+        T yv = T(0);
+        if constexpr (kApply)
+          yv = apply_yz(lom, lok, mx[0], kx[0], mx[1], kx[1], pa[S - 1][0], pb[S - 1][0]);
+        finish(IntTag<0>{}, yv);
+      }
+      {
+        T yv = T(0);
+        if constexpr (kApply)
+          yv = apply_yz(mx[TY - 1], kx[TY - 1], mx[TY], kx[TY], him, hik, pa[S - 1][TY], pb[S - 1][TY]);
+        finish(IntTag<TY>{}, yv);
+      }
+    }
+    if constexpr (kApply)
+      ++ex;
+  };
+
+  // ---- the march (mf_cheb_fused_body; the stages start one super-pass earlier, see above)
+  auto super_pass = [&](int c1, auto sl) {
+    T pfx[R], pfb[R];
+    const __amdgpu_buffer_rsrc_t rs_x = rs_vec(a.x), rs_b = rs_vec(a.b);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+    {
+      pfx[r] = T(0);
+      if constexpr (!ZERO0)
+        pfx[r] = ld_vec(rs_x, r, c1 + 2);
+      pfb[r] = ld_vec(rs_b, r, c1 + 1);
+    }
+    if (c1 < a.Nz)
+      stage_pass(IntTag<1>{}, c1, [&](int s, int d) { return sl(s, d); });
+    if (c1 >= max(Z0 - 2, 1) && c1 <= a.Nz)
+      stage_pass(IntTag<2>{}, c1 - 1, [&](int s, int d) { return sl(s, d - 1); });
+    if (c1 >= max(Z0, 2))
+      stage_pass(IntTag<3>{}, c1 - 2, [&](int s, int d) { return sl(s, d - 2); });
+#pragma unroll
+    for (int s = K - 1; s >= 1; --s)
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        bq[s][r] = bq[s - 1][r];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+    {
+      bq[0][r] = pfb[r];
+#pragma unroll
+      for (int s = 0; s + 2 <= K; ++s)
+        xq[s][r] = xn[s][r];
+      if constexpr (!ZERO0)
+        *ring_at(0, sl(0, 2), r) = pfx[r];
+    }
+  };
+  const int c_last = min(Z1 + 1, a.Nz + 1);
+  int c1 = cb, base2 = 0;
+  auto sl_at = [&](auto jt) {
+    constexpr int j = decltype(jt)::value;
+    return [&](int, int k) { return (base2 + j + k) & 1; };
+  };
+  for (;;)
+  {
+    super_pass(c1, sl_at(IntTag<0>{}));
+    if (++c1 > c_last)
+      break;
+    super_pass(c1, sl_at(IntTag<1>{}));
+    if (++c1 > c_last)
+      break;
+    super_pass(c1, sl_at(IntTag<2>{}));
+    if (++c1 > c_last)
+      break;
+    base2 = (base2 + K) & 1;
+  }
+}
+
+template <typename T, bool NARROW_TOO, bool ZERO0>
+__global__ __launch_bounds__(64 * kWgWaves12, 3) void mf_cheb_fused_uniform_kernel(MfUniformArgs<T> a)
+{
+  // (the tile order of mf_cheb_fused_kernel)
+  const unsigned int n_tiles = NARROW_TOO ? a.wide_tiles + a.ntiles_y2 * a.ntiles_z : a.wide_tiles;
+  unsigned int w = blockIdx.x;
+  if (n_tiles >= 64)
+  {
+    const unsigned int per_xcd = (n_tiles + 7) / 8;
+    w = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    if (w >= n_tiles)
+      return;
+  }
+  if constexpr (NARROW_TOO)
+  {
+    if (w >= a.wide_tiles)
+    {
+      mf_cheb_uniform_body<T, kWgRows12, true, ZERO0, kWgWaves12>(a, w);
+      return;
+    }
+  }
+  mf_cheb_uniform_body<T, kWgRows12, false, ZERO0, kWgWaves12>(a, w);
+}
+
+// The same stencil on the other shapes of the three-term sweep (up to eight wavefronts of TY = 2, 3 or 4 rows, two per SIMD; a
+// narrow last column as ordinary tiles): a uniform operator gives the same bits on every tile shape.
+template <typename T, int TY, bool ZERO0>
+__global__ __launch_bounds__(512, 2) void mf_cheb_fused_uniform_rows_kernel(MfUniformArgs<T> a)
+{
+  // (the tile order of mf_cheb_fused_kernel)
+  const unsigned int n_tiles = a.wide_tiles;
+  unsigned int w = blockIdx.x;
+  if (n_tiles >= 64)
+  {
+    const unsigned int per_xcd = (n_tiles + 7) / 8;
+    w = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    if (w >= n_tiles)
+      return;
+  }
+  mf_cheb_uniform_body<T, TY, false, ZERO0, 0>(a, w);
+}
 } // namespace
 
 // ---- host side --------------------------------------------------------------------------------------------------
@@ -1277,8 +1701,78 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
         return with_guess(std::true_type());
     with_guess(std::false_type());
   };
+  // one coefficient for the whole mesh (uniform_coefficient): the operator as three 1-D stencils.  MFMG_MF_UNIFORM_SWEEP=0 keeps
+  // the mode-space kernels (the A/B switch); the reference arithmetic keeps its own.
+  // (read at every sweep, not once: a process can measure both)
+  char const *uniform_env = std::getenv("MFMG_MF_UNIFORM_SWEEP");
+  const bool uniform_off = uniform_env && std::string(uniform_env) == "0";
+  // (every tile shape of the three-term sweep has the stencil: the results of an operator do not depend on the shape asked for)
+  bool uniform_taken = false;
+  if constexpr (std::is_same<T, double>::value)
+    if (_uniform && modes && !uniform_off && n_terms == 3 && dbg == 0)
+    {
+      MfUniformArgs<T> u{};
+      u.x = a.x;
+      u.b = a.b;
+      u.out = a.out;
+      u.out_prev = a.out_prev;
+      u.Nx = a.Nx;
+      u.Ny = a.Ny;
+      u.Nz = a.Nz;
+      u.ncols = a.ncols;
+      u.ntiles_y = a.ntiles_y;
+      u.ntiles_z = a.ntiles_z;
+      u.own = a.own;
+      u.halo = a.halo;
+      u.TZ = a.TZ;
+      double f[3];
+      MfArgs<T> fa{};
+      mf_cell_factors(fa, _h, f); // (kd as the other kernels get it)
+      const double c = _uniform_coef;
+      u.q[0] = 4. * f[1] * c / 3.;
+      u.q[1] = -2. * f[1] * c / 3.;
+      u.q[2] = 8. * f[0] * c / 3.;
+      u.q[3] = 2. * f[0] * c / 3.;
+      u.z[0] = 4. * f[2] * c / 9.;
+      u.z[1] = 4. / 3.;
+      u.z[2] = -2. * f[2] * c / 9.;
+      u.z[3] = 1. / 3.;
+      // D^-1 of a free DoF as the other kernels derive it: 1 / (kd * the sum of the eight cell coefficients)
+      const double dinv = 1. / (fa.kd * (8. * c));
+      for (int s = 0; s < 3; ++s)
+      {
+        u.alpha[s] = a.alpha[s];
+        u.beta[s] = a.beta[s];
+        u.bd[s] = a.beta[s] * dinv;
+      }
+      u.aff = a.aff;
+      u.vec_bytes = a.vec_bytes;
+      // (the narrow pairing of a last chunk column: the twelve-wavefront kernel alone carries that body)
+      u.ntiles_y2 = wg12 ? a.ntiles_y2 : 0u;
+      u.wide_tiles = wg12 ? a.wide_tiles : a.ncols * a.ntiles_y * a.ntiles_z;
+      const unsigned int n_blocks_u = mf_xcd_grid((uint64_t)u.wide_tiles + (uint64_t)u.ntiles_y2 * a.ntiles_z);
+      const size_t lds_u = ((size_t)nw * ring_planes(3, true) * (ty + 1) + (size_t)2 * nw * (ty == 2 ? 2 : 4)) * 64 * sizeof(T);
+      ASSERT_THROW(lds_u <= kMfMaxLds, "tile of the multi-term sweep too large for the LDS");
+      auto go_u = [&](auto kernel) { mf_launch(kernel, MfGrid{n_blocks_u, nw, lds_u, st}, u); };
+      if (wg12)
+        with_flag(narrow, [&](auto nt) {
+          constexpr bool NT = decltype(nt)::value;
+          if (zero_guess)
+            go_u(mf_cheb_fused_uniform_kernel<T, NT, true>);
+          else
+            go_u(mf_cheb_fused_uniform_kernel<T, NT, false>);
+        });
+      else if (ty == 3 && zero_guess)
+        go_u(mf_cheb_fused_uniform_rows_kernel<T, 3, true>); // (fused_zero_guess_available: three rows)
+      else
+        with_tile_rows<4>(ty, [&](auto tt) { go_u(mf_cheb_fused_uniform_rows_kernel<T, decltype(tt)::value, false>); });
+      ++_uniform_sweeps;
+      uniform_taken = true;
+    }
   // (timing experiments, FP64: the kernels without barrier / without division)
-  if (wg12)
+  if (uniform_taken)
+    ;
+  else if (wg12)
   {
     // (one launch also where the narrow tiles are asked to be split off: the shape has no kernels of one body)
     if constexpr (std::is_same<T, double>::value)

@@ -687,6 +687,30 @@ __global__ void mf_sweep_dinv_kernel(unsigned char const *rec, size_t rec_bytes,
     dinv[(unsigned int)id0 & kIdMask] = T(1) / (kd * sum8);
   }
 }
+
+// Do all real cells hold the coefficient of cell (0, 0, 0), bit for bit (cell-constant records)?  Counts the others.
+template <typename T>
+__global__ void mf_uniform_coefficient_kernel(unsigned char const *rec, size_t rec_bytes, int nx, int ny, int nz, int Ny, int ncols, int own,
+                                              int halo, int *n_other)
+{
+  typedef typename std::conditional<sizeof(T) == 8, unsigned long long, unsigned int>::type bits_t;
+  const int64_t n = (int64_t)nx * ny * nz;
+  int l0;
+  const size_t r0 = chunk_of(0, 0, 0, Ny, ncols, own, halo, l0);
+  const bits_t first = reinterpret_cast<bits_t const *>(rec + r0 * rec_bytes + Rec<T, true>::kCoefOff)[l0];
+  bool other = false;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+  {
+    const int i = t % nx;
+    const int j = (t / nx) % ny;
+    const int k = t / ((int64_t)nx * ny);
+    int lane;
+    const size_t r = chunk_of(i, j, k, Ny, ncols, own, halo, lane);
+    other = other || reinterpret_cast<bits_t const *>(rec + r * rec_bytes + Rec<T, true>::kCoefOff)[lane] != first;
+  }
+  if (other)
+    atomicAdd(n_other, 1);
+}
 } // namespace
 
 // ---- dim = 2 --------------------------------------------------------------------------------------------------
@@ -1070,6 +1094,28 @@ MatrixFreeLaplaceDevice<T>::MatrixFreeLaplaceDevice(HipHandle &handle, mfmg_hip_
                          _N[1], _N[2], _ncols, _own, _halo, fa.kd, _sweep_dinv.data());
       MFMG_HIP_CHECK(hipGetLastError());
       _sweep_dinv_read = true;
+    }
+  }
+  // one coefficient for the whole mesh (uniform_coefficient): decided here, once -- the records do not change afterwards
+  {
+    bool plain_box = _compact && _affine_ids && _halo >= 3 && !_dinv_in_record && !sub_mesh && !handle.comm.enabled() && _affine.faces == 63;
+    for (int d = 0; d < 3; ++d)
+      plain_box = plain_box && _affine.ghost_lo[d] == 0 && _affine.ghost_hi[d] == 0;
+    if (plain_box)
+    {
+      MFMG_HIP_CHECK(hipMemsetAsync(bad.data(), 0, sizeof(int), st));
+      hipLaunchKernelGGL(mf_uniform_coefficient_kernel<T>, dim3(n_blocks_for(nc, 256, 1 << 16)), dim3(256), 0, st, _rec.data(), _rec_bytes,
+                         _n[0], _n[1], _n[2], _N[1], _ncols, _own, _halo, bad.data());
+      MFMG_HIP_CHECK(hipGetLastError());
+      if (bad.download(st)[0] == 0)
+      {
+        // (the one coefficient: cell (0, 0, 0) sits in lane _halo of the first record)
+        T c0 = T(0);
+        MFMG_HIP_CHECK(hipMemcpyAsync(&c0, _rec.data() + Rec<T, true>::kCoefOff + (size_t)_halo * sizeof(T), sizeof(T), hipMemcpyDeviceToHost, st));
+        MFMG_HIP_CHECK(hipStreamSynchronize(st));
+        _uniform_coef = double(c0);
+        _uniform = _uniform_coef > 0.;
+      }
     }
   }
   MFMG_HIP_CHECK(hipStreamSynchronize(st));

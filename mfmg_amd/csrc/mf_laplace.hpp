@@ -145,6 +145,14 @@ public:
                           bool sub_mesh = false);
   bool cell_constant_layout() const { return _compact; }
   bool diagonal_in_record() const { return _dinv_in_record; }
+  // One coefficient for the whole mesh: the cell-constant layout with a numbering the kernel computes, all six faces Dirichlet,
+  // no ghost layers, no D^-1 in the records, and every stored cell coefficient of the same bits (a reduction on the device at
+  // construction).  The operator on the free DoFs is then one 27-point stencil and D^-1 one number: the three-term FP64 sweep
+  // applies it as three 1-D stencils on every tile shape (mf_cheb_fused.hip: mf_cheb_fused_uniform_kernel for twelve wavefronts of
+  // two rows, mf_cheb_fused_uniform_rows_kernel for the others) unless MFMG_MF_UNIFORM_SWEEP=0 or the reference arithmetic is asked for.
+  bool uniform_coefficient() const { return _uniform; }
+  // sweeps that took that kernel so far
+  int64_t uniform_sweep_launches() const { return _uniform_sweeps; }
 
   int64_t n_dofs() const { return _n_dofs; }
   int dim() const { return _dim; }
@@ -331,6 +339,9 @@ private:
   DeviceBuffer<T> _diag, _dinv;
   DeviceBuffer<T> _sweep_dinv; // (see sweep_diagonal_inverse)
   bool _sweep_dinv_read = false;
+  bool _uniform = false; // (see uniform_coefficient)
+  double _uniform_coef = 0.;
+  mutable int64_t _uniform_sweeps = 0;
   int _tile_y = 0, _tile_z = 0, _tile_waves = 0;
   bool _compact = false;
   bool _dinv_in_record = true; // D^-1 is part of the chunk records (always for eight coefficients per cell)

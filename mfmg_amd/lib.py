@@ -158,6 +158,7 @@ def load() -> C.CDLL:
         "mfmg_hip_mf_laplace_ids_computed": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_mf_laplace_f32_ids_computed": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_mf_laplace_cell_constant_layout": (C.c_int, [vp, P(C.c_int)]),
+        "mfmg_hip_mf_laplace_uniform_coefficient": (C.c_int, [vp, P(C.c_int), P(i64)]),
         "mfmg_hip_context_halo_layout": (C.c_int, [vp, i32, P(i64), P(i64), P(i64), P(i64)]),
         "mfmg_hip_cell_contraction": (C.c_int, [vp, C.c_int, C.c_int, i64, vp, vp, vp, P(dbl)]),
         "mfmg_hip_profile_enable": (C.c_int, [vp, C.c_int]),
@@ -313,7 +314,8 @@ def load() -> C.CDLL:
                    "mfmg_hip_hierarchy_solve_fgmres_block", "mfmg_hip_block_fgmres_plan", "mfmg_hip_block_krylov_orthogonalize",
                    "mfmg_hip_block_krylov_combine", "mfmg_hip_mf_laplace_f32_block_launch", "mfmg_hip_mf_laplace_f32_block_available",
                    "mfmg_hip_mf_laplace_f32_set_block_tile", "mfmg_hip_mf_laplace_f32_get_block_tile",
-                   "mfmg_hip_hierarchy_apply_f32_block", "mfmg_hip_hierarchy_block_info_f32"}
+                   "mfmg_hip_hierarchy_apply_f32_block", "mfmg_hip_hierarchy_block_info_f32",
+                   "mfmg_hip_mf_laplace_uniform_coefficient"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
