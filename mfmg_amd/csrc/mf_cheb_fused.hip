@@ -1096,6 +1096,13 @@ __global__ __launch_bounds__(512, 2) void mf_cheb_fused_narrow_kernel(MfFusedArg
 //    cell rows that is its middle row, the only row its neighbours do not hold; both neighbours complete the row they share from the
 //    same operands in the same order (row below + row above).  Two values per wavefront and stage pass (four with three or four
 //    cell rows), one barrier.
+//  - Twelve wavefronts (mf_cheb_fused_uniform_kernel) share no row at all.  A node row is completed from the (mx, kx) of the rows
+//    below and above it, so the second evaluation of a shared row -- which the cell form needs, its two cell rows both contribute --
+//    is repetition here.  Each wavefront holds R = 3 node rows of its own, Yw = tyi RY - K + 3 wv with RY = 12 * 3 - 2 K = 30 owned
+//    rows per tile.  It exports (mx, kx) of its rows 0 and R - 1 (four values per stage pass); its row 0 is completed with the lower
+//    neighbour's row R - 1 as "below", its row R - 1 with the upper neighbour's row 0 as "above", its middle row from its own; the
+//    first and the last wavefront take zeros on the missing side (halo rows).  Still one barrier and the operands in the same
+//    order: the bits of the other shapes.
 template <typename T>
 struct MfUniformArgs
 {
@@ -1118,12 +1125,15 @@ struct MfUniformArgs
 // TY, NWC: cell rows per wavefront; the number of wavefronts where the kernel fixes it (0: that of the launch).  Every shape
 // evaluates a DoF through the same expressions, so the results do not depend on the shape either.
 // XV: values a wavefront exports per stage pass -- (mx, kx) of its node row TY - 1 for the neighbour above and of its node row 1
-// for the neighbour below; with two cell rows these are one row.
+// for the neighbour below; with two cell rows these are one row.  DISJ (NWC = 12): the R node rows of a wavefront are its own, it
+// exports its rows R - 1 and 0 (see above).
 template <typename T, int TY, bool NARROW, bool ZERO0, int NWC>
 __device__ __forceinline__ void mf_cheb_uniform_body(MfUniformArgs<T> const &a, unsigned int w)
 {
 #pragma clang fp contract(off)
-  constexpr int K = 3, R = TY + 1, XV = TY == 2 ? 2 : 4;
+  constexpr bool DISJ = NWC == kWgWaves12;
+  static_assert(!DISJ || TY == kWgRows12, "disjoint node rows: three per wavefront");
+  constexpr int K = 3, R = TY + 1, XV = (TY == 2 && !DISJ) ? 2 : 4;
   const int NW = NWC > 0 ? NWC : (int)(blockDim.x >> 6);
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63;
@@ -1157,8 +1167,8 @@ __device__ __forceinline__ void mf_cheb_uniform_body(MfUniformArgs<T> const &a, 
   const int ci = tc * a.own - a.halo + lx;
   const bool lane_free = ci >= 1 && ci < a.Nx - 1;
   const bool col_owned = tile_live && lx >= a.halo && lx < a.halo + a.own && ci < a.Nx;
-  const int RY = NW * TY - 2 * K + 1;
-  const int Yw = tyi * RY - K + wv * TY;
+  const int RY = DISJ ? NW * R - 2 * K : NW * TY - 2 * K + 1;
+  const int Yw = tyi * RY - K + wv * (DISJ ? R : TY);
   const int own_y0 = tyi * RY, own_y1 = min(own_y0 + RY, a.Ny);
   const int Z0 = tzi * a.TZ, Z1 = min(Z0 + a.TZ, a.Nz);
   const unsigned int off_lane = (unsigned int)(a.aff.base + min(max(ci, 0), a.Nx - 1) * a.aff.s0) * (unsigned int)sizeof(T);
@@ -1189,8 +1199,19 @@ __device__ __forceinline__ void mf_cheb_uniform_body(MfUniformArgs<T> const &a, 
   {
     const int j = Yw + r;
     row_free_lane[r] = lane_free && j >= 1 && j < a.Ny - 1;
-    row_own_lane[r] = col_owned && r < TY && j >= own_y0 && j < own_y1; // (the node row two wavefronts share is stored by the upper one)
+    if constexpr (DISJ)
+      // no row is shared.  The owned rows of a tile are whole wavefronts, 1 .. NW - 2 (K = R), up to the last row of the mesh:
+      // one mask for the three rows -- a free DoF lies inside the mesh, a Dirichlet DoF asks for its row where it is stored
+      // (row_in_mesh: rarely, and three lane masks less to carry through the march)
+      row_own_lane[r] = col_owned && wv >= 1 && wv < NW - 1;
+    else
+      row_own_lane[r] = col_owned && r < TY && j >= own_y0 && j < own_y1; // (the node row two wavefronts share is stored by the upper one)
   }
+  int yw_lane = Yw;
+  auto row_in_mesh = [&](int r) -> bool {
+    asm volatile("" : "+v"(yw_lane)); // (anew at every use: not a mask per row held across the march)
+    return yw_lane + r < a.Ny;
+  };
   auto rs_vec = [&](T const *p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(p), 0, a.vec_bytes, 0x00020000); };
   const int want_prev_i = a.out_prev != nullptr ? 1 : 0;
   auto want_prev_f = [&]() -> bool { return fresh(want_prev_i) != 0; };
@@ -1287,12 +1308,12 @@ __device__ __forceinline__ void mf_cheb_uniform_body(MfUniformArgs<T> const &a, 
     if constexpr (kApply)
     {
       T *xp = xport + (size_t)((ex & 1) * NW + wv) * XV * 64;
-      xp[0] = mx[TY - 1];
-      xp[64] = kx[TY - 1];
+      xp[0] = mx[DISJ ? R - 1 : TY - 1];
+      xp[64] = kx[DISJ ? R - 1 : TY - 1];
       if constexpr (XV == 4)
       {
-        xp[128] = mx[1];
-        xp[192] = kx[1];
+        xp[128] = mx[DISJ ? 0 : 1];
+        xp[192] = kx[DISJ ? 0 : 1];
       }
     }
     // the y-stencil of a node row from the rows below (b), its own and above (a); then the z-stencil with the carries
@@ -1317,7 +1338,7 @@ __device__ __forceinline__ void mf_cheb_uniform_body(MfUniformArgs<T> const &a, 
         const T x1 = fmadd<T>(-held_bd[0], yv - lb, x0);
         *ring_at(1, sl(1, 0), r) = fr ? x1 : T(0);
         // Dirichlet DoFs: identity rows with D^-1 = 1 -- the whole recurrence here
-        if (st && !fr)
+        if (st && !fr && (!DISJ || row_in_mesh(r)))
         {
           T xa = x0, xb = fmadd<T>(-a.beta[0], x0 - lb, x0); // x_{s-1}, x_s
 #pragma unroll
@@ -1369,6 +1390,7 @@ __device__ __forceinline__ void mf_cheb_uniform_body(MfUniformArgs<T> const &a, 
     if constexpr (kApply)
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     // the rows shared with the neighbours: both wavefronts complete them, with the same operands in the same order
+    // (DISJ: the wavefront's first and last row, completed by it alone from the neighbour's last / first row)
     {
       T lom = T(0), lok = T(0), him = T(0), hik = T(0);
       const int wvu = fresh(wv);
@@ -1538,6 +1560,31 @@ bool MatrixFreeLaplaceDevice<T>::fused_wg12_capable(int n_terms) const
   return std::is_same<T, double>::value && n_terms == 3 && !_dinv_in_record;
 }
 
+// MFMG_MF_FUSED_DBG (timing experiments: the kernels without barrier / without division), read once
+static int fused_dbg()
+{
+  static const int dbg = std::getenv("MFMG_MF_FUSED_DBG") ? std::atoi(std::getenv("MFMG_MF_FUSED_DBG")) : 0;
+  return dbg;
+}
+
+// The stencil sweep of a uniform coefficient on twelve wavefronts (smoother_sweep: mf_cheb_fused_uniform_kernel): the node rows of
+// its wavefronts are disjoint, a y-tile owns 12 * 3 - 2 * 3 = 30 rows.  MFMG_MF_UNIFORM_SWEEP is read at every call, as there.
+template <typename T>
+bool MatrixFreeLaplaceDevice<T>::uniform_disjoint_rows(int n_terms, int nw, int ty) const
+{
+  if (!(std::is_same<T, double>::value && _uniform && !_fused_reference_arithmetic && n_terms == 3 && fused_dbg() == 0 && nw == kWgWaves12 && ty == kWgRows12))
+    return false;
+  char const *uniform_env = std::getenv("MFMG_MF_UNIFORM_SWEEP");
+  return !(uniform_env && std::string(uniform_env) == "0");
+}
+
+// owned node rows of a y-tile
+template <typename T>
+int MatrixFreeLaplaceDevice<T>::fused_tile_owned_rows(int n_terms, int nw, int ty) const
+{
+  return uniform_disjoint_rows(n_terms, nw, ty) ? nw * (ty + 1) - 2 * n_terms : nw * ty - 2 * n_terms + 1;
+}
+
 template <typename T>
 void MatrixFreeLaplaceDevice<T>::choose_fused_tile(int n_terms, int &nw, int &ty, int &tz) const
 {
@@ -1575,7 +1622,7 @@ void MatrixFreeLaplaceDevice<T>::choose_fused_tile(int n_terms, int &nw, int &ty
   }
   ASSERT_THROW(((nw >= 1 && nw <= 8) || (nw == kWgWaves12 && ty == kWgRows12)) && (ty == 2 || ty == 3 || ty == 4),
                "tile of the multi-term sweep: 1..8 wavefronts of 2, 3 or 4 rows, or 12 of 2");
-  const int ry = nw * ty - 2 * n_terms + 1;
+  const int ry = fused_tile_owned_rows(n_terms, nw, ty);
   ASSERT_THROW(ry >= 1, "tile of the multi-term sweep too small for its halo rows");
   if (tz > 0)
     return;
@@ -1619,7 +1666,9 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
   a.Ny = _N[1];
   a.Nz = _N[2];
   a.ncols = (unsigned int)_ncols;
-  const int ry = nw * ty - 2 * n_terms + 1;
+  // (a uniform coefficient on twelve wavefronts: the tiles of mf_cheb_fused_uniform_kernel, which this call then launches)
+  const bool disjoint_rows = uniform_disjoint_rows(n_terms, nw, ty);
+  const int ry = fused_tile_owned_rows(n_terms, nw, ty);
   a.ntiles_y = (unsigned int)((_N[1] + ry - 1) / ry);
   a.ntiles_z = (unsigned int)((_N[2] + tz - 1) / tz);
   a.own = _own;
@@ -1682,7 +1731,7 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
   };
   // the arithmetic of the cell kernel: mode space (default) or the bit-for-bit twin of the one-term kernel (set_fused_reference)
   const bool modes = !_fused_reference_arithmetic;
-  static const int dbg = std::getenv("MFMG_MF_FUSED_DBG") ? std::atoi(std::getenv("MFMG_MF_FUSED_DBG")) : 0;
+  const int dbg = fused_dbg();
   // the kernel <K, TY, DREC, MODES> with or without the body of a narrow last column (fused_narrow_capable: two shapes carry it)
   // and, from a zero guess, its ZERO0 form (fused_zero_guess_available: one shape has it)
   auto sweep = [&](auto kt, auto tt, auto dt, auto mt) {
@@ -1704,8 +1753,9 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
   // one coefficient for the whole mesh (uniform_coefficient): the operator as three 1-D stencils.  MFMG_MF_UNIFORM_SWEEP=0 keeps
   // the mode-space kernels (the A/B switch); the reference arithmetic keeps its own.
   // (read at every sweep, not once: a process can measure both)
+  // (twelve wavefronts: the tiles above are those of the answer uniform_disjoint_rows gave, the switch is not read a second time)
   char const *uniform_env = std::getenv("MFMG_MF_UNIFORM_SWEEP");
-  const bool uniform_off = uniform_env && std::string(uniform_env) == "0";
+  const bool uniform_off = wg12 ? !disjoint_rows : (uniform_env && std::string(uniform_env) == "0");
   // (every tile shape of the three-term sweep has the stencil: the results of an operator do not depend on the shape asked for)
   bool uniform_taken = false;
   if constexpr (std::is_same<T, double>::value)
@@ -1751,7 +1801,7 @@ void MatrixFreeLaplaceDevice<T>::smoother_sweep(int n_terms, T const *alpha, T c
       u.ntiles_y2 = wg12 ? a.ntiles_y2 : 0u;
       u.wide_tiles = wg12 ? a.wide_tiles : a.ncols * a.ntiles_y * a.ntiles_z;
       const unsigned int n_blocks_u = mf_xcd_grid((uint64_t)u.wide_tiles + (uint64_t)u.ntiles_y2 * a.ntiles_z);
-      const size_t lds_u = ((size_t)nw * ring_planes(3, true) * (ty + 1) + (size_t)2 * nw * (ty == 2 ? 2 : 4)) * 64 * sizeof(T);
+      const size_t lds_u = ((size_t)nw * ring_planes(3, true) * (ty + 1) + (size_t)2 * nw * (ty == 2 && !wg12 ? 2 : 4)) * 64 * sizeof(T);
       ASSERT_THROW(lds_u <= kMfMaxLds, "tile of the multi-term sweep too large for the LDS");
       auto go_u = [&](auto kernel) { mf_launch(kernel, MfGrid{n_blocks_u, nw, lds_u, st}, u); };
       if (wg12)
@@ -1815,6 +1865,10 @@ template bool MatrixFreeLaplaceDevice<double>::fused_sweep_available(int) const;
 template bool MatrixFreeLaplaceDevice<float>::fused_sweep_available(int) const;
 template bool MatrixFreeLaplaceDevice<double>::fused_wg12_capable(int) const;
 template bool MatrixFreeLaplaceDevice<float>::fused_wg12_capable(int) const;
+template bool MatrixFreeLaplaceDevice<double>::uniform_disjoint_rows(int, int, int) const;
+template bool MatrixFreeLaplaceDevice<float>::uniform_disjoint_rows(int, int, int) const;
+template int MatrixFreeLaplaceDevice<double>::fused_tile_owned_rows(int, int, int) const;
+template int MatrixFreeLaplaceDevice<float>::fused_tile_owned_rows(int, int, int) const;
 template void MatrixFreeLaplaceDevice<double>::choose_fused_tile(int, int &, int &, int &) const;
 template void MatrixFreeLaplaceDevice<float>::choose_fused_tile(int, int &, int &, int &) const;
 template void MatrixFreeLaplaceDevice<double>::smoother_sweep(int, double const *, double const *, double const *, double const *, double *,

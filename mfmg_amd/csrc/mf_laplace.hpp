@@ -149,7 +149,7 @@ public:
   // no ghost layers, no D^-1 in the records, and every stored cell coefficient of the same bits (a reduction on the device at
   // construction).  The operator on the free DoFs is then one 27-point stencil and D^-1 one number: the three-term FP64 sweep
   // applies it as three 1-D stencils on every tile shape (mf_cheb_fused.hip: mf_cheb_fused_uniform_kernel for twelve wavefronts of
-  // two rows, mf_cheb_fused_uniform_rows_kernel for the others) unless MFMG_MF_UNIFORM_SWEEP=0 or the reference arithmetic is asked for.
+  // two rows, which then hold three node rows each of their own, mf_cheb_fused_uniform_rows_kernel for the others) unless MFMG_MF_UNIFORM_SWEEP=0 or the reference arithmetic is asked for.
   bool uniform_coefficient() const { return _uniform; }
   // sweeps that took that kernel so far
   int64_t uniform_sweep_launches() const { return _uniform_sweeps; }
@@ -319,6 +319,10 @@ private:
   mutable int64_t _block_launches = 0;
   void choose_fused_tile(int n_terms, int &nw, int &ty, int &tz) const;
   bool fused_wg12_capable(int n_terms) const; // the sweep has the kernel of twelve wavefronts of two rows
+  // the sweep of that shape runs mf_cheb_fused_uniform_kernel, whose wavefronts hold three node rows of their own: 30 owned rows
+  // per y-tile, not 19 (asked at every call: MFMG_MF_UNIFORM_SWEEP is read anew)
+  bool uniform_disjoint_rows(int n_terms, int nw, int ty) const;
+  int fused_tile_owned_rows(int n_terms, int nw, int ty) const;
   int _fused_tile[3] = {0, 0, 0};
   bool _fused_reference_arithmetic = false;
 
