@@ -699,11 +699,7 @@ int mfmg_hip_halo_box_messages(const int64_t *local_nodes, const int64_t *own0, 
     s.comps = comps;
     s.width = width;
     for (int d = 0; d < 3; ++d)
-    {
       require(own0[d] >= 0 && own_n[d] >= width && own0[d] + own_n[d] <= local_nodes[d], "the owned box lies outside the local box");
-      require(!has_low[d] || own0[d] >= width, "fewer ghost layers below than the exchange is wide");
-      require(!has_high[d] || local_nodes[d] - own0[d] - own_n[d] >= width, "fewer ghost layers above than the exchange is wide");
-    }
     s.n_xy[0] = local_nodes[0];
     s.n_xy[1] = local_nodes[1];
     s.n_layers = local_nodes[2];
@@ -719,6 +715,7 @@ int mfmg_hip_halo_box_messages(const int64_t *local_nodes, const int64_t *own0, 
     s.owned_count = own_n[2];
     s.has_low = has_low[2] != 0;
     s.has_high = has_high[2] != 0;
+    halo_check_width(s); // (the condition of every exchange: exchange_box, exchange_on, exchange_reverse_add)
     HaloRegions own, ghost;
     int p[26];
     int64_t c[26];

@@ -431,6 +431,24 @@ struct HaloSpace
   }
 };
 
+// What every exchange of `s` (box or slab, forward or reverse) takes for granted, `s.width` layers deep: along every axis with a
+// neighbour the owned range is at least that thick -- the layers sent (forward) resp. added to (reverse) are owned ones, not
+// ghost layers taken for owned -- and that many ghost layers lie on the neighbour's side.  Host arithmetic only.
+inline void halo_check_width(HaloSpace const &s)
+{
+  if (s.width < 1)
+    throw InvalidArgumentExc("a halo exchange is at least one layer wide");
+  for (int d = 0; d < 3; ++d)
+  {
+    if ((s.low(d) || s.high(d)) && s.own_n(d) < s.width)
+      throw InvalidArgumentExc("the owned box is thinner than the exchange is wide");
+    if (s.low(d) && s.own0(d) < s.width)
+      throw InvalidArgumentExc("fewer ghost layers below than the exchange is wide");
+    if (s.high(d) && s.dim(d) - s.own0(d) - s.own_n(d) < s.width)
+      throw InvalidArgumentExc("fewer ghost layers above than the exchange is wide");
+  }
+}
+
 // the sub-boxes of a local array that one box exchange packs (or unpacks): region r = nodes [b, b + n) per axis, its entries
 // at off[r] .. off[r + 1] of the packed buffer
 struct HaloRegions
@@ -696,6 +714,7 @@ struct HipHandle
     static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "halo exchange of double or float vectors");
     if (!std::is_same<T, double>::value && reverse)
       throw std::runtime_error("internal: float vectors have no reverse-add exchange");
+    halo_check_width(s);
     HaloRegions own, ghost;
     int peers[26];
     int64_t counts[26];
@@ -733,6 +752,7 @@ struct HipHandle
       MFMG_HIP_CHECK(hipEventRecord(ev_packed, pack_stream));
       MFMG_HIP_CHECK(hipStreamWaitEvent(st, ev_packed, 0));
     }
+    halo_check_width(s);
     if (s.split_xy() || !std::is_same<T, double>::value)
     {
       exchange_box(s, v, false, st);
@@ -845,6 +865,7 @@ struct HipHandle
     if (!comm.enabled() || space <= 0)
       return;
     HaloSpace &s = space_checked(space);
+    halo_check_width(s);
     if (s.split_xy())
     {
       exchange_box(s, v, true, stream);

@@ -23,10 +23,11 @@ import mfmg_oracle as O  # noqa: E402
 class Mailboxes:
     """Transport between the threads of one process: a queue per ordered pair of ranks, a barrier for the collectives."""
 
-    def __init__(self, n):
+    def __init__(self, n, timeout=300):
         self.n = n
+        self.timeout = timeout          # seconds a rank waits for a message or at a barrier before it gives up
         self.q = {(a, b): queue.Queue() for a in range(n) for b in range(n)}
-        self.barrier = threading.Barrier(n, timeout=300)
+        self.barrier = threading.Barrier(n, timeout=timeout)
         self.slots = [None] * n
 
     def callbacks(self, rank):
@@ -34,7 +35,7 @@ class Mailboxes:
             for p, s in zip(peers, send):
                 self.q[(rank, p)].put(np.array(s, copy=True))
             for p, r in zip(peers, recv):
-                r[:] = self.q[(p, rank)].get(timeout=300)
+                r[:] = self.q[(p, rank)].get(timeout=self.timeout)
 
         def allreduce(values, op):
             self.slots[rank] = np.array(values, copy=True)

@@ -92,3 +92,21 @@ def test_an_exchange_wider_than_the_ghost_layers_is_refused(mfmg_lib):
     part = M.BoxPartition((16, 16, 48), 1, (1, 1, 2), low_ghost_cells=2)
     with pytest.raises(M.lib.MfmgInvalidArgument):
         _messages(part, 3)
+
+
+def test_the_condition_of_an_exchange_says_what_is_missing(mfmg_lib):
+    """halo_check_width, the condition every exchange checks before it packs: the owned box `width` thick, `width` ghost layers on
+    every side with a neighbour -- and nothing asked of an axis without neighbours."""
+    from mfmg_amd import lib as L
+    box = {"dims": (5, 4, 9), "own0": (0, 0, 3), "own_n": (5, 4, 4), "comps": 2}      # three ghost planes below, two above
+    none, z = [False] * 3, [False, False, True]
+    peers, counts, _, _ = box_messages(box, z, z, 2, 1, (1, 1, 3))
+    assert list(peers) == [0, 2] and list(counts) == [2 * 5 * 4 * 2] * 2
+    for low, high, width, text in ((z, z, 3, "fewer ghost layers above"), (z, none, 4, "fewer ghost layers below"),
+                                   (none, z, 3, "fewer ghost layers above")):
+        with pytest.raises(L.MfmgInvalidArgument, match=text):
+            box_messages(box, low, high, width, 1, (1, 1, 3))
+    assert len(box_messages(box, z, none, 3, 1, (1, 1, 3))[0]) == 1                  # three planes below: enough for width 3
+    thin = dict(box, own_n=(5, 4, 1), dims=(5, 4, 9))
+    with pytest.raises(L.MfmgInvalidArgument):
+        box_messages(thin, z, z, 2, 1, (1, 1, 3))
