@@ -808,6 +808,36 @@ int mfmg_hip_block_cg_direction(mfmg_hip_context_t ctx, int64_t n, int32_t k, in
 int mfmg_hip_block_cg_update(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64_t ld, const double *P, const double *AP, double *R,
                              int64_t ldx, double *X, const int32_t *slot_col, const double *rz, const double *pap, double *rr_out);
 
+/* ---- blocks of vectors on several ranks (additions, no change of the ABI version) ----
+ * On a context with a communicator mfmg_hip_hierarchy_apply_block, _vmult_block, _smoother_apply_block, _operator_apply_block and
+ * _solve_cg_block take the ranks' LOCAL vectors as columns (ghost entries are don't-care on entry, unspecified in results): on
+ * the entries a rank owns a column gets the bits the one-vector call on the same ranks gives that vector.  Whether groups of 4
+ * and 2 columns run as blocks is agreed ONCE, when the hierarchy is created: the minimum over the ranks of what each rank's fine
+ * operator offers (one collective; mfmg_hip_hierarchy_block_info reports the agreed width, the same on every rank -- 1 where one
+ * rank keeps one coefficient per cell or has a tail slab: every rank then loops over the columns).  Where it is 4, a smoother term
+ * or residual on a group exchanges the group's x in ONE block exchange and launches the block kernel on the local mesh (not
+ * overlapped with interior tiles); restriction, coarse cycle and prolongation run column by column with their own exchanges.
+ * _solve_cg_block forms (r, z), (p, A p) and (r, r) over the owned entries of all live slots in one launch each and sums them over
+ * the ranks in one all-reduce each: three per iteration whatever n_vectors, plus one for the initial residuals; every rank gets the
+ * same counts and histories.  The bits of mfmg_hip_hierarchy_solve_cg on the same ranks hold where the transport sums an element in
+ * the same order whatever the length of the message (any transport on two ranks).
+ * STILL refused on a communicator (MFMG_HIP_ERROR_INVALID_ARGUMENT): mfmg_hip_hierarchy_solve_fgmres_block,
+ * mfmg_hip_hierarchy_apply_f32_block, mfmg_hip_mf_laplace_block_launch / _f32_block_launch (launches on one rank's memory, no
+ * exchange) and the stand-alone kernel calls mfmg_hip_block_dots / _cg_direction / _cg_update / _block_krylov_*.
+ * mfmg_hip_context_exchange_block: the forward exchange (owner -> ghost) of the n_vectors columns V + c ld of the fine DoF space
+ * (space must be 1), `width` planes deep (the rule of mfmg_hip_context_exchange_f32): ONE packing launch, ONE grouped send/recv,
+ * ONE unpacking launch.  Every existing neighbour gets one message: the one-vector message of column 0, then that of column 1,
+ * ... -- n_vectors times the one-vector doubles, counted as one exchange.  Slabs pack too.  Layout rules of the block entry points
+ * (1 .. 64 columns, ld even and at least the local vector's size, base aligned to 16 bytes).  Nothing happens without a
+ * communicator.
+ * mfmg_hip_block_dots_box: out[s] = the part of (X_s, Y_s) over the OWNED entries of k slots of a rank's local vectors (the box of
+ * mfmg_hip_krylov_orthogonalize_box; ld >= the entries of the local box), formed in the order the one-vector owned dot product
+ * forms its rank-local sum: bit-equal to it, whatever the ghost entries hold.  The reduction of a distributed _solve_cg_block,
+ * launched on a context WITHOUT a communicator (tests). */
+int mfmg_hip_context_exchange_block(mfmg_hip_context_t ctx, int32_t space, int32_t n_vectors, int64_t ld, double *V, int width);
+int mfmg_hip_block_dots_box(mfmg_hip_context_t ctx, const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n, int32_t comps,
+                            int32_t k, int64_t ld, const double *X, const double *Y, double *out);
+
 /* ---- flexible GMRES on a block of right-hand sides (additions, no change of the ABI version) ----
  * mfmg_hip_hierarchy_solve_fgmres_block: mfmg_hip_hierarchy_solve_fgmres for every column of the blocks b and x (layout and checks
  * of the block entry points above; restart >= 1, tolerances >= 0, preconditioner_fp32 0 or 1 -- 1 needs "fine level precision"

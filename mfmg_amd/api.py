@@ -272,6 +272,27 @@ class Context:
         assert v.dtype == torch.float32 and v.is_contiguous()
         check(self._lib.mfmg_hip_context_exchange_f32(self.handle, int(space), v.data_ptr(), int(width)))
 
+    def exchange_block(self, space: int, V: torch.Tensor, width: int = 1):
+        """One forward halo exchange (owner -> ghost) of every row of the block V -- a 2-D float64 tensor of shape (k, m),
+        stride(1) == 1, ld = stride(0) even and at least the local vector's size, the base aligned to 16 bytes -- in the fine DoF
+        space (space 1), `width` planes deep: one packing launch, one grouped send/recv with one message per neighbour (the
+        one-vector messages of the rows one after the other), one unpacking launch; counted as one exchange.  Every row gets the
+        bits of HaloTransport.exchange of that row.  Nothing happens without a HaloTransport."""
+        k, ld, pv = _block_ptr(V)
+        check(self._lib.mfmg_hip_context_exchange_block(self.handle, int(space), k, ld, pv, int(width)))
+
+    def block_dots_box(self, box, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+        """out[s] = the part of (X[s], Y[s]) over the owned entries of a rank's local vectors, box = (local_nodes, own0, own_n,
+        comps) as for krylov_orthogonalize: the reduction of solve_cg_block on several ranks, on a context WITHOUT a communicator.
+        Per row the bits of the rank-local sum of HaloTransport.owned_dot; the ghost entries never enter it.  A device tensor."""
+        local_nodes, own0, own_n, comps = box
+        k, ld, px = _block_ptr(X)
+        i3 = C.c_int64 * 3
+        out = torch.empty(k, dtype=torch.float64, device=X.device)
+        check(self._lib.mfmg_hip_block_dots_box(self.handle, i3(*local_nodes), i3(*own0), i3(*own_n), int(comps), k, ld, px,
+                                                _same_block(k, ld, Y), _dev_ptr(out)))
+        return out
+
     def krylov_orthogonalize(self, V: torch.Tensor, w: torch.Tensor, n_columns: int, passes: int = 2, box=None):
         """The fused Gram-Schmidt kernels of solve_fgmres on their own: `passes` times { c = V^T w; w -= V c } in place, against
         the first n_columns columns of V ([columns, ld] contiguous: column-major with leading dimension ld >= len(w)).
@@ -927,7 +948,9 @@ class Hierarchy:
     def apply_block(self, B: torch.Tensor, X: torch.Tensor):
         """The cycle of apply() on every row of the blocks B and X: 2-D float64 tensors of shape (k, m), stride(1) == 1, with one
         leading dimension ld = stride(0) >= n_dofs (even; the bases aligned to 16 bytes).  Row c of X gets the bits of
-        apply(B[c], X[c])."""
+        apply(B[c], X[c]).  On a context with a HaloTransport the rows are the rank's local vectors and that holds on the entries
+        the rank owns; a group of 4 or 2 rows then exchanges its ghost planes in one message per neighbour where the ranks agreed
+        on blocks at setup (block_info()["width"] == 4), else every rank loops over the rows."""
         k, ld, pb = _block_ptr(B)
         check(self._lib.mfmg_hip_hierarchy_apply_block(self.handle, k, ld, pb, _same_block(k, ld, X)))
 
@@ -940,7 +963,8 @@ class Hierarchy:
         check(self._lib.mfmg_hip_hierarchy_smoother_apply_block(self.handle, level, k, ld, pb, _same_block(k, ld, X)))
 
     def block_info(self) -> dict:
-        """width: vectors of the widest group the fine level runs as one launch (1 = the loop over the vectors); block_launches /
+        """width: vectors of the widest group the fine level runs as one launch (1 = the loop over the vectors; on several ranks
+        the value all ranks agreed on at setup); block_launches /
         column_launches: launches of the block kernel, and vectors that went through the one-vector entry point, in the last
         block call."""
         f = (C.c_int64 * 3)()
@@ -1182,7 +1206,11 @@ class Hierarchy:
         solve_cg(B[c], X[c], tolerances[c], max_iterations), bit for bit.  A column that converged costs nothing further.
         Returns (iterations, histories, work): k ints, k arrays, and a dict with the column-applications of the preconditioner
         and of the operator (each the sum of the iterations), the launches of the block kernel and the slot moves.  Raises the
-        error of solve_cg when a column is unconverged at max_iterations; X and `last_block_solve` (the same triple) are filled."""
+        error of solve_cg when a column is unconverged at max_iterations; X and `last_block_solve` (the same triple) are filled.
+        On a context with a HaloTransport B and X hold the rank's local vectors: the three reductions of an iteration run over the
+        owned entries of all live rows and cross the ranks in one all-reduce each; every rank gets the same counts and histories,
+        and the bits of solve_cg on the same ranks where the transport adds an element in the same order whatever the length of
+        the message (any transport on two ranks)."""
         k, ld, pb = _block_ptr(B)
         px = _same_block(k, ld, X)
         tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tolerances, dtype=np.float64), (k,)))

@@ -750,6 +750,26 @@ int mfmg_hip_context_exchange_f32(mfmg_hip_context_t ctx, int32_t space, float *
   });
 }
 
+int mfmg_hip_context_exchange_block(mfmg_hip_context_t ctx, int32_t space, int32_t n_vectors, int64_t ld, double *V, int width)
+{
+  return guarded([&] {
+    require(ctx != nullptr && V != nullptr, "null argument");
+    HipHandle &h = *ctx->handle;
+    require(space == 1, "blocks of vectors are exchanged in the fine DoF space (1) only");
+    // (the same answer on every rank, as for mfmg_hip_context_exchange_f32)
+    require(width >= 1 && width <= 3 && width <= h.comm.low_ghost_cells, "width: 1 to 3 planes, at most the ghost planes every rank holds");
+    // (the layout rules of the block entry points)
+    require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
+    require(ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 16 bytes)");
+    require(reinterpret_cast<uintptr_t>(V) % 16 == 0, "the base of a block must be aligned to 16 bytes");
+    if (!h.comm.enabled())
+      return;
+    require(ld >= h.space_checked(space).n_local(), "the leading dimension of a block must be at least the vector size");
+    h.reserve_exchange_block(n_vectors, width);
+    h.exchange_block(n_vectors, ld, V, width);
+  });
+}
+
 int mfmg_hip_context_owned_dot(mfmg_hip_context_t ctx, int32_t space, const double *x, const double *y, double *result)
 {
   return guarded([&] {
@@ -1796,10 +1816,12 @@ int mfmg_hip_hierarchy_apply(mfmg_hip_hierarchy_t h, const double *b, double *x)
 
 namespace
 {
-void check_block(mfmg_hip_hierarchy_t h, int level, int32_t n_vectors, int64_t ld, const double *b, const double *x)
+// (on_ranks: the entry point runs on a context with a communicator -- the cycle, the smoother, the operator and CG; block FGMRES
+// does not)
+void check_block(mfmg_hip_hierarchy_t h, int level, int32_t n_vectors, int64_t ld, const double *b, const double *x, bool on_ranks = true)
 {
   require(h && b && x, "null argument");
-  require(!h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+  require(on_ranks || !h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
   require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
   const int64_t n = level_size(h, level);
   require(ld >= n, "the leading dimension of a block must be at least the vector size");
@@ -2209,6 +2231,13 @@ struct BlockViews
 // them in one reduction, the direction, the operator on the block, (p, A p), the update with the partials of (r, r) folded in,
 // ONE device-to-host copy of the active slots' (r, r) and ONE synchronisation.  Every kernel gives a slot the bits the one-vector
 // driver gives its vector, so x, the iteration count and the history of a column are those of mfmg_hip_hierarchy_solve_cg.
+// Several ranks: the blocks hold the ranks' local vectors.  The operator and the cycle exchange what they read (a group of columns
+// one message per neighbour where the ranks agreed on blocks); direction and update run over all local entries; (r, z), (p, A p)
+// and (r, r) run over the owned entries of all live slots in one launch (block_krylov::dots on the OwnedBox of the fine space)
+// and are summed over the ranks in ONE all-reduce each -- three per iteration whatever k, plus one for the initial residuals.
+// Every control decision is taken from all-reduced values, so every rank retires the same columns and leaves the loop in the same
+// iteration.  A column has the bits of the one-vector solve on the same ranks where the transport sums an element in the same
+// order whatever the length of the message (block_krylov.hpp).
 int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
                                       const double *tolerances, int32_t max_iterations, int32_t *n_iterations, double *final_residuals,
                                       double *residual_history, int32_t history_ld, int64_t *work)
@@ -2262,6 +2291,33 @@ int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors,
       MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, rr, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
       MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
     };
+    // several ranks: the reductions over the owned entries, summed over the ranks
+    const bool distributed = handle.comm.enabled();
+    krylov::OwnedBox box;
+    if (distributed)
+    {
+      auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
+      const int space = hop ? hop->domain_space() : 0;
+      require(space > 0 && space < (int)handle.comm.spaces.size() && handle.comm.spaces[space].configured() && handle.comm.transport != nullptr,
+              "the fine operator has no distributed vector space or no transport was registered");
+      box = krylov::OwnedBox(handle.comm.spaces[space]);
+      require(box.n_local() == n, "the fine space does not describe the vectors of the fine level");
+    }
+    // out[s] = (X_s, Y_s) of the first `count` slots on the device; several ranks: over the owned entries, through the host and one
+    // all-reduce, and back (ws.host then holds the sums as well)
+    auto reduce = [&](int count, double const *X, double const *Y, double *out) {
+      if (!distributed)
+        return block_krylov::dots(handle, n, count, wld, X, Y, partials, out);
+      block_krylov::dots(handle, box, count, wld, X, Y, partials, out);
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, out, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+      handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
+      if (out != rr) // ((r, r) is read on the host alone)
+      {
+        MFMG_HIP_CHECK(hipMemcpyAsync(out, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
+        MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (ws.host is written again by the next reduction)
+      }
+    };
     auto record = [&](int c, int it, double v) {
       if (residual_history && it < history_ld)
         residual_history[(int64_t)c * history_ld + it] = v;
@@ -2273,8 +2329,9 @@ int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors,
       for (int c = 0; c < k; ++c)
         vec::sadd<double>(handle, n, -1., 1., b_run + c * wld, R + c * wld);
     }
-    block_krylov::dots(handle, n, k, wld, R, R, partials, rr);
-    fetch(k);
+    reduce(k, R, R, rr);
+    if (!distributed)
+      fetch(k);
     std::vector<double> res(k);
     std::vector<int32_t> iterations(k, 0), flags(k), moves(2 * (size_t)k);
     int n_active = k;
@@ -2330,16 +2387,27 @@ int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors,
         timer_leave_subsection(h->timer);
       }
       preconditioner_columns += n_active;
-      block_krylov::dots(handle, n, n_active, wld, R, Z, partials, rz[cur]);
-      block_krylov::cg_direction(handle, n, n_active, wld, Z, P, rz[cur], rz[1 - cur], it == 0); // p = z + beta p
+      reduce(n_active, R, Z, rz[cur]);
+      if (distributed) // (p.sadd(beta, 1., z) of the one-vector driver on ranks rounds beta p before it adds z)
+        block_krylov::cg_direction_local(handle, n, n_active, wld, Z, P, rz[cur], rz[1 - cur], it == 0);
+      else
+        block_krylov::cg_direction(handle, n, n_active, wld, Z, P, rz[cur], rz[1 - cur], it == 0); // p = z + beta p
       {
         BlockViews pv(handle, n, wld, n_active, P), apv(handle, n, wld, n_active, AP);
         op->apply_block(pv.cptr, apv.ptr);
       }
       operator_columns += n_active;
-      block_krylov::dots(handle, n, n_active, wld, P, AP, partials, pap);
-      block_krylov::cg_update(handle, n, n_active, wld, P, AP, R, wld, x_run, ws.slot_col.data(), rz[cur], pap, partials, rr);
-      fetch(n_active);
+      reduce(n_active, P, AP, pap);
+      if (distributed)
+      {
+        block_krylov::cg_update_local(handle, n, n_active, wld, P, AP, R, wld, x_run, ws.slot_col.data(), rz[cur], pap);
+        reduce(n_active, R, R, rr);
+      }
+      else
+      {
+        block_krylov::cg_update(handle, n, n_active, wld, P, AP, R, wld, x_run, ws.slot_col.data(), rz[cur], pap, partials, rr);
+        fetch(n_active);
+      }
       cur = 1 - cur; // rz[1 - cur] is now the (r, z) of the iteration that just ended
       ++it;
       any = false;
@@ -2699,7 +2767,7 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
 {
   namespace bkb = block_krylov_basis;
   return guarded([&] {
-    check_block(h, 0, n_vectors, ld, b, x);
+    check_block(h, 0, n_vectors, ld, b, x, false);
     require(tolerances != nullptr, "null argument");
     require(max_iterations >= 0, "bad stopping criterion");
     for (int c = 0; c < n_vectors; ++c)
@@ -3115,6 +3183,30 @@ int mfmg_hip_krylov_orthogonalize_box(mfmg_hip_context_t ctx, const int64_t *loc
     krylov::basis_norm_finish(handle, scratch, box);
     krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), w, nullptr, norm_out);
     MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the scratch goes away)
+  });
+}
+
+int mfmg_hip_block_dots_box(mfmg_hip_context_t ctx, const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n, int32_t comps,
+                            int32_t k, int64_t ld, const double *X, const double *Y, double *out)
+{
+  return guarded([&] {
+    require(ctx && local_nodes && own0 && own_n && X && Y && out, "null argument");
+    require(comps >= 1 && k >= 1 && k <= MFMG_HIP_BLOCK_MAX_VECTORS, "bad shape");
+    HipHandle &handle = *ctx->handle;
+    require(!handle.comm.enabled(), "mfmg_hip_block_dots_box runs the kernels of one rank: a context without a communicator");
+    krylov::OwnedBox box;
+    box.comps = comps;
+    for (int d = 0; d < 3; ++d)
+    {
+      require(own0[d] >= 0 && own_n[d] >= 1 && own0[d] + own_n[d] <= local_nodes[d], "the owned box leaves the local box");
+      box.local[d] = local_nodes[d];
+      box.own0[d] = own0[d];
+      box.own_n[d] = own_n[d];
+    }
+    require(ld >= box.n_local(), "bad shape");
+    DeviceBuffer<double> partials((size_t)k * block_krylov::kReduceBlocks);
+    block_krylov::dots(handle, box, k, ld, X, Y, partials.data(), out);
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the partials go away)
   });
 }
 

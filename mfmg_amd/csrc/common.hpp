@@ -582,6 +582,11 @@ void halo_regions_copy(double *v, HaloSpace const &s, HaloRegions const &regions
 // ... of a FLOAT vector against the same buffer of doubles: mode 0 buf = v widened (pack), 1 v = buf narrowed (unpack).  float ->
 // double -> float is exact, and the wire carries what it carries for a double vector of the space: same messages, same counts.
 void halo_regions_copy(float *v, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode, hipStream_t stream);
+// ... of the k columns of a block (column c at V + c ld) against ONE buffer in which region r holds the one-vector message of
+// column 0, then that of column 1, ...: entry q of region r and column c at k off[r] + c (off[r + 1] - off[r]) + q.  mode 0 buf = V
+// (pack), 1 V = buf (unpack); one launch for all columns (vector_ops.hip)
+void halo_regions_copy_block(double *V, int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode,
+                             hipStream_t stream);
 // the owned sub-box (or the whole local box) of a vector of space `s` against the contiguous buf: mode 0 buf = v, 1 v = buf
 void halo_box_copy(double *v, HaloSpace const &s, bool owned_only, double *buf, int mode, hipStream_t stream);
 void gather_indexed(int64_t n, double const *in, int32_t const *index, double *out, hipStream_t stream); // out[i] = in[index[i]]
@@ -736,6 +741,64 @@ struct HipHandle
     ++comm.n_exchanges;
     comm.n_doubles_sent += total;
     halo_regions_copy(v, s, reverse ? own : ghost, recv, reverse ? 2 : 1, st);
+  }
+  // ---- blocks of vectors: the forward exchange of k columns of the fine DoF space, FP64 ----
+  // Doubles per direction that exchange_block stages for k columns, `width` planes deep (k times the one-vector messages).
+  int64_t exchange_block_doubles(int k, int width) const
+  {
+    HaloRegions own, ghost;
+    int peers[26];
+    int64_t counts[26];
+    const int stride[3] = {comm.stride(0), comm.stride(1), comm.stride(2)};
+    return (int64_t)k * halo_box_messages(fine_space(width), comm.rank, stride, own, ghost, peers, counts);
+  }
+  // The staging of the compute stream grows to the messages of k columns.  Where a block path is set up or entered (the operator
+  // that agreed on blocks, the entry point of the C interface), never inside exchange_block: growing drains both streams.
+  void reserve_exchange_block(int k, int width)
+  {
+    if (!comm.enabled() || !comm.spaces[1].configured())
+      return;
+    MemoryKind kind("halo staging: block exchange (k messages per neighbour)");
+    int64_t each = 0;
+    (void)staging_reserve((exchange_block_doubles(k, width) + 1) / 2 + 1, stream, each);
+  }
+  // Forward exchange (owner -> ghost) of the k columns V + c ld of the fine DoF space on the compute stream, `width` planes deep:
+  // ONE packing launch, ONE grouped send/recv, ONE unpacking launch.  Every existing neighbour gets one message -- the one-vector
+  // message of column 0, then that of column 1, ... (halo_box_messages per column): k times the one-vector doubles on the wire in
+  // one group.  A slab takes the packed path as well: its layers are contiguous per column, not per block, and the host transports
+  // are handed one message per peer.  Counts as one exchange.
+  void exchange_block(int k, int64_t ld, double *V, int width)
+  {
+    if (!comm.enabled())
+      return;
+    (void)space_checked(1);
+    const HaloSpace s = fine_space(width);
+    halo_check_width(s);
+    if (k < 1 || ld < s.n_local())
+      throw std::runtime_error("internal: a block exchange needs at least one column and a leading dimension of the local vector's size");
+    HaloRegions own, ghost;
+    int peers[26];
+    int64_t counts[26];
+    const int stride[3] = {comm.stride(0), comm.stride(1), comm.stride(2)};
+    const int64_t total = halo_box_messages(s, comm.rank, stride, own, ghost, peers, counts);
+    if (own.count == 0)
+      return;
+    if ((k * total + 1) / 2 + 1 > halo_staging_each)
+      throw std::runtime_error("internal: the staging of a block exchange was not reserved (reserve_exchange_block)");
+    double *send = halo_staging.data(), *recv = send + 2 * halo_staging_each;
+    double const *send_ptr[26];
+    double *recv_ptr[26];
+    for (int r = 0; r < own.count; ++r)
+    {
+      send_ptr[r] = send + k * own.off[r];
+      recv_ptr[r] = recv + k * own.off[r];
+      counts[r] *= k;
+    }
+    halo_regions_copy_block(V, ld, k, s, own, send, 0, stream);
+    comm.transport->exchange_many(own.count, peers, send_ptr, recv_ptr, counts, stream);
+    ++comm.n_exchanges;
+    comm.n_doubles_sent += k * total;
+    halo_regions_copy_block(V, ld, k, s, ghost, recv, 1, stream);
   }
   // forward exchange on `st`.  Along z the `width` owned layers next to a neighbour and the ghost layers they refresh are
   // contiguous runs of the vector (lexicographic layers): the transport sends from and receives into the vector itself

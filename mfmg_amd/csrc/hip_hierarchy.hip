@@ -856,12 +856,44 @@ bool block_kernel_layout(std::vector<DVector const *> const &columns, int64_t ld
 
 int HipMatrixFreeOperator::block_width() const
 {
-  return (!get_hip_handle().comm.enabled() && _mesh_evaluator->get_device_operator()->block_kernel_available()) ? 4 : 1;
+  auto op = _mesh_evaluator->get_device_operator();
+  // several ranks: what the ranks agreed on when the fine smoother was built (1 before that), never this rank's operator alone
+  if (get_hip_handle().comm.enabled())
+    return std::max(op->block_width_agreed(), 1);
+  return op->block_kernel_available() ? 4 : 1;
 }
 
+// Several ranks: per group of 4 or 2 columns ONE exchange_block of the group's x, one plane deep, then the block launch on the
+// local mesh -- where apply_mode sends the message of one vector per application, a group sends one message per neighbour.  A
+// single column takes the one-vector path with its own exchange.  The exchange is not overlapped with the tiles that read no
+// ghost plane (the block kernel has no region launch): DESIGN.md section 8.
 void HipMatrixFreeOperator::apply_mode_block(MfMode mode, MfBlockOperands<double> const &v) const
 {
-  _mesh_evaluator->get_device_operator()->launch_block(mode, v);
+  auto op = _mesh_evaluator->get_device_operator();
+  HipHandle &handle = get_hip_handle();
+  if (!handle.comm.enabled())
+    return op->launch_block(mode, v);
+  ASSERT_THROW(block_width() > 1, "internal: the ranks did not agree on blocks of vectors");
+  int widths[kMfBlockMaxGroups];
+  const int n_groups = mf_block_groups(v.n_vectors, widths);
+  int c = 0;
+  for (int g = 0; g < n_groups; c += widths[g], ++g)
+  {
+    auto at = [&](double const *p) { return p ? p + (int64_t)c * v.ld : nullptr; };
+    if (widths[g] == 1)
+    {
+      apply_mode(mode, {at(v.x), at(v.b), at(v.x_prev), v.alpha, v.beta, v.out + (int64_t)c * v.ld});
+      continue;
+    }
+    MfBlockOperands<double> s = v;
+    s.x = at(v.x);
+    s.b = at(v.b);
+    s.x_prev = at(v.x_prev);
+    s.out = v.out + (int64_t)c * v.ld;
+    s.n_vectors = widths[g];
+    handle.exchange_block(s.n_vectors, s.ld, const_cast<double *>(s.x), 1);
+    op->launch_block_local(mode, s);
+  }
 }
 
 void HipMatrixFreeOperator::residual_block(std::vector<DVector const *> const &x, std::vector<DVector const *> const &b,
@@ -1138,6 +1170,21 @@ HipSmoother::HipSmoother(std::shared_ptr<Operator<DVector> const> op, std::share
     const int agreed = (int)(h.comm.enabled() ? -h.allreduce_max(-mine) : mine);
     ASSERT_THROW(agreed / 2 <= k, "internal: the ranks agreed on a sweep this rank cannot run");
     _schedule = plan_sweeps(_coefficients, _fused_terms, agreed / 2, (agreed & 1) != 0);
+    // Blocks of vectors change the exchanges as well -- a group of columns sends ONE message per neighbour, a loop over the columns
+    // one per column -- so the ranks run groups as blocks only where every rank's operator has the block kernel (a rank with one
+    // coefficient per cell or a tail slab has not): the smallest offer again, in ONE collective that every rank reaches here.
+    // The staging of the group's exchange is sized here, outside the launch path.
+    if (h.comm.enabled())
+    {
+      auto mf = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator);
+      auto device_op = mf->get_mesh_evaluator()->get_device_operator();
+      const double offer = device_op->block_kernel_available() ? 4. : 1.;
+      const int width = (int)-h.allreduce_max(-offer);
+      ASSERT_THROW(width == 1 || (width == 4 && offer == 4.), "internal: the ranks agreed on a block width this rank cannot run");
+      device_op->set_block_width_agreed(width);
+      if (width > 1)
+        h.reserve_exchange_block(width, 1);
+    }
   }
 }
 

@@ -249,6 +249,10 @@ public:
   // slab) run column by column.  InvalidArgumentExc: n_vectors outside 1 .. 64, ld < n_dofs or odd, a base not aligned to 16
   // bytes (FP32: 8), the out block overlapping the x block, a null operand the mode reads, a context with a communicator.
   void launch_block(MfMode mode, MfBlockOperands<T> const &v) const;
+  // ... the same launches on this rank's local mesh for a caller that has refreshed the ghost entries of the x block itself
+  // (HipMatrixFreeOperator::apply_mode_block on a communicator: one exchange_block, then this).  The checks of launch_block but
+  // the refusal of a communicator; no exchange.
+  void launch_block_local(MfMode mode, MfBlockOperands<T> const &v) const;
   bool block_kernel_available() const;
   // tile of the block kernel (0, 0, 0: chosen from the mesh and the width of the group); ty = 2, 3 or 4
   void set_block_tile(int nw, int ty, int tz)
@@ -260,6 +264,12 @@ public:
   void get_block_tile(int nv, int &nw, int &ty, int &tz) const;
   // launches of the block kernel so far
   int64_t block_launches() const { return _block_launches; }
+  // Several ranks: the widest group ALL ranks run as one launch (4, or 1: every rank loops over the columns), agreed once where
+  // the fine smoother is built (HipSmoother) from what every rank's operator offers; 0 until then.  A rank that looped over
+  // columns while its neighbour sent one block message would leave both waiting, so nothing on ranks asks
+  // block_kernel_available() again.
+  void set_block_width_agreed(int width) { _block_width_agreed = width; }
+  int block_width_agreed() const { return _block_width_agreed; }
 
   // Bytes of one operator application y = A x.
   // survey: the indexed form of SURVEY.md 8(d) -- x, y, 8 index ints, 8 coefficients (112 B/DoF in FP64; one
@@ -317,6 +327,7 @@ private:
   void run_block(MfMode mode, MfBlockOperands<T> const &v, int nv) const;
   int _block_tile[3] = {0, 0, 0};
   mutable int64_t _block_launches = 0;
+  int _block_width_agreed = 0;
   void choose_fused_tile(int n_terms, int &nw, int &ty, int &tz) const;
   bool fused_wg12_capable(int n_terms) const; // the sweep has the kernel of twelve wavefronts of two rows
   // the sweep of that shape runs mf_cheb_fused_uniform_kernel, whose wavefronts hold three node rows of their own: 30 owned rows

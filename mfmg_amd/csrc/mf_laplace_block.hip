@@ -532,6 +532,16 @@ void MatrixFreeLaplaceDevice<T>::launch_block(MfMode mode, MfBlockOperands<T> co
       throw InvalidArgumentExc(what);
   };
   require(!_handle.comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+  launch_block_local(mode, v);
+}
+
+template <typename T>
+void MatrixFreeLaplaceDevice<T>::launch_block_local(MfMode mode, MfBlockOperands<T> const &v) const
+{
+  auto require = [](bool cond, char const *what) {
+    if (!cond)
+      throw InvalidArgumentExc(what);
+  };
   require(v.n_vectors >= 1 && v.n_vectors <= kMfBlockMaxVectors, "a block holds 1 to 64 vectors");
   require(v.ld >= _n_dofs, "the leading dimension of a block must be at least n_dofs");
   // (a lane reads one element at a time: a column need only be aligned to two elements, 16 bytes in FP64 and 8 in FP32)
@@ -579,9 +589,11 @@ template MfTile MatrixFreeLaplaceDevice<double>::choose_block_tile(int) const;
 template void MatrixFreeLaplaceDevice<double>::get_block_tile(int, int &, int &, int &) const;
 template void MatrixFreeLaplaceDevice<double>::run_block(MfMode, MfBlockOperands<double> const &, int) const;
 template void MatrixFreeLaplaceDevice<double>::launch_block(MfMode, MfBlockOperands<double> const &) const;
+template void MatrixFreeLaplaceDevice<double>::launch_block_local(MfMode, MfBlockOperands<double> const &) const;
 template bool MatrixFreeLaplaceDevice<float>::block_kernel_available() const;
 template MfTile MatrixFreeLaplaceDevice<float>::choose_block_tile(int) const;
 template void MatrixFreeLaplaceDevice<float>::get_block_tile(int, int &, int &, int &) const;
 template void MatrixFreeLaplaceDevice<float>::run_block(MfMode, MfBlockOperands<float> const &, int) const;
 template void MatrixFreeLaplaceDevice<float>::launch_block(MfMode, MfBlockOperands<float> const &) const;
+template void MatrixFreeLaplaceDevice<float>::launch_block_local(MfMode, MfBlockOperands<float> const &) const;
 } // namespace mfmg

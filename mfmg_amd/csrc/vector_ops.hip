@@ -140,6 +140,29 @@ __global__ void regions_copy_f32_kernel(float *v, int comps, int64_t nx, int64_t
   }
 }
 
+// the same regions of the gridDim.y columns of a block (column c at V + c ld) against one buffer that holds, per region, the
+// one-vector message of column 0, then that of column 1, ...: mode 0 buf = V, 1 V = buf.  blockIdx.y is the column, so the
+// consecutive lanes of a wavefront stay on consecutive entries of one column, in the vector and in the buffer alike.
+__global__ void regions_copy_block_kernel(double *V, int64_t ld, int comps, int64_t nx, int64_t ny, HaloRegions t, double *buf, int mode)
+{
+  const int64_t n = t.off[t.count], k = gridDim.y, c = blockIdx.y;
+  double *v = V + c * ld;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+  {
+    int r = 0;
+    while (r + 1 < t.count && i >= t.off[r + 1])
+      ++r;
+    const int64_t q = i - t.off[r], rx = (int64_t)t.n[r][0] * comps;
+    const int64_t x = q % rx, j = (q / rx) % t.n[r][1], z = q / (rx * t.n[r][1]);
+    double *p = v + ((z + t.b[r][2]) * ny + (j + t.b[r][1])) * nx * comps + (int64_t)t.b[r][0] * comps + x;
+    double *m = buf + k * t.off[r] + c * (t.off[r + 1] - t.off[r]) + q;
+    if (mode == 0)
+      *m = *p;
+    else
+      *p = *m;
+  }
+}
+
 // the sub-box [b0, b0 + bn) of the lexicographic array of nodes `dims` (comps entries per node) against the contiguous buf
 // (mode 0: buf = v, 1: v = buf)
 __global__ void box_copy_kernel(double *v, int comps, int64_t nx, int64_t ny, int64_t bx0, int64_t by0, int64_t bz0, int64_t bnx,
@@ -437,6 +460,27 @@ void halo_regions_copy(float *v, HaloSpace const &s, HaloRegions const &regions,
       if (regions.b[r][d] < 0 || regions.n[r][d] < 0 || regions.b[r][d] + regions.n[r][d] > s.dim(d))
         throw std::runtime_error("internal: a halo region reaches beyond the local box (exchange wider than the ghost layers held)");
   hipLaunchKernelGGL(vec::regions_copy_f32_kernel, dim3(n_blocks_for(n, block_size, 4096)), dim3(block_size), 0, stream, v, s.comps,
+                     s.n_xy[0], s.n_xy[1], regions, buf, mode);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void halo_regions_copy_block(double *V, int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode,
+                             hipStream_t stream)
+{
+  s.check();
+  if (mode != 0 && mode != 1)
+    throw std::runtime_error("internal: blocks of vectors are packed and unpacked, not added to");
+  if (k < 1 || k > 64 || ld < s.n_local())
+    throw std::runtime_error("internal: a block of 1 to 64 columns, each at least the local vector long");
+  const int64_t n = regions.count > 0 ? regions.off[regions.count] : 0;
+  if (n <= 0)
+    return;
+  // every region lies inside the local box: an entry outside it would be a write beyond the column
+  for (int r = 0; r < regions.count; ++r)
+    for (int d = 0; d < 3; ++d)
+      if (regions.b[r][d] < 0 || regions.n[r][d] < 0 || regions.b[r][d] + regions.n[r][d] > s.dim(d))
+        throw std::runtime_error("internal: a halo region reaches beyond the local box (exchange wider than the ghost layers held)");
+  hipLaunchKernelGGL(vec::regions_copy_block_kernel, dim3(n_blocks_for(n, block_size, 4096), k), dim3(block_size), 0, stream, V, ld, s.comps,
                      s.n_xy[0], s.n_xy[1], regions, buf, mode);
   MFMG_HIP_CHECK(hipGetLastError());
 }

@@ -357,6 +357,11 @@ class HaloTransport:
         """Context.exchange_f32: the forward exchange of a float32 vector of the fine DoF space, `width` planes deep."""
         self.ctx.exchange_f32(space, v, width)
 
+    def exchange_block(self, space: int, V: torch.Tensor, width: int = 1):
+        """Context.exchange_block: the forward exchange of every row of a block of fine-level vectors in one group, one message
+        per neighbour (what the block smoother terms and residuals of a distributed run do by themselves; for tests)."""
+        self.ctx.exchange_block(space, V, width)
+
     def box_messages(self, space: int, width: int = 1):
         """The messages of one box exchange of `space`, `width` layers deep, as the library lays them out (host arithmetic only):
         (peers, counts, send_entries, recv_entries) -- positions in the local vector, message after message."""
