@@ -750,7 +750,8 @@ int mfmg_hip_host_params_get(const char *params_info, const char *path, char *va
  * mfmg_hip_hierarchy_apply_block: x[c] = the result of mfmg_hip_hierarchy_apply(b[c], x[c]) for every column, bit for bit;
  * _vmult_block the same with the argument order of _vmult; _smoother_apply_block that of _smoother_apply.  Where the fine level
  * has the block kernel the block is taken in the groups of mfmg_hip_block_groups and pre-smoothing, residual and post-smoothing
- * run as launches on the group; restriction, coarse cycle and prolongation run column by column.  Elsewhere the one-vector
+ * run as launches on the group; the restriction of the group's residuals and the prolongation of its corrections are one launch
+ * each where the restrictor has block transfers (below), and the coarse cycle runs column by column.  Elsewhere the one-vector
  * entry point runs per column.  With "internal numbering" lexicographic the columns are gathered into and scattered out of the
  * library's block workspace (one group wide).
  * mfmg_hip_hierarchy_block_info: fields[0] width of the widest group the fine level runs as one launch (1 = the loop over the
@@ -761,6 +762,24 @@ int mfmg_hip_hierarchy_apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, in
 int mfmg_hip_hierarchy_vmult_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, double *x, const double *b);
 int mfmg_hip_hierarchy_smoother_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld, const double *b, double *x);
 int mfmg_hip_hierarchy_block_info(mfmg_hip_hierarchy_t h, int64_t *fields);
+
+/* ---- restriction and prolongation on a block of vectors (additions, no change of the ABI version) ----
+ * mfmg_hip_hierarchy_restrictor_apply_block: mfmg_hip_hierarchy_restrictor_apply(level, in[c], out[c], mode) for every column,
+ * bit for bit (column c of `in` at in + c * ld_in, of `out` at out + c * ld_out).  mode is MFMG_HIP_NO_TRANS, MFMG_HIP_TRANS or
+ * MFMG_HIP_TRANS_SUBTRACT.  1 to 64 vectors; each leading dimension at least the size of its vectors and even; the bases aligned to
+ * 16 bytes; the blocks must not overlap.  A restrictor in the agglomerate-wise form reads its stored values once per group of 4
+ * or 2 columns (the groups of mfmg_hip_block_groups), a single column and every other restrictor go through the one-vector
+ * kernels.  A context with a communicator is refused.  With "internal numbering" lexicographic and level 1 the fine side is
+ * gathered into and scattered out of the library's block workspace column by column.
+ * mfmg_hip_hierarchy_transfer_block_info: fields[0] columns of the widest block restriction of `level` (1 = the loop over the
+ * columns), fields[1] the same of its prolongation (1 for the table-driven 2 x 2 x 2 kernels, which read no stored values per
+ * agglomerate); of the last block call on this hierarchy (a cycle, a solve or _restrictor_apply_block): fields[2] launches of
+ * the block restriction, fields[3] launches of the block prolongation, fields[4] columns whose restriction or prolongation went
+ * through the one-vector kernels. */
+#define MFMG_HIP_TRANSFER_BLOCK_INFO_FIELDS 5
+int mfmg_hip_hierarchy_restrictor_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld_in, const double *in,
+                                              int64_t ld_out, double *out, int mode);
+int mfmg_hip_hierarchy_transfer_block_info(mfmg_hip_hierarchy_t h, int32_t level, int64_t fields[5]);
 
 /* ---- preconditioned CG on a block of right-hand sides (additions, no change of the ABI version) ----
  * mfmg_hip_hierarchy_solve_cg_block: mfmg_hip_hierarchy_solve_cg for every column of the blocks b and x (layout and checks of

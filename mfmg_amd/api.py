@@ -977,6 +977,27 @@ class Hierarchy:
         ni, no = (nf, nc) if mode == _lib.NO_TRANS else (nc, nf)
         check(self._lib.mfmg_hip_hierarchy_restrictor_apply(self.handle, level, _dev_ptr(vin, ni), _dev_ptr(vout, no), mode))
 
+    def restrictor_apply_block(self, level: int, Vin: torch.Tensor, Vout: torch.Tensor, mode: int = _lib.NO_TRANS):
+        """restrictor_apply(level, Vin[c], Vout[c], mode) for every row of the blocks Vin and Vout (2-D float64 tensors of shape
+        (k, m), stride(1) == 1; each leading dimension stride(0) even and at least the size of its vectors, the bases aligned
+        to 16 bytes), bit for bit.  A restrictor in the agglomerate-wise form reads its stored values once per group of 4 or 2
+        rows (transfer_block_info()); one rank only."""
+        k, ld_in, pi = _block_ptr(Vin)
+        ko, ld_out, po = _block_ptr(Vout)
+        if ko != k:
+            raise ValueError("the blocks of one call share the number of vectors")
+        check(self._lib.mfmg_hip_hierarchy_restrictor_apply_block(self.handle, level, k, ld_in, pi, ld_out, po, mode))
+
+    def transfer_block_info(self, level: int = 1) -> dict:
+        """restrict_width / prolong_width: rows of the widest block restriction / prolongation of `level` (1 = the loop over
+        the rows); restrict_launches / prolong_launches: launches of the block kernels, and column_launches: rows whose
+        restriction or prolongation went through the one-vector kernels, in the last block call on this hierarchy (a cycle, a
+        solve or restrictor_apply_block)."""
+        f = (C.c_int64 * 5)()
+        check(self._lib.mfmg_hip_hierarchy_transfer_block_info(self.handle, level, f))
+        return {"restrict_width": int(f[0]), "prolong_width": int(f[1]), "restrict_launches": int(f[2]),
+                "prolong_launches": int(f[3]), "column_launches": int(f[4])}
+
     _RESTRICT_KERNELS = {1: "rows", 2: "pair222", 3: "pair"}
     _PROLONG_KERNELS = {1: "nodes", 2: "block222"}
 

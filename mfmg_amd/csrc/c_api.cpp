@@ -1,5 +1,6 @@
 // extern "C" boundary of libmfmg_hip.so (include/mfmg_hip.h): exceptions of the C++
 // mirror are mapped to status codes; messages are kept per thread.
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -366,6 +367,8 @@ struct mfmg_hip_hierarchy_s
   DeviceBuffer<double> block_work[2];
   int64_t block_info[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0};
   int64_t block_info_f32[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0}; // ... and the last FP32 block call
+  // the transfer counters of every level (transfer_counters below) when the last block call began
+  std::vector<std::array<int64_t, 3>> transfer_snapshot;
   DeviceBuffer<float> block_work_f32[2];
   float *block_workspace_f32(int i, size_t n)
   {
@@ -1818,9 +1821,31 @@ namespace
 {
 // (on_ranks: the entry point runs on a context with a communicator -- the cycle, the smoother, the operator and CG; block FGMRES
 // does not)
+// Block transfers of the restrictor of `level` so far: launches of the block restriction and of the block prolongation, columns
+// whose transfers went through the one-vector kernels (those of the cycles of apply_block count for level 1)
+void transfer_counters(mfmg_hip_hierarchy_t h, int level, int64_t counters[3])
+{
+  counters[0] = counters[1] = counters[2] = 0;
+  if (level < 1 || level >= (int)h->hierarchy->levels().size())
+    return;
+  if (auto r = std::dynamic_pointer_cast<HipMatrixOperator const>(h->hierarchy->levels()[level].get_restrictor()))
+    r->transfer_block_counters(counters);
+  if (level == 1)
+    counters[2] += h->hierarchy->transfer_columns_looped();
+}
+
+// a block call begins: mfmg_hip_hierarchy_transfer_block_info reports what happened since
+void begin_block_call(mfmg_hip_hierarchy_t h)
+{
+  h->transfer_snapshot.resize(h->hierarchy->levels().size());
+  for (size_t level = 0; level < h->transfer_snapshot.size(); ++level)
+    transfer_counters(h, (int)level, h->transfer_snapshot[level].data());
+}
+
 void check_block(mfmg_hip_hierarchy_t h, int level, int32_t n_vectors, int64_t ld, const double *b, const double *x, bool on_ranks = true)
 {
   require(h && b && x, "null argument");
+  begin_block_call(h); // (every block entry point passes here first)
   require(on_ranks || !h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
   require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
   const int64_t n = level_size(h, level);
@@ -3299,6 +3324,94 @@ int mfmg_hip_hierarchy_restrictor_apply(mfmg_hip_hierarchy_t h, int32_t level, c
       if (permute)
         h->perm->scatter(static_cast<double const *>(h->workspace(0)), out);
     }
+  });
+}
+
+int mfmg_hip_hierarchy_restrictor_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld_in, const double *in,
+                                              int64_t ld_out, double *out, int mode)
+{
+  return guarded([&] {
+    require(h && in && out, "null argument");
+    require(mode == MFMG_HIP_NO_TRANS || mode == MFMG_HIP_TRANS || mode == MFMG_HIP_TRANS_SUBTRACT, "unknown operator mode");
+    require(level >= 1 && level < (int)h->hierarchy->levels().size(), "restrictors live on levels >= 1");
+    require(!h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+    require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
+    const int64_t n_fine = level_size(h, level - 1), n_coarse = level_size(h, level);
+    const bool restriction = mode == MFMG_HIP_NO_TRANS;
+    const int64_t n_in = restriction ? n_fine : n_coarse, n_out = restriction ? n_coarse : n_fine;
+    require(ld_in >= n_in && ld_out >= n_out, "the leading dimension of a block must be at least the vector size");
+    require(ld_in % 2 == 0 && ld_out % 2 == 0, "the leading dimension of a block must be even (columns aligned to 16 bytes)");
+    require(reinterpret_cast<uintptr_t>(in) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0, "the base of a block must be aligned to 16 bytes");
+    const int64_t extent_in = (int64_t)(n_vectors - 1) * ld_in + n_in, extent_out = (int64_t)(n_vectors - 1) * ld_out + n_out;
+    require(in + extent_in <= out || out + extent_out <= in, "the blocks in and out overlap");
+    begin_block_call(h);
+    auto r = h->hierarchy->levels()[level].get_restrictor();
+    auto hr = std::dynamic_pointer_cast<HipMatrixOperator const>(r);
+    require(hr != nullptr, "the restrictor of this level is no matrix operator");
+    const auto what = restriction ? HipMatrixOperator::Transfer::restrict_to_coarse
+                                  : (mode == MFMG_HIP_TRANS ? HipMatrixOperator::Transfer::prolongate : HipMatrixOperator::Transfer::prolongate_subtract);
+    // the fine side of the restrictor of level 1 in the internal numbering: gathered into / scattered out of the block workspace,
+    // one group at a time (for_block_groups); otherwise the whole block in one call, which cuts it into the same groups
+    const bool permute = h->perm && level == 1;
+    int widths[kMfBlockMaxGroups] = {n_vectors};
+    const int n_groups = permute ? mf_block_groups(n_vectors, widths) : 1;
+    const int64_t wld = n_fine + (n_fine & 1);
+    int64_t c0 = 0;
+    for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+    {
+      const int w = widths[g];
+      double const *gi = in + c0 * ld_in;
+      double *go = out + c0 * ld_out;
+      int64_t gld_in = ld_in, gld_out = ld_out;
+      if (permute && restriction)
+      {
+        double *wi = h->block_workspace(0, (size_t)w * wld);
+        for (int c = 0; c < w; ++c)
+          h->perm->gather(gi + c * ld_in, wi + c * wld);
+        gi = wi;
+        gld_in = wld;
+      }
+      else if (permute)
+      {
+        double *wo = h->block_workspace(1, (size_t)w * wld);
+        if (mode == MFMG_HIP_TRANS_SUBTRACT)
+          for (int c = 0; c < w; ++c)
+            h->perm->gather(static_cast<double const *>(go + c * ld_out), wo + c * wld);
+        go = wo;
+        gld_out = wld;
+      }
+      std::vector<DVector> iv, ov;
+      iv.reserve(w);
+      ov.reserve(w);
+      std::vector<DVector const *> ip;
+      std::vector<DVector *> op;
+      for (int c = 0; c < w; ++c)
+      {
+        iv.emplace_back(*h->handle, n_in, const_cast<double *>(gi) + c * gld_in);
+        ov.emplace_back(*h->handle, n_out, go + c * gld_out);
+        ip.push_back(&iv.back());
+        op.push_back(&ov.back());
+      }
+      hr->transfer_block(ip, op, what);
+      if (permute && !restriction)
+        for (int c = 0; c < w; ++c)
+          h->perm->scatter(static_cast<double const *>(go + c * wld), out + (c0 + c) * ld_out);
+    }
+  });
+}
+
+int mfmg_hip_hierarchy_transfer_block_info(mfmg_hip_hierarchy_t h, int32_t level, int64_t fields[5])
+{
+  return guarded([&] {
+    require(h && fields, "null argument");
+    require(level >= 1 && level < (int)h->hierarchy->levels().size(), "restrictors live on levels >= 1");
+    auto r = h->hierarchy->levels()[level].get_restrictor();
+    fields[0] = r->transfer_block_width(OperatorMode::NO_TRANS);
+    fields[1] = r->transfer_block_width(OperatorMode::TRANS);
+    int64_t now[3];
+    transfer_counters(h, level, now);
+    for (int i = 0; i < 3; ++i)
+      fields[2 + i] = (size_t)level < h->transfer_snapshot.size() ? now[i] - h->transfer_snapshot[level][i] : 0;
   });
 }
 

@@ -854,6 +854,73 @@ bool block_kernel_layout(std::vector<DVector const *> const &columns, int64_t ld
 }
 } // namespace
 
+// ---- blocks of vectors through a restrictor ----
+int HipMatrixOperator::transfer_block_width(OperatorMode mode) const
+{
+  if (!_structured || _matrix->handle().comm.enabled() || _reverse_range_space > 0)
+    return 1;
+  return mode == OperatorMode::NO_TRANS ? _structured->restrict_block_width() : _structured->prolong_block_width();
+}
+
+void HipMatrixOperator::transfer_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y, Transfer what) const
+{
+  ASSERT_THROW(x.size() == y.size() && !x.empty(), "the blocks of a transfer need the same number of columns");
+  const bool restriction = what == Transfer::restrict_to_coarse;
+  const int64_t ldx = block_leading_dimension(x), ldy = block_leading_dimension(as_const(y));
+  if (transfer_block_width(restriction ? OperatorMode::NO_TRANS : OperatorMode::TRANS) == 1 || x.size() == 1 ||
+      x.size() > (size_t)kMfBlockMaxVectors || ldx == 0 || ldy == 0 || !block_kernel_layout(x, ldx) || !block_kernel_layout(as_const(y), ldy))
+  {
+    for (size_t c = 0; c < x.size(); ++c)
+    {
+      if (what == Transfer::prolongate_subtract)
+        apply_subtract(*x[c], *y[c], OperatorMode::TRANS);
+      else
+        apply(*x[c], *y[c], restriction ? OperatorMode::NO_TRANS : OperatorMode::TRANS);
+    }
+    _transfer_columns_looped += (int64_t)x.size();
+    return;
+  }
+  const int64_t n_in = restriction ? _matrix->n() : _matrix->m(), n_out = restriction ? _matrix->m() : _matrix->n();
+  ASSERT_THROW(x[0]->size() == n_in && y[0]->size() == n_out, "vector sizes do not match the operator");
+  if (restriction)
+    _transfer_columns_looped += _structured->restrict_to_coarse_block((int)x.size(), ldx, x[0]->get_values(), ldy, y[0]->get_values());
+  else
+    _transfer_columns_looped += _structured->prolongate_block((int)x.size(), ldx, x[0]->get_values(), ldy, y[0]->get_values(),
+                                                              what == Transfer::prolongate_subtract);
+}
+
+void HipMatrixOperator::apply_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y) const
+{
+  transfer_block(x, y, Transfer::restrict_to_coarse);
+}
+
+void HipMatrixOperator::apply_subtract_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y, OperatorMode mode) const
+{
+  if (mode == OperatorMode::NO_TRANS)
+    return Operator<DVector>::apply_subtract_block(x, y, mode);
+  transfer_block(x, y, Transfer::prolongate_subtract);
+}
+
+std::vector<std::shared_ptr<DVector>> HipMatrixOperator::build_domain_block(int width, int64_t ld) const
+{
+  const int64_t n = _matrix->n();
+  ASSERT_THROW(width >= 1 && ld >= n, "a block needs a leading dimension of at least the vector size");
+  HipHandle &handle = _matrix->handle();
+  auto storage = std::make_shared<DeviceBuffer<double>>((size_t)width * ld); // (hipMalloc: aligned to 256 bytes)
+  vec::set<double>(handle, (int64_t)width * ld, 0., storage->data());
+  std::vector<std::shared_ptr<DVector>> columns;
+  for (int c = 0; c < width; ++c)
+    columns.emplace_back(new DVector(handle, n, storage->data() + (int64_t)c * ld), [storage](DVector *v) { delete v; });
+  return columns;
+}
+
+void HipMatrixOperator::transfer_block_counters(int64_t counters[3]) const
+{
+  counters[0] = _structured ? _structured->restrict_block_launches() : 0;
+  counters[1] = _structured ? _structured->prolong_block_launches() : 0;
+  counters[2] = _transfer_columns_looped;
+}
+
 int HipMatrixFreeOperator::block_width() const
 {
   auto op = _mesh_evaluator->get_device_operator();

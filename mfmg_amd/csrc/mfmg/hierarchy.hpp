@@ -237,9 +237,12 @@ public:
   // The cycle of apply() on the columns of a block of vectors (several right-hand sides): x[c] gets the bits of apply(b[c], x[c]).
   // Where the fine level offers no block kernel (Smoother / Operator::block_width() == 1) that is what runs.  Otherwise the
   // block is taken in the groups of mf_block_groups (at most four columns) and the whole cycle runs per group: pre-smoothing and
-  // residual on the block -- the operator's data read once for the group --, then restriction, coarse cycle and prolongation
-  // column by column with the kernels of apply(), then post-smoothing on the block.  The workspace is one group wide whatever
-  // the number of columns; it is built at the first block call.  The columns of b and of x must share one leading dimension.
+  // residual on the block -- the operator's data read once for the group --, then the restriction of the group's residuals into
+  // a coarse block and, after the coarse cycle column by column with the kernels of apply(), the prolongation of the group in
+  // one launch each where the restrictor offers it (Operator::transfer_block_width: its stored values read once for the group;
+  // column by column otherwise, and the restriction as in apply() where R (A x - b) is formed in one pass), then post-smoothing
+  // on the block.  The workspaces are one group wide whatever the number of columns; they are built at the first block call.
+  // The columns of b and of x must share one leading dimension.
   void apply_block(std::vector<VectorType const *> const &b, std::vector<VectorType *> const &x) const
   {
     ASSERT_THROW(b.size() == x.size() && !b.empty(), "a block needs as many right-hand sides as iterates");
@@ -259,6 +262,7 @@ public:
         for (size_t c = c0; c < c0 + w; ++c)
           apply(*b[c], *x[c]);
         _block_columns_looped += (int64_t)w;
+        _transfer_columns_looped += (int64_t)w;
         continue;
       }
       timer_enter_subsection(_timer, "Apply: fine levels");
@@ -271,10 +275,30 @@ public:
           *xc = 0.;
       for (unsigned int i = 0; i < _n_smoothing_steps; ++i)
         smoother->apply_block(bg, xg);
-      // the residual of the group in one launch, unless the restrictor forms R (A x - b) in one pass as apply() then does
+      // the coarse vectors of the group: columns of one block where the restrictor has block transfers (right-hand sides, then
+      // iterates), the level's two workspace vectors for one column after the other otherwise
       auto b_coarse = level_coarse.workspace_vector(1);
       auto x_coarse = level_coarse.workspace_vector(2);
-      const bool one_pass = restrictor->restrict_residual(*a, *xg[0], *bg[0], *b_coarse);
+      const bool wide_restrict = restrictor->transfer_block_width(OperatorMode::NO_TRANS) > 1,
+                 wide_prolong = restrictor->transfer_block_width(OperatorMode::TRANS) > 1;
+      std::vector<VectorType *> bc(w, b_coarse.get()), xc(w, x_coarse.get());
+      if (wide_restrict || wide_prolong)
+      {
+        if (_coarse_block_workspace.size() < 2 * w)
+        {
+          MemoryKind kind("hierarchy: coarse block workspace (right-hand sides and iterates of one group on the first coarse level)");
+          _coarse_block_workspace.clear(); // (before the wider one is built)
+          const int64_t n_coarse = b_coarse->size();
+          _coarse_block_workspace = level_coarse.get_operator()->build_domain_block(2 * (int)w, n_coarse + (n_coarse & 1));
+        }
+        for (size_t c = 0; c < w; ++c)
+        {
+          bc[c] = _coarse_block_workspace[c].get();
+          xc[c] = _coarse_block_workspace[w + c].get();
+        }
+      }
+      // the residual of the group in one launch, unless the restrictor forms R (A x - b) in one pass as apply() then does
+      const bool one_pass = restrictor->restrict_residual(*a, *xg[0], *bg[0], *bc[0]);
       std::vector<VectorType *> res;
       if (!one_pass)
       {
@@ -290,15 +314,25 @@ public:
           res.push_back(_block_workspace[c].get());
         a->residual_block(std::vector<VectorType const *>(xg.begin(), xg.end()), bg, res);
       }
+      // restriction and prolongation of the group in one launch each where the restrictor reads its stored values once for the
+      // columns; the coarse cycle column by column in between
+      const bool block_restrict = !one_pass && wide_restrict;
+      if (block_restrict)
+        restrictor->apply_block(std::vector<VectorType const *>(res.begin(), res.end()), bc);
       for (size_t c = 0; c < w; ++c)
       {
-        if (!one_pass)
-          restrictor->apply(*res[c], *b_coarse);
-        else if (c > 0)
-          ASSERT_THROW(restrictor->restrict_residual(*a, *xg[c], *bg[c], *b_coarse), "internal: the one-pass residual restriction was refused");
-        apply(*b_coarse, *x_coarse, 1);
-        restrictor->apply_subtract(*x_coarse, *xg[c], OperatorMode::TRANS);
+        if (!one_pass && !block_restrict)
+          restrictor->apply(*res[c], *bc[c]);
+        else if (one_pass && c > 0)
+          ASSERT_THROW(restrictor->restrict_residual(*a, *xg[c], *bg[c], *bc[c]), "internal: the one-pass residual restriction was refused");
+        apply(*bc[c], *xc[c], 1);
+        if (!wide_prolong)
+          restrictor->apply_subtract(*xc[c], *xg[c], OperatorMode::TRANS);
       }
+      if (wide_prolong)
+        restrictor->apply_subtract_block(std::vector<VectorType const *>(xc.begin(), xc.end()), xg, OperatorMode::TRANS);
+      if (!wide_prolong || (!one_pass && !block_restrict))
+        _transfer_columns_looped += (int64_t)w;
       for (unsigned int i = 0; i < _n_smoothing_steps; ++i)
         smoother->apply_block(bg, xg);
       timer_leave_subsection(_timer);
@@ -306,6 +340,9 @@ public:
   }
   // columns of the last apply_block that went through apply() one by one
   int64_t block_columns_looped() const { return _block_columns_looped; }
+  // columns of all apply_block calls so far whose restriction or prolongation on the fine level went through the one-vector
+  // kernels (the launches of the block transfers are counted where they happen, by the restrictor)
+  int64_t transfer_columns_looped() const { return _transfer_columns_looped; }
   // width of the widest group apply_block runs as one launch on the fine level (1: the loop over the columns)
   int block_width() const
   {
@@ -326,6 +363,7 @@ public:
     auto ap = a->multiply_transpose(restrictor);
     auto a_coarse = restrictor->multiply(ap);
     _levels[1].set_operator(a_coarse);
+    _coarse_block_workspace.clear();
     _helpers->set_coarse_space_hint(restrictor);
     _levels[1].set_solver(_helpers->build_coarse_solver(a_coarse, _params));
   }
@@ -351,5 +389,7 @@ private:
   mutable std::vector<std::shared_ptr<VectorType>> _block_workspace; // apply_block: the residuals of one group
   mutable int64_t _block_workspace_ld = 0;
   mutable int64_t _block_columns_looped = 0;
+  mutable std::vector<std::shared_ptr<VectorType>> _coarse_block_workspace; // apply_block: b_c and x_c of one group
+  mutable int64_t _transfer_columns_looped = 0;
 };
 } // namespace mfmg

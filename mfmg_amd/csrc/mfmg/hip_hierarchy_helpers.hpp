@@ -129,6 +129,19 @@ public:
   void residual(DVector const &x, DVector const &b, DVector &res) const override;
   void apply_subtract(DVector const &x, DVector &y, OperatorMode mode) const override;
   void apply_local(DVector const &x, DVector &y) const override { _matrix->vmult(y.get_values(), x.get_values()); }
+  // Blocks of vectors through a restrictor in the agglomerate-wise form (StructuredRestrictorDevice::restrict_to_coarse_block /
+  // prolongate_block: the planes read once per group of 4 or 2 columns): on one rank, for columns at equal even distances with
+  // bases aligned to 16 bytes.  Otherwise the loops of Operator.  Every column gets the bits of apply / apply_subtract.
+  int transfer_block_width(OperatorMode mode) const override;
+  void apply_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y) const override;
+  void apply_subtract_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y, OperatorMode mode) const override;
+  // y[c] = R x[c], y[c] = R^T x[c] or y[c] -= R^T x[c] on the columns of a block, by the block kernels where the above holds
+  // (the coarse vectors of a group, Hierarchy::apply_block: the columns of one block)
+  std::vector<std::shared_ptr<DVector>> build_domain_block(int width, int64_t ld) const override;
+  enum class Transfer { restrict_to_coarse, prolongate, prolongate_subtract };
+  void transfer_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y, Transfer what) const;
+  // so far: launches of the block restriction / prolongation, columns of transfer_block that went through the one-vector kernels
+  void transfer_block_counters(int64_t counters[3]) const;
 
   void smoother_step(DVector const &b, DVector const &x, DVector const *x_prev, double alpha, double beta,
                      DVector &out) const override;
@@ -184,6 +197,7 @@ private:
   std::shared_ptr<Operator<DVector> const> _rr_operator; // the fine operator the rows of R A were probed for
   int _rr_space = 0; // distributed runs: the fine space with two ghost layers refreshed per side (the 5 layers of R A)
   mutable double const *_prefetched_rhs = nullptr; // the b whose ghost entries are travelling on the exchange stream
+  mutable int64_t _transfer_columns_looped = 0;
   mutable DeviceBuffer<double> _dinv;
 };
 

@@ -92,5 +92,14 @@ public:
     apply(x, *tmp, mode);
     y.add(-1., *tmp);
   }
+  // Extension, called on a RESTRICTOR: blocks of vectors through the transfers.  transfer_block_width(mode): columns the widest
+  // launch of apply_block (NO_TRANS) / apply_subtract_block (TRANS) takes (1: only the loop over the columns exists).
+  // apply_subtract_block: y[c] -= op(A) x[c] for every column c, each with the bits of apply_subtract.
+  virtual int transfer_block_width(OperatorMode /*mode*/) const { return 1; }
+  virtual void apply_subtract_block(std::vector<vector_type const *> const &x, std::vector<vector_type *> const &y, OperatorMode mode) const
+  {
+    for (size_t c = 0; c < x.size(); ++c)
+      apply_subtract(*x[c], *y[c], mode);
+  }
 };
 } // namespace mfmg

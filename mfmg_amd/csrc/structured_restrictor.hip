@@ -10,6 +10,8 @@
 //            every sector.
 #include "structured_restrictor.hpp"
 
+#include "mf_laplace.hpp" // mf_block_groups
+
 #include <omp.h>
 
 #include <algorithm>
@@ -246,6 +248,244 @@ __global__ __launch_bounds__(256) void sr_prolong_kernel(SrArgs s, double const 
   const double sum = sr_node_value(s, y, node);
   const int64_t id = s.node_dof ? (int64_t)s.node_dof[node] : node;
   out[id] = subtract ? out[id] - sum : sum;
+}
+
+// ---- blocks of vectors: K = 2 or 4 columns per launch (column c of x at x + c * ldx) ---------------------------------------
+// The planes are the largest stream of the transfers (16 B per agglomerate and patch node against 8 B of fine vector per node
+// and column): a block launch fetches every plane pair / table entry / class-table entry ONCE for its K columns.  Column c
+// gets the bits of the one-vector launch on that column: every sum is formed over the same terms in the same order with the
+// same expression shapes.  Leading dimensions are even and the bases aligned to 16 bytes (the double2 accesses).
+
+// rows form: one thread per coarse row, K sums
+template <int K>
+__global__ __launch_bounds__(256) void sr_restrict_rows_block_kernel(SrArgs s, double const *x, int64_t ldx, double *y, int64_t ldy)
+{
+  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (r >= s.n_coarse)
+    return;
+  const int64_t ag = r / s.n_eig;
+  const int ai = ag % s.na[0], aj = (ag / s.na[0]) % s.na[1], ak = ag / ((int64_t)s.na[0] * s.na[1]);
+  const int64_t base = (int64_t)ai * s.a[0] + (int64_t)s.N[0] * ((int64_t)aj * s.a[1] + (int64_t)s.N[1] * ((int64_t)ak * s.a[2]));
+  double sum[K];
+#pragma unroll
+  for (int c = 0; c < K; ++c)
+    sum[c] = 0.;
+  int m = 0;
+  for (int mz = 0; mz <= s.a[2]; ++mz)
+    for (int my = 0; my <= s.a[1]; ++my)
+    {
+      const int64_t row = base + (int64_t)s.N[0] * (my + (int64_t)s.N[1] * mz);
+#pragma unroll 3
+      for (int mx = 0; mx <= s.a[0]; ++mx, ++m)
+      {
+        const int64_t node = row + mx;
+        const int64_t id = s.node_dof ? (int64_t)s.node_dof[node] : node;
+        const double pv = sr_plane(s, (size_t)m * s.n_coarse + r);
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+          sum[c] += pv * x[id + c * ldx];
+      }
+    }
+#pragma unroll
+  for (int c = 0; c < K; ++c)
+    y[r + c * ldy] = sum[c];
+}
+
+// pair form: one thread per agglomerate, both rows of the K columns.  A = 2: the one-vector kernel keeps its 27 x values and 27
+// pairs in flight together; K times the x values do not fit a register file that way, so the requests go out one z-layer of
+// the patch at a time: 9 pairs and 9 K values, then the 18 K multiply-adds of the layer in the order m = 0 .. 26.
+template <int A, int K>
+__global__ __launch_bounds__(256) void sr_restrict_pair_block_kernel(SrArgs s, double const *x, int64_t ldx, double *y, int64_t ldy)
+{
+  const int a0 = A > 0 ? A : s.a[0], a1 = A > 0 ? A : s.a[1], a2 = A > 0 ? A : s.a[2];
+  // (the XCD re-dealing of sr_restrict_pair_kernel: the grid is a multiple of 8)
+  const int64_t bid = (int64_t)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const int64_t ag = bid * (int64_t)blockDim.x + threadIdx.x;
+  if (2 * ag >= s.n_coarse)
+    return;
+  const int ai = ag % s.na[0], aj = (ag / s.na[0]) % s.na[1], ak = ag / ((int64_t)s.na[0] * s.na[1]);
+  const int64_t base = (int64_t)ai * a0 + (int64_t)s.N[0] * ((int64_t)aj * a1 + (int64_t)s.N[1] * ((int64_t)ak * a2));
+  const size_t stride = (size_t)s.n_coarse / 2;
+  const bool regular = s.exc != nullptr && s.exc[ag] == 0;
+  const unsigned int cl = (!regular && s.cls != nullptr) ? s.cls[ag] : 0xffffu;
+  // one source of pairs per thread: entry m at src[m * step] -- the reference table, the class table, or the planes in double;
+  // planes kept in float are widened as they arrive
+  const bool from_float = !regular && cl == 0xffffu && s.planes_f != nullptr;
+  double2 const *src = reinterpret_cast<double2 const *>(s.table);
+  size_t step = 1;
+  if (!regular && cl != 0xffffu)
+    src = reinterpret_cast<double2 const *>(s.class_table) + (size_t)cl * s.patch;
+  else if (!regular && !from_float)
+  {
+    src = reinterpret_cast<double2 const *>(s.planes) + ag;
+    step = stride;
+  }
+  float2 const *src_f = reinterpret_cast<float2 const *>(s.planes_f) + ag;
+  double sum0[K], sum1[K];
+#pragma unroll
+  for (int c = 0; c < K; ++c)
+    sum0[c] = sum1[c] = 0.;
+  if constexpr (A == 2)
+  {
+    // (not unrolled: unrolled, the requests of all three layers were hoisted to the front -- 334 VGPRs at K = 4)
+#pragma unroll 1
+    for (int mz = 0; mz < 3; ++mz)
+    {
+      double xv[9][K];
+      double2 pv[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q)
+      {
+        const int64_t node = base + (q % 3) + (int64_t)s.N[0] * (q / 3 + (int64_t)s.N[1] * mz);
+        const int64_t id = s.node_dof ? (int64_t)s.node_dof[node] : node;
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+          xv[q][c] = x[id + c * ldx];
+      }
+      if (from_float)
+      {
+#pragma unroll
+        for (int q = 0; q < 9; ++q)
+        {
+          const float2 v = src_f[(size_t)(9 * mz + q) * stride];
+          pv[q] = make_double2((double)v.x, (double)v.y);
+        }
+      }
+      else
+      {
+#pragma unroll
+        for (int q = 0; q < 9; ++q)
+          pv[q] = src[(size_t)(9 * mz + q) * step];
+      }
+#pragma unroll
+      for (int q = 0; q < 9; ++q)
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+        {
+          sum0[c] += pv[q].x * xv[q][c];
+          sum1[c] += pv[q].y * xv[q][c];
+        }
+    }
+  }
+  else
+  {
+    int m = 0;
+    for (int mz = 0; mz <= a2; ++mz)
+      for (int my = 0; my <= a1; ++my)
+      {
+        const int64_t row = base + (int64_t)s.N[0] * (my + (int64_t)s.N[1] * mz);
+#pragma unroll 3
+        for (int mx = 0; mx <= a0; ++mx, ++m)
+        {
+          const int64_t node = row + mx;
+          const int64_t id = s.node_dof ? (int64_t)s.node_dof[node] : node;
+          double2 pv;
+          if (from_float)
+          {
+            const float2 v = src_f[(size_t)m * stride];
+            pv = make_double2((double)v.x, (double)v.y);
+          }
+          else
+            pv = src[(size_t)m * step];
+#pragma unroll
+          for (int c = 0; c < K; ++c)
+          {
+            const double xv = x[id + c * ldx];
+            sum0[c] += pv.x * xv;
+            sum1[c] += pv.y * xv;
+          }
+        }
+      }
+  }
+#pragma unroll
+  for (int c = 0; c < K; ++c)
+    reinterpret_cast<double2 *>(y + c * ldy)[ag] = make_double2(sum0[c], sum1[c]);
+}
+
+// nodes form of R^T y: one thread per fine node, the K sums of sr_node_value (z, y, x candidates, then the eigenvectors) from
+// plane pairs read once; SUB (out -= R^T y) as a template parameter, the K entries of out requested first
+template <bool SUB, int K>
+__global__ __launch_bounds__(256) void sr_prolong_block_kernel(SrArgs s, double const *y, int64_t ldy, double *out, int64_t ldo)
+{
+  const int64_t node = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t n_nodes = (int64_t)s.N[0] * s.N[1] * s.N[2];
+  if (node >= n_nodes)
+    return;
+  const int64_t id = s.node_dof ? (int64_t)s.node_dof[node] : node;
+  double o[K], sum[K];
+#pragma unroll
+  for (int c = 0; c < K; ++c)
+  {
+    o[c] = SUB ? out[id + c * ldo] : 0.;
+    sum[c] = 0.;
+  }
+  const int i = node % s.N[0], j = (node / s.N[0]) % s.N[1], k = node / ((int64_t)s.N[0] * s.N[1]);
+  int ax[2], mx[2], ay[2], my[2], az[2], mz[2];
+  auto candidates = [](int idx, int a, int na, int ag[2], int mm[2]) {
+    ag[0] = idx / a;
+    mm[0] = idx % a;
+    if (ag[0] >= na)
+      ag[0] = -1;
+    ag[1] = (idx % a == 0 && idx / a >= 1) ? idx / a - 1 : -1;
+    mm[1] = a;
+  };
+  candidates(i, s.a[0], s.na[0], ax, mx);
+  candidates(j, s.a[1], s.na[1], ay, my);
+  candidates(k, s.a[2], s.na[2], az, mz);
+  const int px = s.a[0] + 1, py = s.a[1] + 1;
+  const bool table = s.exc_node != nullptr && s.exc_node[node] == 0;
+  for (int cz = 0; cz < 2; ++cz)
+  {
+    if (az[cz] < 0)
+      continue;
+    for (int cy = 0; cy < 2; ++cy)
+    {
+      if (ay[cy] < 0)
+        continue;
+      for (int cx = 0; cx < 2; ++cx)
+      {
+        if (ax[cx] < 0)
+          continue;
+        const int64_t ag = ax[cx] + (int64_t)s.na[0] * (ay[cy] + (int64_t)s.na[1] * az[cz]);
+        const int m = mx[cx] + px * (my[cy] + py * mz[cz]);
+        const size_t p0 = (size_t)m * s.n_coarse + ag * s.n_eig;
+        double const *yy = y + ag * s.n_eig;
+        if (s.n_eig == 2)
+        {
+          double2 yv[K];
+#pragma unroll
+          for (int c = 0; c < K; ++c)
+            yv[c] = *reinterpret_cast<double2 const *>(yy + c * ldy);
+          double2 pv;
+          if (table)
+            pv = *reinterpret_cast<double2 const *>(s.table + 2 * m);
+          else
+          {
+            const unsigned int cl = s.cls != nullptr ? s.cls[ag] : 0xffffu;
+            pv = cl != 0xffffu ? reinterpret_cast<double2 const *>(s.class_table)[(size_t)cl * s.patch + m]
+                               : sr_plane_pair(s, p0 / 2);
+          }
+#pragma unroll
+          for (int c = 0; c < K; ++c)
+          {
+            sum[c] += pv.x * yv[c].x;
+            sum[c] += pv.y * yv[c].y;
+          }
+        }
+        else
+          for (int e = 0; e < s.n_eig; ++e)
+          {
+            const double pv = sr_plane(s, p0 + e);
+#pragma unroll
+            for (int c = 0; c < K; ++c)
+              sum[c] += pv * yy[e + c * ldy];
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < K; ++c)
+    out[id + c * ldo] = SUB ? o[c] - sum[c] : sum[c];
 }
 
 // the nodes of the listed agglomerate positions: a thread per node (the first workgroups of the block kernel)
@@ -1245,6 +1485,114 @@ void StructuredRestrictorDevice::restrict_to_coarse(double const *x, double *y) 
                        _handle.stream, s, x, y);
   KernelProfiler::end(stop, _handle.stream);
   MFMG_HIP_CHECK(hipGetLastError());
+}
+
+namespace
+{
+void check_block_operands(int k, int64_t ld_in, int64_t n_in, void const *in, int64_t ld_out, int64_t n_out, void const *out)
+{
+  ASSERT_THROW(k >= 1 && k <= kMfBlockMaxVectors, "a block holds 1 to 64 vectors");
+  ASSERT_THROW(in != nullptr && out != nullptr && in != out, "bad vectors");
+  ASSERT_THROW(ld_in >= n_in && ld_out >= n_out, "the leading dimension of a block must be at least the vector size");
+  ASSERT_THROW(ld_in % 2 == 0 && ld_out % 2 == 0, "the leading dimension of a block must be even (columns aligned to 16 bytes)");
+  ASSERT_THROW(reinterpret_cast<uintptr_t>(in) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+               "the base of a block must be aligned to 16 bytes");
+}
+} // namespace
+
+int StructuredRestrictorDevice::restrict_to_coarse_block(int k, int64_t ldx, double const *x, int64_t ldy, double *y) const
+{
+  check_block_operands(k, ldx, _n_fine, x, ldy, _n_coarse, y);
+  SrArgs s = make_args(_planes.data(), _planes_f32.size() ? _planes_f32.data() : nullptr, _identity_numbering ? nullptr : _node_dof.data(), _n_coarse, _N, _na, _a,
+                       _n_eig, _patch, _exc.size() ? _exc.data() : nullptr, _exc_node.size() ? _exc_node.data() : nullptr, _table.data(),
+                       _cls.size() ? _cls.data() : nullptr, _class_table.data());
+  const int kernel = restrict_kernel();
+  int widths[kMfBlockMaxGroups];
+  const int n_groups = mf_block_groups(k, widths);
+  int looped = 0;
+  int64_t c0 = 0;
+  for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+  {
+    const int w = widths[g];
+    double const *gx = x + c0 * ldx;
+    double *gy = y + c0 * ldy;
+    if (w == 1)
+    {
+      restrict_to_coarse(gx, gy);
+      ++looped;
+      continue;
+    }
+    ASSERT_THROW(w == 2 || w == 4, "internal: a group of a block is 4, 2 or 1 columns wide");
+    hipEvent_t stop = _handle.profiler.begin("sr_restrict_block_kernel", algorithmic_bytes() + 8. * (w - 1) * double(_n_fine + _n_coarse),
+                                             _handle.stream);
+    if (kernel != kRestrictRows)
+    {
+      const dim3 grid((unsigned int)(((_n_coarse / 2 + 255) / 256 + 7) / 8 * 8));
+      if (kernel == kRestrictPair2 && w == 4)
+        hipLaunchKernelGGL((sr_restrict_pair_block_kernel<2, 4>), grid, dim3(256), 0, _handle.stream, s, gx, ldx, gy, ldy);
+      else if (kernel == kRestrictPair2)
+        hipLaunchKernelGGL((sr_restrict_pair_block_kernel<2, 2>), grid, dim3(256), 0, _handle.stream, s, gx, ldx, gy, ldy);
+      else if (w == 4)
+        hipLaunchKernelGGL((sr_restrict_pair_block_kernel<0, 4>), grid, dim3(256), 0, _handle.stream, s, gx, ldx, gy, ldy);
+      else
+        hipLaunchKernelGGL((sr_restrict_pair_block_kernel<0, 2>), grid, dim3(256), 0, _handle.stream, s, gx, ldx, gy, ldy);
+    }
+    else
+    {
+      const dim3 grid((unsigned int)((_n_coarse + 255) / 256));
+      if (w == 4)
+        hipLaunchKernelGGL(sr_restrict_rows_block_kernel<4>, grid, dim3(256), 0, _handle.stream, s, gx, ldx, gy, ldy);
+      else
+        hipLaunchKernelGGL(sr_restrict_rows_block_kernel<2>, grid, dim3(256), 0, _handle.stream, s, gx, ldx, gy, ldy);
+    }
+    KernelProfiler::end(stop, _handle.stream);
+    MFMG_HIP_CHECK(hipGetLastError());
+    ++_restrict_block_launches;
+  }
+  return looped;
+}
+
+int StructuredRestrictorDevice::prolongate_block(int k, int64_t ldy, double const *y, int64_t ldo, double *out, bool subtract) const
+{
+  check_block_operands(k, ldy, _n_coarse, y, ldo, _n_fine, out);
+  SrArgs s = make_args(_planes.data(), _planes_f32.size() ? _planes_f32.data() : nullptr, _identity_numbering ? nullptr : _node_dof.data(), _n_coarse, _N, _na, _a,
+                       _n_eig, _patch, _exc.size() ? _exc.data() : nullptr, _exc_node.size() ? _exc_node.data() : nullptr, _table.data(),
+                       _cls.size() ? _cls.data() : nullptr, _class_table.data());
+  const bool block = prolong_block_width() > 1;
+  int widths[kMfBlockMaxGroups];
+  const int n_groups = mf_block_groups(k, widths);
+  int looped = 0;
+  int64_t c0 = 0;
+  for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+  {
+    const int w = widths[g];
+    double const *gy = y + c0 * ldy;
+    double *go = out + c0 * ldo;
+    if (w == 1 || !block)
+    {
+      for (int c = 0; c < w; ++c)
+        prolongate(gy + c * ldy, go + c * ldo, subtract);
+      looped += w;
+      continue;
+    }
+    ASSERT_THROW(w == 2 || w == 4, "internal: a group of a block is 4, 2 or 1 columns wide");
+    hipEvent_t stop = _handle.profiler.begin("sr_prolong_block_kernel",
+                                             algorithmic_bytes() + 8. * (w - 1) * double(_n_fine + _n_coarse) + (subtract ? 8. * w * double(_n_fine) : 0.),
+                                             _handle.stream);
+    const dim3 grid((unsigned int)((_n_fine + 255) / 256));
+    if (subtract && w == 4)
+      hipLaunchKernelGGL((sr_prolong_block_kernel<true, 4>), grid, dim3(256), 0, _handle.stream, s, gy, ldy, go, ldo);
+    else if (subtract)
+      hipLaunchKernelGGL((sr_prolong_block_kernel<true, 2>), grid, dim3(256), 0, _handle.stream, s, gy, ldy, go, ldo);
+    else if (w == 4)
+      hipLaunchKernelGGL((sr_prolong_block_kernel<false, 4>), grid, dim3(256), 0, _handle.stream, s, gy, ldy, go, ldo);
+    else
+      hipLaunchKernelGGL((sr_prolong_block_kernel<false, 2>), grid, dim3(256), 0, _handle.stream, s, gy, ldy, go, ldo);
+    KernelProfiler::end(stop, _handle.stream);
+    MFMG_HIP_CHECK(hipGetLastError());
+    ++_prolong_block_launches;
+  }
+  return looped;
 }
 
 void StructuredRestrictorDevice::prolongate(double const *y, double *out, bool subtract) const

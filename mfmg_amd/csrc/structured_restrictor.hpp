@@ -36,6 +36,20 @@ public:
   void prolongate(double const *y, double *out, bool subtract) const;
   double algorithmic_bytes() const; // the CSR figure of SURVEY.md 8d for one application
 
+  // ---- blocks of vectors: the planes read once for a group of columns ------------------------------------------------------
+  // Column c of x at x + c * ldx, of y at y + c * ldy (leading dimensions at least the vector size and even, bases aligned to
+  // 16 bytes).  The k columns are cut into the groups of mf_block_groups (4, 4, ..., 2, 1): one launch per group of 4 or 2 where
+  // a block kernel exists (restrict_block_width / prolong_block_width), the one-vector method per column otherwise.  Every column
+  // gets the bits of the one-vector method.  Both return the columns that went through the one-vector method.
+  int restrict_to_coarse_block(int k, int64_t ldx, double const *x, int64_t ldy, double *y) const;
+  int prolongate_block(int k, int64_t ldy, double const *y, int64_t ldo, double *out, bool subtract) const;
+  int restrict_block_width() const { return 4; }
+  // (the table-driven 2 x 2 x 2 kernels read no stored values per agglomerate: no block form, the loop over the columns)
+  int prolong_block_width() const { return prolong_kernel() == kProlongNodes ? 4 : 1; }
+  // block launches so far
+  int64_t restrict_block_launches() const { return _restrict_block_launches; }
+  int64_t prolong_block_launches() const { return _prolong_block_launches; }
+
   // ---- b_c = R (A x - b) in ONE pass over x and b (residual_restriction.hip) ----------------------------------
   // For a fine operator that repeats its rows from agglomerate to agglomerate (constant coefficient: every
   // agglomerate at the same distance from the faces of the box sees the same 5 x 5 x 5 rows of R A), the product R A is
@@ -108,6 +122,7 @@ private:
   int _n_classes = 0;
   int64_t _n_regular = 0;
   bool _restrict_rows = false; // MFMG_SR_RESTRICT=rows: the row kernel whatever n_eig and the agglomerate
+  mutable int64_t _restrict_block_launches = 0, _prolong_block_launches = 0;
   // the block kernel as a march (structured_restrictor.hip): the box of agglomerate positions the tables serve (empty: hi < lo)
   // and the layers of a march (0: chosen per launch grid); MFMG_SR_PROLONG=block keeps the thread-per-position kernel
   bool _prolong_march = false;

@@ -266,6 +266,8 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_operator_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
         "mfmg_hip_hierarchy_smoother_apply": (C.c_int, [vp, i32, vp, vp]),
         "mfmg_hip_hierarchy_restrictor_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
+        "mfmg_hip_hierarchy_restrictor_apply_block": (C.c_int, [vp, i32, i32, i64, vp, i64, vp, C.c_int]),
+        "mfmg_hip_hierarchy_transfer_block_info": (C.c_int, [vp, i32, P(i64)]),
         "mfmg_hip_hierarchy_restrictor_form": (C.c_int, [vp, i32, P(i32), i32]),
         "mfmg_hip_hierarchy_restrictor_eigensolver_info": (C.c_int, [vp, P(i64), i32]),
         "mfmg_hip_hierarchy_restrictor_eigensolver_seconds": (C.c_int, [vp, P(dbl)]),
@@ -317,7 +319,8 @@ def load() -> C.CDLL:
                    "mfmg_hip_block_krylov_combine", "mfmg_hip_mf_laplace_f32_block_launch", "mfmg_hip_mf_laplace_f32_block_available",
                    "mfmg_hip_mf_laplace_f32_set_block_tile", "mfmg_hip_mf_laplace_f32_get_block_tile",
                    "mfmg_hip_hierarchy_apply_f32_block", "mfmg_hip_hierarchy_block_info_f32",
-                   "mfmg_hip_mf_laplace_uniform_coefficient", "mfmg_hip_context_exchange_block", "mfmg_hip_block_dots_box"}
+                   "mfmg_hip_mf_laplace_uniform_coefficient", "mfmg_hip_context_exchange_block", "mfmg_hip_block_dots_box",
+                   "mfmg_hip_hierarchy_restrictor_apply_block", "mfmg_hip_hierarchy_transfer_block_info"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
