@@ -840,9 +840,10 @@ int mfmg_hip_block_cg_update(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64
  * the ranks in one all-reduce each: three per iteration whatever n_vectors, plus one for the initial residuals; every rank gets the
  * same counts and histories.  The bits of mfmg_hip_hierarchy_solve_cg on the same ranks hold where the transport sums an element in
  * the same order whatever the length of the message (any transport on two ranks).
- * STILL refused on a communicator (MFMG_HIP_ERROR_INVALID_ARGUMENT): mfmg_hip_hierarchy_solve_fgmres_block,
- * mfmg_hip_hierarchy_apply_f32_block, mfmg_hip_mf_laplace_block_launch / _f32_block_launch (launches on one rank's memory, no
- * exchange) and the stand-alone kernel calls mfmg_hip_block_dots / _cg_direction / _cg_update / _block_krylov_*.
+ * STILL refused on a communicator (MFMG_HIP_ERROR_INVALID_ARGUMENT): mfmg_hip_mf_laplace_block_launch / _f32_block_launch (launches
+ * on one rank's memory, no exchange) and the stand-alone kernel calls mfmg_hip_block_dots / _cg_direction / _cg_update /
+ * _block_krylov_*.  (mfmg_hip_hierarchy_apply_f32_block runs on ranks, mfmg_hip_hierarchy_solve_fgmres_block where the context
+ * enabled it: see below.)
  * mfmg_hip_context_exchange_block: the forward exchange (owner -> ghost) of the n_vectors columns V + c ld of the fine DoF space
  * (space must be 1), `width` planes deep (the rule of mfmg_hip_context_exchange_f32): ONE packing launch, ONE grouped send/recv,
  * ONE unpacking launch.  Every existing neighbour gets one message: the one-vector message of column 0, then that of column 1,
@@ -856,6 +857,42 @@ int mfmg_hip_block_cg_update(mfmg_hip_context_t ctx, int64_t n, int32_t k, int64
 int mfmg_hip_context_exchange_block(mfmg_hip_context_t ctx, int32_t space, int32_t n_vectors, int64_t ld, double *V, int width);
 int mfmg_hip_block_dots_box(mfmg_hip_context_t ctx, const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n, int32_t comps,
                             int32_t k, int64_t ld, const double *X, const double *Y, double *out);
+
+/* ---- flexible GMRES on blocks and the FP32 block level on several ranks (additions, no change of the ABI version) ----
+ * mfmg_hip_context_set_block_fgmres_on_ranks(ctx, 1) lets mfmg_hip_hierarchy_solve_fgmres_block through on a context with a
+ * communicator; without it the call stays refused there (MFMG_HIP_ERROR_INVALID_ARGUMENT), as it always was, so that a caller
+ * that relies on the refusal keeps it.  The solve is collective: enable it on the context of EVERY rank, before the solve.
+ * The blocks then hold the ranks' local vectors.  Both
+ * Gram-Schmidt passes, the norms and the scaling run over the owned entries of ALL live slots in one launch each; the j + 1
+ * coefficients of a pass of all live slots cross the ranks in ONE all-reduce, their ||w||^2 in one more: three all-reduces per
+ * iteration whatever n_vectors, plus one per cycle start.  Every control decision is taken from all-reduced values, so every rank
+ * retires, hands over (a breakdown) and restarts the same columns in the same iteration.  On the entries a rank owns every column
+ * gets x, the iteration count, the final residual and the history of mfmg_hip_hierarchy_solve_fgmres on the same ranks where the
+ * transport sums an element in the same order whatever the length of the message (any transport on two ranks).  work[] reports as
+ * on one rank.
+ * mfmg_hip_hierarchy_block_solve_allreduces: *n = the all-reduces of the last mfmg_hip_hierarchy_solve_fgmres_block on this
+ * hierarchy, those of columns handed to the one-vector loop included (0 on one rank).
+ * mfmg_hip_hierarchy_apply_f32_block and preconditioner_fp32 = 1 on ranks: per group of 4 or 2 float columns ONE
+ * mfmg_hip_context_exchange_block_f32 of the group's x, one plane deep, in front of each block launch (not overlapped);
+ * restriction, coarse cycle and prolongation per column with their own exchanges.  Whether groups run as blocks is agreed once, when
+ * the hierarchy is built (the smallest offer of 4 | 1 over the ranks: mfmg_hip_hierarchy_block_info_f32 fields[0]); where a rank
+ * offers 1 every rank loops over the columns.  On owned entries a column has the bits of mfmg_hip_hierarchy_apply_f32 on the same
+ * ranks.
+ * mfmg_hip_context_exchange_block_f32: mfmg_hip_context_exchange_block for the columns of a FLOAT block (ld even, base aligned to
+ * 8 bytes): the packing launch widens into the staging of the FP64 block exchange, the unpacking launch narrows -- the same
+ * messages, peers and counters (one exchange, n_vectors times the one-vector doubles); every ghost entry gets the bits of
+ * mfmg_hip_context_exchange_f32 of its column.
+ * mfmg_hip_block_krylov_orthogonalize_box: mfmg_hip_block_krylov_orthogonalize over the OWNED entries of a rank's local vectors
+ * (the box of mfmg_hip_krylov_orthogonalize_box replaces n; vectors of comps * the local nodes entries), on a context WITHOUT a
+ * communicator -- the sum over the ranks is the identity (tests).  Per live slot the bits of mfmg_hip_krylov_orthogonalize_box
+ * with passes = 2; ghost entries, padding and slots that are not live are neither used nor written.  No float copy: on ranks the
+ * driver narrows the whole local vector. */
+int mfmg_hip_context_set_block_fgmres_on_ranks(mfmg_hip_context_t ctx, int enable);
+int mfmg_hip_hierarchy_block_solve_allreduces(mfmg_hip_hierarchy_t h, int64_t *n);
+int mfmg_hip_context_exchange_block_f32(mfmg_hip_context_t ctx, int32_t space, int32_t n_vectors, int64_t ld, float *V, int width);
+int mfmg_hip_block_krylov_orthogonalize_box(mfmg_hip_context_t ctx, const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n,
+                                            int32_t comps, int32_t k, int64_t ld, int32_t j, int32_t n_live, const int32_t *live_slots,
+                                            double *V, double *v_next, double *h_out, double *norm_out);
 
 /* ---- flexible GMRES on a block of right-hand sides (additions, no change of the ABI version) ----
  * mfmg_hip_hierarchy_solve_fgmres_block: mfmg_hip_hierarchy_solve_fgmres for every column of the blocks b and x (layout and checks

@@ -281,6 +281,19 @@ class Context:
         k, ld, pv = _block_ptr(V)
         check(self._lib.mfmg_hip_context_exchange_block(self.handle, int(space), k, ld, pv, int(width)))
 
+    def set_block_fgmres_on_ranks(self, enable: bool = True):
+        """Lets Hierarchy.solve_fgmres_block run on this context when it has a HaloTransport; without it the call is refused
+        there, as it always was.  The solve is collective: every rank enables it on its context before the solve."""
+        check(self._lib.mfmg_hip_context_set_block_fgmres_on_ranks(self.handle, 1 if enable else 0))
+
+    def exchange_block_f32(self, space: int, V: torch.Tensor, width: int = 1):
+        """exchange_block for the rows of a float32 block (ld = stride(0) even, the base aligned to 8 bytes): one packing launch
+        that widens into the staging of the FP64 block exchange, one grouped send/recv, one unpacking launch that narrows; the
+        messages and counters of exchange_block.  Every row gets the bits of exchange_f32 of that row.  Nothing happens without
+        a HaloTransport."""
+        k, ld, pv = _block_ptr(V, torch.float32)
+        check(self._lib.mfmg_hip_context_exchange_block_f32(self.handle, int(space), k, ld, pv, int(width)))
+
     def block_dots_box(self, box, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
         """out[s] = the part of (X[s], Y[s]) over the owned entries of a rank's local vectors, box = (local_nodes, own0, own_n,
         comps) as for krylov_orthogonalize: the reduction of solve_cg_block on several ranks, on a context WITHOUT a communicator.
@@ -378,6 +391,31 @@ class Context:
         ptr = lambda t: None if t is None else t.data_ptr()
         check(self._lib.mfmg_hip_block_krylov_orthogonalize(self.handle, int(n), k, ld, int(j), len(live), slots, pv, ptr(v_next),
                                                             ptr(v_next_f32), h.data_ptr(), norm.data_ptr()))
+        return h, norm
+
+    def block_krylov_orthogonalize_box(self, box, V: torch.Tensor, j: int, live, v_next=None):
+        """block_krylov_orthogonalize over the owned entries of a rank's local vectors, box = (local_nodes, own0, own_n, comps) as
+        for krylov_orthogonalize: the kernels of solve_fgmres_block on several ranks, on a context WITHOUT a communicator (the sum
+        over the ranks is the identity).  Returns (h, norm) as block_krylov_orthogonalize; v_next (k, ld) float64 receives the
+        owned entries of w_s / ||w_s||.  Per live slot the bits of krylov_orthogonalize(..., box=box); ghost entries, the padding
+        between the rows and the slots that are not live are neither used nor written."""
+        nv, k, ld, pv = self._basis_block(V)
+        local_nodes, own0, own_n, comps = box
+        if not 0 <= j < nv - 1:
+            raise ValueError("the block holds no vector j + 1")
+        if ld < comps * local_nodes[0] * local_nodes[1] * local_nodes[2]:
+            raise ValueError("the leading dimension is smaller than the local vectors of the box")
+        if v_next is not None and (v_next.dtype != torch.float64 or tuple(v_next.shape) != (k, ld) or not v_next.is_contiguous()
+                                   or v_next.device != V.device):
+            raise ValueError("v_next is a contiguous (k, ld) float64 tensor on the device of V")
+        h = torch.full((k, j + 1), float("nan"), dtype=torch.float64, device=V.device)
+        norm = torch.full((k,), float("nan"), dtype=torch.float64, device=V.device)
+        slots = (C.c_int32 * max(len(live), 1))(*[int(s) for s in live])
+        i3 = C.c_int64 * 3
+        check(self._lib.mfmg_hip_block_krylov_orthogonalize_box(self.handle, i3(*local_nodes), i3(*own0), i3(*own_n), int(comps), k, ld,
+                                                                int(j), len(live), slots, pv,
+                                                                None if v_next is None else v_next.data_ptr(), h.data_ptr(),
+                                                                norm.data_ptr()))
         return h, norm
 
     def block_krylov_combine(self, n: int, Z: torch.Tensor, y: torch.Tensor, live, slot_col, X: torch.Tensor):
@@ -907,7 +945,10 @@ class Hierarchy:
 
     def apply_f32_block(self, B: torch.Tensor, X: torch.Tensor):
         """The cycle of apply_f32() on every row of the float32 blocks B and X (shape (k, m), stride(1) == 1, one even leading
-        dimension ld = stride(0) >= n_dofs, bases aligned to 8 bytes).  Row c of X gets the bits of apply_f32(B[c], X[c])."""
+        dimension ld = stride(0) >= n_dofs, bases aligned to 8 bytes).  Row c of X gets the bits of apply_f32(B[c], X[c]).  On a
+        context with a HaloTransport the rows are the rank's local float vectors and that holds on the entries the rank owns; a
+        group of 4 or 2 rows exchanges its ghost planes in one message per neighbour where the ranks agreed on float blocks at
+        setup (block_info_f32()["width"] == 4), else every rank loops over the rows."""
         k, ld, pb = _block_ptr(B, torch.float32)
         check(self._lib.mfmg_hip_hierarchy_apply_f32_block(self.handle, k, ld, pb, _same_block(k, ld, X, torch.float32)))
 
@@ -1281,7 +1322,13 @@ class Hierarchy:
         Returns (iterations, histories, work): k ints, k arrays, and a dict with the column-applications of the preconditioner
         and of the operator inside Arnoldi steps (each the sum of the iterations), the launches of the block kernel and the
         cycle-start residuals formed.  Raises the error of solve_fgmres when a column is unconverged at max_iterations; X and
-        `last_block_solve` (the same triple, with the final residuals as `residuals` in the dict) are filled."""
+        `last_block_solve` (the same triple, with the final residuals as `residuals` in the dict) are filled.
+        On a context with a HaloTransport the call is refused unless every rank called Context.set_block_fgmres_on_ranks(); then
+        B and X hold the rank's local vectors: the Gram-Schmidt passes and the norms run over
+        the owned entries of all live rows and cross the ranks in one all-reduce each -- three per iteration whatever k, one per
+        cycle start, counted in work["allreduces"]; every rank gets the same counts and histories, and the bits of solve_fgmres
+        on the same ranks where the transport adds an element in the same order whatever the length of the message (any
+        transport on two ranks)."""
         if preconditioner not in ("double", "float"):
             raise _lib.MfmgInvalidArgument('preconditioner must be "double" or "float"')
         k, ld, pb = _block_ptr(B)
@@ -1296,9 +1343,13 @@ class Hierarchy:
                                                                  1 if preconditioner == "float" else 0,
                                                                  its.ctypes.data_as(C.POINTER(C.c_int32)), dp(res), dp(hist),
                                                                  hist.shape[1], work.ctypes.data_as(C.POINTER(C.c_int64)))
+        n_allreduces = C.c_int64()
+        count = getattr(self._lib, "mfmg_hip_hierarchy_block_solve_allreduces", None)  # (a comparison library may lack it)
+        if count is not None:
+            count(self.handle, C.byref(n_allreduces))
         out = ([int(i) for i in its], [hist[c, : its[c] + 1].copy() for c in range(k)],
                {"preconditioner_columns": int(work[0]), "operator_columns": int(work[1]), "block_launches": int(work[2]),
-                "cycle_starts": int(work[3]), "residuals": [float(r) for r in res]})
+                "cycle_starts": int(work[3]), "allreduces": int(n_allreduces.value), "residuals": [float(r) for r in res]})
         self.last_block_solve = out
         check(status)
         return out

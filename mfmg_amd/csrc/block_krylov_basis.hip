@@ -2,6 +2,9 @@
 // body of its one-vector kernel (krylov_basis_bodies.hpp, shared with krylov_basis.hip) with the pointers of one slot: grid.x walks
 // the entries exactly as there, the last grid dimension indexes the list of live slots.  Streaming kernels, wave64, 256 threads,
 // 16-byte accesses; the loads of a group of kGroup = 8 basis vectors are issued before the first is used.
+// The owned-box kernels (several ranks) wrap the owned-box bodies the same way: the grid in x and the walk over the rows of the box
+// are those of the one-vector owned-box kernels (krylov_basis.hip, head comment), the walk in 32-bit integers where the local vector
+// allows it.
 #include "block_krylov_basis.hpp"
 
 #include "krylov_basis_bodies.hpp"
@@ -71,7 +74,88 @@ __global__ __launch_bounds__(block_size) void scale_store_kernel(SlotList live, 
                       v_next_f32 ? v_next_f32 + s * ld : nullptr, norm_out + s * norm_stride, wsum);
 }
 
+// ---- owned-box kernels: the owned-box bodies with the pointers of one slot; Index: the type the walk over the rows runs in ----
+// blockIdx.y: the group of kGroup columns, blockIdx.z: the live slot; partials[slot][column][block]
+template <typename Index>
+__global__ __launch_bounds__(block_size) void box_dots_kernel(SlotList live, RowWalk walk, int64_t ld, int64_t ldv, int n_columns,
+                                                               int partial_columns, double const *__restrict__ V,
+                                                               double const *__restrict__ w, double *__restrict__ partials)
+{
+  __shared__ double wsum[kGroup][kWaves];
+  const RowWalkT<Index> g(walk);
+  const int64_t s = live.id[blockIdx.z];
+  const int c0 = blockIdx.y * kGroup;
+  const int nc = min(kGroup, n_columns - c0);
+  box_dots_group<2>(nc, g, ldv, V + s * ld + (int64_t)c0 * ldv, w + s * ld, partials + (s * partial_columns + c0) * gridDim.x, wsum);
+}
+
+// blockIdx.x: the column, blockIdx.y: the live slot; the coefficients of the pass PACKED in the order of the list
+__global__ __launch_bounds__(block_size) void box_dots_finish_kernel(SlotList live, int n_partials, int partial_columns, int n_columns,
+                                                                      double const *__restrict__ partials, double *h_pass, double *h_total,
+                                                                      int64_t cstride, int accumulate)
+{
+  __shared__ double wsum[kWaves];
+  const int64_t s = live.id[blockIdx.y];
+  double *const pass = h_pass + (int64_t)blockIdx.y * n_columns + blockIdx.x;
+  dots_finish_body(n_partials, partials + (s * partial_columns + blockIdx.x) * n_partials, pass,
+                   h_total ? h_total + s * cstride + blockIdx.x : pass, accumulate, wsum);
+}
+
+template <typename Index>
+__global__ __launch_bounds__(block_size) void box_norm_partials_kernel(SlotList live, RowWalk walk, int64_t ld, double const *__restrict__ w,
+                                                                        double *__restrict__ norm_partials)
+{
+  __shared__ double wsum[kGroup][kWaves];
+  const RowWalkT<Index> g(walk);
+  const int64_t s = live.id[blockIdx.y];
+  box_dots_group<2>(1, g, ld, w + s * ld, w + s * ld, norm_partials + s * kMaxBlocks, wsum);
+}
+
+// blockIdx.x: the entry of the list; out[entry] = the partials of its slot in a fixed order
+__global__ __launch_bounds__(block_size) void norm_finish_kernel(SlotList live, int n_partials, double const *__restrict__ norm_partials,
+                                                                  double *out)
+{
+  __shared__ double wsum[kWaves];
+  const int64_t s = live.id[blockIdx.x];
+  dots_finish_body(n_partials, norm_partials + s * kMaxBlocks, out + blockIdx.x, out + blockIdx.x, 0, wsum);
+}
+
+// blockIdx.y: the live slot, its coefficients at c + blockIdx.y * n_columns
+template <bool kNorm, typename Index>
+__global__ __launch_bounds__(block_size) void box_axpy_kernel(SlotList live, RowWalk walk, int64_t ld, int64_t ldv, int n_columns,
+                                                               double const *__restrict__ V, double const *__restrict__ c,
+                                                               double *__restrict__ out, double *__restrict__ norm_partials)
+{
+  __shared__ double wsum[1][kWaves];
+  const RowWalkT<Index> g(walk);
+  const int64_t s = live.id[blockIdx.y];
+  box_axpy_body<2, kNorm>(g, ldv, n_columns, V + s * ld, c + (int64_t)blockIdx.y * n_columns, -1., out + s * ld,
+                          norm_partials + s * kMaxBlocks, wsum);
+}
+
+template <typename Index>
+__global__ __launch_bounds__(block_size) void box_scale_store_kernel(SlotList live, RowWalk walk, int64_t ld,
+                                                                      double const *__restrict__ norm_squared, double const *w, double *v_next,
+                                                                      double *__restrict__ norm_out, int64_t norm_stride)
+{
+  const RowWalkT<Index> g(walk);
+  const int64_t s = live.id[blockIdx.y];
+  box_scale_store_body<2>(g, norm_squared + blockIdx.y, w + s * ld, v_next ? v_next + s * ld : nullptr,
+                          norm_out ? norm_out + s * norm_stride : nullptr);
+}
+
 bool aligned16(void const *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// the walk of an owned-box block launch (16-byte accesses) and whether it fits 32-bit integers
+bool short_index(krylov::OwnedBox const &box) { return box.n_local() < (int64_t(1) << 31); }
+
+void check_box(krylov::OwnedBox const &b, int64_t n, int64_t ld)
+{
+  ASSERT_THROW(b.comps >= 1, "block krylov basis: no component");
+  for (int d = 0; d < 3; ++d)
+    ASSERT_THROW(b.own0[d] >= 0 && b.own_n[d] >= 1 && b.own0[d] + b.own_n[d] <= b.local[d], "block krylov basis: the owned box leaves the local box");
+  ASSERT_THROW(n == b.n_local() && ld >= n && ld % 2 == 0, "block krylov basis: the box does not describe the vectors of the block");
+}
 
 void check_list(SlotList const &live, int slots)
 {
@@ -142,6 +226,108 @@ void scale_store(HipHandle &h, Scratch &s, SlotList const &live, int64_t n, int6
       h.profiler.begin("block_basis_scale_store", v_next == nullptr ? 0. : double(n) * (16. + (v_next_f32 ? 4. : 0.)) * live.count, h.stream);
   hipLaunchKernelGGL(scale_store_kernel, dim3(v_next == nullptr ? 1u : (unsigned)nb, live.count), dim3(block_size), 0, h.stream, live, n, ld, nb,
                      s.norm_partials.data(), w, v_next, v_next_f32, norm_out, norm_stride);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+// ---- owned-box launches ---------------------------------------------------------------------------------------------------------
+void dots(HipHandle &h, Scratch &s, SlotList const &live, krylov::OwnedBox const &box, Basis const &V, int n_columns, double const *w,
+          double *h_total, int64_t cstride, bool accumulate)
+{
+  check_list(live, s.slots);
+  check_basis(V, n_columns);
+  check_box(box, V.n, V.ld);
+  if (n_columns == 0)
+    return;
+  ASSERT_THROW(n_columns <= s.columns && aligned16(w), "block krylov basis: more columns than the scratch was built for, or w not aligned");
+  const unsigned int nb = krylov::reduction_blocks(box), n_groups = (unsigned)((n_columns + kGroup - 1) / kGroup);
+  const RowWalk g = row_walk(box, 2, nb);
+  const dim3 grid(nb, n_groups, live.count);
+  hipEvent_t stop = h.profiler.begin("block_basis_dots_box", 8. * double(box.n_owned()) * (n_columns + (int)n_groups) * live.count, h.stream);
+  if (short_index(box))
+    hipLaunchKernelGGL(box_dots_kernel<uint32_t>, grid, dim3(block_size), 0, h.stream, live, g, V.ld, V.ldv, n_columns, s.columns, V.base, w,
+                       s.dot_partials.data());
+  else
+    hipLaunchKernelGGL(box_dots_kernel<int64_t>, grid, dim3(block_size), 0, h.stream, live, g, V.ld, V.ldv, n_columns, s.columns, V.base, w,
+                       s.dot_partials.data());
+  hipLaunchKernelGGL(box_dots_finish_kernel, dim3(n_columns, live.count), dim3(block_size), 0, h.stream, live, (int)nb, s.columns, n_columns,
+                     s.dot_partials.data(), s.pass_coefficients.data(), h_total, cstride, accumulate ? 1 : 0);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+namespace
+{
+template <bool kNorm>
+void launch_box_axpy(HipHandle &h, Scratch &s, SlotList const &live, krylov::OwnedBox const &box, Basis const &V, int n_columns, double *w)
+{
+  const unsigned int nb = krylov::reduction_blocks(box);
+  const RowWalk g = row_walk(box, 2, nb);
+  const dim3 grid(nb, live.count);
+  if (short_index(box))
+    hipLaunchKernelGGL((box_axpy_kernel<kNorm, uint32_t>), grid, dim3(block_size), 0, h.stream, live, g, V.ld, V.ldv, n_columns, V.base,
+                       s.pass_coefficients.data(), w, s.norm_partials.data());
+  else
+    hipLaunchKernelGGL((box_axpy_kernel<kNorm, int64_t>), grid, dim3(block_size), 0, h.stream, live, g, V.ld, V.ldv, n_columns, V.base,
+                       s.pass_coefficients.data(), w, s.norm_partials.data());
+}
+} // namespace
+
+void update(HipHandle &h, Scratch &s, SlotList const &live, krylov::OwnedBox const &box, Basis const &V, int n_columns, double *w,
+            bool with_norm)
+{
+  check_list(live, s.slots);
+  check_basis(V, n_columns);
+  check_box(box, V.n, V.ld);
+  ASSERT_THROW(n_columns <= s.columns && aligned16(w), "block krylov basis: more columns than the scratch was built for, or w not aligned");
+  hipEvent_t stop = h.profiler.begin("block_basis_update_box", 8. * double(box.n_owned()) * (n_columns + 2) * live.count, h.stream);
+  if (with_norm)
+    launch_box_axpy<true>(h, s, live, box, V, n_columns, w);
+  else
+    launch_box_axpy<false>(h, s, live, box, V, n_columns, w);
+  KernelProfiler::end(stop, h.stream);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void norm_partials(HipHandle &h, Scratch &s, SlotList const &live, krylov::OwnedBox const &box, int64_t ld, double const *w)
+{
+  check_list(live, s.slots);
+  check_box(box, box.n_local(), ld);
+  ASSERT_THROW(aligned16(w), "block krylov basis: bad shape");
+  const unsigned int nb = krylov::reduction_blocks(box);
+  const RowWalk g = row_walk(box, 2, nb);
+  if (short_index(box))
+    hipLaunchKernelGGL(box_norm_partials_kernel<uint32_t>, dim3(nb, live.count), dim3(block_size), 0, h.stream, live, g, ld, w,
+                       s.norm_partials.data());
+  else
+    hipLaunchKernelGGL(box_norm_partials_kernel<int64_t>, dim3(nb, live.count), dim3(block_size), 0, h.stream, live, g, ld, w,
+                       s.norm_partials.data());
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void norm_finish(HipHandle &h, Scratch &s, SlotList const &live, krylov::OwnedBox const &box)
+{
+  check_list(live, s.slots);
+  hipLaunchKernelGGL(norm_finish_kernel, dim3(live.count), dim3(block_size), 0, h.stream, live, (int)krylov::reduction_blocks(box),
+                     s.norm_partials.data(), s.norm_squared.data());
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void scale_store(HipHandle &h, SlotList const &live, krylov::OwnedBox const &box, int64_t ld, double const *norm_squared, double const *w,
+                 double *v_next, double *norm_out, int64_t norm_stride)
+{
+  check_list(live, kMaxSlots);
+  check_box(box, box.n_local(), ld);
+  ASSERT_THROW(norm_squared != nullptr && aligned16(w) && aligned16(v_next), "block krylov basis: bad shape");
+  const unsigned int nb = v_next == nullptr ? 1u : krylov::reduction_blocks(box);
+  const RowWalk g = row_walk(box, 2, nb);
+  hipEvent_t stop = h.profiler.begin("block_basis_scale_store_box", v_next == nullptr ? 0. : 16. * double(box.n_owned()) * live.count, h.stream);
+  if (short_index(box))
+    hipLaunchKernelGGL(box_scale_store_kernel<uint32_t>, dim3(nb, live.count), dim3(block_size), 0, h.stream, live, g, ld, norm_squared, w,
+                       v_next, norm_out, norm_stride);
+  else
+    hipLaunchKernelGGL(box_scale_store_kernel<int64_t>, dim3(nb, live.count), dim3(block_size), 0, h.stream, live, g, ld, norm_squared, w,
+                       v_next, norm_out, norm_stride);
   KernelProfiler::end(stop, h.stream);
   MFMG_HIP_CHECK(hipGetLastError());
 }

@@ -367,6 +367,7 @@ struct mfmg_hip_hierarchy_s
   DeviceBuffer<double> block_work[2];
   int64_t block_info[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0};
   int64_t block_info_f32[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0}; // ... and the last FP32 block call
+  int64_t block_solve_allreduces = 0; // all-reduces of the last mfmg_hip_hierarchy_solve_fgmres_block (0 on one rank)
   // the transfer counters of every level (transfer_counters below) when the last block call began
   std::vector<std::array<int64_t, 3>> transfer_snapshot;
   DeviceBuffer<float> block_work_f32[2];
@@ -520,6 +521,14 @@ int mfmg_hip_context_set_low_ghost_cells(mfmg_hip_context_t ctx, int32_t cells)
     for (int d = 0; d < 3; ++d)
       require(c.ghost_lo[d] == 0 || c.ghost_lo[d] == cells, "the local mesh of this rank holds another number of ghost cell layers below");
     c.low_ghost_cells = cells;
+  });
+}
+
+int mfmg_hip_context_set_block_fgmres_on_ranks(mfmg_hip_context_t ctx, int enable)
+{
+  return guarded([&] {
+    require(ctx != nullptr, "null context");
+    ctx->handle->block_fgmres_on_ranks = enable != 0;
   });
 }
 
@@ -770,6 +779,26 @@ int mfmg_hip_context_exchange_block(mfmg_hip_context_t ctx, int32_t space, int32
     require(ld >= h.space_checked(space).n_local(), "the leading dimension of a block must be at least the vector size");
     h.reserve_exchange_block(n_vectors, width);
     h.exchange_block(n_vectors, ld, V, width);
+  });
+}
+
+int mfmg_hip_context_exchange_block_f32(mfmg_hip_context_t ctx, int32_t space, int32_t n_vectors, int64_t ld, float *V, int width)
+{
+  return guarded([&] {
+    require(ctx != nullptr && V != nullptr, "null argument");
+    HipHandle &h = *ctx->handle;
+    require(space == 1, "blocks of vectors are exchanged in the fine DoF space (1) only");
+    // (the same answer on every rank, as for mfmg_hip_context_exchange_f32)
+    require(width >= 1 && width <= 3 && width <= h.comm.low_ghost_cells, "width: 1 to 3 planes, at most the ghost planes every rank holds");
+    // (the layout rules of the FP32 block entry points)
+    require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
+    require(ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 8 bytes)");
+    require(reinterpret_cast<uintptr_t>(V) % 8 == 0, "the base of a block must be aligned to 8 bytes");
+    if (!h.comm.enabled())
+      return;
+    require(ld >= h.space_checked(space).n_local(), "the leading dimension of a block must be at least the vector size");
+    h.reserve_exchange_block(n_vectors, width);
+    h.exchange_block_f32(n_vectors, ld, V, width);
   });
 }
 
@@ -2043,7 +2072,12 @@ int mfmg_hip_hierarchy_apply_f32_block(mfmg_hip_hierarchy_t h, int32_t n_vectors
   return guarded([&] {
     require(h != nullptr, "null argument");
     require(h->fine_f32 != nullptr, "the hierarchy was not built with \"fine level precision\" float");
-    require(!h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
+    {
+      // several ranks: the float level exchanges in the fine DoF space, through the registered transport
+      HaloCommunicator const &comm = h->handle->comm;
+      require(!comm.enabled() || (comm.spaces[1].configured() && comm.transport != nullptr),
+              "a context with a communicator needs its fine DoF space configured and a transport registered");
+    }
     require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
     require(b && x, "null argument");
     const int64_t n = level_size(h, 0);
@@ -2564,6 +2598,7 @@ struct FgmresOutcome
   double residual = 0.;
   bool converged = false;
   int64_t cycle_starts = 0; // residuals b - A x formed: the first one and one per restart / breakdown
+  int64_t allreduces = 0;   // several ranks: the all-reduces of the iteration (3 per iteration, 1 per cycle start)
 };
 
 // The iteration of mfmg_hip_hierarchy_solve_fgmres on vectors in the numbering the hierarchy runs in (`b_run`, `x_run`), with
@@ -2608,10 +2643,12 @@ extern "C++" FgmresOutcome fgmres_run(mfmg_hip_hierarchy_t h, const double *b_ru
       throw std::runtime_error("internal: the fine halo space does not describe the fine vectors");
   }
   // `count` doubles at `dev` summed over the ranks: to the host (ws.host), one all-reduce, back to `dev`; the sums stay in ws.host
+  int64_t allreduces = 0;
   auto allreduce = [&](double *dev, int count) {
     MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
     MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
     handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
+    ++allreduces;
     MFMG_HIP_CHECK(hipMemcpyAsync(dev, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
   };
   // ||w||^2 over the owned entries of all ranks from this rank's s.norm_partials: on the device (scratch.norm_squared) and returned
@@ -2737,6 +2774,7 @@ extern "C++" FgmresOutcome fgmres_run(mfmg_hip_hierarchy_t h, const double *b_ru
   out.iterations = it;
   out.residual = res;
   out.converged = converged;
+  out.allreduces = allreduces;
   return out;
 }
 } // namespace
@@ -2785,6 +2823,16 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
 // (block_krylov_basis::plan).  A column that breaks down ends its cycle by itself and would be out of step: it gets its update,
 // and fgmres_run finishes it from (x, it) -- all a cycle start knows.  Every kernel gives a slot the bits the one-vector driver
 // gives its vector, so x, the count, the final residual and the history of a column are those of mfmg_hip_hierarchy_solve_fgmres.
+// Several ranks (enabled per context with mfmg_hip_context_set_block_fgmres_on_ranks, on every rank alike; refused otherwise): the
+// blocks hold the ranks' local vectors.  The operator and the cycle exchange what they read (a group of columns
+// one message per neighbour where the ranks agreed on blocks); the Gram-Schmidt passes, the norms and scale_store run over the
+// owned entries of all live slots in one launch each (the OwnedBox overloads of block_krylov_basis.hpp), the combination over all
+// local entries.  The j + 1 coefficients of a pass of ALL live slots cross the ranks in ONE all-reduce, their ||w||^2 in one more:
+// three per iteration whatever k, plus one per cycle start.  The Hessenberg columns are on the host once summed: no fetch.  Every
+// control decision -- convergence, breakdown, retirement, restart, the end of the loop -- is taken from all-reduced values, so
+// every rank retires the same columns, hands the same column to fgmres_run (collective there) and leaves the loop in the same
+// iteration.  A column has the bits of the one-vector solve on the same ranks where the transport sums an element in the same
+// order whatever the length of the message (block_krylov.hpp).
 int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
                                           const double *tolerances, int32_t max_iterations, int32_t restart, int32_t preconditioner_fp32,
                                           int32_t *n_iterations, double *final_residuals, double *residual_history, int32_t history_ld,
@@ -2792,7 +2840,8 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
 {
   namespace bkb = block_krylov_basis;
   return guarded([&] {
-    check_block(h, 0, n_vectors, ld, b, x, false);
+    // (a communicator: only where the caller enabled the block solve on the context, on every rank alike)
+    check_block(h, 0, n_vectors, ld, b, x, h && h->handle->block_fgmres_on_ranks);
     require(tolerances != nullptr, "null argument");
     require(max_iterations >= 0, "bad stopping criterion");
     for (int c = 0; c < n_vectors; ++c)
@@ -2807,6 +2856,18 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
     const int64_t n = level_size(h, 0);
     const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
     auto op = h->hierarchy->levels()[0].get_operator();
+    // several ranks: the passes over the owned entries, summed over the ranks (the preconditions of fgmres_run)
+    const bool distributed = handle.comm.enabled();
+    krylov::OwnedBox box;
+    if (distributed)
+    {
+      auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
+      const int space = hop ? hop->domain_space() : 0;
+      require(space > 0 && space < (int)handle.comm.spaces.size() && handle.comm.spaces[space].configured() && handle.comm.transport != nullptr,
+              "the fine operator has no distributed vector space or no transport was registered");
+      box = krylov::OwnedBox(handle.comm.spaces[space]);
+      require(box.n_local() == n, "the fine space does not describe the vectors of the fine level");
+    }
     // "internal numbering" lexicographic: b and x are gathered once into library blocks and x is scattered once, as in
     // mfmg_hip_hierarchy_solve_cg_block.  Otherwise the bases take the caller's leading dimension, so that the operator runs from
     // the caller's x into the basis on one block layout.
@@ -2839,7 +2900,7 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
     float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
     const bool zero_first = !h->hierarchy->is_preconditioner(); // the cycle then starts from what z holds: from zero, as in fgmres_run
     const int64_t launches_before = block_kernel_launches(h);
-    int64_t preconditioner_columns = 0, operator_columns = 0, cycle_starts = 0;
+    int64_t preconditioner_columns = 0, operator_columns = 0, cycle_starts = 0, allreduces = 0;
     const int64_t fp32_launches_before = fp32 ? h->fine_f32->block_launches() : 0;
     int64_t fp32_columns_looped = 0;
 
@@ -2875,6 +2936,28 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
       MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
     };
     auto fetched = [&](bkb::SlotList const &l, int s) { return ws.host + (s - l.id[0]) * cstride; };
+    // several ranks: `count` doubles at `dev` summed over the ranks -- to the host (ws.host), ONE all-reduce, back to `dev`; the
+    // sums stay in ws.host (which holds slots x (2 columns + 1) doubles: the live slots' coefficients of a pass fit)
+    auto allreduce = [&](double *dev, int count) {
+      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
+      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
+      handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
+      ++allreduces;
+      MFMG_HIP_CHECK(hipMemcpyAsync(dev, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
+    };
+    // ||w_s||^2 over the owned entries of all ranks from this rank's norm partials, for the slots of `l` in the order of the list:
+    // on the device (scratch.norm_squared) and in ws.host
+    auto norms_squared_of_all = [&](bkb::SlotList const &l) {
+      bkb::norm_finish(handle, scratch, l, box);
+      allreduce(scratch.norm_squared.data(), l.count);
+    };
+    // the float copies of the vectors v_s at `v` as the one-vector driver makes them on ranks: the whole local vector (what its
+    // ghost entries hold is exchanged over by the FP32 level where it reads them)
+    auto narrow_live = [&](bkb::SlotList const &l, double const *v) {
+      if (fp32)
+        for (int i = 0; i < l.count; ++i)
+          vec::narrow(handle, n, v + l.id[i] * wld, v_f32 + l.id[i] * wld);
+    };
     // `run(start, width)` for every maximal run of consecutive live slots (with `by_column`: whose columns follow each other too)
     auto for_runs = [&](bool by_column, std::function<void(int, int)> const &run) {
       int32_t n_groups = 0, n_packed = 0;
@@ -2901,12 +2984,22 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
       });
       for (int i = 0; i < l.count; ++i)
         vec::sadd<double>(handle, n, -1., 1., b_run + l.col[i] * wld, V.vector(0, l.id[i]));
+      cycle_starts += l.count;
+      if (distributed)
+      {
+        bkb::norm_partials(handle, scratch, l, box, wld, V.vector(0));
+        norms_squared_of_all(l);
+        for (int i = 0; i < l.count; ++i)
+          res[l.col[i]] = std::sqrt(ws.host[i]);
+        bkb::scale_store(handle, l, box, wld, scratch.norm_squared.data(), V.vector(0), V.vector(0), nullptr, 0);
+        narrow_live(l, V.vector(0));
+        return;
+      }
       bkb::norm_partials(handle, scratch, l, n, wld, V.vector(0));
       bkb::scale_store(handle, scratch, l, n, wld, V.vector(0), V.vector(0), v_f32, coef, cstride);
       fetch(l, 1);
       for (int i = 0; i < l.count; ++i)
         res[l.col[i]] = fetched(l, l.id[i])[0];
-      cycle_starts += l.count;
     };
     // z_j = M^-1 v_j on the live slots, from a zero start whatever "is preconditioner" says
     auto precondition = [&](int j) {
@@ -2985,20 +3078,46 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
         });
         operator_columns += l.count;
         double *const w = V.vector(j + 1);
-        for (int pass = 0; pass < 2; ++pass)
+        if (distributed)
         {
-          bkb::dots(handle, scratch, l, V, j + 1, w, coef, cstride, pass == 1);
-          bkb::update(handle, scratch, l, V, j + 1, w, pass == 1);
+          // the columns h_0 .. h_j, ||w|| of all live slots are summed over the ranks on their way: no fetch
+          for (int pass = 0; pass < 2; ++pass)
+          {
+            bkb::dots(handle, scratch, l, box, V, j + 1, w, nullptr, 0, false);
+            allreduce(scratch.pass_coefficients.data(), l.count * (j + 1));
+            for (int i = 0; i < l.count; ++i)
+            {
+              double *const c = columns[l.col[i]].column(j);
+              double const *const sum = ws.host + (size_t)i * (j + 1);
+              for (int q = 0; q <= j; ++q)
+                c[q] = pass == 0 ? sum[q] : c[q] + sum[q];
+            }
+            bkb::update(handle, scratch, l, box, V, j + 1, w, pass == 1);
+          }
+          norms_squared_of_all(l);
+          for (int i = 0; i < l.count; ++i)
+            columns[l.col[i]].column(j)[j + 1] = std::sqrt(ws.host[i]);
+          bkb::scale_store(handle, l, box, wld, scratch.norm_squared.data(), w, w, nullptr, 0);
+          narrow_live(l, w);
         }
-        bkb::scale_store(handle, scratch, l, n, wld, w, w, v_f32, coef + j + 1, cstride);
-        fetch(l, j + 2);
+        else
+        {
+          for (int pass = 0; pass < 2; ++pass)
+          {
+            bkb::dots(handle, scratch, l, V, j + 1, w, coef, cstride, pass == 1);
+            bkb::update(handle, scratch, l, V, j + 1, w, pass == 1);
+          }
+          bkb::scale_store(handle, scratch, l, n, wld, w, w, v_f32, coef + j + 1, cstride);
+          fetch(l, j + 2);
+        }
         ++it;
         bkb::SlotList leaving, broken;
         for (int i = 0; i < l.count; ++i)
         {
           const int s = l.id[i], c = l.col[i];
           FgmresColumn &col = columns[c];
-          std::copy(fetched(l, s), fetched(l, s) + j + 2, col.column(j));
+          if (!distributed)
+            std::copy(fetched(l, s), fetched(l, s) + j + 2, col.column(j));
           const double r = col.rotate();
           iterations[c] = it;
           // a breakdown is not taken at its word: the column gets its update, and the residual fgmres_run recomputes is what is
@@ -3031,6 +3150,7 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
           res[c] = out.residual;
           converged[c] = out.converged;
           cycle_starts += out.cycle_starts;
+          allreduces += out.allreduces;
           preconditioner_columns += out.iterations - it;
           operator_columns += out.iterations - it;
         }
@@ -3073,6 +3193,7 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
       work[2] = block_kernel_launches(h) - launches_before;
       work[3] = cycle_starts;
     }
+    h->block_solve_allreduces = allreduces; // (mfmg_hip_hierarchy_block_solve_allreduces)
     if (fp32)
     {
       // (mfmg_hip_hierarchy_block_info_f32: the preconditioner applications of this solve)
@@ -3082,6 +3203,14 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
     }
     if (!all)
       throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations on every column of the block (SolverControl::NoConvergence)");
+  });
+}
+
+int mfmg_hip_hierarchy_block_solve_allreduces(mfmg_hip_hierarchy_t h, int64_t *n)
+{
+  return guarded([&] {
+    require(h && n, "null argument");
+    *n = h->block_solve_allreduces;
   });
 }
 
@@ -3142,6 +3271,44 @@ int mfmg_hip_block_krylov_orthogonalize(mfmg_hip_context_t ctx, int64_t n, int32
       bkb::update(handle, scratch, l, B, j + 1, w, pass == 1);
     }
     bkb::scale_store(handle, scratch, l, n, ld, w, v_next, v_next_f32, norm_out, 1);
+    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the scratch goes away)
+  });
+}
+
+int mfmg_hip_block_krylov_orthogonalize_box(mfmg_hip_context_t ctx, const int64_t *local_nodes, const int64_t *own0, const int64_t *own_n,
+                                            int32_t comps, int32_t k, int64_t ld, int32_t j, int32_t n_live, const int32_t *live_slots,
+                                            double *V, double *v_next, double *h_out, double *norm_out)
+{
+  namespace bkb = block_krylov_basis;
+  return guarded([&] {
+    require(ctx && local_nodes && own0 && own_n && V && h_out && norm_out, "null argument");
+    require(comps >= 1 && j >= 0, "bad shape");
+    HipHandle &handle = *ctx->handle;
+    require(!handle.comm.enabled(), "mfmg_hip_block_krylov_orthogonalize_box runs the kernels of one rank: a context without a communicator");
+    krylov::OwnedBox box;
+    box.comps = comps;
+    for (int d = 0; d < 3; ++d)
+    {
+      require(own0[d] >= 0 && own_n[d] >= 1 && own0[d] + own_n[d] <= local_nodes[d], "the owned box leaves the local box");
+      box.local[d] = local_nodes[d];
+      box.own0[d] = own0[d];
+      box.own_n[d] = own_n[d];
+    }
+    require(ld >= box.n_local(), "bad shape");
+    require(ld % 2 == 0 && reinterpret_cast<uintptr_t>(V) % 16 == 0 && reinterpret_cast<uintptr_t>(v_next) % 16 == 0,
+            "the basis block needs an even leading dimension and a base aligned to 16 bytes");
+    const bkb::SlotList l = checked_slot_list(k, n_live, live_slots, nullptr, k);
+    bkb::Scratch scratch(k, j + 1);
+    const bkb::Basis B{box.n_local(), ld, (int64_t)k * ld, V};
+    double *const w = B.vector(j + 1);
+    for (int pass = 0; pass < 2; ++pass)
+    {
+      // (one rank: the sum over the ranks is the identity)
+      bkb::dots(handle, scratch, l, box, B, j + 1, w, h_out, j + 1, pass == 1);
+      bkb::update(handle, scratch, l, box, B, j + 1, w, pass == 1);
+    }
+    bkb::norm_finish(handle, scratch, l, box);
+    bkb::scale_store(handle, l, box, ld, scratch.norm_squared.data(), w, v_next, norm_out, 1);
     MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the scratch goes away)
   });
 }

@@ -587,6 +587,10 @@ void halo_regions_copy(float *v, HaloSpace const &s, HaloRegions const &regions,
 // (pack), 1 V = buf (unpack); one launch for all columns (vector_ops.hip)
 void halo_regions_copy_block(double *V, int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode,
                              hipStream_t stream);
+// ... of the k columns of a FLOAT block against the same buffer of doubles, laid out the same: mode 0 buf = V widened (pack),
+// 1 V = buf narrowed (unpack); one launch for all columns (vector_ops.hip)
+void halo_regions_copy_block(float *V, int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode,
+                             hipStream_t stream);
 // the owned sub-box (or the whole local box) of a vector of space `s` against the contiguous buf: mode 0 buf = v, 1 v = buf
 void halo_box_copy(double *v, HaloSpace const &s, bool owned_only, double *buf, int mode, hipStream_t stream);
 void gather_indexed(int64_t n, double const *in, int32_t const *index, double *out, hipStream_t stream); // out[i] = in[index[i]]
@@ -601,6 +605,9 @@ struct HipHandle
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_packed = nullptr, ev_unpacked = nullptr, ev_async = nullptr;
   bool overlap_exchange = true;
+  // mfmg_hip_hierarchy_solve_fgmres_block on a communicator: off until the caller enables it on the context of EVERY rank
+  // (mfmg_hip_context_set_block_fgmres_on_ranks) -- the solve is collective, and a caller that has not asked for it keeps the refusal
+  bool block_fgmres_on_ranks = false;
   // matrix-free operators built from this handle may keep one coefficient per cell when a cell's eight are equal
   bool allow_cell_constant = true;
   // ... and then keep D^-1 in the chunk records (8 more bytes per DoF and smoother launch) instead of deriving it
@@ -767,7 +774,14 @@ struct HipHandle
   // message of column 0, then that of column 1, ... (halo_box_messages per column): k times the one-vector doubles on the wire in
   // one group.  A slab takes the packed path as well: its layers are contiguous per column, not per block, and the host transports
   // are handed one message per peer.  Counts as one exchange.
-  void exchange_block(int k, int64_t ld, double *V, int width)
+  void exchange_block(int k, int64_t ld, double *V, int width) { exchange_block_of(k, ld, V, width); }
+  // The same exchange of the k columns of a FLOAT block: the block form of the widened float exchange (exchange_box<float>).  The
+  // packing launch widens into the staging of exchange_block, the unpacking launch narrows out of it: messages, peers, counters and
+  // the staging reservation are those of exchange_block for that width, so a rank pair cannot disagree on a size, and a column's
+  // ghost entries get the bits of the one-vector float exchange (float -> double -> float is exact).
+  void exchange_block_f32(int k, int64_t ld, float *V, int width) { exchange_block_of(k, ld, V, width); }
+  template <typename T>
+  void exchange_block_of(int k, int64_t ld, T *V, int width)
   {
     if (!comm.enabled())
       return;

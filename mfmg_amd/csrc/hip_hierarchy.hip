@@ -1490,14 +1490,24 @@ HipFloatFineLevel::HipFloatFineLevel(HipHandle &handle, mfmg_hip_mesh_desc const
   // materials of the ranks may differ, and the float sweep has other tiles.  ONE collective that every rank reaches here.
   // (... and on the sweep from x_0 = 0 that spares the first pre-smoothing step of a preconditioner application the exchange of x,
   // encoded as in HipSmoother: 2 K + z.  One rank keeps zeroing x: its cycle is what it was.)
+  // Blocks of float vectors change the exchanges as well (a group of columns sends one message per neighbour), so groups run as
+  // blocks only where every rank's float operator has the block kernel: the smallest offer of 4 | 1, a second value of the SAME
+  // all-reduce.
   bool from_zero = false;
+  _block_offer = _op.block_kernel_available() ? 4 : 1;
   if (handle.comm.enabled())
   {
+    if (!handle.comm.transport)
+      throw std::runtime_error("no halo transport was registered with the context");
     const double mine = 2. * offered + (offered == 3 && _op.fused_zero_guess_available(3) ? 1. : 0.);
-    const int agreed = (int)-handle.allreduce_max(-mine);
+    double smallest[2] = {-mine, -double(_block_offer)}; // (the maximum of the negated values)
+    handle.comm.transport->allreduce(smallest, 2, 1, handle.stream);
+    const int agreed = (int)-smallest[0], width = (int)-smallest[1];
     ASSERT_THROW(agreed / 2 <= offered && agreed / 2 <= handle.comm.sweep_terms(), "internal: the ranks agreed on a sweep this rank cannot run");
+    ASSERT_THROW(width == 1 || (width == 4 && _block_offer == 4), "internal: the ranks agreed on a block width this rank cannot run");
     offered = agreed / 2;
     from_zero = (agreed & 1) != 0;
+    _block_offer = width;
   }
   _schedule = plan_sweeps(_smoother->coefficients(), fused, offered, from_zero);
   // (several ranks: a polynomial longer than the agreed sweep starts with that sweep -- two terms where the ranks hold one ghost
@@ -1506,6 +1516,9 @@ HipFloatFineLevel::HipFloatFineLevel(HipHandle &handle, mfmg_hip_mesh_desc const
       (int)_smoother->coefficients().size() > offered)
     _schedule.out_of_place = std::min(offered, fused);
   _b_ghost_width = handle.comm.enabled() && _schedule.out_of_place > 0 ? _schedule.out_of_place - 1 : 0;
+  // (the staging of a group's exchange is sized here, outside the launch path; the schedule follows from agreed values alone)
+  if (handle.comm.enabled() && block_width() > 1)
+    handle.reserve_exchange_block(block_width(), 1);
 }
 
 // One application of the FP32 operator.  Several ranks: as HipMatrixFreeOperator::apply_mode -- x is exchanged one plane deep, the
@@ -1672,7 +1685,6 @@ void HipFloatFineLevel::apply_block(int k, int64_t ld, float const *b, float *x)
     if (!cond)
       throw InvalidArgumentExc(what);
   };
-  require(!hd.comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
   require(k >= 1 && k <= kMfBlockMaxVectors, "a block holds 1 to 64 vectors");
   require(b != nullptr && x != nullptr, "null vector");
   require(ld >= n, "the leading dimension of a block must be at least n_dofs");
@@ -1683,7 +1695,15 @@ void HipFloatFineLevel::apply_block(int k, int64_t ld, float const *b, float *x)
   _block_columns_looped = 0;
   auto const &levels = _hierarchy.levels();
   auto const &fine = *levels[0].get_operator();
-  const bool block = block_width() > 1;
+  const bool block = block_width() > 1; // (several ranks: agreed at construction, so every rank takes the same branches below)
+  const bool distributed = hd.comm.enabled();
+  // one launch of the block kernel on a group; several ranks: behind ONE exchange of the group's x, one plane deep
+  auto launch_group = [&](MfMode mode, MfBlockOperands<float> const &v) {
+    if (!distributed)
+      return _op.launch_block(mode, v);
+    hd.exchange_block_f32(v.n_vectors, v.ld, const_cast<float *>(v.x), 1);
+    _op.launch_block_local(mode, v);
+  };
   int widths[kMfBlockMaxGroups];
   const int n_groups = mf_block_groups(k, widths);
   int64_t c0 = 0;
@@ -1737,7 +1757,7 @@ void HipFloatFineLevel::apply_block(int k, int64_t ld, float const *b, float *x)
             _smoother->coefficients(), 0, static_cast<Block const *>(&it), &other, [&](int i) { return i == 0 ? &sa : &sb; },
             [&](Block const *cur, Block const *prev, float alpha, float beta, Block *out) {
               float const *xp = prev ? prev->p : nullptr;
-              _op.launch_block(mf_smoother_mode(xp, alpha), {cur->p, gb, xp, out->p, ld, w, alpha, beta});
+              launch_group(mf_smoother_mode(xp, alpha), {cur->p, gb, xp, out->p, ld, w, alpha, beta});
             },
             [&](int, float const *, float const *, Block const *, Block *, Block *) { ASSERT_THROW(false, "internal: no sweep on a block"); });
         std::swap(it, other);
@@ -1752,7 +1772,7 @@ void HipFloatFineLevel::apply_block(int k, int64_t ld, float const *b, float *x)
     // b_c = R (A x - b) in one pass per column where apply() forms it so; otherwise the residual of the group in one launch
     const bool one_pass = hip_restrictor && hip_restrictor->restrict_residual_f32(fine, it.p, gb, *_b_coarse);
     if (!one_pass)
-      _op.launch_block(MfMode::residual, {it.p, gb, nullptr, res, ld, w, 0.f, 0.f});
+      launch_group(MfMode::residual, {it.p, gb, nullptr, res, ld, w, 0.f, 0.f});
     for (int c = 0; c < w; ++c)
     {
       if (!one_pass)

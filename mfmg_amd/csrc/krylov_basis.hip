@@ -23,7 +23,7 @@ namespace krylov
 {
 namespace
 {
-using namespace body; // (krylov_basis_bodies.hpp: the bodies of the contiguous kernels, shared with the block kernels)
+using namespace body; // (krylov_basis_bodies.hpp: the bodies of the contiguous and of the owned-box kernels, shared with the block kernels)
 
 // ---- the contiguous kernels: one vector pass each, the bodies of krylov_basis_bodies.hpp -------------------------------------------
 // blockIdx.y: the group of kGroup columns; partials[column][block]
@@ -66,107 +66,7 @@ __global__ __launch_bounds__(block_size) void scale_store_kernel(int64_t n, int 
   scale_store_body<W>(n, n_partials, partials, w, v_next, v_next_f32, norm_out, wsum);
 }
 
-// ---- owned-box kernels -----------------------------------------------------------------------------------------------------------
-// The rows of an OwnedBox (whole axes joined) and the walk of one launch over their slots
-struct RowWalk
-{
-  int64_t base, row_len, stride_y, stride_z, n_y, n_z; // row (y, z) = the entries [s, s + row_len), s = base + y stride_y + z stride_z
-  int64_t n_local;                                     // entries of the local vector: a pair that ends past it is not loaded
-  int64_t slots;                                       // slots per row
-  int64_t d_slot, d_y, d_z;                            // the grid stride in slots = d_slot + slots (d_y + n_y d_z)
-};
-
-template <int W>
-struct Cursor
-{
-  int64_t slot, y, z;
-  __device__ __forceinline__ explicit Cursor(RowWalk const &g)
-  {
-    const int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, row = u / g.slots;
-    slot = u % g.slots;
-    y = row % g.n_y;
-    z = row / g.n_y;
-  }
-  __device__ __forceinline__ bool inside(RowWalk const &g) const { return z < g.n_z; }
-  __device__ __forceinline__ void advance(RowWalk const &g)
-  {
-    slot += g.d_slot;
-    y += g.d_y;
-    z += g.d_z;
-    if (slot >= g.slots)
-    {
-      slot -= g.slots;
-      ++y;
-    }
-    if (y >= g.n_y)
-    {
-      y -= g.n_y;
-      ++z;
-    }
-  }
-  // first entry of the slot (W = 2: even) and which of its W entries the row holds
-  __device__ __forceinline__ int64_t entries(RowWalk const &g, bool (&in)[W]) const
-  {
-    const int64_t s = g.base + y * g.stride_y + z * g.stride_z;
-    if constexpr (W == 1)
-    {
-      in[0] = true; // (slots = row_len)
-      return s + slot;
-    }
-    else
-    {
-      const int64_t e = ((s >> 1) + slot) << 1; // (e + 1 >= s)
-      in[0] = e >= s && e < s + g.row_len;
-      in[1] = e + 1 < s + g.row_len;
-      return e;
-    }
-  }
-};
-
-// the products of one slot: WL = the width of the loads (WL < W: the one pair that ends past the vector, its first entry alone)
-template <int W, int WL, int NC>
-__device__ __forceinline__ void dots_slot(double (&acc)[NC], bool const (&in)[W], double const *__restrict__ V, int64_t ld,
-                                          double const *__restrict__ w)
-{
-  double v[NC][WL], ww[WL];
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-    load<WL>(V + c * ld, v[c]);
-  load<WL>(w, ww);
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-  {
-#pragma unroll
-    for (int k = 0; k < WL; ++k)
-    {
-      const double t = fma(v[c][k], ww[k], acc[c]);
-      acc[c] = in[k] ? t : acc[c]; // (not a product with 0: a ghost entry may hold NaN)
-    }
-  }
-}
-
-template <int W, int NC>
-__device__ __forceinline__ void box_dots_body(RowWalk const &g, int64_t ld, double const *__restrict__ V, double const *__restrict__ w,
-                                              double *__restrict__ partials, double (*wsum)[kWaves])
-{
-  double acc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-    acc[c] = 0.;
-  for (Cursor<W> cur(g); cur.inside(g); cur.advance(g))
-  {
-    bool in[W];
-    const int64_t e = cur.entries(g, in);
-    if (!in[0] && !in[W - 1])
-      continue;
-    if (W == 1 || e + 1 < g.n_local)
-      dots_slot<W, W, NC>(acc, in, V + e, ld, w + e);
-    else
-      dots_slot<W, 1, NC>(acc, in, V + e, ld, w + e);
-  }
-  block_column_sums<NC>(acc, partials, wsum);
-}
-
+// ---- owned-box kernels: the bodies of krylov_basis_bodies.hpp on one vector ------------------------------------------------------
 template <int W>
 __global__ __launch_bounds__(block_size) void box_dots_kernel(RowWalk g, int64_t ld, int n_columns, double const *__restrict__ V,
                                                                double const *__restrict__ w, double *__restrict__ partials)
@@ -176,29 +76,7 @@ __global__ __launch_bounds__(block_size) void box_dots_kernel(RowWalk g, int64_t
   const int nc = min(kGroup, n_columns - c0);
   V += (int64_t)c0 * ld;
   partials += (int64_t)c0 * gridDim.x;
-  switch (nc)
-  {
-  case 1: box_dots_body<W, 1>(g, ld, V, w, partials, wsum); break;
-  case 2: box_dots_body<W, 2>(g, ld, V, w, partials, wsum); break;
-  case 3: box_dots_body<W, 3>(g, ld, V, w, partials, wsum); break;
-  case 4: box_dots_body<W, 4>(g, ld, V, w, partials, wsum); break;
-  case 5: box_dots_body<W, 5>(g, ld, V, w, partials, wsum); break;
-  case 6: box_dots_body<W, 6>(g, ld, V, w, partials, wsum); break;
-  case 7: box_dots_body<W, 7>(g, ld, V, w, partials, wsum); break;
-  default: box_dots_body<W, 8>(g, ld, V, w, partials, wsum); break;
-  }
-}
-
-// the owned entries of a slot stored: both halves of a pair in one 16-byte store, an edge slot its one entry
-template <int W>
-__device__ __forceinline__ void store_owned(double *p, double const (&r)[W], bool const (&in)[W])
-{
-  if (in[0] && in[W - 1])
-    store<W>(p, r);
-  else if (in[0])
-    p[0] = r[0];
-  else if (in[W - 1])
-    p[W - 1] = r[W - 1];
+  box_dots_group<W>(nc, g, ld, V, w, partials, wsum);
 }
 
 template <int W, bool kNorm>
@@ -207,69 +85,14 @@ __global__ __launch_bounds__(block_size) void box_axpy_kernel(RowWalk g, int64_t
                                                                double *__restrict__ norm_partials)
 {
   __shared__ double wsum[1][kWaves];
-  double nrm[1] = {0.};
-  for (Cursor<W> cur(g); cur.inside(g); cur.advance(g))
-  {
-    bool in[W];
-    const int64_t e = cur.entries(g, in);
-    if (!in[0] && !in[W - 1])
-      continue;
-    double acc[W];
-    if (W == 1 || e + 1 < g.n_local)
-    {
-      // (a ghost half is computed with its pair -- the entries of a pair do not meet -- and dropped)
-      load<W>(out + e, acc);
-      axpy_columns<W>(acc, V + e, ld, n_columns, c, sign);
-    }
-    else
-    {
-      double first[1] = {out[e]};
-      axpy_columns<1>(first, V + e, ld, n_columns, c, sign);
-      acc[0] = first[0];
-      acc[W - 1] = first[0];
-    }
-    store_owned<W>(out + e, acc, in);
-    if (kNorm)
-    {
-#pragma unroll
-      for (int k = 0; k < W; ++k)
-      {
-        const double t = fma(acc[k], acc[k], nrm[0]);
-        nrm[0] = in[k] ? t : nrm[0];
-      }
-    }
-  }
-  if (kNorm)
-    block_column_sums<1>(nrm, norm_partials, wsum);
+  box_axpy_body<W, kNorm>(g, ld, n_columns, V, c, sign, out, norm_partials, wsum);
 }
 
-// norm_squared: ||w||^2 over all ranks, one device scalar (the partials of a rank are not the norm: the caller summed them)
 template <int W>
 __global__ __launch_bounds__(block_size) void box_scale_store_kernel(RowWalk g, double const *__restrict__ norm_squared, double const *w,
                                                                       double *v_next, double *__restrict__ norm_out)
 {
-  const double norm = sqrt(norm_squared[0]);
-  if (owns_tail() && norm_out != nullptr)
-    norm_out[0] = norm;
-  if (v_next == nullptr)
-    return;
-  const double inv = norm > 0. ? 1. / norm : 0.;
-  for (Cursor<W> cur(g); cur.inside(g); cur.advance(g))
-  {
-    bool in[W];
-    const int64_t e = cur.entries(g, in);
-    if (!in[0] && !in[W - 1])
-      continue;
-    double r[W];
-    if (W == 1 || e + 1 < g.n_local)
-      load<W>(w + e, r);
-    else
-      r[0] = r[W - 1] = w[e];
-#pragma unroll
-    for (int k = 0; k < W; ++k)
-      r[k] *= inv;
-    store_owned<W>(v_next + e, r, in);
-  }
+  box_scale_store_body<W>(g, norm_squared, w, v_next, norm_out);
 }
 
 bool aligned16(void const *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -392,6 +215,10 @@ void rows_of(OwnedBox const &b, RowWalk &g)
   }
 }
 
+} // namespace
+
+namespace body
+{
 RowWalk row_walk(OwnedBox const &b, int W, unsigned int n_blocks)
 {
   RowWalk g;
@@ -403,7 +230,7 @@ RowWalk row_walk(OwnedBox const &b, int W, unsigned int n_blocks)
   g.d_z = rows / g.n_y;
   return g;
 }
-} // namespace
+} // namespace body
 
 unsigned int reduction_blocks(OwnedBox const &box)
 {

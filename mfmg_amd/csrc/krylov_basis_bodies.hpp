@@ -1,7 +1,8 @@
-// Device bodies of the contiguous orthogonalisation kernels (krylov_basis.hpp), shared by the one-vector kernels of
-// krylov_basis.hip and the block kernels of block_krylov_basis.hip: the loops, the reductions and the expressions exist once, so a
-// slot of a block launch gets the bits of the one-vector launch.  A body sees one vector pass: its pointers are those of one w (one
-// slot), blockIdx.x / gridDim.x walk the entries, and every further grid dimension belongs to the kernel around it.
+// Device bodies of the orthogonalisation kernels (krylov_basis.hpp), the contiguous ones and the owned-box ones, shared by the
+// one-vector kernels of krylov_basis.hip and the block kernels of block_krylov_basis.hip: the loops, the reductions and the
+// expressions exist once, so a slot of a block launch gets the bits of the one-vector launch.  A body sees one vector pass: its
+// pointers are those of one w (one slot), blockIdx.x / gridDim.x walk the entries, and every further grid dimension belongs to the
+// kernel around it.
 // Device code only: include from a .hip file.
 #pragma once
 
@@ -283,6 +284,221 @@ __device__ __forceinline__ void scale_store_body(int64_t n, int n_partials, doub
       if (v_next_f32 != nullptr)
         v_next_f32[e] = (float)r;
     }
+}
+// ---- owned-box bodies (krylov_basis.hip, head comment: the slots of a row, the mixed-radix grid stride) ---------------------------
+// The rows of an OwnedBox (whole axes joined) and the walk of one launch over their slots.  Index: the type the walk and the
+// entry of a slot are computed in -- int64_t, or 32 bits where the local vector is shorter than 2^31 entries (the block kernels);
+// the entries a thread visits and the order of every sum do not depend on it.
+template <typename Index>
+struct RowWalkT
+{
+  Index base, row_len, stride_y, stride_z, n_y, n_z; // row (y, z) = the entries [s, s + row_len), s = base + y stride_y + z stride_z
+  Index n_local;                                     // entries of the local vector: a pair that ends past it is not loaded
+  Index slots;                                       // slots per row
+  Index d_slot, d_y, d_z;                            // the grid stride in slots = d_slot + slots (d_y + n_y d_z)
+  RowWalkT() = default;
+  template <typename From>
+  __host__ __device__ explicit RowWalkT(RowWalkT<From> const &o)
+      : base((Index)o.base), row_len((Index)o.row_len), stride_y((Index)o.stride_y), stride_z((Index)o.stride_z), n_y((Index)o.n_y),
+        n_z((Index)o.n_z), n_local((Index)o.n_local), slots((Index)o.slots), d_slot((Index)o.d_slot), d_y((Index)o.d_y), d_z((Index)o.d_z)
+  {
+  }
+};
+using RowWalk = RowWalkT<int64_t>;
+
+// the walk of a launch of n_blocks blocks over the box with accesses of W entries (host; krylov_basis.hip)
+RowWalk row_walk(OwnedBox const &box, int W, unsigned int n_blocks);
+
+template <int W, typename Index = int64_t>
+struct Cursor
+{
+  Index slot, y, z;
+  __device__ __forceinline__ explicit Cursor(RowWalkT<Index> const &g)
+  {
+    const Index u = (Index)blockIdx.x * (Index)blockDim.x + (Index)threadIdx.x, row = u / g.slots;
+    slot = u % g.slots;
+    y = row % g.n_y;
+    z = row / g.n_y;
+  }
+  __device__ __forceinline__ bool inside(RowWalkT<Index> const &g) const { return z < g.n_z; }
+  __device__ __forceinline__ void advance(RowWalkT<Index> const &g)
+  {
+    slot += g.d_slot;
+    y += g.d_y;
+    z += g.d_z;
+    if (slot >= g.slots)
+    {
+      slot -= g.slots;
+      ++y;
+    }
+    if (y >= g.n_y)
+    {
+      y -= g.n_y;
+      ++z;
+    }
+  }
+  // first entry of the slot (W = 2: even) and which of its W entries the row holds
+  __device__ __forceinline__ Index entries(RowWalkT<Index> const &g, bool (&in)[W]) const
+  {
+    const Index s = g.base + y * g.stride_y + z * g.stride_z;
+    if constexpr (W == 1)
+    {
+      in[0] = true; // (slots = row_len)
+      return s + slot;
+    }
+    else
+    {
+      const Index e = ((s >> 1) + slot) << 1; // (e + 1 >= s)
+      in[0] = e >= s && e < s + g.row_len;
+      in[1] = e + 1 < s + g.row_len;
+      return e;
+    }
+  }
+};
+
+// the products of one slot: WL = the width of the loads (WL < W: the one pair that ends past the vector, its first entry alone)
+template <int W, int WL, int NC>
+__device__ __forceinline__ void dots_slot(double (&acc)[NC], bool const (&in)[W], double const *__restrict__ V, int64_t ld,
+                                          double const *__restrict__ w)
+{
+  double v[NC][WL], ww[WL];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    load<WL>(V + c * ld, v[c]);
+  load<WL>(w, ww);
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+  {
+#pragma unroll
+    for (int k = 0; k < WL; ++k)
+    {
+      const double t = fma(v[c][k], ww[k], acc[c]);
+      acc[c] = in[k] ? t : acc[c]; // (not a product with 0: a ghost entry may hold NaN)
+    }
+  }
+}
+
+template <int W, int NC, typename Index>
+__device__ __forceinline__ void box_dots_body(RowWalkT<Index> const &g, int64_t ld, double const *__restrict__ V,
+                                              double const *__restrict__ w, double *__restrict__ partials, double (*wsum)[kWaves])
+{
+  double acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    acc[c] = 0.;
+  for (Cursor<W, Index> cur(g); cur.inside(g); cur.advance(g))
+  {
+    bool in[W];
+    const Index e = cur.entries(g, in);
+    if (!in[0] && !in[W - 1])
+      continue;
+    if (W == 1 || e + 1 < g.n_local)
+      dots_slot<W, W, NC>(acc, in, V + e, ld, w + e);
+    else
+      dots_slot<W, 1, NC>(acc, in, V + e, ld, w + e);
+  }
+  block_column_sums<NC>(acc, partials, wsum);
+}
+
+// one group of nc <= kGroup columns (nc is the same in every thread of the grid row); partials[column][block]
+template <int W, typename Index>
+__device__ __forceinline__ void box_dots_group(int nc, RowWalkT<Index> const &g, int64_t ld, double const *__restrict__ V,
+                                               double const *__restrict__ w, double *__restrict__ partials, double (*wsum)[kWaves])
+{
+  switch (nc)
+  {
+  case 1: box_dots_body<W, 1>(g, ld, V, w, partials, wsum); break;
+  case 2: box_dots_body<W, 2>(g, ld, V, w, partials, wsum); break;
+  case 3: box_dots_body<W, 3>(g, ld, V, w, partials, wsum); break;
+  case 4: box_dots_body<W, 4>(g, ld, V, w, partials, wsum); break;
+  case 5: box_dots_body<W, 5>(g, ld, V, w, partials, wsum); break;
+  case 6: box_dots_body<W, 6>(g, ld, V, w, partials, wsum); break;
+  case 7: box_dots_body<W, 7>(g, ld, V, w, partials, wsum); break;
+  default: box_dots_body<W, 8>(g, ld, V, w, partials, wsum); break;
+  }
+}
+
+// the owned entries of a slot stored: both halves of a pair in one 16-byte store, an edge slot its one entry
+template <int W>
+__device__ __forceinline__ void store_owned(double *p, double const (&r)[W], bool const (&in)[W])
+{
+  if (in[0] && in[W - 1])
+    store<W>(p, r);
+  else if (in[0])
+    p[0] = r[0];
+  else if (in[W - 1])
+    p[W - 1] = r[W - 1];
+}
+
+// the owned entries of out += sign * sum_i c[i] V_i; kNorm: norm_partials[block] = the block's part of ||out||^2 over them
+template <int W, bool kNorm, typename Index>
+__device__ __forceinline__ void box_axpy_body(RowWalkT<Index> const &g, int64_t ld, int n_columns, double const *__restrict__ V,
+                                              double const *__restrict__ c, double sign, double *__restrict__ out,
+                                              double *__restrict__ norm_partials, double (*wsum)[kWaves])
+{
+  double nrm[1] = {0.};
+  for (Cursor<W, Index> cur(g); cur.inside(g); cur.advance(g))
+  {
+    bool in[W];
+    const Index e = cur.entries(g, in);
+    if (!in[0] && !in[W - 1])
+      continue;
+    double acc[W];
+    if (W == 1 || e + 1 < g.n_local)
+    {
+      // (a ghost half is computed with its pair -- the entries of a pair do not meet -- and dropped)
+      load<W>(out + e, acc);
+      axpy_columns<W>(acc, V + e, ld, n_columns, c, sign);
+    }
+    else
+    {
+      double first[1] = {out[e]};
+      axpy_columns<1>(first, V + e, ld, n_columns, c, sign);
+      acc[0] = first[0];
+      acc[W - 1] = first[0];
+    }
+    store_owned<W>(out + e, acc, in);
+    if (kNorm)
+    {
+#pragma unroll
+      for (int k = 0; k < W; ++k)
+      {
+        const double t = fma(acc[k], acc[k], nrm[0]);
+        nrm[0] = in[k] ? t : nrm[0];
+      }
+    }
+  }
+  if (kNorm)
+    block_column_sums<1>(nrm, norm_partials, wsum);
+}
+
+// norm_squared: ||w||^2 over all ranks, one device scalar (the partials of a rank are not the norm: the caller summed them)
+template <int W, typename Index>
+__device__ __forceinline__ void box_scale_store_body(RowWalkT<Index> const &g, double const *__restrict__ norm_squared, double const *w,
+                                                     double *v_next, double *__restrict__ norm_out)
+{
+  const double norm = sqrt(norm_squared[0]);
+  if (owns_tail() && norm_out != nullptr)
+    norm_out[0] = norm;
+  if (v_next == nullptr)
+    return;
+  const double inv = norm > 0. ? 1. / norm : 0.;
+  for (Cursor<W, Index> cur(g); cur.inside(g); cur.advance(g))
+  {
+    bool in[W];
+    const Index e = cur.entries(g, in);
+    if (!in[0] && !in[W - 1])
+      continue;
+    double r[W];
+    if (W == 1 || e + 1 < g.n_local)
+      load<W>(w + e, r);
+    else
+      r[0] = r[W - 1] = w[e];
+#pragma unroll
+    for (int k = 0; k < W; ++k)
+      r[k] *= inv;
+    store_owned<W>(v_next + e, r, in);
+  }
 }
 } // namespace body
 } // namespace krylov

@@ -377,14 +377,18 @@ public:
   // one V-cycle on the FP32 vectors b, x of the fine DoFs
   void apply(float const *b, float *x) const;
   // The cycle of apply() on the k columns of a float block (column c of b at b + c * ld; 1 to 64 columns, ld >= n_dofs and even,
-  // the bases aligned to 8 bytes, one rank): every column of x gets the bits of apply().  The block is taken in the groups of
+  // the bases aligned to 8 bytes): every column of x gets the bits of apply().  The block is taken in the groups of
   // mf_block_groups and the cycle runs per group, in the shape of Hierarchy::apply_block: the smoother terms and the residual as
   // launches of mf_laplace_block_f32_kernel on the group, the restriction, the coarse cycle and the prolongation column by
   // column.  A group of one runs apply(); so does every group where the float operator has no block kernel or the schedule has a
   // multi-term sweep (cell-constant layout).  The workspace is one group wide whatever k is, built at the first block call.
+  // Several ranks: the columns are the ranks' local vectors and get the bits of apply() on the entries the rank owns.  In front of
+  // each block launch the group's x travels in ONE HipHandle::exchange_block_f32, one plane deep (not overlapped with the tiles
+  // that read no ghost plane, as in FP64); restriction, coarse cycle and prolongation exchange per column as in apply().  Whether
+  // groups run as blocks was agreed across the ranks at construction (block_width()): where any rank offers 1, all ranks loop.
   void apply_block(int k, int64_t ld, float const *b, float *x) const;
-  // widest group apply_block runs as one launch (1: the loop over the columns)
-  int block_width() const { return (_op.block_kernel_available() && _schedule.out_of_place == 0) ? 4 : 1; }
+  // widest group apply_block runs as one launch (1: the loop over the columns); several ranks: the smallest offer of the ranks
+  int block_width() const { return (_block_offer == 4 && _schedule.out_of_place == 0) ? 4 : 1; }
   // launches of mf_laplace_block_f32_kernel so far; columns of the last apply_block that went through apply()
   int64_t block_launches() const { return _op.block_launches(); }
   int64_t block_columns_looped() const { return _block_columns_looped; }
@@ -408,6 +412,7 @@ private:
   MatrixFreeLaplaceDevice<float> _op;
   SweepSchedule _schedule; // of this operator's offer (several ranks: of what every rank's offers): out of place only
   int _b_ghost_width = 0;  // several ranks: planes of ghost entries of b the sweeps read (0: none)
+  int _block_offer = 1;    // 4 where the float operator has the block kernel -- on every rank (agreed with the sweep)
   // the right-hand side of the cycle that is running: in flight on the exchange stream / fresh (HipHandle::rhs_*, for float)
   mutable float const *_b_of_cycle = nullptr, *_b_in_flight = nullptr, *_b_fresh = nullptr;
   mutable int _b_fresh_width = 0;

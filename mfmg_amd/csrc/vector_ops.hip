@@ -163,6 +163,26 @@ __global__ void regions_copy_block_kernel(double *V, int64_t ld, int comps, int6
   }
 }
 
+// the same regions of the gridDim.y columns of a FLOAT block against the buffer of doubles of regions_copy_block_kernel, laid out
+// the same: mode 0 buf = V widened, 1 V = buf narrowed (exact both ways for what a float holds).  blockIdx.y is the column.
+__global__ void regions_copy_block_f32_kernel(float *V, int64_t ld, int comps, int64_t nx, int64_t ny, HaloRegions t, double *buf, int mode)
+{
+  const int64_t n = t.off[t.count], k = gridDim.y, c = blockIdx.y;
+  float *v = V + c * ld;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+  {
+    int r = 0;
+    while (r + 1 < t.count && i >= t.off[r + 1])
+      ++r;
+    float *p = v + halo_region_entry(t, comps, nx, ny, i);
+    double *m = buf + k * t.off[r] + c * (t.off[r + 1] - t.off[r]) + (i - t.off[r]);
+    if (mode == 0)
+      *m = (double)*p;
+    else
+      *p = (float)*m;
+  }
+}
+
 // the sub-box [b0, b0 + bn) of the lexicographic array of nodes `dims` (comps entries per node) against the contiguous buf
 // (mode 0: buf = v, 1: v = buf)
 __global__ void box_copy_kernel(double *v, int comps, int64_t nx, int64_t ny, int64_t bx0, int64_t by0, int64_t bz0, int64_t bnx,
@@ -464,8 +484,11 @@ void halo_regions_copy(float *v, HaloSpace const &s, HaloRegions const &regions,
   MFMG_HIP_CHECK(hipGetLastError());
 }
 
-void halo_regions_copy_block(double *V, int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode,
-                             hipStream_t stream)
+namespace
+{
+// the entries of the regions of one column, checked: a block of 1 to 64 columns that are packed or unpacked, every region inside
+// the local box (an entry outside it would be a write beyond the column); 0: nothing to copy
+int64_t checked_block_regions(int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, int mode)
 {
   s.check();
   if (mode != 0 && mode != 1)
@@ -474,14 +497,34 @@ void halo_regions_copy_block(double *V, int64_t ld, int k, HaloSpace const &s, H
     throw std::runtime_error("internal: a block of 1 to 64 columns, each at least the local vector long");
   const int64_t n = regions.count > 0 ? regions.off[regions.count] : 0;
   if (n <= 0)
-    return;
-  // every region lies inside the local box: an entry outside it would be a write beyond the column
+    return 0;
   for (int r = 0; r < regions.count; ++r)
     for (int d = 0; d < 3; ++d)
       if (regions.b[r][d] < 0 || regions.n[r][d] < 0 || regions.b[r][d] + regions.n[r][d] > s.dim(d))
         throw std::runtime_error("internal: a halo region reaches beyond the local box (exchange wider than the ghost layers held)");
+  return n;
+}
+} // namespace
+
+void halo_regions_copy_block(double *V, int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode,
+                             hipStream_t stream)
+{
+  const int64_t n = checked_block_regions(ld, k, s, regions, mode);
+  if (n <= 0)
+    return;
   hipLaunchKernelGGL(vec::regions_copy_block_kernel, dim3(n_blocks_for(n, block_size, 4096), k), dim3(block_size), 0, stream, V, ld, s.comps,
                      s.n_xy[0], s.n_xy[1], regions, buf, mode);
+  MFMG_HIP_CHECK(hipGetLastError());
+}
+
+void halo_regions_copy_block(float *V, int64_t ld, int k, HaloSpace const &s, HaloRegions const &regions, double *buf, int mode,
+                             hipStream_t stream)
+{
+  const int64_t n = checked_block_regions(ld, k, s, regions, mode);
+  if (n <= 0)
+    return;
+  hipLaunchKernelGGL(vec::regions_copy_block_f32_kernel, dim3(n_blocks_for(n, block_size, 4096), k), dim3(block_size), 0, stream, V, ld,
+                     s.comps, s.n_xy[0], s.n_xy[1], regions, buf, mode);
   MFMG_HIP_CHECK(hipGetLastError());
 }
 

@@ -362,6 +362,11 @@ class HaloTransport:
         per neighbour (what the block smoother terms and residuals of a distributed run do by themselves; for tests)."""
         self.ctx.exchange_block(space, V, width)
 
+    def exchange_block_f32(self, space: int, V: torch.Tensor, width: int = 1):
+        """Context.exchange_block_f32: exchange_block for the rows of a float32 block, widened to double on the wire (what the
+        FP32 block smoother terms and residuals of a distributed run do by themselves; for tests)."""
+        self.ctx.exchange_block_f32(space, V, width)
+
     def box_messages(self, space: int, width: int = 1):
         """The messages of one box exchange of `space`, `width` layers deep, as the library lays them out (host arithmetic only):
         (peers, counts, send_entries, recv_entries) -- positions in the local vector, message after message."""

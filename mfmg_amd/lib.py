@@ -261,6 +261,10 @@ def load() -> C.CDLL:
         "mfmg_hip_krylov_orthogonalize_box": (C.c_int, [vp, P(i64), P(i64), P(i64), i32, i64, i32, vp, vp, vp, vp, i32]),
         "mfmg_hip_context_exchange_block": (C.c_int, [vp, i32, i32, i64, vp, C.c_int]),
         "mfmg_hip_block_dots_box": (C.c_int, [vp, P(i64), P(i64), P(i64), i32, i32, i64, vp, vp, vp]),
+        "mfmg_hip_hierarchy_block_solve_allreduces": (C.c_int, [vp, P(i64)]),
+        "mfmg_hip_context_set_block_fgmres_on_ranks": (C.c_int, [vp, C.c_int]),
+        "mfmg_hip_context_exchange_block_f32": (C.c_int, [vp, i32, i32, i64, vp, C.c_int]),
+        "mfmg_hip_block_krylov_orthogonalize_box": (C.c_int, [vp, P(i64), P(i64), P(i64), i32, i32, i64, i32, i32, P(i32), vp, vp, vp, vp]),
         "mfmg_hip_hierarchy_n_levels": (C.c_int, [vp, P(i32)]),
         "mfmg_hip_hierarchy_level_size": (C.c_int, [vp, i32, P(i64)]),
         "mfmg_hip_hierarchy_operator_apply": (C.c_int, [vp, i32, vp, vp, C.c_int]),
@@ -320,7 +324,9 @@ def load() -> C.CDLL:
                    "mfmg_hip_mf_laplace_f32_set_block_tile", "mfmg_hip_mf_laplace_f32_get_block_tile",
                    "mfmg_hip_hierarchy_apply_f32_block", "mfmg_hip_hierarchy_block_info_f32",
                    "mfmg_hip_mf_laplace_uniform_coefficient", "mfmg_hip_context_exchange_block", "mfmg_hip_block_dots_box",
-                   "mfmg_hip_hierarchy_restrictor_apply_block", "mfmg_hip_hierarchy_transfer_block_info"}
+                   "mfmg_hip_hierarchy_restrictor_apply_block", "mfmg_hip_hierarchy_transfer_block_info",
+                   "mfmg_hip_hierarchy_block_solve_allreduces", "mfmg_hip_context_exchange_block_f32",
+                   "mfmg_hip_block_krylov_orthogonalize_box", "mfmg_hip_context_set_block_fgmres_on_ranks"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
