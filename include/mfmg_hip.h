@@ -459,6 +459,16 @@ int mfmg_hip_mf_laplace_cell_constant_layout(mfmg_hip_mf_laplace_t op, int *in_u
 int mfmg_hip_mf_laplace_uniform_coefficient(mfmg_hip_mf_laplace_t op, int *uniform, int64_t *sweeps);
 /* the tile in use */
 int mfmg_hip_mf_laplace_get_tile(mfmg_hip_mf_laplace_t op, int *n_waves, int *tile_y, int *tile_z);
+/* mfmg_hip_mf_z_tiles (host only: no context, no GPU): the z-tiling the operator launches read for n_layers DoF layers and the
+ * tile height tz -- starts[t] is the first layer of z-tile t, starts[n_tiles] = n_layers, so tile t owns the layers [starts[t],
+ * starts[t + 1]).  graded = 0: the uniform table, ceil(n_layers / tz) tiles of tz layers (what a launch on a region of tiles
+ * reads).  graded != 0: what a whole-mesh launch of the one-term operator and every launch of the block operator read: with
+ * m = (n_layers / 8 + tz / 2) / tz + 1 and n_layers / 8 >= 2 m every eighth of the layers is cut into m tiles whose heights
+ * fall off linearly (257 layers, tz = 8: 10, 8, 7, 4, 3), 8 m tiles, some taller than tz; the uniform table otherwise.  The
+ * experiment knobs MFMG_MF_GRADE_M and MFMG_MF_GRADE_OFF are not read here.  `starts` has room for `capacity` entries;
+ * MFMG_HIP_ERROR_INVALID_ARGUMENT for a null pointer, n_layers < 1, tz < 1 or capacity < n_tiles + 1 (n_layers + 1 always
+ * suffices).  (addition, no change of the ABI version) */
+int mfmg_hip_mf_z_tiles(int32_t n_layers, int32_t tz, int graded, int32_t *starts, int32_t capacity, int32_t *n_tiles);
 
 /* ---- blocks of vectors: several right-hand sides against one operator (additions, no change of the ABI version) ----
  * A block is n_vectors (1 .. 64) columns of doubles with a common leading dimension: column c starts at base + c * ld elements,

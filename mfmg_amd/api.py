@@ -134,6 +134,20 @@ def block_groups(n_vectors: int):
     return [int(w[i]) for i in range(n.value)]
 
 
+def mf_z_tiles(n_layers: int, tz: int, graded: bool = True):
+    """The z-tiling of the matrix-free operator for n_layers DoF layers and the tile height tz: the tile starts followed by
+    n_layers, so z-tile t owns the layers [tab[t], tab[t + 1]).  graded: what a whole-mesh launch of the one-term operator and
+    every launch of the block operator read (graded where every eighth of the layers holds enough of them, uniform elsewhere);
+    otherwise the uniform table of a region launch.  Host only."""
+    lib = _lib.load()
+    n_layers, tz = int(n_layers), int(tz)
+    capacity = max(n_layers, 0) + 1
+    starts = (C.c_int32 * capacity)()
+    n = C.c_int32()
+    check(lib.mfmg_hip_mf_z_tiles(n_layers, tz, int(bool(graded)), starts, capacity, C.byref(n)))
+    return list(starts[:n.value + 1])
+
+
 def block_cg_retire(retire_flags, slot_col):
     """The slot moves of solve_cg_block when the slots flagged in retire_flags (one per active slot) retire: returns
     (moves, slot_col, n_active) -- moves a list of (from, to) pairs, slot_col the updated slot -> column map (its first n_active

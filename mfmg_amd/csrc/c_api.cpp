@@ -13,6 +13,7 @@
 #include "dof_permutation.hpp"
 #include "halo_transport.hpp"
 #include "krylov_basis.hpp"
+#include "mf_z_tiles.hpp"
 #include "mfmg/hierarchy.hpp"
 
 using namespace mfmg;
@@ -1426,6 +1427,19 @@ int mfmg_hip_block_groups(int32_t n_vectors, int32_t *widths, int32_t *n_groups)
     for (int g = 0; g < n; ++g)
       widths[g] = w[g];
     *n_groups = n;
+  });
+}
+
+int mfmg_hip_mf_z_tiles(int32_t n_layers, int32_t tz, int graded, int32_t *starts, int32_t capacity, int32_t *n_tiles)
+{
+  return guarded([&] {
+    require(starts && n_tiles, "null argument");
+    require(n_layers >= 1 && tz >= 1, "z-tiling: at least one layer and a tile height of at least 1");
+    const std::vector<int> tab = mf_z_tiles(n_layers, tz, graded != 0);
+    require((int64_t)capacity >= (int64_t)tab.size(), "z-tiling: `starts` holds n_tiles + 1 entries");
+    for (size_t t = 0; t < tab.size(); ++t)
+      starts[t] = tab[t];
+    *n_tiles = (int32_t)tab.size() - 1;
   });
 }
 

@@ -47,6 +47,7 @@
 #include <utility>
 
 #include "mf_device.hpp"
+#include "mf_z_tiles.hpp"
 
 namespace mfmg
 {
@@ -1319,47 +1320,20 @@ MfTile MatrixFreeLaplaceDevice<T>::choose_tile() const
 // chip drains for as long as the last tiles take (measured: 257^3 DoFs, three rounds of (4, 3, 8) tiles, 10 % of the launch
 // against the same mesh four times as long in z).  So the tiles that are dispatched LAST are made SHORT: every XCD gets a
 // contiguous run of layers (one eighth of the mesh, as before) cut into the same number of z-tiles whose heights fall
-// off linearly -- 257 layers, tz = 8: 10, 8, 6, 5, 3 instead of 8, 8, 8, 8 -- at the price of one more halo layer per
-// XCD.  Results do not depend on the tiling (bit for bit).  Ranges of z-tiles (the overlapped exchange of a distributed
-// run) keep the uniform tiling: tile t owns the layers [t tz, (t + 1) tz).
+// off linearly -- 257 layers, tz = 8: 10, 8, 7, 4, 3 (in the last eighth, which has 33 layers, 10, 9, 6, 5, 3) instead of
+// 8, 8, 8, 8 -- at the price of one more halo layer per XCD.  Results do not depend on the tiling (bit for bit).  Ranges of
+// z-tiles (the overlapped exchange of a distributed run) keep the uniform tiling: tile t owns the layers [t tz, (t + 1) tz).
+// The rule itself is mf_z_tiles (mf_z_tiles.hpp, host only; mfmg_hip_mf_z_tiles reads it without a GPU): here are its cache,
+// its upload and the two experiment knobs.
 template <typename T>
 int const *MatrixFreeLaplaceDevice<T>::z_tiling(int tz, bool graded, int &n_tiles) const
 {
   ZTiling &zt = graded ? _zt_graded : _zt_uniform;
   if (zt.tz != tz)
   {
-    std::vector<int> tab;
-    const int Nz = _N[2];
     static const int m_extra = std::getenv("MFMG_MF_GRADE_M") ? std::atoi(std::getenv("MFMG_MF_GRADE_M")) : 1;
     static const double w_off = std::getenv("MFMG_MF_GRADE_OFF") ? std::atof(std::getenv("MFMG_MF_GRADE_OFF")) : 0.5;
-    const int m = (Nz / 8 + tz / 2) / tz + m_extra; // z-tiles per XCD
-    if (graded && Nz / 8 >= 2 * m)
-    {
-      double total = 0.;
-      for (int k = 0; k < m; ++k)
-        total += m - k + w_off;
-      for (int s = 0; s < 8; ++s)
-      {
-        const int l0 = (int)((int64_t)s * Nz / 8), l1 = (int)((int64_t)(s + 1) * Nz / 8);
-        double cum = 0.;
-        int prev = l0;
-        for (int k = 0; k < m; ++k)
-        {
-          tab.push_back(prev);
-          cum += m - k + w_off;
-          int next = k + 1 == m ? l1 : l0 + (int)std::lround((l1 - l0) * cum / total);
-          next = std::min(std::max(next, prev + 1), l1 - (m - 1 - k)); // every tile owns at least one layer
-          prev = next;
-        }
-      }
-      tab.push_back(Nz);
-    }
-    else
-    {
-      for (int l = 0; l < Nz; l += tz)
-        tab.push_back(l);
-      tab.push_back(Nz);
-    }
+    const std::vector<int> tab = mf_z_tiles(_N[2], tz, graded, m_extra, w_off);
     zt.n_tiles = (int)tab.size() - 1;
     zt.dev.upload(tab.data(), tab.size(), _handle.stream);
     MFMG_HIP_CHECK(hipStreamSynchronize(_handle.stream)); // (the host vector goes out of scope)

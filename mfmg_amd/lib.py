@@ -220,6 +220,7 @@ def load() -> C.CDLL:
         "mfmg_hip_mf_laplace_f32_residual": (C.c_int, [vp, vp, vp, vp]),
         "mfmg_hip_mf_laplace_f32_smoother_step": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_float, vp]),
         "mfmg_hip_block_groups": (C.c_int, [i32, P(i32), P(i32)]),
+        "mfmg_hip_mf_z_tiles": (C.c_int, [i32, i32, C.c_int, P(i32), i32, P(i32)]),
         "mfmg_hip_mf_laplace_block_launch": (C.c_int, [vp, C.c_int, i32, i64, vp, vp, vp, dbl, dbl, vp]),
         "mfmg_hip_mf_laplace_block_available": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_mf_laplace_set_block_tile": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
@@ -326,7 +327,8 @@ def load() -> C.CDLL:
                    "mfmg_hip_mf_laplace_uniform_coefficient", "mfmg_hip_context_exchange_block", "mfmg_hip_block_dots_box",
                    "mfmg_hip_hierarchy_restrictor_apply_block", "mfmg_hip_hierarchy_transfer_block_info",
                    "mfmg_hip_hierarchy_block_solve_allreduces", "mfmg_hip_context_exchange_block_f32",
-                   "mfmg_hip_block_krylov_orthogonalize_box", "mfmg_hip_context_set_block_fgmres_on_ranks"}
+                   "mfmg_hip_block_krylov_orthogonalize_box", "mfmg_hip_context_set_block_fgmres_on_ranks",
+                   "mfmg_hip_mf_z_tiles"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
