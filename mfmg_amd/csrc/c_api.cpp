@@ -13,6 +13,7 @@
 #include "dof_permutation.hpp"
 #include "halo_transport.hpp"
 #include "krylov_basis.hpp"
+#include "krylov_drivers.hpp"
 #include "mf_z_tiles.hpp"
 #include "mfmg/hierarchy.hpp"
 
@@ -95,253 +96,6 @@ struct mfmg_hip_host_amg_s
   std::vector<AmgLevelHost> levels;
 };
 
-// What mfmg_hip_hierarchy_solve_fgmres keeps between solves: the basis V[ld x (columns + 1)], the preconditioned vectors
-// Z[ld x columns] (krylov_basis.hpp), the float vectors around an FP32 preconditioner, the Hessenberg column / y on the device
-// and their pinned host mirror.  Grown on demand, never shrunk: a solve allocates nothing once its restart length has been seen.
-struct KrylovWorkspace
-{
-  int64_t ld = 0;
-  int columns = 0;
-  DeviceBuffer<double> V, Z, coefficients; // coefficients: [0, columns]: h_0 .. h_j, ||w||; [columns + 1, 2 columns]: y
-  DeviceBuffer<float> v_f32, z_f32;
-  std::unique_ptr<krylov::Scratch> scratch;
-  double *host = nullptr; // pinned, as `coefficients`
-  // An allocation that fails (the basis is 2 m + 1 fine vectors) throws out of here with the workspace EMPTY (ld = columns = 0,
-  // no buffer): the next solve allocates afresh, it never runs on a half-built workspace.
-  void reserve(int64_t n, int m, bool fp32)
-  {
-    const int64_t want_ld = krylov::leading_dimension(n);
-    if (want_ld != ld || m > columns)
-    {
-      MemoryKind kind("Krylov basis");
-      release(); // (before the larger one is allocated)
-      V.resize((size_t)want_ld * (m + 1));
-      Z.resize((size_t)want_ld * m);
-      coefficients.resize((size_t)2 * m + 2);
-      scratch.reset(new krylov::Scratch(m + 1));
-      MFMG_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&host), ((size_t)2 * m + 2) * sizeof(double)));
-      ld = want_ld; // only now: everything above stands
-      columns = m;
-    }
-    if (fp32 && (v_f32.size() != (size_t)ld || z_f32.size() != (size_t)ld))
-    {
-      MemoryKind kind("Krylov basis");
-      v_f32.release();
-      z_f32.release();
-      v_f32.resize((size_t)ld);
-      z_f32.resize((size_t)ld);
-    }
-  }
-  void release()
-  {
-    ld = 0;
-    columns = 0;
-    release_host();
-    V.release();
-    Z.release();
-    coefficients.release();
-    v_f32.release();
-    z_f32.release();
-    scratch.reset();
-  }
-  void release_host()
-  {
-    if (host)
-      (void)hipHostFree(host);
-    host = nullptr;
-  }
-  ~KrylovWorkspace() { release_host(); }
-};
-
-// What mfmg_hip_hierarchy_solve_cg_block keeps between solves: the working blocks r, z, p, A p [ld x columns], with "internal
-// numbering" lexicographic the gathered b and x, the partials of the block reductions [columns x 1024], the per-slot scalars
-// ((r, z) of this / the previous iteration, (p, A p), (r, r): four rows of `columns`), the slot -> column map and the pinned host
-// mirror of the (r, r) and the map.  Grown on demand, never shrunk; a failed allocation leaves the workspace EMPTY.
-struct BlockCgWorkspace
-{
-  int64_t ld = 0;
-  int columns = 0;
-  bool permuted = false;
-  DeviceBuffer<double> R, Z, P, AP, B, X, partials, scalars;
-  DeviceBuffer<int32_t> slot_col;
-  double *host = nullptr;        // pinned: `columns` doubles ...
-  int32_t *host_col = nullptr;   // ... and behind them `columns` slot -> column entries
-  void reserve(int64_t want_ld, int k, bool permute, hipStream_t stream)
-  {
-    if (want_ld == ld && k <= columns && (!permute || permuted))
-      return;
-    MemoryKind kind("block CG working set");
-    const int want = std::max(k, want_ld == ld ? columns : 0);
-    release(); // (before the larger one is allocated)
-    const size_t block = (size_t)want_ld * want;
-    DeviceBuffer<double> *blocks[6] = {&R, &Z, &P, &AP, &B, &X};
-    for (int i = 0; i < (permute ? 6 : 4); ++i)
-    {
-      blocks[i]->resize(block);
-      // (zeros: the tails between the columns are never written, and a preconditioner that reads its start vector finds numbers)
-      MFMG_HIP_CHECK(hipMemsetAsync(blocks[i]->data(), 0, block * sizeof(double), stream));
-    }
-    partials.resize((size_t)want * block_krylov::kReduceBlocks);
-    scalars.resize((size_t)4 * want);
-    slot_col.resize((size_t)want);
-    MFMG_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&host), (size_t)want * (sizeof(double) + sizeof(int32_t))));
-    host_col = reinterpret_cast<int32_t *>(host + want);
-    ld = want_ld; // only now: everything above stands
-    columns = want;
-    permuted = permute;
-  }
-  void release()
-  {
-    ld = 0;
-    columns = 0;
-    permuted = false;
-    release_host();
-    for (DeviceBuffer<double> *b : {&R, &Z, &P, &AP, &B, &X, &partials, &scalars})
-      b->release();
-    slot_col.release();
-  }
-  void release_host()
-  {
-    if (host)
-      (void)hipHostFree(host);
-    host = nullptr;
-    host_col = nullptr;
-  }
-  ~BlockCgWorkspace() { release_host(); }
-};
-
-// The host arithmetic of flexible GMRES for ONE right-hand side, used by the one-vector and the block driver alike: the
-// triangular factor of the Hessenberg matrix (column-major with m + 1 rows), the Givens rotations, the rotated right-hand side g,
-// the breakdown flag and the back-substitution for y.
-struct FgmresColumn
-{
-  int m;
-  std::vector<double> R, cs, sn, g;
-  int k = 0; // columns of this cycle
-  bool breakdown = false;
-  explicit FgmresColumn(int m) : m(m), R((size_t)(m + 1) * m), cs(m), sn(m), g(m + 1) {}
-  void begin_cycle(double residual)
-  {
-    std::fill(g.begin(), g.end(), 0.);
-    g[0] = residual;
-    k = 0;
-    breakdown = false;
-  }
-  // where the caller puts h_0 .. h_j, ||w|| of step j
-  double *column(int j) { return &R[(size_t)j * (m + 1)]; }
-  // the column of step k goes through the rotations; returns |g_{k+1}|, the residual norm of the least-squares problem
-  double rotate()
-  {
-    const int j = k;
-    double *const c = column(j);
-    for (int i = 0; i < j; ++i)
-    {
-      const double t = cs[i] * c[i] + sn[i] * c[i + 1];
-      c[i + 1] = -sn[i] * c[i] + cs[i] * c[i + 1];
-      c[i] = t;
-    }
-    // h_{j+1,j} = 0: the Krylov space is exhausted -- v_{j+1} is zero (basis_scale_store), the cycle ends with the update
-    breakdown = c[j + 1] == 0.;
-    const double d = std::hypot(c[j], c[j + 1]);
-    cs[j] = d > 0. ? c[j] / d : 1.;
-    sn[j] = d > 0. ? c[j + 1] / d : 0.;
-    c[j] = d;
-    c[j + 1] = 0.;
-    g[j + 1] = -sn[j] * g[j];
-    g[j] = cs[j] * g[j];
-    ++k;
-    return std::abs(g[j + 1]);
-  }
-  // R y = g over the k columns of this cycle (a zero pivot -- a singular Hessenberg matrix -- contributes nothing: no division by zero)
-  void solve(double *y) const
-  {
-    for (int i = k - 1; i >= 0; --i)
-    {
-      double s = g[i];
-      for (int l = i + 1; l < k; ++l)
-        s -= R[(size_t)l * (m + 1) + i] * y[l];
-      const double pivot = R[(size_t)i * (m + 1) + i];
-      y[i] = pivot != 0. ? s / pivot : 0.;
-    }
-  }
-};
-
-// What mfmg_hip_hierarchy_solve_fgmres_block keeps between solves, for `slots` columns and restart cycles of `columns` vectors:
-// the bases V [(columns + 1) x slots x ld] and Z [columns x slots x ld] (block_krylov_basis.hpp), the float vectors around an FP32
-// preconditioner [slots x ld] twice, with "internal numbering" lexicographic the gathered b and x, the scratch of the launches,
-// per slot the Hessenberg column (columns + 1 doubles) and y (columns doubles) on the device and their pinned host mirror.
-// Grown on demand, never shrunk; a failed allocation leaves the workspace EMPTY.
-struct BlockFgmresWorkspace
-{
-  int64_t ld = 0;
-  int slots = 0, columns = 0;
-  bool permuted = false, fp32 = false;
-  DeviceBuffer<double> V, Z, B, X, coefficients, y;
-  DeviceBuffer<float> v_f32, z_f32;
-  std::unique_ptr<block_krylov_basis::Scratch> scratch;
-  double *host = nullptr; // pinned: slots x (columns + 1) coefficients, then slots x columns entries of y
-  double *host_y() const { return host + (size_t)slots * (columns + 1); }
-  void reserve(int64_t want_ld, int k, int m, bool permute, bool with_fp32, hipStream_t stream)
-  {
-    if (want_ld == ld && k <= slots && m <= columns && (!permute || permuted) && (!with_fp32 || fp32))
-      return;
-    MemoryKind kind("block FGMRES working set");
-    const bool same = want_ld == ld;
-    const int want_slots = std::max(k, same ? slots : 0), want_columns = std::max(m, same ? columns : 0);
-    permute = permute || (same && permuted);
-    with_fp32 = with_fp32 || (same && fp32);
-    release(); // (before the larger one is allocated)
-    const size_t block = (size_t)want_ld * want_slots;
-    // (zeros: the tails between the columns are never written, and a cycle that reads its start vector finds numbers)
-    auto zeros = [&](DeviceBuffer<double> &b, size_t count) {
-      b.resize(count);
-      MFMG_HIP_CHECK(hipMemsetAsync(b.data(), 0, count * sizeof(double), stream));
-    };
-    zeros(V, block * ((size_t)want_columns + 1));
-    zeros(Z, block * (size_t)want_columns);
-    if (permute)
-    {
-      zeros(B, block);
-      zeros(X, block);
-    }
-    if (with_fp32)
-    {
-      v_f32.resize(block);
-      z_f32.resize(block);
-      MFMG_HIP_CHECK(hipMemsetAsync(v_f32.data(), 0, block * sizeof(float), stream));
-      MFMG_HIP_CHECK(hipMemsetAsync(z_f32.data(), 0, block * sizeof(float), stream));
-    }
-    scratch.reset(new block_krylov_basis::Scratch(want_slots, want_columns + 1));
-    coefficients.resize((size_t)want_slots * (want_columns + 1));
-    y.resize((size_t)want_slots * want_columns);
-    MFMG_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&host), (size_t)want_slots * (2 * (size_t)want_columns + 1) * sizeof(double)));
-    ld = want_ld; // only now: everything above stands
-    slots = want_slots;
-    columns = want_columns;
-    permuted = permute;
-    fp32 = with_fp32;
-  }
-  void release()
-  {
-    ld = 0;
-    slots = columns = 0;
-    permuted = fp32 = false;
-    release_host();
-    for (DeviceBuffer<double> *b : {&V, &Z, &B, &X, &coefficients, &y})
-      b->release();
-    v_f32.release();
-    z_f32.release();
-    scratch.reset();
-  }
-  void release_host()
-  {
-    if (host)
-      (void)hipHostFree(host);
-    host = nullptr;
-  }
-  ~BlockFgmresWorkspace() { release_host(); }
-};
-
 struct mfmg_hip_hierarchy_s
 {
   HipHandle *handle = nullptr;
@@ -361,9 +115,7 @@ struct mfmg_hip_hierarchy_s
   std::unique_ptr<DofPermutation> perm;
   DeviceBuffer<double> work[2];
   DeviceBuffer<float> work_f32[2];
-  KrylovWorkspace krylov;
-  BlockCgWorkspace block_cg;
-  BlockFgmresWorkspace block_fgmres;
+  KrylovWorkspaces krylov; // what the drivers of krylov_drivers.hpp keep between solves
   // block entry points: the permuted columns of one group (b, x) and what the last block call did
   DeviceBuffer<double> block_work[2];
   int64_t block_info[MFMG_HIP_BLOCK_INFO_FIELDS] = {1, 0, 0};
@@ -406,6 +158,51 @@ struct mfmg_hip_hierarchy_s
     return work_f32[i].data();
   }
 };
+
+namespace
+{
+int64_t level_size(mfmg_hip_hierarchy_t h, int level)
+{
+  require(level >= 0 && level < (int)h->hierarchy->levels().size(), "level out of range");
+  return level_size(*h->hierarchy, level);
+}
+
+// the blocks b and x of n_vectors columns of level `level`, of doubles or floats: columns are aligned to two scalars
+template <typename T>
+void check_block_shape(mfmg_hip_hierarchy_t h, int level, int32_t n_vectors, int64_t ld, const T *b, const T *x)
+{
+  constexpr bool f64 = sizeof(T) == 8;
+  require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
+  require(b && x, "null argument");
+  const int64_t n = level_size(h, level);
+  require(ld >= n, "the leading dimension of a block must be at least the vector size");
+  require(ld % 2 == 0, f64 ? "the leading dimension of a block must be even (columns aligned to 16 bytes)"
+                           : "the leading dimension of a block must be even (columns aligned to 8 bytes)");
+  require(reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && reinterpret_cast<uintptr_t>(x) % (2 * sizeof(T)) == 0,
+          f64 ? "the base of a block must be aligned to 16 bytes" : "the base of a block must be aligned to 8 bytes");
+  const int64_t extent = (int64_t)(n_vectors - 1) * ld + n;
+  require(b + extent <= x || x + extent <= b, "the blocks b and x overlap");
+}
+
+// What the drivers of krylov_drivers.hpp run on.  A one-vector driver gathers permuted vectors into the library's two.
+KrylovSetting krylov_setting(mfmg_hip_hierarchy_t h, bool one_vector)
+{
+  const bool work = one_vector && h->perm;
+  return {*h->handle, *h->hierarchy, h->fine_f32.get(), h->perm.get(), h->timer, {work ? h->workspace(0) : nullptr, work ? h->workspace(1) : nullptr},
+          h->krylov};
+}
+
+// (per column; one column from the one-vector drivers)
+void deliver_result(KrylovResult const &result, int32_t *n_iterations, double *final_residuals, int64_t *work)
+{
+  if (n_iterations)
+    std::copy(result.iterations.begin(), result.iterations.end(), n_iterations);
+  if (final_residuals)
+    std::copy(result.residuals.begin(), result.residuals.end(), final_residuals);
+  if (work)
+    std::copy(result.work, result.work + 4, work);
+}
+} // namespace
 
 extern "C" {
 
@@ -1819,19 +1616,6 @@ int mfmg_hip_hierarchy_destroy(mfmg_hip_hierarchy_t h)
 
 namespace
 {
-int64_t level_size(mfmg_hip_hierarchy_t h, int level)
-{
-  auto const &levels = h->hierarchy->levels();
-  require(level >= 0 && level < (int)levels.size(), "level out of range");
-  auto op = levels[level].get_operator();
-  if (auto m = std::dynamic_pointer_cast<HipMatrixOperator const>(op))
-    return m->get_matrix()->m();
-  return (int64_t)op->grid_complexity();
-}
-} // namespace
-
-namespace
-{
 // Hierarchy::apply on vectors in the caller's numbering while the hierarchy runs in the lexicographic one: ONE launch gathers b
 // -- and x, unless the cycle starts from zero and never reads it --, and the copy into x that ends the cycle is the scatter
 void apply_permuted(mfmg_hip_hierarchy_t h, const double *b, double *x)
@@ -1890,19 +1674,7 @@ void check_block(mfmg_hip_hierarchy_t h, int level, int32_t n_vectors, int64_t l
   require(h && b && x, "null argument");
   begin_block_call(h); // (every block entry point passes here first)
   require(on_ranks || !h->handle->comm.enabled(), "blocks of vectors are not implemented for a context with a communicator");
-  require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
-  const int64_t n = level_size(h, level);
-  require(ld >= n, "the leading dimension of a block must be at least the vector size");
-  require(ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 16 bytes)");
-  require(reinterpret_cast<uintptr_t>(b) % 16 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, "the base of a block must be aligned to 16 bytes");
-  const int64_t extent = (int64_t)(n_vectors - 1) * ld + n;
-  require(b + extent <= x || x + extent <= b, "the blocks b and x overlap");
-}
-
-int64_t block_kernel_launches(mfmg_hip_hierarchy_t h)
-{
-  auto op = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(h->hierarchy->levels()[0].get_operator());
-  return op ? op->get_mesh_evaluator()->get_device_operator()->block_launches() : 0;
+  check_block_shape(h, level, n_vectors, ld, b, x);
 }
 
 // The groups of a block, one after the other: `run` gets the columns of the group as views -- of the caller's vectors, or with
@@ -1934,19 +1706,8 @@ void for_block_groups(mfmg_hip_hierarchy_t h, int level, bool read_x, int32_t n_
       gb = wb;
       gx = wx;
     }
-    std::vector<DVector> bv, xv;
-    bv.reserve(w);
-    xv.reserve(w);
-    std::vector<DVector const *> bp;
-    std::vector<DVector *> xp;
-    for (int c = 0; c < w; ++c)
-    {
-      bv.emplace_back(*h->handle, n, const_cast<double *>(gb) + c * wld);
-      xv.emplace_back(*h->handle, n, gx + c * wld);
-      bp.push_back(&bv.back());
-      xp.push_back(&xv.back());
-    }
-    run(bp, xp);
+    BlockViews bv(*h->handle, n, wld, w, const_cast<double *>(gb)), xv(*h->handle, n, wld, w, gx);
+    run(bv.cptr, xv.ptr);
     if (permute)
       for (int c = 0; c < w; ++c)
         h->perm->scatter(static_cast<double const *>(gx + c * wld), x + (c0 + c) * ld);
@@ -1956,14 +1717,14 @@ void for_block_groups(mfmg_hip_hierarchy_t h, int level, bool read_x, int32_t n_
 void apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x)
 {
   check_block(h, 0, n_vectors, ld, b, x);
-  const int64_t launches = block_kernel_launches(h);
+  const int64_t launches = block_kernel_launches(*h->hierarchy);
   int64_t looped = 0;
   for_block_groups(h, 0, !h->hierarchy->is_preconditioner(), n_vectors, ld, b, x, [&](std::vector<DVector const *> const &bp, std::vector<DVector *> const &xp) {
     h->hierarchy->apply_block(bp, xp);
     looped += h->hierarchy->block_columns_looped();
   });
   h->block_info[0] = h->hierarchy->block_width();
-  h->block_info[1] = block_kernel_launches(h) - launches;
+  h->block_info[1] = block_kernel_launches(*h->hierarchy) - launches;
   h->block_info[2] = looped;
 }
 } // namespace
@@ -1977,17 +1738,8 @@ int mfmg_hip_hierarchy_vmult_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, in
 {
   return guarded([&] {
     require(h != nullptr, "null argument");
-    timer_enter_subsection(h->timer, "Apply");
-    try
-    {
-      apply_block(h, n_vectors, ld, b, x);
-    }
-    catch (...)
-    {
-      timer_leave_subsection(h->timer);
-      throw;
-    }
-    timer_leave_subsection(h->timer);
+    TimerSubsection apply(h->timer, "Apply");
+    apply_block(h, n_vectors, ld, b, x);
   });
 }
 
@@ -1999,7 +1751,7 @@ int mfmg_hip_hierarchy_smoother_apply_block(mfmg_hip_hierarchy_t h, int32_t leve
     check_block(h, level, n_vectors, ld, b, x);
     auto smoother = h->hierarchy->levels()[level].get_smoother();
     require(smoother != nullptr, "this level has no smoother");
-    const int64_t launches = block_kernel_launches(h);
+    const int64_t launches = block_kernel_launches(*h->hierarchy);
     int64_t looped = 0;
     for_block_groups(h, level, true, n_vectors, ld, b, x, [&](std::vector<DVector const *> const &bp, std::vector<DVector *> const &xp) {
       smoother->apply_block(bp, xp);
@@ -2007,7 +1759,7 @@ int mfmg_hip_hierarchy_smoother_apply_block(mfmg_hip_hierarchy_t h, int32_t leve
         looped += (int64_t)bp.size();
     });
     h->block_info[0] = level == 0 ? smoother->block_width() : 1;
-    h->block_info[1] = block_kernel_launches(h) - launches;
+    h->block_info[1] = block_kernel_launches(*h->hierarchy) - launches;
     h->block_info[2] = looped;
   });
 }
@@ -2092,14 +1844,8 @@ int mfmg_hip_hierarchy_apply_f32_block(mfmg_hip_hierarchy_t h, int32_t n_vectors
       require(!comm.enabled() || (comm.spaces[1].configured() && comm.transport != nullptr),
               "a context with a communicator needs its fine DoF space configured and a transport registered");
     }
-    require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
-    require(b && x, "null argument");
+    check_block_shape(h, 0, n_vectors, ld, b, x);
     const int64_t n = level_size(h, 0);
-    require(ld >= n, "the leading dimension of a block must be at least the vector size");
-    require(ld % 2 == 0, "the leading dimension of a block must be even (columns aligned to 8 bytes)");
-    require(reinterpret_cast<uintptr_t>(b) % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 8 == 0, "the base of a block must be aligned to 8 bytes");
-    const int64_t extent = (int64_t)(n_vectors - 1) * ld + n;
-    require(b + extent <= x || x + extent <= b, "the blocks b and x overlap");
     const int64_t launches = h->fine_f32->block_launches();
     if (h->perm)
     {
@@ -2170,9 +1916,8 @@ int mfmg_hip_hierarchy_vmult(mfmg_hip_hierarchy_t h, double *x, const double *b)
     require(h && b && x, "null argument");
     if (h->perm)
     {
-      timer_enter_subsection(h->timer, "Apply");
+      TimerSubsection apply(h->timer, "Apply");
       apply_permuted(h, b, x);
-      timer_leave_subsection(h->timer);
       return;
     }
     const int64_t n = level_size(h, 0);
@@ -2188,129 +1933,13 @@ int mfmg_hip_hierarchy_solve_cg(mfmg_hip_hierarchy_t h, const double *b, double 
   return guarded([&] {
     require(h && b && x, "null argument");
     require(tolerance >= 0. && max_iterations >= 0, "bad stopping criterion");
-    // preconditioned CG as dealii::SolverCG runs it (third-party, restated): r = b - A x, z = M^-1 r, p = z;
-    // alpha = (r,z)/(p,Ap); x += alpha p; r -= alpha Ap; stop on ||r||_2 <= tolerance; beta = (r,z)_new/(r,z)_old
-    HipHandle &handle = *h->handle;
-    const int64_t n = level_size(h, 0);
-    auto op = h->hierarchy->levels()[0].get_operator();
-    auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
-    const int space = hop ? hop->domain_space() : 0;
-    // "internal numbering" lexicographic: b and x are gathered once, the whole iteration -- operator, preconditioner, the four
-    // CG vectors, the dot products -- runs in the internal numbering, and x is scattered once at the end: two launches of the
-    // permutation per solve whatever the iteration count (the residual history is a list of norms)
-    double const *b_run = b;
-    double *x_run = x;
-    if (h->perm)
-    {
-      h->perm->gather2(b, static_cast<double const *>(x), h->workspace(0), h->workspace(1));
-      b_run = h->workspace(0);
-      x_run = h->workspace(1);
-    }
-    DVector bv(handle, n, const_cast<double *>(b_run)), xv(handle, n, x_run);
-    DVector r(handle, n), z(handle, n), p(handle, n), ap(handle, n);
-    auto dot = [&](DVector const &u, DVector const &v) { return distributed_dot(handle, space, u, v); };
-    op->apply(xv, r);
-    r.sadd(-1., 1., bv); // r = b - A x
-    double res = std::sqrt(dot(r, r));
-    int it = 0;
-    auto record = [&](int k, double v) {
-      if (residual_history && k < history_len)
-        residual_history[k] = v;
-    };
-    record(0, res);
-    double rz = 0.;
-    bool converged = res <= tolerance;
-    if (!handle.comm.enabled())
-    {
-      // One rank: the scalars of the iteration stay on the device (vec::cg_direction / cg_update read them there) -- ONE host
-      // round trip per iteration, for the stopping test, instead of three; x and r are updated in one pass.  The same sums in the
-      // same order as below: the same iterates.
-      DeviceBuffer<double> scal(4); // [0], [1]: (r, z) of this / the previous iteration, alternating; [2]: (p, A p); [3]: (r, r)
-      int cur = 0;
-      while (!converged && it < max_iterations)
-      {
-        h->hierarchy->vmult(z, r);
-        vec::dot_async<double>(handle, n, r.get_values(), z.get_values(), scal.data(), cur);
-        if (it == 0)
-          p = z;
-        else
-          vec::cg_direction<double>(handle, n, z.get_values(), p.get_values(), scal.data(), cur, 1 - cur); // p = z + beta p
-        op->apply(p, ap);
-        vec::dot_async<double>(handle, n, p.get_values(), ap.get_values(), scal.data(), 2);
-        vec::cg_update<double>(handle, n, p.get_values(), ap.get_values(), nullptr, xv.get_values(), r.get_values(), nullptr, scal.data(), cur, 2);
-        vec::dot_async<double>(handle, n, r.get_values(), r.get_values(), scal.data(), 3);
-        MFMG_HIP_CHECK(hipMemcpyAsync(handle.host_result, scal.data() + 3, sizeof(double), hipMemcpyDeviceToHost, handle.stream));
-        MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-        res = std::sqrt(handle.host_result[0]);
-        cur = 1 - cur;
-        ++it;
-        record(it, res);
-        converged = res <= tolerance;
-      }
-    }
-    while (!converged && it < max_iterations)
-    {
-      h->hierarchy->vmult(z, r);
-      const double rz_new = dot(r, z);
-      if (it == 0)
-        p = z;
-      else
-        p.sadd(rz_new / rz, 1., z); // p = z + beta p
-      rz = rz_new;
-      op->apply(p, ap);
-      const double alpha = rz / dot(p, ap);
-      xv.add(alpha, p);
-      r.add(-alpha, ap);
-      res = std::sqrt(dot(r, r));
-      ++it;
-      record(it, res);
-      converged = res <= tolerance;
-    }
-    if (n_iterations)
-      *n_iterations = it;
-    if (final_residual)
-      *final_residual = res;
-    if (h->perm)
-      h->perm->scatter(static_cast<double const *>(x_run), x);
-    if (!converged)
+    const KrylovResult result = solve_cg(krylov_setting(h, true), b, x, tolerance, max_iterations, residual_history, history_len);
+    deliver_result(result, n_iterations, final_residual, nullptr);
+    if (!result.all_converged())
       throw std::runtime_error("CG did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
   });
 }
 
-namespace
-{
-// the first `count` columns of a block as vectors (views)
-struct BlockViews
-{
-  std::vector<DVector> store;
-  std::vector<DVector *> ptr;
-  std::vector<DVector const *> cptr;
-  BlockViews(HipHandle &handle, int64_t n, int64_t ld, int count, double *base)
-  {
-    store.reserve(count);
-    for (int c = 0; c < count; ++c)
-    {
-      store.emplace_back(handle, n, base + (int64_t)c * ld);
-      ptr.push_back(&store.back());
-      cptr.push_back(&store.back());
-    }
-  }
-};
-} // namespace
-
-// mfmg_hip_hierarchy_solve_cg on a block of right-hand sides.  All columns iterate in lockstep, so "the first iteration" is the
-// same for every slot; a column that converged leaves the working blocks (block_krylov::plan_retire keeps the active slots
-// contiguous) and costs nothing further.  Per iteration: the cycle on the active slots (Hierarchy::apply_block), (r, z) of all of
-// them in one reduction, the direction, the operator on the block, (p, A p), the update with the partials of (r, r) folded in,
-// ONE device-to-host copy of the active slots' (r, r) and ONE synchronisation.  Every kernel gives a slot the bits the one-vector
-// driver gives its vector, so x, the iteration count and the history of a column are those of mfmg_hip_hierarchy_solve_cg.
-// Several ranks: the blocks hold the ranks' local vectors.  The operator and the cycle exchange what they read (a group of columns
-// one message per neighbour where the ranks agreed on blocks); direction and update run over all local entries; (r, z), (p, A p)
-// and (r, r) run over the owned entries of all live slots in one launch (block_krylov::dots on the OwnedBox of the fine space)
-// and are summed over the ranks in ONE all-reduce each -- three per iteration whatever k, plus one for the initial residuals.
-// Every control decision is taken from all-reduced values, so every rank retires the same columns and leaves the loop in the same
-// iteration.  A column has the bits of the one-vector solve on the same ranks where the transport sums an element in the same
-// order whatever the length of the message (block_krylov.hpp).
 int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
                                       const double *tolerances, int32_t max_iterations, int32_t *n_iterations, double *final_residuals,
                                       double *residual_history, int32_t history_ld, int64_t *work)
@@ -2322,197 +1951,10 @@ int mfmg_hip_hierarchy_solve_cg_block(mfmg_hip_hierarchy_t h, int32_t n_vectors,
     for (int c = 0; c < n_vectors; ++c)
       require(tolerances[c] >= 0., "bad stopping criterion");
     require(residual_history == nullptr || history_ld >= 0, "bad history length");
-    HipHandle &handle = *h->handle;
-    const int k = n_vectors;
-    const int64_t n = level_size(h, 0);
-    auto op = h->hierarchy->levels()[0].get_operator();
-    // "internal numbering" lexicographic: b and x are gathered once into library blocks, the whole iteration runs in the internal
-    // numbering, x is scattered once: 2 k launches of the permutation per solve.  Otherwise the working blocks take the caller's
-    // leading dimension, so that the operator runs from the caller's x into r on one block layout.
-    const bool permute = (bool)h->perm;
-    const int64_t wld = permute ? n + (n & 1) : ld;
-    BlockCgWorkspace &ws = h->block_cg;
-    try
-    {
-      ws.reserve(wld, k, permute, handle.stream);
-    }
-    catch (...)
-    {
-      ws.release();
-      (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
-      throw;
-    }
-    double const *b_run = b;
-    double *x_run = x;
-    if (permute)
-    {
-      for (int c = 0; c < k; ++c)
-        h->perm->gather2(b + c * ld, static_cast<double const *>(x + c * ld), ws.B.data() + c * wld, ws.X.data() + c * wld);
-      b_run = ws.B.data();
-      x_run = ws.X.data();
-    }
-    double *const R = ws.R.data(), *const Z = ws.Z.data(), *const P = ws.P.data(), *const AP = ws.AP.data();
-    double *const partials = ws.partials.data();
-    double *const rz[2] = {ws.scalars.data(), ws.scalars.data() + ws.columns}; // (r, z) of this / the previous iteration, alternating
-    double *const pap = ws.scalars.data() + 2 * ws.columns, *const rr = ws.scalars.data() + 3 * ws.columns;
-    const bool z_is_read = !h->hierarchy->is_preconditioner(); // the cycle then starts from what z holds: the one-vector driver's zero / last z
-    if (z_is_read)
-      MFMG_HIP_CHECK(hipMemsetAsync(Z, 0, sizeof(double) * (size_t)wld * k, handle.stream));
-    const int64_t launches_before = block_kernel_launches(h);
-    int64_t preconditioner_columns = 0, operator_columns = 0, slot_moves = 0;
-    auto fetch = [&](int count) { // (r, r) of the first `count` slots: the one round trip of an iteration
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, rr, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-    };
-    // several ranks: the reductions over the owned entries, summed over the ranks
-    const bool distributed = handle.comm.enabled();
-    krylov::OwnedBox box;
-    if (distributed)
-    {
-      auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
-      const int space = hop ? hop->domain_space() : 0;
-      require(space > 0 && space < (int)handle.comm.spaces.size() && handle.comm.spaces[space].configured() && handle.comm.transport != nullptr,
-              "the fine operator has no distributed vector space or no transport was registered");
-      box = krylov::OwnedBox(handle.comm.spaces[space]);
-      require(box.n_local() == n, "the fine space does not describe the vectors of the fine level");
-    }
-    // out[s] = (X_s, Y_s) of the first `count` slots on the device; several ranks: over the owned entries, through the host and one
-    // all-reduce, and back (ws.host then holds the sums as well)
-    auto reduce = [&](int count, double const *X, double const *Y, double *out) {
-      if (!distributed)
-        return block_krylov::dots(handle, n, count, wld, X, Y, partials, out);
-      block_krylov::dots(handle, box, count, wld, X, Y, partials, out);
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, out, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-      handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
-      if (out != rr) // ((r, r) is read on the host alone)
-      {
-        MFMG_HIP_CHECK(hipMemcpyAsync(out, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
-        MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (ws.host is written again by the next reduction)
-      }
-    };
-    auto record = [&](int c, int it, double v) {
-      if (residual_history && it < history_ld)
-        residual_history[(int64_t)c * history_ld + it] = v;
-    };
-    // r = b - A x, as the one-vector driver forms it: the operator, then r = -r + b per column
-    {
-      BlockViews xv(handle, n, wld, k, x_run), rv(handle, n, wld, k, R);
-      op->apply_block(xv.cptr, rv.ptr);
-      for (int c = 0; c < k; ++c)
-        vec::sadd<double>(handle, n, -1., 1., b_run + c * wld, R + c * wld);
-    }
-    reduce(k, R, R, rr);
-    if (!distributed)
-      fetch(k);
-    std::vector<double> res(k);
-    std::vector<int32_t> iterations(k, 0), flags(k), moves(2 * (size_t)k);
-    int n_active = k;
-    bool any = false;
-    for (int c = 0; c < k; ++c)
-    {
-      res[c] = std::sqrt(ws.host[c]);
-      record(c, 0, res[c]);
-      flags[c] = res[c] <= tolerances[c];
-      any = any || flags[c];
-      ws.host_col[c] = c;
-    }
-    int it = 0, cur = 0;
-    // the slots named by `flags` retire; r, p (and what else the next iteration reads of a slot) of the slots that move follow.
-    // (host_col is written only after the synchronisation that follows the upload before: the copy never reads a changing array)
-    auto retire = [&](bool upload_always) {
-      int n_left = n_active, n_moves = 0;
-      if (any)
-        n_moves = block_krylov::plan_retire(n_active, flags.data(), ws.host_col, moves.data(), &n_left);
-      n_active = n_left;
-      if (n_active == 0 || it >= max_iterations || !(any || upload_always))
-        return;
-      for (int m = 0; m < n_moves; ++m)
-      {
-        const int64_t from = moves[2 * m], to = moves[2 * m + 1];
-        vec::copy<double>(handle, n, R + from * wld, R + to * wld);
-        if (it > 0)
-        {
-          vec::copy<double>(handle, n, P + from * wld, P + to * wld);
-          if (z_is_read)
-            vec::copy<double>(handle, n, Z + from * wld, Z + to * wld);
-          MFMG_HIP_CHECK(hipMemcpyAsync(rz[1 - cur] + to, rz[1 - cur] + from, sizeof(double), hipMemcpyDeviceToDevice, handle.stream));
-        }
-      }
-      slot_moves += n_moves;
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.slot_col.data(), ws.host_col, sizeof(int32_t) * n_active, hipMemcpyHostToDevice, handle.stream));
-    };
-    retire(true);
-    while (n_active > 0 && it < max_iterations)
-    {
-      {
-        BlockViews rv(handle, n, wld, n_active, R), zv(handle, n, wld, n_active, Z);
-        timer_enter_subsection(h->timer, "Apply");
-        try
-        {
-          h->hierarchy->apply_block(rv.cptr, zv.ptr);
-        }
-        catch (...)
-        {
-          timer_leave_subsection(h->timer);
-          throw;
-        }
-        timer_leave_subsection(h->timer);
-      }
-      preconditioner_columns += n_active;
-      reduce(n_active, R, Z, rz[cur]);
-      if (distributed) // (p.sadd(beta, 1., z) of the one-vector driver on ranks rounds beta p before it adds z)
-        block_krylov::cg_direction_local(handle, n, n_active, wld, Z, P, rz[cur], rz[1 - cur], it == 0);
-      else
-        block_krylov::cg_direction(handle, n, n_active, wld, Z, P, rz[cur], rz[1 - cur], it == 0); // p = z + beta p
-      {
-        BlockViews pv(handle, n, wld, n_active, P), apv(handle, n, wld, n_active, AP);
-        op->apply_block(pv.cptr, apv.ptr);
-      }
-      operator_columns += n_active;
-      reduce(n_active, P, AP, pap);
-      if (distributed)
-      {
-        block_krylov::cg_update_local(handle, n, n_active, wld, P, AP, R, wld, x_run, ws.slot_col.data(), rz[cur], pap);
-        reduce(n_active, R, R, rr);
-      }
-      else
-      {
-        block_krylov::cg_update(handle, n, n_active, wld, P, AP, R, wld, x_run, ws.slot_col.data(), rz[cur], pap, partials, rr);
-        fetch(n_active);
-      }
-      cur = 1 - cur; // rz[1 - cur] is now the (r, z) of the iteration that just ended
-      ++it;
-      any = false;
-      for (int s = 0; s < n_active; ++s)
-      {
-        const int c = ws.host_col[s];
-        res[c] = std::sqrt(ws.host[s]);
-        iterations[c] = it;
-        record(c, it, res[c]);
-        flags[s] = res[c] <= tolerances[c];
-        any = any || flags[s];
-      }
-      retire(false);
-    }
-    for (int c = 0; c < k; ++c)
-    {
-      if (n_iterations)
-        n_iterations[c] = iterations[c];
-      if (final_residuals)
-        final_residuals[c] = res[c];
-    }
-    if (permute)
-      for (int c = 0; c < k; ++c)
-        h->perm->scatter(static_cast<double const *>(x_run + c * wld), x + c * ld);
-    if (work)
-    {
-      work[0] = preconditioner_columns;
-      work[1] = operator_columns;
-      work[2] = block_kernel_launches(h) - launches_before;
-      work[3] = slot_moves;
-    }
-    if (n_active > 0)
+    const KrylovResult result =
+      solve_cg_block(krylov_setting(h, false), n_vectors, ld, b, x, tolerances, max_iterations, residual_history, history_ld);
+    deliver_result(result, n_iterations, final_residuals, work);
+    if (!result.all_converged())
       throw std::runtime_error("CG did not reach the tolerance within max_iterations on every column of the block (SolverControl::NoConvergence)");
   });
 }
@@ -2583,215 +2025,15 @@ int mfmg_hip_hierarchy_operator_apply_block(mfmg_hip_hierarchy_t h, int32_t leve
     require(level >= 0 && level < (int)h->hierarchy->levels().size(), "level out of range");
     check_block(h, level, n_vectors, ld, x, y);
     auto op = h->hierarchy->levels()[level].get_operator();
-    const int64_t launches = block_kernel_launches(h);
+    const int64_t launches = block_kernel_launches(*h->hierarchy);
     for_block_groups(h, level, false, n_vectors, ld, x, y, [&](std::vector<DVector const *> const &xp, std::vector<DVector *> const &yp) {
       op->apply_block(xp, yp);
     });
     h->block_info[0] = h->hierarchy->block_width();
-    h->block_info[1] = block_kernel_launches(h) - launches;
+    h->block_info[1] = block_kernel_launches(*h->hierarchy) - launches;
     h->block_info[2] = 0;
   });
 }
-
-// Right-preconditioned flexible GMRES(restart) as dealii::SolverFGMRES runs it (third-party, restated): r = b - A x, v_0 = r / ||r||;
-// step j: z_j = M^-1 v_j, w = A z_j, w orthogonalised against v_0 .. v_j (classical Gram-Schmidt twice, krylov_basis.hpp),
-// v_{j+1} = w / ||w||; the Hessenberg column goes through the Givens rotations on the host, |g_{j+1}| is the residual norm of the
-// least-squares problem and is what SolverControl sees; x += Z y when it is small enough or the basis is full.
-// Several ranks: the vectors are the ranks' local ones, b, x and the basis handed to the operator and the cycle as
-// mfmg_hip_hierarchy_solve_cg hands them (ghost entries are exchanged by whoever reads them, and are don't-care here).  Dots and
-// norms run over the owned entries (krylov::OwnedBox of the fine space) and are summed over the ranks on the host: per iteration
-// one all-reduce of the j + 1 coefficients per Gram-Schmidt pass and one of ||w||^2, three in all.  The Hessenberg column is
-// then on the host already.  EVERY control decision below -- convergence, breakdown, restart, the end of the iteration -- is
-// taken from all-reduced values alone (`res`, the column, the iteration count), so all ranks take the same branch: a rank that
-// left the loop by itself would leave the others waiting in the next exchange.
-namespace
-{
-struct FgmresOutcome
-{
-  int iterations = 0;
-  double residual = 0.;
-  bool converged = false;
-  int64_t cycle_starts = 0; // residuals b - A x formed: the first one and one per restart / breakdown
-  int64_t allreduces = 0;   // several ranks: the all-reduces of the iteration (3 per iteration, 1 per cycle start)
-};
-
-// The iteration of mfmg_hip_hierarchy_solve_fgmres on vectors in the numbering the hierarchy runs in (`b_run`, `x_run`), with
-// restart cycles of m columns, from the iteration count `it_start`: the state at the start of a cycle is x and the count alone, so
-// a solve that is taken up at a cycle start (the block driver hands over a column that broke down) goes on with the bits of the
-// solve that was never interrupted.  history[it] receives the residual of iteration it (it < history_len), history[it_start]
-// that of the cycle start.
-extern "C++" FgmresOutcome fgmres_run(mfmg_hip_hierarchy_t h, const double *b_run, double *x_run, double tolerance, int max_iterations,
-                                      int m, bool fp32, int it_start, double *residual_history, int history_len)
-{
-  HipHandle &handle = *h->handle;
-  const int64_t n = level_size(h, 0);
-  KrylovWorkspace &ws = h->krylov;
-  try
-  {
-    ws.reserve(n, m, fp32);
-  }
-  catch (...)
-  {
-    ws.release();
-    (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
-    throw;
-  }
-  const int64_t ld = ws.ld;
-  krylov::Scratch &scratch = *ws.scratch;
-  double *const V = ws.V.data(), *const Z = ws.Z.data(), *const hcol = ws.coefficients.data(), *const y_dev = hcol + ws.columns + 1;
-  double *const y_host = ws.host + ws.columns + 1;
-  float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
-  auto op = h->hierarchy->levels()[0].get_operator();
-  const bool distributed = handle.comm.enabled();
-  krylov::OwnedBox box;
-  if (distributed)
-  {
-    auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
-    const int space = hop ? hop->domain_space() : 0;
-    if (space <= 0 || !handle.comm.spaces[space].configured())
-      throw std::runtime_error("the fine operator of a distributed run has no halo space");
-    if (!handle.comm.transport)
-      throw std::runtime_error("no halo transport was registered with the context");
-    box = krylov::OwnedBox(handle.comm.spaces[space]);
-    if (box.n_local() != n)
-      throw std::runtime_error("internal: the fine halo space does not describe the fine vectors");
-  }
-  // `count` doubles at `dev` summed over the ranks: to the host (ws.host), one all-reduce, back to `dev`; the sums stay in ws.host
-  int64_t allreduces = 0;
-  auto allreduce = [&](double *dev, int count) {
-    MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
-    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-    handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
-    ++allreduces;
-    MFMG_HIP_CHECK(hipMemcpyAsync(dev, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
-  };
-  // ||w||^2 over the owned entries of all ranks from this rank's s.norm_partials: on the device (scratch.norm_squared) and returned
-  auto norm_squared_of_all = [&] {
-    krylov::basis_norm_finish(handle, scratch, box);
-    allreduce(scratch.norm_squared.data(), 1);
-    return ws.host[0];
-  };
-  DVector bv(handle, n, const_cast<double *>(b_run)), xv(handle, n, x_run);
-  auto fetch = [&](int count) { // the first `count` device coefficients: the one round trip of an iteration
-    MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, hcol, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
-    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-  };
-  // v_0 = r / ||r|| with r = b - A x (and its float copy); returns ||r||
-  auto start_cycle = [&] {
-    DVector r(handle, n, V);
-    op->apply(xv, r);
-    r.sadd(-1., 1., bv);
-    if (distributed)
-    {
-      krylov::basis_norm_partials(handle, scratch, box, V);
-      const double norm = std::sqrt(norm_squared_of_all());
-      krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), V, V, nullptr);
-      // (the whole local vector: what its ghost entries hold is exchanged over by the FP32 level where it reads them)
-      if (fp32)
-        vec::narrow(handle, n, V, v_f32);
-      return norm;
-    }
-    krylov::basis_norm_partials(handle, scratch, n, V);
-    krylov::basis_scale_store(handle, scratch, n, V, V, v_f32, hcol);
-    fetch(1);
-    return ws.host[0];
-  };
-  auto precondition = [&](int j) { // z_j = M^-1 v_j, from a zero start whatever "is preconditioner" says
-    const bool zero_first = !h->hierarchy->is_preconditioner();
-    if (fp32)
-    {
-      if (zero_first)
-        MFMG_HIP_CHECK(hipMemsetAsync(ws.z_f32.data(), 0, sizeof(float) * n, handle.stream));
-      h->fine_f32->apply(v_f32, ws.z_f32.data());
-      vec::widen(handle, n, ws.z_f32.data(), Z + j * ld);
-      return;
-    }
-    DVector vj(handle, n, V + j * ld), zj(handle, n, Z + j * ld);
-    if (zero_first)
-      zj = 0.;
-    h->hierarchy->vmult(zj, vj);
-  };
-  auto record = [&](int k, double v) {
-    if (residual_history && k < history_len)
-      residual_history[k] = v;
-  };
-  FgmresOutcome out;
-  double res = start_cycle();
-  ++out.cycle_starts;
-  int it = it_start;
-  record(it, res);
-  bool converged = res <= tolerance;
-  FgmresColumn col(m);
-  while (!converged && it < max_iterations)
-  {
-    col.begin_cycle(res);
-    while (col.k < m && it < max_iterations && !converged && !col.breakdown)
-    {
-      const int j = col.k;
-      precondition(j);
-      double *const w = V + (int64_t)(j + 1) * ld;
-      {
-        DVector zj(handle, n, Z + j * ld), wv(handle, n, w);
-        op->apply(zj, wv);
-      }
-      double *const c = col.column(j);
-      if (distributed)
-      {
-        // the column h_0 .. h_j, ||w|| is summed over the ranks on its way: no fetch
-        double *const pc = scratch.pass_coefficients.data();
-        for (int pass = 0; pass < 2; ++pass)
-        {
-          krylov::basis_dots(handle, scratch, box, ld, j + 1, V, w, pc, pc, false);
-          allreduce(pc, j + 1);
-          for (int i = 0; i <= j; ++i)
-            c[i] = pass == 0 ? ws.host[i] : c[i] + ws.host[i];
-          krylov::basis_update(handle, scratch, box, ld, j + 1, V, pc, w, pass == 1);
-        }
-        c[j + 1] = std::sqrt(norm_squared_of_all());
-        krylov::basis_scale_store(handle, box, scratch.norm_squared.data(), w, w, nullptr);
-        if (fp32)
-          vec::narrow(handle, n, w, v_f32);
-      }
-      else
-      {
-        for (int pass = 0; pass < 2; ++pass)
-        {
-          krylov::basis_dots(handle, scratch, n, ld, j + 1, V, w, scratch.pass_coefficients.data(), hcol, pass == 1);
-          krylov::basis_update(handle, scratch, n, ld, j + 1, V, scratch.pass_coefficients.data(), w, pass == 1);
-        }
-        krylov::basis_scale_store(handle, scratch, n, w, w, v_f32, hcol + j + 1);
-        fetch(j + 2);
-        std::copy(ws.host, ws.host + j + 2, c);
-      }
-      res = col.rotate();
-      ++it;
-      // a breakdown is not taken at its word (a singular Hessenberg matrix also gives |g_{j+1}| = 0): the cycle ends, and the
-      // residual recomputed below is what is recorded and tested
-      if (!col.breakdown)
-        record(it, res);
-      converged = !col.breakdown && res <= tolerance;
-    }
-    col.solve(y_host);
-    MFMG_HIP_CHECK(hipMemcpyAsync(y_dev, y_host, sizeof(double) * col.k, hipMemcpyHostToDevice, handle.stream));
-    MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (y_host is written again by the next cycle / the next solve)
-    krylov::basis_combine(handle, n, ld, col.k, Z, y_dev, x_run);
-    // after a restart and after a breakdown the residual is the true one, recomputed
-    if (!converged && (it < max_iterations || col.breakdown))
-    {
-      res = start_cycle();
-      ++out.cycle_starts;
-      converged = res <= tolerance;
-      if (col.breakdown)
-        record(it, res);
-    }
-  }
-  out.iterations = it;
-  out.residual = res;
-  out.converged = converged;
-  out.allreduces = allreduces;
-  return out;
-}
-} // namespace
 
 int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, double *x, double tolerance, int32_t max_iterations,
                                     int32_t restart, int32_t preconditioner_fp32, int32_t *n_iterations, double *final_residual,
@@ -2804,57 +2046,22 @@ int mfmg_hip_hierarchy_solve_fgmres(mfmg_hip_hierarchy_t h, const double *b, dou
     require(preconditioner_fp32 == 0 || preconditioner_fp32 == 1, "preconditioner_fp32 must be 0 or 1");
     const bool fp32 = preconditioner_fp32 != 0;
     require(!fp32 || h->fine_f32 != nullptr, "preconditioner_fp32 needs a hierarchy built with \"fine level precision\" float");
-    const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
-    // "internal numbering" lexicographic: as in mfmg_hip_hierarchy_solve_cg -- b and x are gathered once, the basis, the operator
-    // and the preconditioner live in the internal numbering, x is scattered once: two launches of the permutation per solve
-    double const *b_run = b;
-    double *x_run = x;
-    if (h->perm)
-    {
-      h->perm->gather2(b, static_cast<double const *>(x), h->workspace(0), h->workspace(1));
-      b_run = h->workspace(0);
-      x_run = h->workspace(1);
-    }
-    const FgmresOutcome out = fgmres_run(h, b_run, x_run, tolerance, max_iterations, m, fp32, 0, residual_history, history_len);
-    if (n_iterations)
-      *n_iterations = out.iterations;
-    if (final_residual)
-      *final_residual = out.residual;
-    if (h->perm)
-      h->perm->scatter(static_cast<double const *>(x_run), x);
-    if (!out.converged)
+    const KrylovResult result =
+      solve_fgmres(krylov_setting(h, true), b, x, tolerance, max_iterations, restart, fp32, residual_history, history_len);
+    deliver_result(result, n_iterations, final_residual, nullptr);
+    if (!result.all_converged())
       throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
   });
 }
 
-// mfmg_hip_hierarchy_solve_fgmres on a block of right-hand sides.  Every column owns a slot of the bases (block_krylov_basis.hpp);
-// all live columns share the iteration count and, inside a restart cycle, the basis length j.  Per iteration: the cycle and the
-// operator on every maximal run of consecutive live slots (Hierarchy::apply_block, Operator::apply_block), classical Gram-Schmidt
-// twice and scale_store with one launch each for all live slots, ONE device-to-host copy of their j + 2 coefficients and ONE
-// synchronisation, then the rotations per column on the host (FgmresColumn).  A column that converges inside a cycle gets its
-// x += Z y at once and leaves the live list; no basis vector is ever copied -- the slots left behind stay where they are until
-// the cycle ends, and the next cycle packs the surviving columns into the first slots by changing the slot -> column map alone
-// (block_krylov_basis::plan).  A column that breaks down ends its cycle by itself and would be out of step: it gets its update,
-// and fgmres_run finishes it from (x, it) -- all a cycle start knows.  Every kernel gives a slot the bits the one-vector driver
-// gives its vector, so x, the count, the final residual and the history of a column are those of mfmg_hip_hierarchy_solve_fgmres.
-// Several ranks (enabled per context with mfmg_hip_context_set_block_fgmres_on_ranks, on every rank alike; refused otherwise): the
-// blocks hold the ranks' local vectors.  The operator and the cycle exchange what they read (a group of columns
-// one message per neighbour where the ranks agreed on blocks); the Gram-Schmidt passes, the norms and scale_store run over the
-// owned entries of all live slots in one launch each (the OwnedBox overloads of block_krylov_basis.hpp), the combination over all
-// local entries.  The j + 1 coefficients of a pass of ALL live slots cross the ranks in ONE all-reduce, their ||w||^2 in one more:
-// three per iteration whatever k, plus one per cycle start.  The Hessenberg columns are on the host once summed: no fetch.  Every
-// control decision -- convergence, breakdown, retirement, restart, the end of the loop -- is taken from all-reduced values, so
-// every rank retires the same columns, hands the same column to fgmres_run (collective there) and leaves the loop in the same
-// iteration.  A column has the bits of the one-vector solve on the same ranks where the transport sums an element in the same
-// order whatever the length of the message (block_krylov.hpp).
+// (a communicator: only where the caller enabled the block solve on the context with
+// mfmg_hip_context_set_block_fgmres_on_ranks, on every rank alike; refused otherwise)
 int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x,
                                           const double *tolerances, int32_t max_iterations, int32_t restart, int32_t preconditioner_fp32,
                                           int32_t *n_iterations, double *final_residuals, double *residual_history, int32_t history_ld,
                                           int64_t *work)
 {
-  namespace bkb = block_krylov_basis;
   return guarded([&] {
-    // (a communicator: only where the caller enabled the block solve on the context, on every rank alike)
     check_block(h, 0, n_vectors, ld, b, x, h && h->handle->block_fgmres_on_ranks);
     require(tolerances != nullptr, "null argument");
     require(max_iterations >= 0, "bad stopping criterion");
@@ -2865,357 +2072,13 @@ int mfmg_hip_hierarchy_solve_fgmres_block(mfmg_hip_hierarchy_t h, int32_t n_vect
     require(residual_history == nullptr || history_ld >= 0, "bad history length");
     const bool fp32 = preconditioner_fp32 != 0;
     require(!fp32 || h->fine_f32 != nullptr, "preconditioner_fp32 needs a hierarchy built with \"fine level precision\" float");
-    HipHandle &handle = *h->handle;
-    const int k = n_vectors;
-    const int64_t n = level_size(h, 0);
-    const int m = std::max(1, std::min(restart, max_iterations)); // columns a restart cycle can reach
-    auto op = h->hierarchy->levels()[0].get_operator();
-    // several ranks: the passes over the owned entries, summed over the ranks (the preconditions of fgmres_run)
-    const bool distributed = handle.comm.enabled();
-    krylov::OwnedBox box;
-    if (distributed)
-    {
-      auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
-      const int space = hop ? hop->domain_space() : 0;
-      require(space > 0 && space < (int)handle.comm.spaces.size() && handle.comm.spaces[space].configured() && handle.comm.transport != nullptr,
-              "the fine operator has no distributed vector space or no transport was registered");
-      box = krylov::OwnedBox(handle.comm.spaces[space]);
-      require(box.n_local() == n, "the fine space does not describe the vectors of the fine level");
-    }
-    // "internal numbering" lexicographic: b and x are gathered once into library blocks and x is scattered once, as in
-    // mfmg_hip_hierarchy_solve_cg_block.  Otherwise the bases take the caller's leading dimension, so that the operator runs from
-    // the caller's x into the basis on one block layout.
-    const bool permute = (bool)h->perm;
-    const int64_t wld = permute ? n + (n & 1) : ld;
-    BlockFgmresWorkspace &ws = h->block_fgmres;
-    try
-    {
-      ws.reserve(wld, k, m, permute, fp32, handle.stream);
-    }
-    catch (...)
-    {
-      ws.release();
-      (void)hipGetLastError(); // (the failed allocation is reported by the exception, not by the next launch check)
-      throw;
-    }
-    double const *b_run = b;
-    double *x_run = x;
-    if (permute)
-    {
-      for (int c = 0; c < k; ++c)
-        h->perm->gather2(b + c * ld, static_cast<double const *>(x + c * ld), ws.B.data() + c * wld, ws.X.data() + c * wld);
-      b_run = ws.B.data();
-      x_run = ws.X.data();
-    }
-    bkb::Scratch &scratch = *ws.scratch;
-    const bkb::Basis V{n, wld, (int64_t)k * wld, ws.V.data()}, Z{n, wld, (int64_t)k * wld, ws.Z.data()};
-    const int64_t cstride = ws.columns + 1, ystride = ws.columns;
-    double *const coef = ws.coefficients.data();
-    float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
-    const bool zero_first = !h->hierarchy->is_preconditioner(); // the cycle then starts from what z holds: from zero, as in fgmres_run
-    const int64_t launches_before = block_kernel_launches(h);
-    int64_t preconditioner_columns = 0, operator_columns = 0, cycle_starts = 0, allreduces = 0;
-    const int64_t fp32_launches_before = fp32 ? h->fine_f32->block_launches() : 0;
-    int64_t fp32_columns_looped = 0;
-
-    std::vector<int32_t> live(k, 1), slot_col(k), run_start(k), run_width(k), run_groups(k), group_width(k), packed(k);
-    for (int s = 0; s < k; ++s)
-      slot_col[s] = s;
-    int n_live = k;
-    std::vector<double> res(k, 0.);
-    std::vector<int32_t> iterations(k, 0);
-    std::vector<char> converged(k, 0);
-    std::vector<FgmresColumn> columns(k, FgmresColumn(m));
-
-    auto record = [&](int c, int it, double v) {
-      if (residual_history && it < history_ld)
-        residual_history[(int64_t)c * history_ld + it] = v;
-    };
-    auto live_list = [&] {
-      bkb::SlotList l;
-      for (int s = 0; s < k; ++s)
-        if (live[s])
-        {
-          l.id[l.count] = s;
-          l.col[l.count++] = slot_col[s];
-        }
-      return l;
-    };
-    // the first `count` coefficients of every slot in `l`: the one round trip of an iteration.  One copy from the first to the
-    // last of the slots; the coefficients of slot s are then at fetched(l, s)
-    auto fetch = [&](bkb::SlotList const &l, int count) {
-      const int first = l.id[0], last = l.id[l.count - 1];
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, coef + first * cstride, sizeof(double) * ((last - first) * cstride + count), hipMemcpyDeviceToHost,
-                                    handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-    };
-    auto fetched = [&](bkb::SlotList const &l, int s) { return ws.host + (s - l.id[0]) * cstride; };
-    // several ranks: `count` doubles at `dev` summed over the ranks -- to the host (ws.host), ONE all-reduce, back to `dev`; the
-    // sums stay in ws.host (which holds slots x (2 columns + 1) doubles: the live slots' coefficients of a pass fit)
-    auto allreduce = [&](double *dev, int count) {
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream));
-      handle.comm.transport->allreduce(ws.host, count, 0, handle.stream);
-      ++allreduces;
-      MFMG_HIP_CHECK(hipMemcpyAsync(dev, ws.host, sizeof(double) * count, hipMemcpyHostToDevice, handle.stream));
-    };
-    // ||w_s||^2 over the owned entries of all ranks from this rank's norm partials, for the slots of `l` in the order of the list:
-    // on the device (scratch.norm_squared) and in ws.host
-    auto norms_squared_of_all = [&](bkb::SlotList const &l) {
-      bkb::norm_finish(handle, scratch, l, box);
-      allreduce(scratch.norm_squared.data(), l.count);
-    };
-    // the float copies of the vectors v_s at `v` as the one-vector driver makes them on ranks: the whole local vector (what its
-    // ghost entries hold is exchanged over by the FP32 level where it reads them)
-    auto narrow_live = [&](bkb::SlotList const &l, double const *v) {
-      if (fp32)
-        for (int i = 0; i < l.count; ++i)
-          vec::narrow(handle, n, v + l.id[i] * wld, v_f32 + l.id[i] * wld);
-    };
-    // `run(start, width)` for every maximal run of consecutive live slots (with `by_column`: whose columns follow each other too)
-    auto for_runs = [&](bool by_column, std::function<void(int, int)> const &run) {
-      int32_t n_groups = 0, n_packed = 0;
-      const int n_runs = bkb::plan(k, live.data(), slot_col.data(), run_start.data(), run_width.data(), run_groups.data(), group_width.data(),
-                                   &n_groups, packed.data(), &n_packed);
-      for (int r = 0; r < n_runs; ++r)
-      {
-        int s0 = run_start[r];
-        const int end = s0 + run_width[r];
-        for (int s = s0 + 1; s <= end; ++s)
-          if (s == end || (by_column && slot_col[s] != slot_col[s - 1] + 1))
-          {
-            run(s0, s - s0);
-            s0 = s;
-          }
-      }
-    };
-    // v_0 = r / ||r|| with r = b - A x for every live slot (and its float copy); res[column] = ||r||
-    auto start_cycle = [&] {
-      const bkb::SlotList l = live_list();
-      for_runs(true, [&](int s0, int width) {
-        BlockViews xv(handle, n, wld, width, x_run + slot_col[s0] * wld), rv(handle, n, wld, width, V.vector(0, s0));
-        op->apply_block(xv.cptr, rv.ptr);
-      });
-      for (int i = 0; i < l.count; ++i)
-        vec::sadd<double>(handle, n, -1., 1., b_run + l.col[i] * wld, V.vector(0, l.id[i]));
-      cycle_starts += l.count;
-      if (distributed)
-      {
-        bkb::norm_partials(handle, scratch, l, box, wld, V.vector(0));
-        norms_squared_of_all(l);
-        for (int i = 0; i < l.count; ++i)
-          res[l.col[i]] = std::sqrt(ws.host[i]);
-        bkb::scale_store(handle, l, box, wld, scratch.norm_squared.data(), V.vector(0), V.vector(0), nullptr, 0);
-        narrow_live(l, V.vector(0));
-        return;
-      }
-      bkb::norm_partials(handle, scratch, l, n, wld, V.vector(0));
-      bkb::scale_store(handle, scratch, l, n, wld, V.vector(0), V.vector(0), v_f32, coef, cstride);
-      fetch(l, 1);
-      for (int i = 0; i < l.count; ++i)
-        res[l.col[i]] = fetched(l, l.id[i])[0];
-    };
-    // z_j = M^-1 v_j on the live slots, from a zero start whatever "is preconditioner" says
-    auto precondition = [&](int j) {
-      if (fp32)
-      {
-        // the FP32 cycle on every run of live slots, on the float copies scale_store left
-        for_runs(false, [&](int s0, int width) {
-          float *const zf = ws.z_f32.data() + s0 * wld;
-          if (zero_first)
-            for (int c = 0; c < width; ++c)
-              MFMG_HIP_CHECK(hipMemsetAsync(zf + c * wld, 0, sizeof(float) * n, handle.stream));
-          h->fine_f32->apply_block(width, wld, v_f32 + s0 * wld, zf);
-          fp32_columns_looped += h->fine_f32->block_columns_looped();
-          for (int c = 0; c < width; ++c)
-            vec::widen(handle, n, zf + c * wld, Z.vector(j, s0 + c));
-        });
-        return;
-      }
-      for_runs(false, [&](int s0, int width) {
-        if (zero_first)
-          MFMG_HIP_CHECK(hipMemsetAsync(Z.vector(j, s0), 0, sizeof(double) * (size_t)wld * width, handle.stream));
-        BlockViews vv(handle, n, wld, width, V.vector(j, s0)), zv(handle, n, wld, width, Z.vector(j, s0));
-        timer_enter_subsection(h->timer, "Apply");
-        try
-        {
-          h->hierarchy->apply_block(vv.cptr, zv.ptr);
-        }
-        catch (...)
-        {
-          timer_leave_subsection(h->timer);
-          throw;
-        }
-        timer_leave_subsection(h->timer);
-      });
-    };
-    // x_col += Z y over the j columns of this cycle for the slots of `l`, each with its own y
-    auto combine = [&](bkb::SlotList const &l, int j) {
-      const int first = l.id[0], last = l.id[l.count - 1];
-      double *const y_host = ws.host_y();
-      for (int i = 0; i < l.count; ++i)
-        columns[l.col[i]].solve(y_host + l.id[i] * ystride);
-      MFMG_HIP_CHECK(hipMemcpyAsync(ws.y.data() + first * ystride, y_host + first * ystride, sizeof(double) * ((last - first) * ystride + j),
-                                    hipMemcpyHostToDevice, handle.stream));
-      MFMG_HIP_CHECK(hipStreamSynchronize(handle.stream)); // (the host copy of y is written again by the next retirement)
-      bkb::combine(handle, l, Z, j, ws.y.data(), ystride, x_run, wld);
-    };
-    auto retire_converged_at_start = [&] {
-      for (int s = 0; s < k; ++s)
-        if (live[s] && res[slot_col[s]] <= tolerances[slot_col[s]])
-        {
-          converged[slot_col[s]] = 1;
-          live[s] = 0;
-          --n_live;
-        }
-    };
-
-    start_cycle();
-    for (int c = 0; c < k; ++c)
-      record(c, 0, res[c]);
-    retire_converged_at_start();
-    int it = 0;
-    while (n_live > 0 && it < max_iterations)
-    {
-      for (int s = 0; s < k; ++s)
-        if (live[s])
-          columns[slot_col[s]].begin_cycle(res[slot_col[s]]);
-      int j = 0;
-      for (; j < m && it < max_iterations && n_live > 0; ++j)
-      {
-        const bkb::SlotList l = live_list();
-        precondition(j);
-        preconditioner_columns += l.count;
-        for_runs(false, [&](int s0, int width) {
-          BlockViews zv(handle, n, wld, width, Z.vector(j, s0)), wv(handle, n, wld, width, V.vector(j + 1, s0));
-          op->apply_block(zv.cptr, wv.ptr);
-        });
-        operator_columns += l.count;
-        double *const w = V.vector(j + 1);
-        if (distributed)
-        {
-          // the columns h_0 .. h_j, ||w|| of all live slots are summed over the ranks on their way: no fetch
-          for (int pass = 0; pass < 2; ++pass)
-          {
-            bkb::dots(handle, scratch, l, box, V, j + 1, w, nullptr, 0, false);
-            allreduce(scratch.pass_coefficients.data(), l.count * (j + 1));
-            for (int i = 0; i < l.count; ++i)
-            {
-              double *const c = columns[l.col[i]].column(j);
-              double const *const sum = ws.host + (size_t)i * (j + 1);
-              for (int q = 0; q <= j; ++q)
-                c[q] = pass == 0 ? sum[q] : c[q] + sum[q];
-            }
-            bkb::update(handle, scratch, l, box, V, j + 1, w, pass == 1);
-          }
-          norms_squared_of_all(l);
-          for (int i = 0; i < l.count; ++i)
-            columns[l.col[i]].column(j)[j + 1] = std::sqrt(ws.host[i]);
-          bkb::scale_store(handle, l, box, wld, scratch.norm_squared.data(), w, w, nullptr, 0);
-          narrow_live(l, w);
-        }
-        else
-        {
-          for (int pass = 0; pass < 2; ++pass)
-          {
-            bkb::dots(handle, scratch, l, V, j + 1, w, coef, cstride, pass == 1);
-            bkb::update(handle, scratch, l, V, j + 1, w, pass == 1);
-          }
-          bkb::scale_store(handle, scratch, l, n, wld, w, w, v_f32, coef + j + 1, cstride);
-          fetch(l, j + 2);
-        }
-        ++it;
-        bkb::SlotList leaving, broken;
-        for (int i = 0; i < l.count; ++i)
-        {
-          const int s = l.id[i], c = l.col[i];
-          FgmresColumn &col = columns[c];
-          if (!distributed)
-            std::copy(fetched(l, s), fetched(l, s) + j + 2, col.column(j));
-          const double r = col.rotate();
-          iterations[c] = it;
-          // a breakdown is not taken at its word: the column gets its update, and the residual fgmres_run recomputes is what is
-          // recorded and tested
-          if (!col.breakdown)
-          {
-            res[c] = r;
-            record(c, it, r);
-            converged[c] = r <= tolerances[c];
-          }
-          if (col.breakdown || converged[c])
-          {
-            leaving.id[leaving.count] = s;
-            leaving.col[leaving.count++] = c;
-            live[s] = 0;
-            --n_live;
-          }
-          if (col.breakdown)
-            broken.col[broken.count++] = c;
-        }
-        if (leaving.count > 0)
-          combine(leaving, j + 1);
-        for (int i = 0; i < broken.count; ++i)
-        {
-          // (the one-vector loop from this column's x and the shared count: the cycle start is the whole state)
-          const int c = broken.col[i];
-          const FgmresOutcome out = fgmres_run(h, b_run + c * wld, x_run + c * wld, tolerances[c], max_iterations, m, fp32, it,
-                                               residual_history ? residual_history + (int64_t)c * history_ld : nullptr, history_ld);
-          iterations[c] = out.iterations;
-          res[c] = out.residual;
-          converged[c] = out.converged;
-          cycle_starts += out.cycle_starts;
-          allreduces += out.allreduces;
-          preconditioner_columns += out.iterations - it;
-          operator_columns += out.iterations - it;
-        }
-      }
-      if (n_live > 0)
-        combine(live_list(), j);
-      if (n_live == 0 || it >= max_iterations)
-        break;
-      // restart: the survivors move to the first slots (the map alone changes), the residual is the true one, recomputed
-      {
-        int32_t n_groups = 0, n_packed = 0;
-        bkb::plan(k, live.data(), slot_col.data(), run_start.data(), run_width.data(), run_groups.data(), group_width.data(), &n_groups,
-                  packed.data(), &n_packed);
-        for (int s = 0; s < k; ++s)
-        {
-          live[s] = s < n_packed;
-          if (s < n_packed)
-            slot_col[s] = packed[s];
-        }
-      }
-      start_cycle();
-      retire_converged_at_start();
-    }
-    bool all = true;
-    for (int c = 0; c < k; ++c)
-    {
-      if (n_iterations)
-        n_iterations[c] = iterations[c];
-      if (final_residuals)
-        final_residuals[c] = res[c];
-      all = all && converged[c];
-    }
-    if (permute)
-      for (int c = 0; c < k; ++c)
-        h->perm->scatter(static_cast<double const *>(x_run + c * wld), x + c * ld);
-    if (work)
-    {
-      work[0] = preconditioner_columns;
-      work[1] = operator_columns;
-      work[2] = block_kernel_launches(h) - launches_before;
-      work[3] = cycle_starts;
-    }
-    h->block_solve_allreduces = allreduces; // (mfmg_hip_hierarchy_block_solve_allreduces)
-    if (fp32)
-    {
-      // (mfmg_hip_hierarchy_block_info_f32: the preconditioner applications of this solve)
-      h->block_info_f32[0] = h->fine_f32->block_width();
-      h->block_info_f32[1] = h->fine_f32->block_launches() - fp32_launches_before;
-      h->block_info_f32[2] = fp32_columns_looped;
-    }
-    if (!all)
+    const KrylovResult result = solve_fgmres_block(krylov_setting(h, false), n_vectors, ld, b, x, tolerances, max_iterations, restart, fp32,
+                                                   residual_history, history_ld);
+    deliver_result(result, n_iterations, final_residuals, work);
+    h->block_solve_allreduces = result.allreduces; // (mfmg_hip_hierarchy_block_solve_allreduces)
+    if (fp32) // (mfmg_hip_hierarchy_block_info_f32: the preconditioner applications of this solve)
+      std::copy(result.block_info_f32, result.block_info_f32 + MFMG_HIP_BLOCK_INFO_FIELDS, h->block_info_f32);
+    if (!result.all_converged())
       throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations on every column of the block (SolverControl::NoConvergence)");
   });
 }

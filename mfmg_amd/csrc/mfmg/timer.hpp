@@ -141,4 +141,20 @@ inline void timer_leave_subsection(std::shared_ptr<TimerOutput> timer)
   if (roctx_api().pop)
     roctx_api().pop();
 }
+
+// a subsection that is left when the scope is, by an exception too
+class TimerSubsection
+{
+public:
+  TimerSubsection(std::shared_ptr<TimerOutput> timer, std::string const &section) : _timer(std::move(timer))
+  {
+    timer_enter_subsection(_timer, section);
+  }
+  TimerSubsection(TimerSubsection const &) = delete;
+  TimerSubsection &operator=(TimerSubsection const &) = delete;
+  ~TimerSubsection() { timer_leave_subsection(_timer); }
+
+private:
+  std::shared_ptr<TimerOutput> _timer;
+};
 } // namespace mfmg
