@@ -761,7 +761,8 @@ int mfmg_hip_host_params_get(const char *params_info, const char *path, char *va
  * _vmult_block the same with the argument order of _vmult; _smoother_apply_block that of _smoother_apply.  Where the fine level
  * has the block kernel the block is taken in the groups of mfmg_hip_block_groups and pre-smoothing, residual and post-smoothing
  * run as launches on the group; the restriction of the group's residuals and the prolongation of its corrections are one launch
- * each where the restrictor has block transfers (below), and the coarse cycle runs column by column.  Elsewhere the one-vector
+ * each where the restrictor has block transfers (below), and the coarse cycle runs on the group where the coarse solver has a
+ * block width above 1 (mfmg_hip_hierarchy_coarse_block_info below), column by column otherwise.  Elsewhere the one-vector
  * entry point runs per column.  With "internal numbering" lexicographic the columns are gathered into and scattered out of the
  * library's block workspace (one group wide).
  * mfmg_hip_hierarchy_block_info: fields[0] width of the widest group the fine level runs as one launch (1 = the loop over the
@@ -772,6 +773,30 @@ int mfmg_hip_hierarchy_apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, in
 int mfmg_hip_hierarchy_vmult_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, double *x, const double *b);
 int mfmg_hip_hierarchy_smoother_apply_block(mfmg_hip_hierarchy_t h, int32_t level, int32_t n_vectors, int64_t ld, const double *b, double *x);
 int mfmg_hip_hierarchy_block_info(mfmg_hip_hierarchy_t h, int64_t *fields);
+
+/* ---- stored-value SpMV and the coarse cycle on a block of vectors (additions, no change of the ABI version) ----
+ * mfmg_hip_csr_launch_block: mfmg_hip_csr_launch on the n_vectors columns of blocks -- column c of x at x + c ld_x, of b, x_prev
+ * and out at c ld_out (the matrix may be rectangular); dinv is ONE vector shared by the columns.  Every column gets the bits of
+ * mfmg_hip_csr_launch on that column.  The block is cut by mfmg_hip_block_groups; where mfmg_hip_csr_block_info reports the width
+ * 4 a group of 4 or 2 columns is one launch that reads the stored values once (profiler name csr_block_kernel): a matrix whose
+ * launch is exactly one kernel over values that do not repeat -- mfmg_hip_csr_form kind 2 or 3 with field 8 (regular) 0, or kind
+ * 4.  Elsewhere (tables, node classes, twins, listed rows, the CSR kernels, a released matrix), and for a single column, the
+ * one-vector kernels run column by column.  MFMG_HIP_ERROR_INVALID_ARGUMENT: n_vectors outside 1..64, a leading dimension below
+ * the vector size or odd, a base not aligned to 16 bytes, out overlapping x, a null operand the mode reads.
+ * mfmg_hip_csr_block_info: fields[0] the width (4 or 1), fields[1] launches of the block kernels and fields[2] columns that went
+ * through the one-vector kernels, of all mfmg_hip_csr_launch_block calls on the matrix so far.
+ * mfmg_hip_hierarchy_coarse_apply_block: mfmg_hip_hierarchy_coarse_apply on every column of the blocks b and x (one leading
+ * dimension; layout and checks of the block entry points above), bit for bit.  With solver.type amg the cycle of the aggregation
+ * hierarchy runs on groups of 4 and 2 columns, every matrix that has the block kernels read once per group; the loop over the
+ * columns with solver.amg.n_cycles > 1, a gathered level, a communicator, and for the other solver types.
+ * mfmg_hip_hierarchy_coarse_block_info: fields[0] the widest group any matrix of the coarse cycle takes (1: the loop), and for
+ * the last block call of the coarse solver (the one above, or inside mfmg_hip_hierarchy_apply_block / _vmult_block / a block
+ * solve) fields[1] launches of the block kernels, fields[2] one-vector launches of the matrices of the cycle. */
+int mfmg_hip_csr_launch_block(mfmg_hip_csr_t a, int mode, int32_t n_vectors, int64_t ld_x, const double *x, int64_t ld_out, const double *b,
+                              const double *dinv, const double *x_prev, double alpha, double beta, double *out);
+int mfmg_hip_csr_block_info(mfmg_hip_csr_t a, int64_t fields[3]);
+int mfmg_hip_hierarchy_coarse_apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x);
+int mfmg_hip_hierarchy_coarse_block_info(mfmg_hip_hierarchy_t h, int64_t fields[3]);
 
 /* ---- restriction and prolongation on a block of vectors (additions, no change of the ABI version) ----
  * mfmg_hip_hierarchy_restrictor_apply_block: mfmg_hip_hierarchy_restrictor_apply(level, in[c], out[c], mode) for every column,

@@ -594,6 +594,28 @@ class SparseMatrixDevice:
         check(self._lib.mfmg_hip_csr_launch(self.handle, mode, _dev_ptr(x, n), opt(b), opt(dinv), opt(x_prev), alpha,
                                             beta, _dev_ptr(out, m)))
 
+    def launch_block(self, mode: int, X, out, B=None, dinv=None, X_prev=None, alpha: float = 0.0, beta: float = 0.0):
+        """launch() on every row of the blocks X and out (2-D float64 tensors of shape (k, m), stride(1) == 1; each leading
+        dimension stride(0) even and at least the size of its vectors, the bases aligned to 16 bytes): row c of out gets the
+        bits of launch(mode, X[c], out[c], B[c], dinv, X_prev[c], ...).  B and X_prev share the leading dimension of out; dinv
+        is one vector.  Where block_info()["width"] is 4 the stored values are read once per group of 4 or 2 rows."""
+        m, n = self.shape
+        k, ld_x, px = _block_ptr(X)
+        ko, ld_out, po = _block_ptr(out)
+        if ko != k:
+            raise ValueError("the blocks of one call share the number of vectors")
+        opt = lambda t: _same_block(k, ld_out, t) if t is not None else None
+        check(self._lib.mfmg_hip_csr_launch_block(self.handle, mode, k, ld_x, px, ld_out, opt(B),
+                                                  _dev_ptr(dinv, m) if dinv is not None else None, opt(X_prev), alpha, beta, po))
+
+    def block_info(self) -> dict:
+        """width: rows of the widest group launch_block runs as one launch (4: stored values that do not repeat; 1: the loop
+        over the rows); block_launches / column_launches: launches of the block kernels, and rows that went through the
+        one-vector kernels, of all launch_block calls on this matrix so far."""
+        f = (C.c_int64 * 3)()
+        check(self._lib.mfmg_hip_csr_block_info(self.handle, f))
+        return {"width": int(f[0]), "block_launches": int(f[1]), "column_launches": int(f[2])}
+
     _FORM_FIELDS = ("kind", "csr_kernel", "lanes", "c", "stored_d", "full_d", "symmetric_half", "float_planes", "regular",
                     "all_in_classes", "classes", "class_slots", "listed", "listed_route", "regular_kernel", "class_kernel",
                     "stored_kernel", "row_base_slots", "node_class_c", "node_class_d", "pairs", "csr_released",
@@ -1089,6 +1111,21 @@ class Hierarchy:
     def coarse_apply(self, b, x):
         n = self.level_size(self.n_levels - 1)
         check(self._lib.mfmg_hip_hierarchy_coarse_apply(self.handle, _dev_ptr(b, n), _dev_ptr(x, n)))
+
+    def coarse_apply_block(self, B: torch.Tensor, X: torch.Tensor):
+        """coarse_apply() on every row of the blocks B and X (shape (k, m), layout as for apply_block), bit for bit.  With
+        solver.type amg the cycle runs on groups of 4 and 2 rows, every matrix with stored values that do not repeat read once
+        per group (coarse_block_info())."""
+        k, ld, pb = _block_ptr(B)
+        check(self._lib.mfmg_hip_hierarchy_coarse_apply_block(self.handle, k, ld, pb, _same_block(k, ld, X)))
+
+    def coarse_block_info(self) -> dict:
+        """width: the widest group any matrix of the coarse cycle takes (1: the loop over the rows); block_launches /
+        column_launches: launches of the block kernels and one-vector launches of the matrices of the cycle in the last block
+        call of the coarse solver (coarse_apply_block, or inside apply_block / vmult_block / a block solve)."""
+        f = (C.c_int64 * 3)()
+        check(self._lib.mfmg_hip_hierarchy_coarse_block_info(self.handle, f))
+        return {"width": int(f[0]), "block_launches": int(f[1]), "column_launches": int(f[2])}
 
     def set_restrictor(self, matrix):
         rp, cl, vl, shape = _csr_arrays(matrix)

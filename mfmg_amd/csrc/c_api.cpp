@@ -1085,6 +1085,43 @@ int mfmg_hip_csr_launch(mfmg_hip_csr_t a, int mode, const double *x, const doubl
   });
 }
 
+int mfmg_hip_csr_launch_block(mfmg_hip_csr_t a, int mode, int32_t n_vectors, int64_t ld_x, const double *x, int64_t ld_out, const double *b,
+                              const double *dinv, const double *x_prev, double alpha, double beta, double *out)
+{
+  return guarded([&] {
+    require(a && x && out, "null argument");
+    require(mode >= MFMG_HIP_CSR_APPLY && mode <= MFMG_HIP_CSR_PLUS_SCALED, "unknown SpMV mode");
+    auto m = a->op->get_matrix();
+    // (the rules of the other block entry points, and the operands apply_mode asks for, refused as invalid arguments)
+    require(n_vectors >= 1 && n_vectors <= MFMG_HIP_BLOCK_MAX_VECTORS, "a block holds 1 to 64 vectors");
+    require(ld_x >= m->n() && ld_out >= m->m(), "the leading dimension of a block must be at least the vector size");
+    require(ld_x % 2 == 0 && ld_out % 2 == 0, "the leading dimension of a block must be even (columns aligned to 16 bytes)");
+    const bool smoother = mode == MFMG_HIP_CSR_FIRST || mode == MFMG_HIP_CSR_NEXT;
+    const bool need_b = smoother || mode == MFMG_HIP_CSR_RESIDUAL || mode == MFMG_HIP_CSR_PLUS_SCALED,
+               need_dinv = smoother || mode == MFMG_HIP_CSR_PLUS_SCALED, need_prev = mode == MFMG_HIP_CSR_NEXT;
+    require(!need_b || b, "this SpMV mode needs b");
+    require(!need_dinv || dinv, "this SpMV mode needs the inverse diagonal");
+    require(!need_prev || x_prev, "this SpMV mode needs x_prev");
+    require(!smoother || m->m() == m->n(), "the smoother needs a square matrix");
+    auto aligned = [](const double *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    require(aligned(x) && aligned(out) && (!need_b || aligned(b)) && (!need_dinv || aligned(dinv)) && (!need_prev || aligned(x_prev)),
+            "the base of a block must be aligned to 16 bytes");
+    const double *x_end = x + (size_t)(n_vectors - 1) * ld_x + m->n(), *out_end = out + (size_t)(n_vectors - 1) * ld_out + m->m();
+    require(x_end <= out || out_end <= x, "the blocks x and out overlap");
+    m->apply_mode_block(static_cast<CsrMode>(mode), n_vectors, x, ld_x, b, dinv, x_prev, alpha, beta, out, ld_out);
+  });
+}
+
+int mfmg_hip_csr_block_info(mfmg_hip_csr_t a, int64_t fields[3])
+{
+  return guarded([&] {
+    require(a && fields, "null argument");
+    auto m = a->op->get_matrix();
+    fields[0] = m->block_width();
+    m->block_counters(fields[1], fields[2]);
+  });
+}
+
 int mfmg_hip_csr_form(mfmg_hip_csr_t a, int64_t *fields, int32_t n)
 {
   return guarded([&] {
@@ -1667,6 +1704,9 @@ void begin_block_call(mfmg_hip_hierarchy_t h)
   h->transfer_snapshot.resize(h->hierarchy->levels().size());
   for (size_t level = 0; level < h->transfer_snapshot.size(); ++level)
     transfer_counters(h, (int)level, h->transfer_snapshot[level].data());
+  // ... and mfmg_hip_hierarchy_coarse_block_info what the coarse solver's block calls launched since
+  if (auto hs = std::dynamic_pointer_cast<HipSolver const>(h->hierarchy->levels().back().get_solver()))
+    hs->reset_block_counters();
 }
 
 void check_block(mfmg_hip_hierarchy_t h, int level, int32_t n_vectors, int64_t ld, const double *b, const double *x, bool on_ranks = true)
@@ -2681,6 +2721,40 @@ int mfmg_hip_hierarchy_coarse_apply(mfmg_hip_hierarchy_t h, const double *b, dou
     const int64_t n = level_size(h, last);
     DVector bv(*h->handle, n, const_cast<double *>(b)), xv(*h->handle, n, x);
     h->hierarchy->levels()[last].get_solver()->apply(bv, xv);
+  });
+}
+
+int mfmg_hip_hierarchy_coarse_apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x)
+{
+  return guarded([&] {
+    require(h != nullptr, "null argument");
+    const int last = (int)h->hierarchy->levels().size() - 1;
+    begin_block_call(h);
+    check_block_shape(h, last, n_vectors, ld, b, x);
+    const int64_t n = level_size(h, last);
+    std::vector<std::unique_ptr<DVector>> views;
+    std::vector<DVector const *> bp;
+    std::vector<DVector *> xp;
+    for (int32_t c = 0; c < n_vectors; ++c)
+    {
+      views.emplace_back(new DVector(*h->handle, n, const_cast<double *>(b) + (int64_t)c * ld));
+      bp.push_back(views.back().get());
+      views.emplace_back(new DVector(*h->handle, n, x + (int64_t)c * ld));
+      xp.push_back(views.back().get());
+    }
+    h->hierarchy->levels()[last].get_solver()->apply_block(bp, xp);
+  });
+}
+
+int mfmg_hip_hierarchy_coarse_block_info(mfmg_hip_hierarchy_t h, int64_t fields[3])
+{
+  return guarded([&] {
+    require(h && fields, "null argument");
+    auto solver = h->hierarchy->levels().back().get_solver();
+    fields[0] = solver->block_width();
+    fields[1] = fields[2] = 0;
+    if (auto hs = std::dynamic_pointer_cast<HipSolver const>(solver))
+      hs->block_counters(fields[1], fields[2]);
   });
 }
 

@@ -891,14 +891,81 @@ void HipMatrixOperator::transfer_block(std::vector<DVector const *> const &x, st
 
 void HipMatrixOperator::apply_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y) const
 {
-  transfer_block(x, y, Transfer::restrict_to_coarse);
+  if (_structured)
+    return transfer_block(x, y, Transfer::restrict_to_coarse);
+  ASSERT_THROW(x.size() == y.size() && !x.empty(), "a block needs as many results as vectors");
+  if (!matrix_block(CsrMode::apply, x, nullptr, nullptr, nullptr, 0., 0., y))
+    Operator<DVector>::apply_block(x, y);
 }
 
 void HipMatrixOperator::apply_subtract_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y, OperatorMode mode) const
 {
   if (mode == OperatorMode::NO_TRANS)
-    return Operator<DVector>::apply_subtract_block(x, y, mode);
+  {
+    if (!matrix_block(CsrMode::subtract, x, nullptr, nullptr, nullptr, 0., 0., y))
+      Operator<DVector>::apply_subtract_block(x, y, mode);
+    return;
+  }
   transfer_block(x, y, Transfer::prolongate_subtract);
+}
+
+// ---- blocks of vectors through a plain matrix operator ----
+int HipMatrixOperator::block_width() const
+{
+  if (_structured || _matrix->handle().comm.enabled() || _reverse_range_space > 0)
+    return 1;
+  return _matrix->block_width();
+}
+
+bool HipMatrixOperator::matrix_block(CsrMode mode, std::vector<DVector const *> const &x, std::vector<DVector const *> const *b,
+                                     double const *dinv, std::vector<DVector const *> const *x_prev, double alpha, double beta,
+                                     std::vector<DVector *> const &out) const
+{
+  const size_t k = x.size();
+  if (block_width() == 1 || k <= 1 || k > (size_t)kMfBlockMaxVectors || out.size() != k || (b && b->size() != k) ||
+      (x_prev && x_prev->size() != k))
+    return false;
+  const int64_t ld_x = block_leading_dimension(x), ld_out = block_leading_dimension(as_const(out));
+  if (ld_x == 0 || ld_out == 0 || !block_kernel_layout(x, ld_x) || !block_kernel_layout(as_const(out), ld_out) ||
+      (b && !block_kernel_layout(*b, ld_out)) || (x_prev && !block_kernel_layout(*x_prev, ld_out)) ||
+      (dinv && reinterpret_cast<uintptr_t>(dinv) % 16 != 0))
+    return false;
+  if (x[0]->size() != _matrix->n() || out[0]->size() != _matrix->m() || (b && (*b)[0]->size() != _matrix->m()) ||
+      (x_prev && (*x_prev)[0]->size() != _matrix->m()))
+    return false;
+  // (the kernels read x while they write out: blocks that overlap go column by column, where only equal vectors are refused)
+  double const *xb = x[0]->get_values(), *ob = out[0]->get_values();
+  if (!(xb + (int64_t)(k - 1) * ld_x + _matrix->n() <= ob || ob + (int64_t)(k - 1) * ld_out + _matrix->m() <= xb))
+    return false;
+  _matrix->apply_mode_block(mode, (int)k, xb, ld_x, b ? (*b)[0]->get_values() : nullptr, dinv, x_prev ? (*x_prev)[0]->get_values() : nullptr,
+                            alpha, beta, out[0]->get_values(), ld_out);
+  return true;
+}
+
+void HipMatrixOperator::residual_block(std::vector<DVector const *> const &x, std::vector<DVector const *> const &b,
+                                       std::vector<DVector *> const &res) const
+{
+  if (!matrix_block(CsrMode::residual, x, &b, nullptr, nullptr, 0., 0., res))
+    Operator<DVector>::residual_block(x, b, res);
+}
+
+void HipMatrixOperator::smoother_step_block(int w, int64_t ld, double const *b, double const *x, double const *x_prev, double alpha,
+                                            double beta, double *out) const
+{
+  ASSERT_THROW(block_width() > 1, "internal: a smoother term on a block of a matrix without the block kernels");
+  // (SparseMatrixDevice::smoother_step: a term without momentum is a `first` term, which reads no x_prev)
+  const bool first = x_prev == nullptr || alpha == 0.;
+  _matrix->apply_mode_block(first ? CsrMode::first : CsrMode::next, w, x, ld, b, get_diagonal_inverse(), first ? nullptr : x_prev,
+                            first ? 0. : alpha, beta, out, ld);
+}
+
+void HipMatrixOperator::apply_plus_scaled_block(std::vector<DVector const *> const &x, double const *dinv, std::vector<DVector const *> const &b,
+                                                double beta, std::vector<DVector *> const &y) const
+{
+  if (matrix_block(CsrMode::plus_scaled, x, &b, dinv, nullptr, 0., beta, y))
+    return;
+  for (size_t c = 0; c < x.size(); ++c)
+    apply_plus_scaled(*x[c], dinv, *b[c], beta, *y[c]);
 }
 
 std::vector<std::shared_ptr<DVector>> HipMatrixOperator::build_domain_block(int width, int64_t ld) const
@@ -1387,59 +1454,112 @@ int HipSmoother::block_width() const
 {
   // (a schedule with a multi-term sweep belongs to the cell-constant layout, which has no block kernel)
   auto mf = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator);
-  return (mf && _schedule.in_place == 0) ? mf->block_width() : 1;
+  if (mf)
+    return _schedule.in_place == 0 ? mf->block_width() : 1;
+  // (a matrix operator has no sweep: its polynomial goes term by term in either direction)
+  auto mo = std::dynamic_pointer_cast<HipMatrixOperator const>(_hip_operator);
+  return (mo && _schedule.in_place == 0 && _schedule.out_of_place == 0) ? mo->block_width() : 1;
+}
+
+int64_t HipSmoother::group_layout(std::vector<DVector const *> const &b, std::vector<DVector const *> const &x_in,
+                                  std::vector<DVector const *> const &x_out) const
+{
+  const int64_t ld = block_leading_dimension(x_out);
+  if (block_width() == 1 || x_out.size() == 1 || x_out.size() > (size_t)kMfBlockMaxVectors || ld == 0 || !block_kernel_layout(x_out, ld) ||
+      !block_kernel_layout(b, ld) || !block_kernel_layout(x_in, ld))
+    return 0;
+  return ld;
+}
+
+void HipSmoother::run_group(int w, int64_t ld, int64_t n, double const *b, double const *x_in, double *x_out) const
+{
+  auto mf = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator);
+  auto mo = std::dynamic_pointer_cast<HipMatrixOperator const>(_hip_operator);
+  HipHandle &handle = _hip_operator->get_hip_handle();
+  for (auto &s : _block_scratch)
+    if (s.size() < (size_t)w * ld)
+    {
+      MemoryKind kind("smoother: block scratch vectors (one group of right-hand sides)");
+      s.resize((size_t)w * ld);
+      vec::set<double>(handle, (int64_t)w * ld, 0., s.data());
+    }
+  struct Block
+  {
+    double *p;
+  };
+  Block xi{const_cast<double *>(x_in)}, xo{x_out}, sa{_block_scratch[0].data()}, sb{_block_scratch[1].data()};
+  auto step = [&](Block const *cur, Block const *prev, double alpha, double beta, Block *out) {
+    double const *xp = prev ? prev->p : nullptr;
+    if (mf)
+      mf->apply_mode_block(mf_smoother_mode(xp, alpha), {cur->p, b, xp, out->p, ld, w, alpha, beta});
+    else
+      mo->smoother_step_block(w, ld, b, cur->p, xp, alpha, beta, out->p);
+  };
+  if (_coefficients.size() == 1 && x_in == x_out)
+  {
+    step(&xi, nullptr, 0., _coefficients[0].second, &sa);
+    for (int c = 0; c < w; ++c)
+      vec::copy<double>(handle, n, sa.p + (int64_t)c * ld, xo.p + (int64_t)c * ld);
+    return;
+  }
+  run_polynomial<double>(
+      _coefficients, 0, static_cast<Block const *>(&xi), &xo, [&](int i) { return i == 0 ? &sa : &sb; }, step,
+      [&](int, double const *, double const *, Block const *, Block *, Block *) { ASSERT_THROW(false, "internal: no sweep on a block"); });
 }
 
 void HipSmoother::apply_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const
 {
   ASSERT_THROW(b.size() == x.size() && !x.empty(), "a block needs as many right-hand sides as iterates");
-  auto mf = std::dynamic_pointer_cast<HipMatrixFreeOperator const>(_hip_operator);
-  const int64_t ld = block_leading_dimension(as_const(x));
-  if (block_width() == 1 || x.size() == 1 || x.size() > (size_t)kMfBlockMaxVectors || ld == 0 || !block_kernel_layout(as_const(x), ld) ||
-      !block_kernel_layout(b, ld))
+  const int64_t ld = group_layout(b, as_const(x), as_const(x));
+  if (ld == 0)
     return Smoother<DVector>::apply_block(b, x);
   // groups of the block: every group runs the polynomial of apply(), its terms as launches on the group
   int widths[kMfBlockMaxGroups];
   const int n_groups = mf_block_groups((int)x.size(), widths);
-  HipHandle &handle = _hip_operator->get_hip_handle();
-  const int64_t n = x[0]->size();
   size_t c0 = 0;
   for (int g = 0; g < n_groups; c0 += widths[g], ++g)
   {
-    const int w = widths[g];
-    if (w == 1)
-    {
+    if (widths[g] == 1)
       apply(*b[c0], *x[c0]);
-      continue;
-    }
-    for (auto &s : _block_scratch)
-      if (s.size() < (size_t)w * ld)
-      {
-        MemoryKind kind("smoother: block scratch vectors (one group of right-hand sides)");
-        s.resize((size_t)w * ld);
-        vec::set<double>(handle, (int64_t)w * ld, 0., s.data());
-      }
-    struct Block
-    {
-      double *p;
-    };
-    Block xb{x[c0]->get_values()}, sa{_block_scratch[0].data()}, sb{_block_scratch[1].data()};
-    double const *bp = b[c0]->get_values();
-    auto step = [&](Block const *cur, Block const *prev, double alpha, double beta, Block *out) {
-      double const *xp = prev ? prev->p : nullptr;
-      mf->apply_mode_block(mf_smoother_mode(xp, alpha), {cur->p, bp, xp, out->p, ld, w, alpha, beta});
-    };
-    if (_coefficients.size() == 1)
-    {
-      step(&xb, nullptr, 0., _coefficients[0].second, &sa);
-      for (int c = 0; c < w; ++c)
-        vec::copy<double>(handle, n, sa.p + (int64_t)c * ld, xb.p + (int64_t)c * ld);
-      continue;
-    }
-    run_polynomial<double>(
-        _coefficients, 0, static_cast<Block const *>(&xb), &xb, [&](int i) { return i == 0 ? &sa : &sb; }, step,
-        [&](int, double const *, double const *, Block const *, Block *, Block *) { ASSERT_THROW(false, "internal: no sweep on a block"); });
+    else
+      run_group(widths[g], ld, x[0]->size(), b[c0]->get_values(), x[c0]->get_values(), x[c0]->get_values());
   }
+}
+
+void HipSmoother::apply_to_block(std::vector<DVector const *> const &b, std::vector<DVector const *> const &x_in,
+                                 std::vector<DVector *> const &x_out) const
+{
+  ASSERT_THROW(b.size() == x_out.size() && x_in.size() == x_out.size() && !x_out.empty(), "a block needs as many right-hand sides as iterates");
+  const int64_t ld = group_layout(b, x_in, as_const(x_out));
+  int widths[kMfBlockMaxGroups];
+  const int n_groups = mf_block_groups((int)x_out.size(), widths);
+  size_t c0 = 0;
+  for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+  {
+    if (ld == 0 || widths[g] == 1)
+      for (size_t c = c0; c < c0 + (size_t)widths[g]; ++c)
+        apply_to(*b[c], *x_in[c], *x_out[c]);
+    else
+    {
+      ASSERT_THROW(x_in[c0]->get_values() != x_out[c0]->get_values(), "apply_to needs two vectors");
+      run_group(widths[g], ld, x_out[0]->size(), b[c0]->get_values(), x_in[c0]->get_values(), x_out[c0]->get_values());
+    }
+  }
+}
+
+void HipSmoother::apply_zero_guess_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const
+{
+  ASSERT_THROW(b.size() == x.size() && !x.empty(), "a block needs as many right-hand sides as iterates");
+  // (apply_zero_guess: one term needs no operator application, x_1 = beta_0 D^-1 b per column; more terms run apply() from x = 0)
+  if (_coefficients.size() == 1)
+  {
+    for (size_t c = 0; c < x.size(); ++c)
+      apply_zero_guess(*b[c], *x[c]);
+    return;
+  }
+  for (auto *xc : x)
+    *xc = 0.;
+  apply_block(b, x);
 }
 
 void HipSmoother::apply_zero_guess(DVector const &b, DVector &x) const
@@ -2109,6 +2229,150 @@ void HipSolver::amg_cycle(size_t level, DVector const &b, DVector &x) const
     amg_cycle(level + 1, *L.b_coarse, *L.x_coarse);
   L.prolongator->apply_subtract(*L.x_coarse, *L.x_work, OperatorMode::NO_TRANS);
   L.smoother->apply_to(b, *L.x_work, x);
+}
+
+// ---- the V-cycle on a block of vectors ----
+namespace
+{
+// `width` vectors of n entries as the columns of one zeroed block at the distance ld
+std::vector<std::shared_ptr<DVector>> build_block(HipHandle &handle, int64_t n, int width, int64_t ld)
+{
+  auto storage = std::make_shared<DeviceBuffer<double>>((size_t)width * ld); // (hipMalloc: aligned to 256 bytes)
+  vec::set<double>(handle, (int64_t)width * ld, 0., storage->data());
+  std::vector<std::shared_ptr<DVector>> columns;
+  for (int c = 0; c < width; ++c)
+    columns.emplace_back(new DVector(handle, n, storage->data() + (int64_t)c * ld), [storage](DVector *v) { delete v; });
+  return columns;
+}
+template <typename V>
+std::vector<V *> first_columns(std::vector<std::shared_ptr<DVector>> const &block, size_t w)
+{
+  std::vector<V *> columns;
+  for (size_t c = 0; c < w; ++c)
+    columns.push_back(block[c].get());
+  return columns;
+}
+} // namespace
+
+bool HipSolver::block_cycle_available() const
+{
+  return _solver == "amg" && _amg_cycles <= 1 && _amg_gather_level < 0 && !_handle.comm.enabled() && !_amg.empty();
+}
+
+int HipSolver::block_width() const
+{
+  if (!block_cycle_available())
+    return 1;
+  int width = 1;
+  for (auto const &L : _amg)
+    for (auto const &op : {L.a, L.restrictor, L.prolongator, L.smoothed_prolongator})
+      if (op)
+        width = std::max(width, op->block_width());
+  return width;
+}
+
+void HipSolver::matrix_launch_counters(int64_t &block_launches, int64_t &vector_launches) const
+{
+  block_launches = vector_launches = 0;
+  auto count = [&](std::shared_ptr<SparseMatrixDevice<double>> const &m) {
+    if (!m)
+      return;
+    int64_t blocks = 0, columns = 0;
+    m->block_counters(blocks, columns);
+    block_launches += blocks;
+    vector_launches += m->vector_launches();
+  };
+  for (auto const &L : _amg)
+    for (auto const &op : {L.a, L.restrictor, L.prolongator, L.smoothed_prolongator})
+      if (op)
+        count(op->get_matrix());
+  count(_amg_bottom.l_inv_p);
+  count(_amg_bottom.u_inv);
+}
+
+void HipSolver::apply_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const
+{
+  ASSERT_THROW(b.size() == x.size() && !b.empty(), "a block needs as many right-hand sides as iterates");
+  int64_t blocks0 = 0, vectors0 = 0;
+  matrix_launch_counters(blocks0, vectors0);
+  const int64_t ld = block_leading_dimension(b);
+  const bool block = block_cycle_available() && b.size() > 1 && b.size() <= (size_t)kMfBlockMaxVectors && ld != 0 &&
+                     block_kernel_layout(b, ld) && block_kernel_layout(as_const(x), ld);
+  if (!block)
+    Solver<DVector>::apply_block(b, x);
+  else
+  {
+    const int64_t n = _matrix_operator->get_matrix()->m();
+    ASSERT_THROW(b[0]->size() == n && x[0]->size() == n, "vector sizes do not match the coarse operator");
+    int widths[kMfBlockMaxGroups];
+    const int n_groups = mf_block_groups((int)b.size(), widths);
+    size_t c0 = 0;
+    for (int g = 0; g < n_groups; c0 += widths[g], ++g)
+    {
+      if (widths[g] == 1)
+        apply(*b[c0], *x[c0]);
+      else
+        amg_cycle_block(0, ld, std::vector<DVector const *>(b.begin() + c0, b.begin() + c0 + widths[g]),
+                        std::vector<DVector *>(x.begin() + c0, x.begin() + c0 + widths[g]));
+    }
+  }
+  int64_t blocks1 = 0, vectors1 = 0;
+  matrix_launch_counters(blocks1, vectors1);
+  _last_block_launches += blocks1 - blocks0;
+  _last_vector_launches += vectors1 - vectors0;
+}
+
+// amg_cycle, step by step, on the w columns b and x (each a block at the distance ld)
+void HipSolver::amg_cycle_block(size_t level, int64_t ld, std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const
+{
+  AmgLevel const &L = _amg[level];
+  const size_t w = b.size();
+  if (level + 1 == _amg.size())
+  {
+    for (size_t c = 0; c < w; ++c)
+      solve_direct(_amg_bottom, b[c]->get_values(), x[c]->get_values());
+    return;
+  }
+  constexpr int group = 4; // (the widest group of mf_block_groups)
+  const int64_t n_coarse = L.restrictor->get_matrix()->m(), ld_coarse = n_coarse + (n_coarse & 1);
+  if (L.res_block.empty() || L.block_ld != ld)
+  {
+    MemoryKind kind("coarse solver: block workspaces of the aggregation levels (one group of right-hand sides)");
+    L.res_block.clear(); // (before the new ones are built)
+    L.x_work_block.clear();
+    const int64_t n = L.a->get_matrix()->m();
+    L.res_block = build_block(_handle, n, group, ld);
+    L.x_work_block = build_block(_handle, n, group, ld);
+    if (L.b_coarse_block.empty())
+    {
+      L.b_coarse_block = build_block(_handle, n_coarse, group, ld_coarse);
+      L.x_coarse_block = build_block(_handle, n_coarse, group, ld_coarse);
+    }
+    L.block_ld = ld;
+  }
+  const auto res = first_columns<DVector>(L.res_block, w), x_work = first_columns<DVector>(L.x_work_block, w),
+             b_coarse = first_columns<DVector>(L.b_coarse_block, w), x_coarse = first_columns<DVector>(L.x_coarse_block, w);
+  // (no level below is gathered: block_cycle_available)
+  if ((int)level >= _amg_pre_smoothing_levels)
+  {
+    // V(0,1) on this level, as in amg_cycle: b itself is restricted and the correction added
+    L.restrictor->apply_block(b, b_coarse);
+    amg_cycle_block(level + 1, ld_coarse, as_const(b_coarse), x_coarse);
+    if (L.smoothed_prolongator)
+    {
+      L.smoothed_prolongator->apply_plus_scaled_block(as_const(x_coarse), L.a->get_diagonal_inverse(), b, L.smoothed_beta, x);
+      return;
+    }
+    L.prolongator->apply_block(as_const(x_coarse), x_work);
+    L.smoother->apply_to_block(b, as_const(x_work), x);
+    return;
+  }
+  L.smoother->apply_zero_guess_block(b, x_work);
+  L.a->residual_block(as_const(x_work), b, res);
+  L.restrictor->apply_block(as_const(res), b_coarse);
+  amg_cycle_block(level + 1, ld_coarse, as_const(b_coarse), x_coarse);
+  L.prolongator->apply_subtract_block(as_const(x_coarse), x_work, OperatorMode::NO_TRANS);
+  L.smoother->apply_to_block(b, as_const(x_work), x);
 }
 
 void HipSolver::amg_cycle_gathered(size_t level, DVector const &b_local, DVector &x_local) const

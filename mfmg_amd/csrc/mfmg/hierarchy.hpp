@@ -238,7 +238,8 @@ public:
   // Where the fine level offers no block kernel (Smoother / Operator::block_width() == 1) that is what runs.  Otherwise the
   // block is taken in the groups of mf_block_groups (at most four columns) and the whole cycle runs per group: pre-smoothing and
   // residual on the block -- the operator's data read once for the group --, then the restriction of the group's residuals into
-  // a coarse block and, after the coarse cycle column by column with the kernels of apply(), the prolongation of the group in
+  // a coarse block and, after the coarse cycle -- on the group where the coarse solver offers it (Solver::block_width: its matrices
+  // read once for the columns), column by column with the kernels of apply() otherwise --, the prolongation of the group in
   // one launch each where the restrictor offers it (Operator::transfer_block_width: its stored values read once for the group;
   // column by column otherwise, and the restriction as in apply() where R (A x - b) is formed in one pass), then post-smoothing
   // on the block.  The workspaces are one group wide whatever the number of columns; they are built at the first block call.
@@ -282,7 +283,11 @@ public:
       const bool wide_restrict = restrictor->transfer_block_width(OperatorMode::NO_TRANS) > 1,
                  wide_prolong = restrictor->transfer_block_width(OperatorMode::TRANS) > 1;
       std::vector<VectorType *> bc(w, b_coarse.get()), xc(w, x_coarse.get());
-      if (wide_restrict || wide_prolong)
+      // ... and where the coarse solver runs its cycle on a group (Solver::block_width: the matrices of its levels read once for
+      // the columns): then the group is solved in one call between the restrictions and the prolongations
+      auto coarse_solver = _levels.size() == 2 ? level_coarse.get_solver() : nullptr;
+      const bool wide_solve = coarse_solver && coarse_solver->block_width() > 1 && coarse_solver->ignores_initial_guess();
+      if (wide_restrict || wide_prolong || wide_solve)
       {
         if (_coarse_block_workspace.size() < 2 * w)
         {
@@ -325,9 +330,20 @@ public:
           restrictor->apply(*res[c], *bc[c]);
         else if (one_pass && c > 0)
           ASSERT_THROW(restrictor->restrict_residual(*a, *xg[c], *bg[c], *bc[c]), "internal: the one-pass residual restriction was refused");
+        if (wide_solve)
+          continue;
         apply(*bc[c], *xc[c], 1);
         if (!wide_prolong)
           restrictor->apply_subtract(*xc[c], *xg[c], OperatorMode::TRANS);
+      }
+      if (wide_solve)
+      {
+        timer_enter_subsection(_timer, "Apply: coarsest level");
+        coarse_solver->apply_block(std::vector<VectorType const *>(bc.begin(), bc.end()), xc);
+        timer_leave_subsection(_timer);
+        if (!wide_prolong)
+          for (size_t c = 0; c < w; ++c)
+            restrictor->apply_subtract(*xc[c], *xg[c], OperatorMode::TRANS);
       }
       if (wide_prolong)
         restrictor->apply_subtract_block(std::vector<VectorType const *>(xc.begin(), xc.end()), xg, OperatorMode::TRANS);

@@ -142,6 +142,20 @@ public:
   void transfer_block(std::vector<DVector const *> const &x, std::vector<DVector *> const &y, Transfer what) const;
   // so far: launches of the block restriction / prolongation, columns of transfer_block that went through the one-vector kernels
   void transfer_block_counters(int64_t counters[3]) const;
+  // Blocks of vectors through a plain matrix operator (no agglomerate-wise form, one rank): 4 where the matrix has the block
+  // kernels (SparseMatrixDevice::block_width: stored values that do not repeat), 1 elsewhere and on a context with a
+  // communicator.  residual_block, apply_block, apply_subtract_block (NO_TRANS), smoother_step_block and apply_plus_scaled_block
+  // then are ONE call of SparseMatrixDevice::apply_mode_block where the columns of every operand are blocks the kernels take
+  // (equal even distances, bases aligned to 16 bytes; b, x_prev and the result at one distance), the loop over the columns with
+  // the one-vector method otherwise.  Every column gets the bits of the one-vector method.
+  int block_width() const override;
+  void residual_block(std::vector<DVector const *> const &x, std::vector<DVector const *> const &b,
+                      std::vector<DVector *> const &res) const override;
+  // (smoother_step on the w columns of blocks at the distance ld, for HipSmoother, which has checked the layout; block_width() > 1)
+  void smoother_step_block(int w, int64_t ld, double const *b, double const *x, double const *x_prev, double alpha, double beta,
+                           double *out) const;
+  void apply_plus_scaled_block(std::vector<DVector const *> const &x, double const *dinv, std::vector<DVector const *> const &b, double beta,
+                               std::vector<DVector *> const &y) const;
 
   void smoother_step(DVector const &b, DVector const &x, DVector const *x_prev, double alpha, double beta,
                      DVector &out) const override;
@@ -190,6 +204,9 @@ public:
   bool restrict_residual_f32(Operator<DVector> const &a, float const *x, float const *b, DVector &b_coarse) const;
 
 private:
+  // the one call of apply_mode_block; false (nothing done) where the operands are not such blocks: the caller loops
+  bool matrix_block(CsrMode mode, std::vector<DVector const *> const &x, std::vector<DVector const *> const *b, double const *dinv,
+                    std::vector<DVector const *> const *x_prev, double alpha, double beta, std::vector<DVector *> const &out) const;
   int _domain_space = 0, _range_space = 0, _reverse_range_space = 0;
   std::shared_ptr<SparseMatrixDevice<double>> _matrix;
   mutable std::shared_ptr<SparseMatrixDevice<double>> _transposed_matrix; // built lazily (cuda_matrix_operator.cu:93-130)
@@ -320,6 +337,12 @@ public:
   // block kernel per term and group of 4 or 2 columns (the matrix-free operator with eight coefficients per cell)
   int block_width() const override;
   void apply_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const override;
+  // ... and of a HipMatrixOperator whose matrix has the block kernels (HipMatrixOperator::block_width: the first coarse operator
+  // of a problem with eight coefficients per cell), with the block forms of apply_zero_guess and apply_to that the coarse cycle
+  // calls: the same run_polynomial, its terms as launches on the group, scratch blocks one group wide.  Columns that do not form
+  // blocks at one even distance (b, x_in and x_out alike) go through the one-vector method one by one.
+  void apply_zero_guess_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const;
+  void apply_to_block(std::vector<DVector const *> const &b, std::vector<DVector const *> const &x_in, std::vector<DVector *> const &x_out) const;
   int fused_terms() const { return _fused_terms; }
   // smoother.sweep_arithmetic "reference": the sweep computes with the one-term kernel's arithmetic, bit for bit
   bool sweep_reference() const { return _sweep_reference; }
@@ -343,6 +366,11 @@ private:
   // the polynomial from x_in into x_out, its first `swept` terms in one sweep (SweepSchedule)
   void run(int swept, DVector const &b, DVector const &x_in, DVector &x_out) const;
   DVector *scratch(int i) const; // built on first use
+  // the polynomial on one group of w = 4 or 2 columns at the distance ld, from x_in into x_out (in place: the same block)
+  void run_group(int w, int64_t ld, int64_t n, double const *b, double const *x_in, double *x_out) const;
+  // whether the columns are blocks run_group takes: 2..64 of them, every operand at one even distance, bases aligned
+  int64_t group_layout(std::vector<DVector const *> const &b, std::vector<DVector const *> const &x_in,
+                       std::vector<DVector const *> const &x_out) const;
 
   std::shared_ptr<HipOperator const> _hip_operator;
   std::string _type;
@@ -436,6 +464,24 @@ public:
 
   void apply(DVector const &b, DVector &x) const override;
   bool ignores_initial_guess() const override { return true; } // every variant starts from zero by itself
+  // The V-cycle of solver.type amg on the columns of a block: the block is cut by mf_block_groups and amg_cycle runs on a group
+  // of 4 or 2 columns, every step -- smoother from zero, residual, P^T, recursion, P with subtraction or P~ with plus_scaled,
+  // post-smoother -- as the block call of the object that offers one (the stored values of its matrix read once for the group),
+  // as the loop over the columns with the call amg_cycle makes otherwise; the bottom solve stays per column.  The per-level
+  // workspaces are blocks one group wide, built at the first block call.  The loop over apply() where n_cycles > 1, a level is
+  // gathered, the context has a communicator, for the solvers pcg and lu_dense, and for columns that are not one block at an
+  // even distance with a base aligned to 16 bytes.  Every column gets the bits of apply().
+  // block_width(): the widest group any matrix of the cycle takes (1 where apply_block loops).
+  int block_width() const override;
+  void apply_block(std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const override;
+  // of the apply_block calls since reset_block_counters (the C boundary resets when a block entry point begins): launches of the
+  // block kernels and one-vector launches of the matrices of the cycle
+  void block_counters(int64_t &block_launches, int64_t &vector_launches) const
+  {
+    block_launches = _last_block_launches;
+    vector_launches = _last_vector_launches;
+  }
+  void reset_block_counters() const { _last_block_launches = _last_vector_launches = 0; }
   std::string const &type() const { return _solver; }
   int n_iterations() const { return _n_iterations; }
 
@@ -460,6 +506,9 @@ public:
     int coarse_product = by_probes;
     bool replicated = false;
     mutable std::shared_ptr<DVector> res, b_coarse, x_coarse, x_work;
+    // apply_block: the same four as blocks one group wide (res and x_work at the distance of the level's b and x)
+    mutable std::vector<std::shared_ptr<DVector>> res_block, b_coarse_block, x_coarse_block, x_work_block;
+    mutable int64_t block_ld = 0;
   };
   std::vector<AmgLevel> const &amg_levels() const { return _amg; }
   // "release setup matrices": the CSR arrays of the table-driven operators of the aggregation hierarchy (SparseMatrixDevice::
@@ -478,6 +527,11 @@ public:
 
 private:
   void amg_cycle(size_t level, DVector const &b, DVector &x) const;
+  // amg_cycle on a group of 2 or 4 columns at the distance ld (apply_block)
+  void amg_cycle_block(size_t level, int64_t ld, std::vector<DVector const *> const &b, std::vector<DVector *> const &x) const;
+  bool block_cycle_available() const;
+  void matrix_launch_counters(int64_t &block_launches, int64_t &vector_launches) const;
+  mutable int64_t _last_block_launches = 0, _last_vector_launches = 0;
   // b, x in the local layout of the gathered level's space: all-gather of the owned parts, replicated cycle from
   // `level` down, the local run of layers copied back (ghost layers included)
   void amg_cycle_gathered(size_t level, DVector const &b_local, DVector &x_local) const;

@@ -234,6 +234,21 @@ public:
   // out (op)= A x with the epilogue of `mode`: what vmult / residual / smoother_step / vmult_subtract / vmult_add /
   // vmult_plus_scaled call, with the operands every mode needs checked
   void apply_mode(CsrMode mode, T const *x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta, T *out) const;
+  // apply_mode on the columns of a block (sparse_matrix_block.hip): column c of x at x + c ld_x, of b, x_prev and out at
+  // c ld_out; dinv is one vector shared by the columns.  The block is cut by mf_block_groups; where block_width() is 4 a group
+  // of 4 or 2 columns is ONE launch that reads the stored values once (profiler name csr_block_kernel), a single column -- and
+  // every column where block_width() is 1 -- runs launch().  Every column gets the bits of apply_mode on that column.  Blocks:
+  // 1..64 columns, leading dimensions even and at least the vector size, bases aligned to 16 bytes, out apart from x.
+  void apply_mode_block(CsrMode mode, int n_vectors, T const *x, int64_t ld_x, T const *b, T const *dinv, T const *x_prev, T alpha,
+                        T beta, T *out, int64_t ld_out) const;
+  // 4 where form() says the launch is exactly one kernel over stored values that do not repeat (FP64): kind 2 or 3 without
+  // regular rows (bdia_spmv_kernel over all rows, bdia_sym_split_kernel), or kind 4 (rowbase_spmv_kernel).  1 everywhere else:
+  // tables or node classes, twins, listed rows walked through stored planes, every CSR kernel, a released matrix.
+  int block_width() const;
+  // launches of the block kernels and columns that went through launch(), of all apply_mode_block calls so far
+  void block_counters(int64_t &block_launches, int64_t &column_launches) const;
+  // applications to ONE vector so far, whoever asked for them (launch())
+  int64_t vector_launches() const { return _vector_launches.load(std::memory_order_relaxed); }
   // algorithmic bytes of one y = A x (12 B/nnz + 4 B/row ptr + x + y)
   double algorithmic_bytes_apply() const
   {
@@ -244,6 +259,9 @@ public:
 private:
   void launch(CsrMode mode, T const *x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta,
               T *out) const;
+  void launch_block(CsrMode mode, int nv, T const *x, int64_t ld_x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta,
+                    T *out, int64_t ld_out) const;
+  mutable std::atomic<int64_t> _block_launches{0}, _column_launches{0}, _vector_launches{0};
 
   // a.pairs of the last launch, for form() only (atomic: launches from several host threads stay free of a data race)
   mutable std::atomic<int> _last_pairs{-1};

@@ -192,6 +192,10 @@ def load() -> C.CDLL:
         "mfmg_hip_csr_smoother_step": (C.c_int, [vp, vp, vp, vp, vp, dbl, dbl, vp]),
         "mfmg_hip_csr_residual": (C.c_int, [vp, vp, vp, vp]),
         "mfmg_hip_csr_launch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, dbl, dbl, vp]),
+        "mfmg_hip_csr_launch_block": (C.c_int, [vp, C.c_int, i32, i64, vp, i64, vp, vp, vp, dbl, dbl, vp]),
+        "mfmg_hip_csr_block_info": (C.c_int, [vp, P(i64)]),
+        "mfmg_hip_hierarchy_coarse_apply_block": (C.c_int, [vp, i32, i64, vp, vp]),
+        "mfmg_hip_hierarchy_coarse_block_info": (C.c_int, [vp, P(i64)]),
         "mfmg_hip_csr_form": (C.c_int, [vp, P(i64), i32]),
         "mfmg_hip_csr_enable_node_twins": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_csr_release_csr": (C.c_int, [vp, P(C.c_int)]),
@@ -328,7 +332,8 @@ def load() -> C.CDLL:
                    "mfmg_hip_hierarchy_restrictor_apply_block", "mfmg_hip_hierarchy_transfer_block_info",
                    "mfmg_hip_hierarchy_block_solve_allreduces", "mfmg_hip_context_exchange_block_f32",
                    "mfmg_hip_block_krylov_orthogonalize_box", "mfmg_hip_context_set_block_fgmres_on_ranks",
-                   "mfmg_hip_mf_z_tiles"}
+                   "mfmg_hip_mf_z_tiles", "mfmg_hip_csr_launch_block", "mfmg_hip_csr_block_info",
+                   "mfmg_hip_hierarchy_coarse_apply_block", "mfmg_hip_hierarchy_coarse_block_info"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
