@@ -998,9 +998,9 @@ int mfmg_hip_csr_transpose(mfmg_hip_csr_t a, mfmg_hip_csr_t *out)
 {
   return guarded([&] {
     require(a && out, "null argument");
-    auto h = new mfmg_hip_csr_s;
+    std::unique_ptr<mfmg_hip_csr_s> h(new mfmg_hip_csr_s); // (a released matrix throws below)
     h->op = std::dynamic_pointer_cast<HipMatrixOperator>(a->op->transpose());
-    *out = h;
+    *out = h.release();
   });
 }
 
@@ -1008,9 +1008,9 @@ int mfmg_hip_csr_multiply(mfmg_hip_csr_t a, mfmg_hip_csr_t b, mfmg_hip_csr_t *ou
 {
   return guarded([&] {
     require(a && b && out, "null argument");
-    auto h = new mfmg_hip_csr_s;
+    std::unique_ptr<mfmg_hip_csr_s> h(new mfmg_hip_csr_s);
     h->op = std::dynamic_pointer_cast<HipMatrixOperator>(a->op->multiply(b->op));
-    *out = h;
+    *out = h.release();
   });
 }
 
