@@ -780,8 +780,8 @@ int mfmg_hip_hierarchy_block_info(mfmg_hip_hierarchy_t h, int64_t *fields);
  * mfmg_hip_csr_launch on that column.  The block is cut by mfmg_hip_block_groups; where mfmg_hip_csr_block_info reports the width
  * 4 a group of 4 or 2 columns is one launch that reads the stored values once (profiler name csr_block_kernel): a matrix whose
  * launch is exactly one kernel over values that do not repeat -- mfmg_hip_csr_form kind 2 or 3 with field 8 (regular) 0, or kind
- * 4.  Elsewhere (tables, node classes, twins, listed rows, the CSR kernels, a released matrix), and for a single column, the
- * one-vector kernels run column by column.  MFMG_HIP_ERROR_INVALID_ARGUMENT: n_vectors outside 1..64, a leading dimension below
+ * 4.  Elsewhere (tables, node classes, twins, listed rows, a released matrix, and the CSR kernels unless
+ * mfmg_hip_csr_set_block_csr below turned their block forms on), and for a single column, the one-vector kernels run column by column.  MFMG_HIP_ERROR_INVALID_ARGUMENT: n_vectors outside 1..64, a leading dimension below
  * the vector size or odd, a base not aligned to 16 bytes, out overlapping x, a null operand the mode reads.
  * mfmg_hip_csr_block_info: fields[0] the width (4 or 1), fields[1] launches of the block kernels and fields[2] columns that went
  * through the one-vector kernels, of all mfmg_hip_csr_launch_block calls on the matrix so far.
@@ -797,6 +797,27 @@ int mfmg_hip_csr_launch_block(mfmg_hip_csr_t a, int mode, int32_t n_vectors, int
 int mfmg_hip_csr_block_info(mfmg_hip_csr_t a, int64_t fields[3]);
 int mfmg_hip_hierarchy_coarse_apply_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const double *b, double *x);
 int mfmg_hip_hierarchy_coarse_block_info(mfmg_hip_hierarchy_t h, int64_t fields[3]);
+
+/* ---- block forms of the CSR kernels (additions, no change of the ABI version) ----
+ * Off by default: a matrix on a CSR kernel (mfmg_hip_csr_form kind 0 or 1) reports the width 1 and runs column by column.
+ * mfmg_hip_csr_set_block_csr(a, 1, info) turns the block forms of the three CSR kernels on for this matrix: where it is FP64 and
+ * its CSR arrays are there, mfmg_hip_csr_block_info then reports 4 and a group of 4 or 2 columns is ONE launch that reads val and
+ * col once (profiler name csr_block_kernel), every column with the bits of mfmg_hip_csr_launch.  The route is read per call, so
+ * mfmg_hip_csr_set_kernel afterwards keeps working.  Matrices on tables, node classes, twins, with listed rows, in float or
+ * released keep the width 1, stored planes and row base keep 4.  info[0] the width after the call, info[1] the kernel of a group
+ * of 4 and info[2] of a group of 2: 0 none, 1 lanes, 2 row_block, 3 lds.  A group of an LDS-cached matrix whose windows of x,
+ * with the table of row pointers, pass 80 KiB takes the lanes kernel at the same lanes per row.
+ * mfmg_hip_hierarchy_set_block_csr: the same switch on every FP64 matrix the cycle applies -- the assembled fine operator, a
+ * restrictor given as CSR, the first coarse operator, A, P^T, P and P~ of every aggregation level and the two triangular inverses
+ * of the bottom, whose solve then runs on the group too.  *n_matrices: how many of them now report the width 4 through a CSR
+ * kernel.  Between block calls at any time; MFMG_HIP_ERROR_INVALID_ARGUMENT on a context with a communicator. */
+int mfmg_hip_csr_set_block_csr(mfmg_hip_csr_t a, int on, int32_t info[3]);
+int mfmg_hip_hierarchy_set_block_csr(mfmg_hip_hierarchy_t h, int on, int32_t *n_matrices);
+/* What mfmg_hip_csr_set_block_csr(.., 1, info) reports on the FP32 instance of the matrix class built from these arrays (the
+ * values narrowed): the block forms are FP64 only, so width 1 and no route.  The C boundary hands out no FP32 matrix; this is the
+ * one way to ask. */
+int mfmg_hip_csr_block_csr_info_f32(mfmg_hip_context_t ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *row_ptr_host,
+                                    const int32_t *col_host, const double *val_host, int32_t info[3]);
 
 /* ---- restriction and prolongation on a block of vectors (additions, no change of the ABI version) ----
  * mfmg_hip_hierarchy_restrictor_apply_block: mfmg_hip_hierarchy_restrictor_apply(level, in[c], out[c], mode) for every column,

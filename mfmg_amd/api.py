@@ -475,6 +475,16 @@ def _csr_arrays(a):
             np.ascontiguousarray(vl, dtype=np.float64), shape)
 
 
+def block_csr_info_f32(ctx, matrix) -> dict:
+    """What SparseMatrixDevice.set_block_csr(True) reports on the FP32 instance of the matrix class (the values narrowed): the
+    block forms of the CSR kernels are FP64 only -- width 1, no route."""
+    rp, cl, vl, shape = _csr_arrays(matrix)
+    f = (C.c_int32 * 3)()
+    check(_lib.load().mfmg_hip_csr_block_csr_info_f32(ctx.handle, shape[0], shape[1], len(vl), rp.ctypes.data, cl.ctypes.data,
+                                                       vl.ctypes.data, f))
+    return {"width": int(f[0]), "route4": SparseMatrixDevice._CSR_KERNELS[int(f[1])], "route2": SparseMatrixDevice._CSR_KERNELS[int(f[2])]}
+
+
 class SparseMatrixDevice:
     """SparseMatrixDevice<double> + CudaMatrixOperator (include/mfmg/cuda/sparse_matrix_device.cuh,
     source/cuda/cuda_matrix_operator.cu)."""
@@ -615,6 +625,16 @@ class SparseMatrixDevice:
         f = (C.c_int64 * 3)()
         check(self._lib.mfmg_hip_csr_block_info(self.handle, f))
         return {"width": int(f[0]), "block_launches": int(f[1]), "column_launches": int(f[2])}
+
+    def set_block_csr(self, on: bool = True) -> dict:
+        """Turn the block forms of the CSR kernels on (or off again) for this matrix: where form() names a CSR kernel, the
+        matrix is FP64 and its CSR arrays are there, block_info()["width"] becomes 4 and launch_block reads val and col once per
+        group of 4 or 2 rows, every row with the bits of launch().  Off by default.  Returns width, and route4 / route2: the
+        kernel a group of 4 / of 2 takes (None, "lanes", "row_block", "lds"; an LDS-cached matrix whose windows do not fit
+        next to each other takes "lanes")."""
+        f = (C.c_int32 * 3)()
+        check(self._lib.mfmg_hip_csr_set_block_csr(self.handle, 1 if on else 0, f))
+        return {"width": int(f[0]), "route4": self._CSR_KERNELS[int(f[1])], "route2": self._CSR_KERNELS[int(f[2])]}
 
     _FORM_FIELDS = ("kind", "csr_kernel", "lanes", "c", "stored_d", "full_d", "symmetric_half", "float_planes", "regular",
                     "all_in_classes", "classes", "class_slots", "listed", "listed_route", "regular_kernel", "class_kernel",
@@ -1126,6 +1146,15 @@ class Hierarchy:
         f = (C.c_int64 * 3)()
         check(self._lib.mfmg_hip_hierarchy_coarse_block_info(self.handle, f))
         return {"width": int(f[0]), "block_launches": int(f[1]), "column_launches": int(f[2])}
+
+    def set_block_csr(self, on: bool = True) -> int:
+        """SparseMatrixDevice.set_block_csr on every FP64 matrix the cycle applies: the assembled fine operator, a restrictor
+        given as CSR, the first coarse operator, A, P^T, P and P~ of the aggregation levels and the triangular inverses of the
+        bottom (whose solve then runs on the group).  Returns how many of them now report the width 4 through a CSR kernel.
+        Off by default; one rank only."""
+        n = C.c_int32()
+        check(self._lib.mfmg_hip_hierarchy_set_block_csr(self.handle, 1 if on else 0, C.byref(n)))
+        return int(n.value)
 
     def set_restrictor(self, matrix):
         rp, cl, vl, shape = _csr_arrays(matrix)

@@ -1122,6 +1122,37 @@ int mfmg_hip_csr_block_info(mfmg_hip_csr_t a, int64_t fields[3])
   });
 }
 
+int mfmg_hip_csr_set_block_csr(mfmg_hip_csr_t a, int on, int32_t info[3])
+{
+  return guarded([&] {
+    require(a && info, "null argument");
+    auto m = a->op->get_matrix();
+    m->set_block_csr(on != 0);
+    info[0] = m->block_width();
+    info[1] = m->block_csr_route(4);
+    info[2] = m->block_csr_route(2);
+  });
+}
+
+int mfmg_hip_csr_block_csr_info_f32(mfmg_hip_context_t ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *row_ptr_host,
+                                    const int32_t *col_host, const double *val_host, int32_t info[3])
+{
+  return guarded([&] {
+    require(ctx && row_ptr_host && info, "null argument");
+    require(n_rows >= 0 && n_cols >= 0 && nnz >= 0, "negative size");
+    require(nnz == 0 || (col_host && val_host), "null column / value array");
+    std::vector<int32_t> rp(row_ptr_host, row_ptr_host + n_rows + 1);
+    require(rp[n_rows] == nnz, "row_ptr[n_rows] != nnz");
+    std::vector<int32_t> cl(col_host, col_host + nnz);
+    std::vector<float> vl(val_host, val_host + nnz);
+    SparseMatrixDevice<float> m(*ctx->handle, n_rows, n_cols, std::move(rp), std::move(cl), std::move(vl));
+    m.set_block_csr(true);
+    info[0] = m.block_width();
+    info[1] = m.block_csr_route(4);
+    info[2] = m.block_csr_route(2);
+  });
+}
+
 int mfmg_hip_csr_form(mfmg_hip_csr_t a, int64_t *fields, int32_t n)
 {
   return guarded([&] {
@@ -2755,6 +2786,40 @@ int mfmg_hip_hierarchy_coarse_block_info(mfmg_hip_hierarchy_t h, int64_t fields[
     fields[1] = fields[2] = 0;
     if (auto hs = std::dynamic_pointer_cast<HipSolver const>(solver))
       hs->block_counters(fields[1], fields[2]);
+  });
+}
+
+int mfmg_hip_hierarchy_set_block_csr(mfmg_hip_hierarchy_t h, int on, int32_t *n_matrices)
+{
+  return guarded([&] {
+    require(h && n_matrices, "null argument");
+    require(!h->handle->comm.enabled(), "the block forms of the CSR kernels are not implemented for a context with a communicator");
+    // every SparseMatrixDevice<double> the cycle applies, each once: the assembled fine operator, a restrictor given as CSR, the
+    // operators of the levels, and what the coarse solver holds (the aggregation hierarchy and the inverses of its bottom)
+    std::vector<SparseMatrixDevice<double> *> seen;
+    int n = 0;
+    auto flip = [&](std::shared_ptr<SparseMatrixDevice<double>> const &m) {
+      if (!m || std::find(seen.begin(), seen.end(), m.get()) != seen.end())
+        return;
+      seen.push_back(m.get());
+      m->set_block_csr(on != 0);
+      if (m->block_width() == 4 && m->block_csr_route(4) != CsrForm::csr_none)
+        ++n;
+    };
+    auto const &levels = h->hierarchy->levels();
+    for (size_t l = 0; l < levels.size(); ++l)
+    {
+      if (auto a = std::dynamic_pointer_cast<HipMatrixOperator const>(levels[l].get_operator()))
+        flip(a->get_matrix());
+      if (l == 0)
+        continue;
+      auto r = std::dynamic_pointer_cast<HipMatrixOperator const>(levels[l].get_restrictor());
+      if (r && !r->has_structured())
+        flip(r->get_matrix());
+    }
+    if (auto hs = std::dynamic_pointer_cast<HipSolver const>(levels.back().get_solver()))
+      hs->for_each_cycle_matrix(flip);
+    *n_matrices = n;
   });
 }
 

@@ -2329,6 +2329,22 @@ void HipSolver::amg_cycle_block(size_t level, int64_t ld, std::vector<DVector co
   const size_t w = b.size();
   if (level + 1 == _amg.size())
   {
+    DenseLu const &f = _amg_bottom;
+    if (f.n > 0 && f.l_inv_p && f.l_inv_p->block_width() == 4 && f.u_inv->block_width() == 4)
+    {
+      // solve_direct on the group: x = U^-1 ((L^-1 P) b), two launches through a group-wide tmp
+      constexpr int group = 4;
+      const int64_t ld_tmp = f.n + (f.n & 1);
+      if (f.tmp_block.size() < (size_t)group * ld_tmp)
+      {
+        MemoryKind kind("coarse solver: block workspace of the bottom solve (one group of right-hand sides)");
+        f.tmp_block.resize((size_t)group * ld_tmp);
+        vec::set<double>(_handle, (int64_t)group * ld_tmp, 0., f.tmp_block.data());
+      }
+      f.l_inv_p->apply_mode_block(CsrMode::apply, (int)w, b[0]->get_values(), ld, nullptr, nullptr, nullptr, 0., 0., f.tmp_block.data(), ld_tmp);
+      f.u_inv->apply_mode_block(CsrMode::apply, (int)w, f.tmp_block.data(), ld_tmp, nullptr, nullptr, nullptr, 0., 0., x[0]->get_values(), ld);
+      return;
+    }
     for (size_t c = 0; c < w; ++c)
       solve_direct(_amg_bottom, b[c]->get_values(), x[c]->get_values());
     return;

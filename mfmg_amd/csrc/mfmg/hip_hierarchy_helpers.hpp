@@ -467,7 +467,8 @@ public:
   // The V-cycle of solver.type amg on the columns of a block: the block is cut by mf_block_groups and amg_cycle runs on a group
   // of 4 or 2 columns, every step -- smoother from zero, residual, P^T, recursion, P with subtraction or P~ with plus_scaled,
   // post-smoother -- as the block call of the object that offers one (the stored values of its matrix read once for the group),
-  // as the loop over the columns with the call amg_cycle makes otherwise; the bottom solve stays per column.  The per-level
+  // as the loop over the columns with the call amg_cycle makes otherwise; the bottom solve is two launches on the group where both
+  // triangular inverses have a block width of 4 (SparseMatrixDevice::set_block_csr), per column otherwise.  The per-level
   // workspaces are blocks one group wide, built at the first block call.  The loop over apply() where n_cycles > 1, a level is
   // gathered, the context has a communicator, for the solvers pcg and lu_dense, and for columns that are not one block at an
   // even distance with a base aligned to 16 bytes.  Every column gets the bits of apply().
@@ -522,6 +523,18 @@ public:
           ++n;
     return n;
   }
+  // f(matrix) for every matrix the cycle of solver.type amg applies: A, P^T, P and P~ of the levels, then the two triangular
+  // inverses of the bottom (SparseMatrixDevice::set_block_csr walks them)
+  template <typename F>
+  void for_each_cycle_matrix(F &&f) const
+  {
+    for (auto const &L : _amg)
+      for (auto const &op : {L.a, L.restrictor, L.prolongator, L.smoothed_prolongator})
+        if (op)
+          f(op->get_matrix());
+    f(_amg_bottom.l_inv_p);
+    f(_amg_bottom.u_inv);
+  }
   // index of the first level that is gathered and solved redundantly on every rank (-1: one rank / none)
   int amg_gather_level() const { return _amg_gather_level; }
 
@@ -550,6 +563,7 @@ private:
     int64_t n = 0;
     std::shared_ptr<SparseMatrixDevice<double>> l_inv_p, u_inv; // n <= kTriangularInverseLimit
     mutable DeviceBuffer<double> tmp;
+    mutable DeviceBuffer<double> tmp_block; // the same for a group of columns, at the even distance n + (n & 1)
     DeviceBuffer<double> lu;                                       // column-major L\\U otherwise
     DeviceBuffer<int32_t> perm;
   };

@@ -186,7 +186,10 @@ int SparseMatrixDevice<T>::block_width() const
   if constexpr (!std::is_same_v<T, double>)
     return 1;
   const CsrForm f = form();
-  return (((f.kind == 2 || f.kind == 3) && f.regular == 0) || f.kind == 4) ? 4 : 1;
+  if (((f.kind == 2 || f.kind == 3) && f.regular == 0) || f.kind == 4)
+    return 4;
+  // (set_block_csr: the CSR kernels, sparse_matrix_block_csr.hip)
+  return block_csr_route(4) != CsrForm::csr_none ? 4 : 1;
 }
 
 template <typename T>
@@ -246,7 +249,8 @@ void SparseMatrixDevice<T>::apply_mode_block(CsrMode mode, int n_vectors, T cons
   }
 }
 
-// one group of 4 or 2 columns of a matrix whose launch is exactly one of the three kernels above (block_width() == 4)
+// one group of 4 or 2 columns of a matrix whose launch is exactly one of the three kernels above, or one of the CSR kernels
+// under set_block_csr (block_width() == 4)
 template <typename T>
 void SparseMatrixDevice<T>::launch_block(CsrMode mode, int nv, T const *x, int64_t ld_x, T const *b, T const *dinv, T const *x_prev,
                                          T alpha, T beta, T *out, int64_t ld_out) const
@@ -254,6 +258,8 @@ void SparseMatrixDevice<T>::launch_block(CsrMode mode, int nv, T const *x, int64
   if constexpr (std::is_same_v<T, double>)
   {
     const CsrForm f = form(); // (every branch below is taken from it, as in launch())
+    if (f.kind == 0 || f.kind == 1)
+      return launch_block_csr(mode, nv, x, ld_x, b, dinv, x_prev, alpha, beta, out, ld_out);
     ASSERT_THROW((((f.kind == 2 || f.kind == 3) && f.regular == 0) || f.kind == 4) && (nv == 2 || nv == 4),
                  "internal: no block kernel for this matrix or group");
     CsrArgs<T> a;

@@ -243,8 +243,20 @@ public:
                         T beta, T *out, int64_t ld_out) const;
   // 4 where form() says the launch is exactly one kernel over stored values that do not repeat (FP64): kind 2 or 3 without
   // regular rows (bdia_spmv_kernel over all rows, bdia_sym_split_kernel), or kind 4 (rowbase_spmv_kernel).  1 everywhere else:
-  // tables or node classes, twins, listed rows walked through stored planes, every CSR kernel, a released matrix.
+  // tables or node classes, twins, listed rows walked through stored planes, a released matrix, and every CSR kernel unless
+  // set_block_csr turned their block forms on.
   int block_width() const;
+  // Opt-in: with it on, block_width() is also 4 where form() reports a CSR kernel (kind 0 or 1), T is double and the CSR arrays
+  // are there; a group of 4 or 2 columns is then ONE launch of the block form of that kernel (sparse_matrix_block_csr.hip), val
+  // and col read once.  Off by default; read per call, so set_kernel afterwards keeps working.  Everywhere else -- tables, node
+  // classes, twins, listed rows, float, a released matrix -- the width stays what it is, and stored planes and row base stay 4.
+  void set_block_csr(bool on) { _block_csr = on; }
+  bool block_csr() const { return _block_csr; }
+  // the kernel a group of nv = 4 or 2 columns takes under set_block_csr: CsrForm::csr_none (the switch does not concern the
+  // matrix as it stands), csr_lanes, csr_row_block or csr_lds.  A group of an LDS-cached matrix whose nv windows, with the table
+  // of row pointers, pass 80 KiB -- two 1024-thread workgroups per CU no longer fit -- takes the lanes kernel at the same lanes
+  // per row: the same bits, since lcol[p] names col[p].
+  int block_csr_route(int nv) const;
   // launches of the block kernels and columns that went through launch(), of all apply_mode_block calls so far
   void block_counters(int64_t &block_launches, int64_t &column_launches) const;
   // applications to ONE vector so far, whoever asked for them (launch())
@@ -261,6 +273,9 @@ private:
               T *out) const;
   void launch_block(CsrMode mode, int nv, T const *x, int64_t ld_x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta,
                     T *out, int64_t ld_out) const;
+  void launch_block_csr(CsrMode mode, int nv, T const *x, int64_t ld_x, T const *b, T const *dinv, T const *x_prev, T alpha, T beta,
+                        T *out, int64_t ld_out) const;
+  bool _block_csr = false;
   mutable std::atomic<int64_t> _block_launches{0}, _column_launches{0}, _vector_launches{0};
 
   // a.pairs of the last launch, for form() only (atomic: launches from several host threads stay free of a data race)

@@ -196,6 +196,9 @@ def load() -> C.CDLL:
         "mfmg_hip_csr_block_info": (C.c_int, [vp, P(i64)]),
         "mfmg_hip_hierarchy_coarse_apply_block": (C.c_int, [vp, i32, i64, vp, vp]),
         "mfmg_hip_hierarchy_coarse_block_info": (C.c_int, [vp, P(i64)]),
+        "mfmg_hip_csr_set_block_csr": (C.c_int, [vp, C.c_int, P(i32)]),
+        "mfmg_hip_hierarchy_set_block_csr": (C.c_int, [vp, C.c_int, P(i32)]),
+        "mfmg_hip_csr_block_csr_info_f32": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, P(i32)]),
         "mfmg_hip_csr_form": (C.c_int, [vp, P(i64), i32]),
         "mfmg_hip_csr_enable_node_twins": (C.c_int, [vp, P(C.c_int)]),
         "mfmg_hip_csr_release_csr": (C.c_int, [vp, P(C.c_int)]),
@@ -333,7 +336,9 @@ def load() -> C.CDLL:
                    "mfmg_hip_hierarchy_block_solve_allreduces", "mfmg_hip_context_exchange_block_f32",
                    "mfmg_hip_block_krylov_orthogonalize_box", "mfmg_hip_context_set_block_fgmres_on_ranks",
                    "mfmg_hip_mf_z_tiles", "mfmg_hip_csr_launch_block", "mfmg_hip_csr_block_info",
-                   "mfmg_hip_hierarchy_coarse_apply_block", "mfmg_hip_hierarchy_coarse_block_info"}
+                   "mfmg_hip_hierarchy_coarse_apply_block", "mfmg_hip_hierarchy_coarse_block_info",
+                   "mfmg_hip_csr_set_block_csr", "mfmg_hip_hierarchy_set_block_csr",
+                   "mfmg_hip_csr_block_csr_info_f32"}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
