@@ -8,8 +8,10 @@ Same command line (`:216-253`: --filename/-f, --dim/-d, --matrix_free/-m, --tole
 `solver.tolerance` from the command line; matrix-free runs force `smoother.type Chebyshev`, `:400-402`), same two modes:
 `"is preconditioner" false` -> 20 V-cycles on rhs = 0 from a random start vector and the convergence rate
 res[20] / res[19] (`:74-101`); true -> CG preconditioned by the hierarchy (`:103-116`).  Differences: the mesh is the
-hyper-cube of `laplace.n_refinements` global refinements with Q1 elements only (`laplace.fe_degree` other than 1 is
-refused; where the file names none the reference takes degree 4, `:269`, this script degree 1), and a matrix-based run whose input file asks for an Ifpack relaxation (Gauss-Seidel, the file's default) takes
+hyper-cube of `laplace.n_refinements` global refinements with Q1 elements, or Q2 elements for a matrix-free CG / FGMRES solve in
+3-D (`laplace.fe_degree 2`: the Q2 operator preconditioned by a Chebyshev smoother around the cycle of the hierarchy on the
+refined Q1 mesh, M.HighOrderSolver; the subtree `"high order"` of the file holds its parameters); other degrees are
+refused (where the file names none the reference takes degree 4, `:269`, this script degree 1), and a matrix-based run whose input file asks for an Ifpack relaxation (Gauss-Seidel, the file's default) takes
 Jacobi, the CUDA back-end's smoother, with a note.
 
 `--numbering dealii` numbers the DoFs as deal.II's DoFHandler::distribute_dofs does (cells in Morton order, vertex DoFs at first
@@ -50,8 +52,13 @@ def main(argv=None):
     if not args.matrix_free and params.get("use_raw_ml", False):
         raise SystemExit("use_raw_ml: ML is not part of the HIP build")
     fe_degree = int(params.get("laplace", {}).get("fe_degree", 1))
-    if fe_degree != 1:
-        raise SystemExit("laplace.fe_degree must be 1: higher degrees are outside the scope of the HIP build")
+    if fe_degree == 2:
+        if not (args.matrix_free and args.dim == 3 and params.get("is preconditioner", True) and args.numbering == "lexicographic"
+                and args.preconditioner_precision == "double"):
+            raise SystemExit("laplace.fe_degree 2 is a matrix-free solve in 3-D (\"is preconditioner\" true, lexicographic "
+                             "numbering, FP64): the Q2 operator preconditioned by the cycle of the refined Q1 mesh")
+    elif fe_degree != 1:
+        raise SystemExit("laplace.fe_degree must be 1 or 2: higher degrees are outside the scope of the HIP build")
     params["fast_ap"] = True
     params.setdefault("eigensolver", {})["type"] = "anasazi"
     params["eigensolver"]["tolerance"] = 1e-3
@@ -67,12 +74,29 @@ def main(argv=None):
     n_ref = int(params.get("laplace", {}).get("n_refinements", 5))
     cells = (2 ** n_ref,) * args.dim
     material = params.get("material_property", {}).get("type", "constant")
+    # (degree 2: the hierarchy is built on the refined Q1 mesh, whose cells decide the coarse solver below)
+    q1_cells = tuple(2 * c for c in cells) if fe_degree == 2 else cells
     if "type" not in params["solver"]:
         n_coarse = 2
-        for c in cells:
+        for c in q1_cells:
             n_coarse *= max(c // int(params.get("agglomeration", {}).get("nx", 2)), 1)
         params["solver"]["type"] = "lu_dense" if n_coarse <= 4096 else "amg"
     ctx = M.Context()
+    if fe_degree == 2:
+        for key in ("laplace", "material_property"):       # (read above; not parameters of the hierarchy)
+            params.pop(key, None)
+        prob2 = M.LaplaceProblemQ2(cells, material, device="cuda")
+        solver = M.HighOrderSolver(ctx, prob2, params)
+        b = torch.rand(prob2.n_dofs, dtype=torch.float64, device="cuda",
+                       generator=torch.Generator(device="cuda").manual_seed(2)) * (prob2.constrained == 0)
+        x = torch.zeros_like(b)
+        if args.solver == "fgmres":
+            its, _ = solver.solve_fgmres(b, x, tolerance=args.tolerance, max_iterations=prob2.n_dofs, restart=args.restart)
+        else:
+            its, _ = solver.solve_cg(b, x, tolerance=args.tolerance, max_iterations=prob2.n_dofs)
+        print(f"Converging after {its} iterations.")
+        print(solver.hierarchy.timer_report())
+        return its
     numbering = None
     if args.numbering == "dealii":
         numbering = M.dealii_numbering(cells)

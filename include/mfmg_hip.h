@@ -1027,6 +1027,75 @@ int mfmg_hip_mf_laplace_f32_get_block_tile(mfmg_hip_mf_laplace_f32_t op, int n_v
 int mfmg_hip_hierarchy_apply_f32_block(mfmg_hip_hierarchy_t h, int32_t n_vectors, int64_t ld, const float *b, float *x);
 int mfmg_hip_hierarchy_block_info_f32(mfmg_hip_hierarchy_t h, int64_t *fields);
 
+/* ---- Q2 elements: the matrix-free operator and a solver on the refined Q1 cycle (additions, no change of the ABI version) ----
+ * LaplaceMatrixFree<3, 2, double> of the reference (FE_Q(2), QGauss(3); tests/laplace_matrix_free.hpp:75-98,129-199) on a
+ * structured hex mesh.  The unknowns sit on the lattice N[d] = 2 n_cells[d] + 1, numbered lexicographically with x fastest: the
+ * only numbering taken, so there is no index array.  Constrained rows return y_c = x_c, constrained entries of x contribute
+ * nothing to other rows.  FP64, 3-D, one rank: dim != 3 and a context with a communicator are refused with
+ * MFMG_HIP_ERROR_NOT_IMPLEMENTED, n_dofs >= 2^31 or n_dofs != N[0] N[1] N[2] with MFMG_HIP_ERROR_INVALID_ARGUMENT; there is no
+ * FP32 and no block form. */
+typedef struct mfmg_hip_q2_mesh_desc
+{
+  int32_t dim;                  /* 3 */
+  int32_t n_cells[3];           /* Q2 cells per direction, x fastest */
+  double cell_size[3];          /* h[d] */
+  int64_t n_dofs;               /* (2 n_cells[0] + 1)(2 n_cells[1] + 1)(2 n_cells[2] + 1) */
+  const double *coefficient;    /* [n_cells_total][27] at the points q = qa + 3 qb + 9 qc of QGauss<1>(3)^3 */
+  const uint8_t *constrained;   /* [n_dofs] 1 = Dirichlet-constrained */
+  int32_t arrays_on_device;     /* 0: host pointers, 1: device pointers */
+} mfmg_hip_q2_mesh_desc;
+typedef struct mfmg_hip_mf_laplace_q2_s *mfmg_hip_mf_laplace_q2_t;
+/* The coefficients are kept as ONE value per cell where the 27 of every cell are equal (detected on the device) unless
+ * mfmg_hip_context_set_cell_constant_layout(ctx, 0) was called before; _cell_constant_layout reports which. */
+int mfmg_hip_mf_laplace_q2_create(mfmg_hip_context_t ctx, const mfmg_hip_q2_mesh_desc *mesh, mfmg_hip_mf_laplace_q2_t *out);
+int mfmg_hip_mf_laplace_q2_destroy(mfmg_hip_mf_laplace_q2_t op);
+int mfmg_hip_mf_laplace_q2_size(mfmg_hip_mf_laplace_q2_t op, int64_t *n_dofs);
+int mfmg_hip_mf_laplace_q2_cell_constant_layout(mfmg_hip_mf_laplace_q2_t op, int *in_use);
+/* y = A x; res = A x - b; out = x + alpha (x - x_prev) - beta D^-1 (A x - b) (x_prev may be null when alpha == 0).  Device
+ * vectors; the output must not alias x, out may be x_prev.  The meaning of the entry points without _q2. */
+int mfmg_hip_mf_laplace_q2_vmult(mfmg_hip_mf_laplace_q2_t op, const double *x, double *y);
+int mfmg_hip_mf_laplace_q2_residual(mfmg_hip_mf_laplace_q2_t op, const double *x, const double *b, double *res);
+int mfmg_hip_mf_laplace_q2_smoother_step(mfmg_hip_mf_laplace_q2_t op, const double *b, const double *x, const double *x_prev,
+                                         double alpha, double beta, double *out);
+/* compute_diagonal and its inverse, constrained entries 1 (copies into device vectors) */
+int mfmg_hip_mf_laplace_q2_diagonal(mfmg_hip_mf_laplace_q2_t op, double *diag);
+int mfmg_hip_mf_laplace_q2_diagonal_inverse(mfmg_hip_mf_laplace_q2_t op, double *dinv);
+/* The tile of one workgroup in cells whose nodes it owns: tile_x x tile_y cells per layer (one more lane column and row
+ * recompute the halo cells of the low faces), tile_z layers per workgroup.  _tile_shapes lists the shapes on offer, three ints
+ * each, the default first (*n_shapes of them; `tiles` may be null; needs no context); _set_tile takes one of them or (0, 0, 0)
+ * for the default, MFMG_HIP_ERROR_INVALID_ARGUMENT otherwise.  Every shape gives the same bits. */
+int mfmg_hip_mf_laplace_q2_tile_shapes(int32_t *n_shapes, int32_t *tiles, int32_t capacity);
+int mfmg_hip_mf_laplace_q2_get_tile(mfmg_hip_mf_laplace_q2_t op, int *tile_x, int *tile_y, int *tile_z);
+int mfmg_hip_mf_laplace_q2_set_tile(mfmg_hip_mf_laplace_q2_t op, int tile_x, int tile_y, int tile_z);
+
+/* The preconditioner of the Q2 operator: a Chebyshev smoother on it around ONE cycle of a Q1 hierarchy the caller built on the
+ * refined problem (2 n cells of size h / 2, the same lattice of unknowns; matrix-free evaluator, one rank, lexicographic
+ * numbering).  apply(b, x), always from zero:  x = S(b, 0);  r = A_2 x - b;  x -= mfmg_hip_hierarchy_vmult(r);  x = S(b, x).
+ * `params_info`: INFO text whose subtree "high order" holds smoother.degree (default 2; 0: no smoothing, the first and the last
+ * step are skipped), smoother.smoothing_range (4), smoother.eig_cg_n_iterations, smoother.lambda_max, smoother.lambda_min (as the
+ * smoother of a hierarchy).  The hierarchy and the operator must outlive the object and belong to the same context.
+ * MFMG_HIP_ERROR_INVALID_ARGUMENT: the fine level of the hierarchy is not of the operator's size, the two were built on different
+ * contexts, or the hierarchy runs in an internal numbering of its own.
+ * _smoother_info: degree (0: none), lambda_min, lambda_max of the Chebyshev polynomial.
+ * _solve_cg / _solve_fgmres: the argument lists of mfmg_hip_hierarchy_solve_cg / _solve_fgmres without the FP32 flag; the
+ * iteration runs on A_2 with _apply as preconditioner.  CG needs a symmetric Q1 cycle (V(1,1), the default).
+ * _solve_cg_block / _solve_fgmres_block: MFMG_HIP_ERROR_NOT_IMPLEMENTED (there is no block form). */
+typedef struct mfmg_hip_high_order_s *mfmg_hip_high_order_t;
+int mfmg_hip_high_order_create(mfmg_hip_hierarchy_t hierarchy, mfmg_hip_mf_laplace_q2_t q2_operator, const char *params_info,
+                               mfmg_hip_high_order_t *out);
+int mfmg_hip_high_order_destroy(mfmg_hip_high_order_t p);
+int mfmg_hip_high_order_apply(mfmg_hip_high_order_t p, const double *b, double *x);
+int mfmg_hip_high_order_smoother_info(mfmg_hip_high_order_t p, int32_t *degree, double *lambda_min, double *lambda_max);
+int mfmg_hip_high_order_solve_cg(mfmg_hip_high_order_t p, const double *b, double *x, double tolerance, int32_t max_iterations,
+                                 int32_t *n_iterations, double *final_residual, double *residual_history, int32_t history_len);
+int mfmg_hip_high_order_solve_fgmres(mfmg_hip_high_order_t p, const double *b, double *x, double tolerance, int32_t max_iterations,
+                                     int32_t restart, int32_t *n_iterations, double *final_residual, double *residual_history,
+                                     int32_t history_len);
+int mfmg_hip_high_order_solve_cg_block(mfmg_hip_high_order_t p, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                       const double *tolerances, int32_t max_iterations);
+int mfmg_hip_high_order_solve_fgmres_block(mfmg_hip_high_order_t p, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                           const double *tolerances, int32_t max_iterations, int32_t restart);
+
 #ifdef __cplusplus
 }
 #endif

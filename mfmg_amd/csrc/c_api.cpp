@@ -16,6 +16,7 @@
 #include "krylov_drivers.hpp"
 #include "mf_z_tiles.hpp"
 #include "mfmg/hierarchy.hpp"
+#include "mfmg/hip_high_order.hpp"
 
 using namespace mfmg;
 
@@ -159,6 +160,19 @@ struct mfmg_hip_hierarchy_s
   }
 };
 
+struct mfmg_hip_mf_laplace_q2_s
+{
+  HipHandle *handle = nullptr;
+  std::shared_ptr<HipQ2Operator> op;
+  MatrixFreeLaplaceQ2Device<double> &device() const { return *op->get_device_operator(); }
+};
+
+struct mfmg_hip_high_order_s
+{
+  mfmg_hip_hierarchy_t hierarchy = nullptr; // borrowed
+  std::unique_ptr<HighOrderPreconditioner> prec;
+};
+
 namespace
 {
 int64_t level_size(mfmg_hip_hierarchy_t h, int level)
@@ -190,6 +204,17 @@ KrylovSetting krylov_setting(mfmg_hip_hierarchy_t h, bool one_vector)
   const bool work = one_vector && h->perm;
   return {*h->handle, *h->hierarchy, h->fine_f32.get(), h->perm.get(), h->timer, {work ? h->workspace(0) : nullptr, work ? h->workspace(1) : nullptr},
           h->krylov};
+}
+
+// ... with the Q2 operator and the high-order preconditioner as the outer pair; the working sets are those of the Q1 hierarchy
+KrylovSetting high_order_setting(mfmg_hip_high_order_t p)
+{
+  KrylovSetting s = krylov_setting(p->hierarchy, true);
+  s.fine_f32 = nullptr;
+  s.outer_operator = p->prec->get_operator();
+  HighOrderPreconditioner const *prec = p->prec.get();
+  s.outer_preconditioner = [prec](DVector const &r, DVector &z) { prec->apply(r, z); };
+  return s;
 }
 
 // (per column; one column from the one-vector drivers)
@@ -3095,6 +3120,227 @@ int mfmg_hip_hierarchy_timer_report(mfmg_hip_hierarchy_t h, char *buf, size_t bu
     std::string s = h->timer->summary();
     std::strncpy(buf, s.c_str(), buf_size - 1);
     buf[buf_size - 1] = '\0';
+  });
+}
+
+// ---- Q2 elements: the matrix-free operator and the solver on the refined Q1 cycle ---------------------------
+int mfmg_hip_mf_laplace_q2_create(mfmg_hip_context_t ctx, const mfmg_hip_q2_mesh_desc *mesh, mfmg_hip_mf_laplace_q2_t *out)
+{
+  return guarded([&] {
+    require(ctx && mesh && out, "null argument");
+    Q2MeshDesc d;
+    d.dim = mesh->dim;
+    for (int k = 0; k < 3; ++k)
+    {
+      d.n_cells[k] = mesh->n_cells[k];
+      d.cell_size[k] = mesh->cell_size[k];
+    }
+    d.n_dofs = mesh->n_dofs;
+    d.coefficient = mesh->coefficient;
+    d.constrained = mesh->constrained;
+    d.arrays_on_device = mesh->arrays_on_device != 0;
+    std::unique_ptr<mfmg_hip_mf_laplace_q2_s> h(new mfmg_hip_mf_laplace_q2_s);
+    h->handle = ctx->handle.get();
+    h->op = std::make_shared<HipQ2Operator>(
+      std::make_shared<MatrixFreeLaplaceQ2Device<double>>(*ctx->handle, d, ctx->handle->allow_cell_constant));
+    *out = h.release();
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_destroy(mfmg_hip_mf_laplace_q2_t op)
+{
+  return guarded([&] { delete op; });
+}
+
+int mfmg_hip_mf_laplace_q2_size(mfmg_hip_mf_laplace_q2_t op, int64_t *n_dofs)
+{
+  return guarded([&] {
+    require(op && n_dofs, "null argument");
+    *n_dofs = op->device().n_dofs();
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_cell_constant_layout(mfmg_hip_mf_laplace_q2_t op, int *in_use)
+{
+  return guarded([&] {
+    require(op && in_use, "null argument");
+    *in_use = op->device().cell_constant_layout() ? 1 : 0;
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_vmult(mfmg_hip_mf_laplace_q2_t op, const double *x, double *y)
+{
+  return guarded([&] {
+    require(op && x && y, "null argument");
+    op->device().vmult(x, y);
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_residual(mfmg_hip_mf_laplace_q2_t op, const double *x, const double *b, double *res)
+{
+  return guarded([&] {
+    require(op && x && b && res, "null argument");
+    op->device().residual(x, b, res);
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_smoother_step(mfmg_hip_mf_laplace_q2_t op, const double *b, const double *x, const double *x_prev,
+                                         double alpha, double beta, double *out)
+{
+  return guarded([&] {
+    require(op && b && x && out, "null argument");
+    op->device().smoother_step(b, x, x_prev, alpha, beta, out);
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_diagonal(mfmg_hip_mf_laplace_q2_t op, double *diag)
+{
+  return guarded([&] {
+    require(op && diag, "null argument");
+    vec::copy<double>(*op->handle, op->device().n_dofs(), op->device().diagonal(), diag);
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_diagonal_inverse(mfmg_hip_mf_laplace_q2_t op, double *dinv)
+{
+  return guarded([&] {
+    require(op && dinv, "null argument");
+    vec::copy<double>(*op->handle, op->device().n_dofs(), op->device().diagonal_inverse(), dinv);
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_tile_shapes(int32_t *n_shapes, int32_t *tiles, int32_t capacity)
+{
+  return guarded([&] {
+    require(n_shapes != nullptr, "null argument");
+    *n_shapes = kQ2TileShapes;
+    if (tiles)
+    {
+      require(capacity >= 3 * kQ2TileShapes, "`tiles` holds three ints per shape");
+      for (int s = 0; s < kQ2TileShapes; ++s)
+      {
+        tiles[3 * s] = kQ2Tiles[s].tx();
+        tiles[3 * s + 1] = kQ2Tiles[s].ty();
+        tiles[3 * s + 2] = kQ2Tiles[s].tz;
+      }
+    }
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_get_tile(mfmg_hip_mf_laplace_q2_t op, int *tile_x, int *tile_y, int *tile_z)
+{
+  return guarded([&] {
+    require(op && tile_x && tile_y && tile_z, "null argument");
+    const Q2Tile t = op->device().get_tile();
+    *tile_x = t.tx();
+    *tile_y = t.ty();
+    *tile_z = t.tz;
+  });
+}
+
+int mfmg_hip_mf_laplace_q2_set_tile(mfmg_hip_mf_laplace_q2_t op, int tile_x, int tile_y, int tile_z)
+{
+  return guarded([&] {
+    require(op != nullptr, "null argument");
+    int shape = (tile_x == 0 && tile_y == 0 && tile_z == 0) ? -1 : kQ2TileShapes;
+    for (int s = 0; s < kQ2TileShapes; ++s)
+      if (kQ2Tiles[s].tx() == tile_x && kQ2Tiles[s].ty() == tile_y && kQ2Tiles[s].tz == tile_z)
+        shape = s;
+    require(shape < kQ2TileShapes, "not a tile shape of the Q2 operator (mfmg_hip_mf_laplace_q2_tile_shapes lists them)");
+    op->device().set_tile(shape);
+  });
+}
+
+int mfmg_hip_high_order_create(mfmg_hip_hierarchy_t hierarchy, mfmg_hip_mf_laplace_q2_t q2_operator, const char *params_info,
+                               mfmg_hip_high_order_t *out)
+{
+  return guarded([&] {
+    require(hierarchy && q2_operator && out, "null argument");
+    require(hierarchy->handle == q2_operator->handle, "the hierarchy and the Q2 operator were built on different contexts");
+    require(hierarchy->perm == nullptr, "the high-order preconditioner needs a Q1 hierarchy that runs in the caller's lexicographic numbering");
+    if (hierarchy->handle->comm.enabled())
+      ASSERT_THROW_NOT_IMPLEMENTED("the high-order preconditioner runs on one rank (the context has a communicator)");
+    const ptree all = ptree::parse_info(params_info ? params_info : "");
+    ptree const *sub = all.get_child_optional("high order");
+    std::unique_ptr<mfmg_hip_high_order_s> p(new mfmg_hip_high_order_s);
+    p->hierarchy = hierarchy;
+    p->prec.reset(new HighOrderPreconditioner(q2_operator->op, *hierarchy->hierarchy, sub ? *sub : ptree()));
+    *out = p.release();
+  });
+}
+
+int mfmg_hip_high_order_destroy(mfmg_hip_high_order_t p)
+{
+  return guarded([&] { delete p; });
+}
+
+int mfmg_hip_high_order_apply(mfmg_hip_high_order_t p, const double *b, double *x)
+{
+  return guarded([&] {
+    require(p && b && x, "null argument");
+    require(b != x, "b and x must be two vectors");
+    HipHandle &handle = *p->hierarchy->handle;
+    const int64_t n = p->prec->size();
+    DVector bv(handle, n, const_cast<double *>(b)), xv(handle, n, x);
+    p->prec->apply(bv, xv);
+  });
+}
+
+int mfmg_hip_high_order_smoother_info(mfmg_hip_high_order_t p, int32_t *degree, double *lambda_min, double *lambda_max)
+{
+  return guarded([&] {
+    require(p && degree && lambda_min && lambda_max, "null argument");
+    HipSmoother const *s = p->prec->smoother();
+    *degree = s ? s->degree() : 0;
+    *lambda_min = s ? s->lambda_min() : 0.;
+    *lambda_max = s ? s->lambda_max() : 0.;
+  });
+}
+
+int mfmg_hip_high_order_solve_cg(mfmg_hip_high_order_t p, const double *b, double *x, double tolerance, int32_t max_iterations,
+                                 int32_t *n_iterations, double *final_residual, double *residual_history, int32_t history_len)
+{
+  return guarded([&] {
+    require(p && b && x, "null argument");
+    require(tolerance >= 0. && max_iterations >= 0, "bad stopping criterion");
+    const KrylovResult result = solve_cg(high_order_setting(p), b, x, tolerance, max_iterations, residual_history, history_len);
+    deliver_result(result, n_iterations, final_residual, nullptr);
+    if (!result.all_converged())
+      throw std::runtime_error("CG did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
+  });
+}
+
+int mfmg_hip_high_order_solve_fgmres(mfmg_hip_high_order_t p, const double *b, double *x, double tolerance, int32_t max_iterations,
+                                     int32_t restart, int32_t *n_iterations, double *final_residual, double *residual_history,
+                                     int32_t history_len)
+{
+  return guarded([&] {
+    require(p && b && x, "null argument");
+    require(tolerance >= 0. && max_iterations >= 0, "bad stopping criterion");
+    require(restart >= 1, "the restart length must be at least 1");
+    const KrylovResult result =
+      solve_fgmres(high_order_setting(p), b, x, tolerance, max_iterations, restart, false, residual_history, history_len);
+    deliver_result(result, n_iterations, final_residual, nullptr);
+    if (!result.all_converged())
+      throw std::runtime_error("FGMRES did not reach the tolerance within max_iterations (SolverControl::NoConvergence)");
+  });
+}
+
+int mfmg_hip_high_order_solve_cg_block(mfmg_hip_high_order_t p, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                       const double *tolerances, int32_t max_iterations)
+{
+  return guarded([&] {
+    require(p && b && x && tolerances, "null argument");
+    (void)solve_cg_block(high_order_setting(p), n_vectors, ld, b, x, tolerances, max_iterations, nullptr, 0);
+  });
+}
+
+int mfmg_hip_high_order_solve_fgmres_block(mfmg_hip_high_order_t p, int32_t n_vectors, int64_t ld, const double *b, double *x,
+                                           const double *tolerances, int32_t max_iterations, int32_t restart)
+{
+  return guarded([&] {
+    require(p && b && x && tolerances, "null argument");
+    (void)solve_fgmres_block(high_order_setting(p), n_vectors, ld, b, x, tolerances, max_iterations, restart, false, nullptr, 0);
   });
 }
 

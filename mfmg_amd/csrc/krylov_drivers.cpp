@@ -84,6 +84,27 @@ struct RunVectors
   }
 };
 
+// the operator a one-vector driver iterates on and its preconditioner z = M^-1 r: the outer pair of the setting, or the
+// hierarchy's fine operator and cycle
+std::shared_ptr<Operator<DVector> const> outer_or_fine_operator(KrylovSetting const &s)
+{
+  if (s.outer_operator)
+    return s.outer_operator;
+  return s.hierarchy.levels()[0].get_operator();
+}
+void precondition(KrylovSetting const &s, DVector const &r, DVector &z)
+{
+  if (s.outer_preconditioner)
+    s.outer_preconditioner(r, z);
+  else
+    s.hierarchy.vmult(z, r);
+}
+void refuse_outer(KrylovSetting const &s, char const *what)
+{
+  if (s.outer_operator || s.outer_preconditioner)
+    ASSERT_THROW_NOT_IMPLEMENTED(what);
+}
+
 // ||r|| of iteration `it` of column c into a history of history_ld entries per column (or none)
 void record(double *history, int history_ld, int c, int it, double v)
 {
@@ -100,7 +121,7 @@ KrylovResult solve_cg(KrylovSetting const &s, const double *b, double *x, double
 {
   HipHandle &handle = s.handle;
   const int64_t n = level_size(s.hierarchy, 0);
-  auto op = s.hierarchy.levels()[0].get_operator();
+  std::shared_ptr<Operator<DVector> const> op = outer_or_fine_operator(s);
   auto hop = std::dynamic_pointer_cast<HipOperator const>(op);
   const int space = hop ? hop->domain_space() : 0;
   const RunVectors run(s.perm, 1, n, b, x, n, s.work[0], s.work[1]);
@@ -123,7 +144,7 @@ KrylovResult solve_cg(KrylovSetting const &s, const double *b, double *x, double
     int cur = 0;
     while (!converged && it < max_iterations)
     {
-      s.hierarchy.vmult(z, r);
+      precondition(s, r, z);
       vec::dot_async<double>(handle, n, r.get_values(), z.get_values(), scal.data(), cur);
       if (it == 0)
         p = z;
@@ -144,7 +165,7 @@ KrylovResult solve_cg(KrylovSetting const &s, const double *b, double *x, double
   }
   while (!converged && it < max_iterations)
   {
-    s.hierarchy.vmult(z, r);
+    precondition(s, r, z);
     const double rz_new = dot(r, z);
     if (it == 0)
       p = z;
@@ -184,6 +205,7 @@ KrylovResult solve_cg(KrylovSetting const &s, const double *b, double *x, double
 KrylovResult solve_cg_block(KrylovSetting const &s, int k, int64_t ld, const double *b, double *x, const double *tolerances,
                             int max_iterations, double *residual_history, int history_ld)
 {
+  refuse_outer(s, "block CG is not implemented for an outer operator (the high-order preconditioner)");
   HipHandle &handle = s.handle;
   const int64_t n = level_size(s.hierarchy, 0);
   auto op = s.hierarchy.levels()[0].get_operator();
@@ -358,7 +380,9 @@ KrylovResult fgmres_run(KrylovSetting const &s, const double *b_run, double *x_r
   double *const V = ws.V.data(), *const Z = ws.Z.data(), *const hcol = ws.coefficients.data(), *const y_dev = hcol + ws.columns + 1;
   double *const host = ws.host.get(), *const y_host = host + ws.columns + 1;
   float *const v_f32 = fp32 ? ws.v_f32.data() : nullptr;
-  auto op = s.hierarchy.levels()[0].get_operator();
+  std::shared_ptr<Operator<DVector> const> op = outer_or_fine_operator(s);
+  if (fp32)
+    refuse_outer(s, "the FP32 preconditioner does not exist for an outer operator");
   const bool distributed = handle.comm.enabled();
   const krylov::OwnedBox box = distributed ? fine_owned_box<std::runtime_error>(s, n) : krylov::OwnedBox();
   RankSum sum_over_ranks{handle, host};
@@ -404,6 +428,11 @@ KrylovResult fgmres_run(KrylovSetting const &s, const double *b_run, double *x_r
       return;
     }
     DVector vj(handle, n, V + j * ld), zj(handle, n, Z + j * ld);
+    if (s.outer_preconditioner)
+    {
+      s.outer_preconditioner(vj, zj);
+      return;
+    }
     if (zero_first)
       zj = 0.;
     s.hierarchy.vmult(zj, vj);
@@ -520,6 +549,7 @@ KrylovResult solve_fgmres(KrylovSetting const &s, const double *b, double *x, do
 KrylovResult solve_fgmres_block(KrylovSetting const &s, int k, int64_t ld, const double *b, double *x, const double *tolerances,
                                 int max_iterations, int restart, bool fp32, double *residual_history, int history_ld)
 {
+  refuse_outer(s, "block FGMRES is not implemented for an outer operator (the high-order preconditioner)");
   namespace bkb = block_krylov_basis;
   HipHandle &handle = s.handle;
   const int64_t n = level_size(s.hierarchy, 0);

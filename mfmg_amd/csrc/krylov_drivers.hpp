@@ -4,6 +4,7 @@
 // lives here: the drivers launch those of vector_ops, krylov_basis, block_krylov and block_krylov_basis.
 #pragma once
 
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -221,6 +222,11 @@ struct KrylovSetting
   std::shared_ptr<TimerOutput> timer;
   double *work[2];              // with `perm`: two vectors of the fine level
   KrylovWorkspaces &workspaces;
+  // An outer operator and its preconditioner z = M^-1 r from zero (mfmg/hip_high_order.hpp: the Q2 operator and the cycle around the
+  // hierarchy), both or neither.  The one-vector drivers then iterate on them instead of the hierarchy's fine operator and cycle; the
+  // block drivers and the FP32 preconditioner refuse them (NotImplementedExc).  Absent: every driver launches what it always did.
+  std::shared_ptr<Operator<DVector> const> outer_operator = nullptr;
+  std::function<void(DVector const &r, DVector &z)> outer_preconditioner = nullptr;
 };
 
 struct KrylovResult

@@ -59,6 +59,19 @@ class MeshDesc(C.Structure):
     ]
 
 
+class Q2MeshDesc(C.Structure):
+    """mfmg_hip_q2_mesh_desc"""
+    _fields_ = [
+        ("dim", C.c_int32),
+        ("n_cells", C.c_int32 * 3),
+        ("cell_size", C.c_double * 3),
+        ("n_dofs", C.c_int64),
+        ("coefficient", C.c_void_p),
+        ("constrained", C.c_void_p),
+        ("arrays_on_device", C.c_int32),
+    ]
+
+
 def build_library(verbose: bool = False) -> str:
     """Compile libmfmg_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-j8"]
@@ -317,6 +330,26 @@ def load() -> C.CDLL:
         "mfmg_hip_hierarchy_coarse_amg_get": (C.c_int, [vp, i32, i32, P(vp)]),
         "mfmg_hip_hierarchy_coarse_amg_smoother": (C.c_int, [vp, i32, P(i32), P(dbl), P(dbl)]),
         "mfmg_hip_hierarchy_coarse_amg_setup_info": (C.c_int, [vp, i32, P(i32), i32]),
+        "mfmg_hip_mf_laplace_q2_create": (C.c_int, [vp, P(Q2MeshDesc), P(vp)]),
+        "mfmg_hip_mf_laplace_q2_destroy": (C.c_int, [vp]),
+        "mfmg_hip_mf_laplace_q2_size": (C.c_int, [vp, P(i64)]),
+        "mfmg_hip_mf_laplace_q2_cell_constant_layout": (C.c_int, [vp, P(C.c_int)]),
+        "mfmg_hip_mf_laplace_q2_vmult": (C.c_int, [vp, vp, vp]),
+        "mfmg_hip_mf_laplace_q2_residual": (C.c_int, [vp, vp, vp, vp]),
+        "mfmg_hip_mf_laplace_q2_smoother_step": (C.c_int, [vp, vp, vp, vp, dbl, dbl, vp]),
+        "mfmg_hip_mf_laplace_q2_diagonal": (C.c_int, [vp, vp]),
+        "mfmg_hip_mf_laplace_q2_diagonal_inverse": (C.c_int, [vp, vp]),
+        "mfmg_hip_mf_laplace_q2_tile_shapes": (C.c_int, [P(i32), P(i32), i32]),
+        "mfmg_hip_mf_laplace_q2_get_tile": (C.c_int, [vp, P(C.c_int), P(C.c_int), P(C.c_int)]),
+        "mfmg_hip_mf_laplace_q2_set_tile": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "mfmg_hip_high_order_create": (C.c_int, [vp, vp, C.c_char_p, P(vp)]),
+        "mfmg_hip_high_order_destroy": (C.c_int, [vp]),
+        "mfmg_hip_high_order_apply": (C.c_int, [vp, vp, vp]),
+        "mfmg_hip_high_order_smoother_info": (C.c_int, [vp, P(i32), P(dbl), P(dbl)]),
+        "mfmg_hip_high_order_solve_cg": (C.c_int, [vp, vp, vp, dbl, i32, P(i32), P(dbl), P(dbl), i32]),
+        "mfmg_hip_high_order_solve_fgmres": (C.c_int, [vp, vp, vp, dbl, i32, i32, P(i32), P(dbl), P(dbl), i32]),
+        "mfmg_hip_high_order_solve_cg_block": (C.c_int, [vp, i32, i64, vp, vp, P(dbl), i32]),
+        "mfmg_hip_high_order_solve_fgmres_block": (C.c_int, [vp, i32, i64, vp, vp, P(dbl), i32, i32]),
     }
     # entry points added without a change of the ABI version: an older build of the library named by MFMG_HIP_LIBRARY (a
     # measurement against the commit before) lacks them and is loaded without; calling one there fails loudly
@@ -339,6 +372,7 @@ def load() -> C.CDLL:
                    "mfmg_hip_hierarchy_coarse_apply_block", "mfmg_hip_hierarchy_coarse_block_info",
                    "mfmg_hip_csr_set_block_csr", "mfmg_hip_hierarchy_set_block_csr",
                    "mfmg_hip_csr_block_csr_info_f32"}
+    added_later |= {name for name in sig if name.startswith(("mfmg_hip_mf_laplace_q2_", "mfmg_hip_high_order_"))}
     for name, (res, args) in sig.items():
         if name in added_later and os.environ.get("MFMG_HIP_LIBRARY") and not hasattr(lib, name):
             continue
